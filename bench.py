@@ -1,8 +1,10 @@
 """
 Benchmark of the cosmos SVI hot path on MI355X.
 
-    python bench.py                                  # 1 GPU, BASELINE config c2, K steps x 5 blocks
+    python bench.py                                  # 1 GPU, BASELINE config c2, one timed block of K steps
     python bench.py --gpus N --steps K --warmup W    # starts its own N rank processes (one per GPU, RCCL)
+    python bench.py --full                           # K steps x 5 blocks plus every other leg (roofline, minibatch, ...)
+    python bench.py --dump-outputs DIR               # also writes the parameters and ELBO after the last timed step
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (same ranks, outer launcher)
 
 Workload (BASELINE.json configs[1] = "c2"): cosmos K=2, 400 AOIs x 1000 frames, P=14, synthetic data with the law of
@@ -15,10 +17,17 @@ cross-unit sums per step.  `--config c3` / `c5` / `c4` put the per-GPU shard of 
 c3 / c5 figures as `north_star_configs`.
 
 Prints ONE JSON line (rank 0).  `value` = AOI-frames/s over all ranks (median of `--blocks` timed blocks of exactly
-`--steps` steps, each bracketed by barrier + synchronize, max over ranks); also reported: ELBO steps/s, the reference's
-default-minibatch operating point, the trained-parameter regime, the HBM roofline of the fused spot-render + log-prob
-kernel (HIP-event timing on its own stream) and the CPU baseline (oracle = dense-torch restatement, timed on this box's
-host cores, float64 as `tapqir fit` and float32 for information).
+`--steps` steps, each bracketed by barrier + synchronize, max over ranks; one block unless `--full` or `--blocks` says
+otherwise), `ms_per_step` = milliseconds per timed step, and ELBO steps/s.  A plain run does nothing else.  With `--full`
+(5 blocks by default) the line also reports the host enqueue time of a step, the reference's default-minibatch operating
+point, the trained-parameter regime, the HBM roofline of the fused spot-render + log-prob kernel (HIP-event timing on its
+own stream), the CPU baseline (oracle = dense-torch restatement, timed on this box's host cores, float64 as `tapqir fit`
+and float32 for information) and, with `--config auto` at 8 / 4 ranks, the c3 / c5 shards.
+
+`--dump-outputs DIR` writes what the timed path hands its caller after the last timed step of rank 0: every named
+parameter of the engine (`DIR/<name>.npy`, float32) and the ELBO (`DIR/elbo.npy`, float64).  Inputs are seeded, so two
+runs with the same arguments start from identical data and parameters.  Above DUMP_LIMIT bytes in all, the large arrays
+are replaced by a fixed, seeded sample of their elements.
 """
 
 import argparse
@@ -538,6 +547,32 @@ def roofline_block(pb, ms_per_step, dev):
     return out
 
 
+DUMP_LIMIT = 64 << 20  # bytes written by --dump-outputs at most
+
+
+def dump_outputs(eng, out_dir):
+    """`--dump-outputs`: the named parameters (float32) and the ELBO (float64) the last step left.  If they exceed
+    DUMP_LIMIT together, every array of more than 65 536 elements is cut to the same fixed, seeded sample of its flattened
+    elements (sorted positions of a randperm with seed 0, so the sample depends only on the array's size), which keeps
+    them within half the limit."""
+    import numpy as np
+    import torch
+
+    arrays = {name: t.detach().float().cpu().numpy() for name, t in eng.named("params").items()}
+    arrays["elbo"] = eng.elbo_out.detach().double().cpu().numpy()
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT:
+        big = [name for name, a in arrays.items() if a.size > 1 << 16]
+        keep = DUMP_LIMIT // 2 // (8 * len(big))
+        for name in big:
+            a = arrays[name].reshape(-1)
+            if a.size > keep:
+                pos = torch.randperm(a.size, generator=torch.Generator().manual_seed(0))[:keep].sort().values.numpy()
+                arrays[name] = a[pos]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def headline(pb, runner, args, prewarm=True):
     """Timed full-batch steps of one problem -> dict of the headline fields."""
     eng = pb.eng
@@ -604,15 +639,8 @@ def worker(args):
         runner.run(eng, args.pre_steps)
         runner.barrier()
     h = headline(pb, runner, args)
-    # host side of a step (outside the timed region): time to ENQUEUE 20 steps on an idle queue; if it approaches
-    # ms_per_step the launch path, not the GPU, sets the pace
-    runner.barrier()
-    th = time.perf_counter()
-    for _ in range(20):
-        eng.step(allreduce=runner.allreduce)
-    host_ms = (time.perf_counter() - th) / 20 * 1e3
-    eng.join()
-    runner.barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
 
     out = {
         "metric": f"{pb.model} SVI AOI-frames/s (= ELBO steps/s x nb x fb), K={pb.K} P={pb.P} full batch",
@@ -620,12 +648,23 @@ def worker(args):
         "rccl_ranks": (dist.get_world_size() if use_dist else 1), "backend": runner.backend,
         "steps": args.steps, "warmup": args.warmup, "blocks": args.blocks,
         "ms_per_step": h["ms_per_step"], "block_ms_per_step": h["block_ms_per_step"],
-        "per_rank_ms_per_step": h["per_rank_ms_per_step"], "host_enqueue_ms_per_step": host_ms,
+        "per_rank_ms_per_step": h["per_rank_ms_per_step"],
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": h["workload"], "baseline_config": cfg, "nb": pb.N, "fb": pb.F,
                    "aoi_sharding": f"{world} x {pb.N} AOIs", "pre_steps": args.pre_steps},
         "elbo_steps_per_sec": h["elbo_steps_per_sec"], "final_elbo": h["final_elbo"],
     }
+
+    if args.full:
+        # host side of a step (outside the timed region): time to ENQUEUE 20 steps on an idle queue; if it approaches
+        # ms_per_step the launch path, not the GPU, sets the pace
+        runner.barrier()
+        th = time.perf_counter()
+        for _ in range(20):
+            eng.step(allreduce=runner.allreduce)
+        out["host_enqueue_ms_per_step"] = (time.perf_counter() - th) / 20 * 1e3
+        eng.join()
+        runner.barrier()
 
     if world == 1 and args.profile_minibatch > 0:
         # profiling runs: N steps at the reference's default minibatch (10 x 512, fresh subsample every step), untimed
@@ -636,7 +675,7 @@ def worker(args):
         eng.join()
         torch.cuda.synchronize()
 
-    if world == 1 and not args.quick:
+    if world == 1 and args.full and not args.quick:
         # ---- roofline of the dominant kernel (same parameter regime as the headline steps) -----------
         out["roofline"] = roofline_block(pb, h["ms_per_step"], dev)
         # ---- reference default minibatch operating point (main.py:1429-1430): nb=10, fb=512 ----------
@@ -689,7 +728,7 @@ def worker(args):
 
     # ---- the other BASELINE configs at the rank counts they are quoted on (driver's SCALE run: N = 8 -> c3, N = 4 -> c5)
     extra = []
-    if args.config == "auto" and args.offsets == "sim" and not args.quick:
+    if args.config == "auto" and args.offsets == "sim" and args.full and not args.quick:
         extra = {8: ["c3"], 4: ["c5"]}.get(world, [])
     if args.also:
         extra += [c for c in args.also.split(",") if c and c != cfg]
@@ -721,14 +760,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="timed blocks of --steps steps; the median block is reported (default 1, with --full 5)")
     ap.add_argument("--config", default="auto", choices=["auto"] + sorted(CONFIGS),
                     help="BASELINE.json config whose per-GPU shard every rank holds (auto = c2, plus c3 at 8 ranks / c5 at 4)")
     ap.add_argument("--also", default="", help="comma-separated configs to time after the headline (north_star_configs)")
     ap.add_argument("--aois", type=int, default=None, help="override the AOIs per GPU of the config")
     ap.add_argument("--frames", type=int, default=None, help="override the frames of the config")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--quick", action="store_true", help="headline only (no minibatch / roofline / CPU legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="5 timed blocks and every leg besides the headline: host enqueue time, roofline, minibatch, "
+                         "trained regime, CPU baseline, c3 / c5 at 8 / 4 ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the parameters (float32) and ELBO (float64) after the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg of --full")
+    ap.add_argument("--quick", action="store_true", help="with --full: headline and host enqueue time only "
+                                                         "(no minibatch / roofline / CPU legs)")
     ap.add_argument("--trained-steps", type=int, default=4000, help="steps before the trained-regime leg (0 = skip)")
     ap.add_argument("--profile-minibatch", type=int, default=0, help="untimed default-minibatch steps after the headline (profiling runs)")
     ap.add_argument("--pre-steps", type=int, default=0, help="untimed full-batch steps before the headline (profiling the trained regime)")
@@ -737,6 +783,8 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal: take the multi-GPU code path (process group, staged step, all-reduce) with one rank")
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
     if args.model == "crosstalk":
         args.config = "c4"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

@@ -7,7 +7,7 @@ for round in 1 2 3; do
   for cfg in "$@"; do
     envs=""
     [ "$cfg" != "-" ] && envs=$(echo $cfg | tr ',' ' ')
-    env $envs timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu --trained-steps ${TRAINED:-0} 2>/dev/null | python -c "
+    env $envs timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu --trained-steps ${TRAINED:-0} 2>/dev/null | python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 r=d['roofline']

@@ -8,7 +8,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # 1. kernel trace + stats of the default bench (no CPU leg)
 rm -rf $O/trace
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python3 $R/bench.py --no-cpu --steps 10 --blocks 3 --trained-steps 0 > $O/bench_traced.json 2> $O/bench_traced.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python3 $R/bench.py --full --no-cpu --steps 10 --blocks 3 --trained-steps 0 > $O/bench_traced.json 2> $O/bench_traced.err
 echo "trace rc=$?"
 f=$(find $O/trace -name "*kernel_trace.csv" | head -1)
 python3 $R/scripts/prof_summary.py $f > $O/kernel_trace_summary.txt
@@ -28,10 +28,10 @@ STEPOUT=steppmc bash $R/scripts/gpu_step_pmc.sh > $O/steppmc.log 2>&1
 cp $R/gpurun_out/steppmc/summary.txt $O/pmc_summary_step.txt
 cd $R
 # 3. bench lines
-timeout -k 10 400 python3 bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "c2 rc=$?"
-timeout -k 10 300 python3 bench.py --config c3 --no-cpu --trained-steps 0 > $O/bench_c3shard.json 2>/dev/null; echo "c3 rc=$?"
-timeout -k 10 300 python3 bench.py --config c4 --no-cpu --trained-steps 0 > $O/bench_c4.json 2>/dev/null; echo "c4 rc=$?"
-timeout -k 10 300 python3 bench.py --config c5 --no-cpu --trained-steps 0 > $O/bench_c5shard.json 2>/dev/null; echo "c5 rc=$?"
-timeout -k 10 300 python3 bench.py --offsets hist --no-cpu --trained-steps 0 > $O/bench_c2_hist50.json 2>/dev/null; echo "hist rc=$?"
+timeout -k 10 400 python3 bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "c2 rc=$?"
+timeout -k 10 300 python3 bench.py --full --config c3 --no-cpu --trained-steps 0 > $O/bench_c3shard.json 2>/dev/null; echo "c3 rc=$?"
+timeout -k 10 300 python3 bench.py --full --config c4 --no-cpu --trained-steps 0 > $O/bench_c4.json 2>/dev/null; echo "c4 rc=$?"
+timeout -k 10 300 python3 bench.py --full --config c5 --no-cpu --trained-steps 0 > $O/bench_c5shard.json 2>/dev/null; echo "c5 rc=$?"
+timeout -k 10 300 python3 bench.py --full --offsets hist --no-cpu --trained-steps 0 > $O/bench_c2_hist50.json 2>/dev/null; echo "hist rc=$?"
 timeout -k 10 300 python3 bench.py --force-dist --quick > $O/bench_c2_forcedist.json 2>/dev/null; echo "forcedist rc=$?"
 ls -la $O

@@ -23,7 +23,7 @@ if [[ $S == *trace* ]]; then
   python3 $R/scripts/prof_summary.py $O/kernel_trace_c2.csv > $O/kernel_trace_summary.txt
   trace c2_trained --quick --steps 20 --blocks 5 --pre-steps 4000
   python3 $R/scripts/prof_summary.py $O/kernel_trace_c2_trained.csv --last 100 > $O/kernel_trace_summary_trained.txt
-  trace c2_hist50 --offsets hist --no-cpu --trained-steps 0 --steps 10 --blocks 3
+  trace c2_hist50 --full --offsets hist --no-cpu --trained-steps 0 --steps 10 --blocks 3
   python3 $R/scripts/prof_summary.py $O/kernel_trace_c2_hist50.csv > $O/kernel_trace_summary_hist50.txt
   trace c3 --quick --config c3 --steps 10 --blocks 3
   python3 $R/scripts/make_trace_json.py $O/kernel_trace.json c2=$O/kernel_trace_c2.csv c2_trained=$O/kernel_trace_c2_trained.csv:100 \
@@ -56,12 +56,12 @@ if [[ $S == *pix* ]]; then
 fi
 if [[ $S == *bench* ]]; then
   cd $R
-  timeout -k 10 500 python3 bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "c2 rc=$?"
-  timeout -k 10 300 python3 bench.py --config c1 --no-cpu --trained-steps 0 > $O/bench_c1.json 2>/dev/null; echo "c1 rc=$?"
-  timeout -k 10 300 python3 bench.py --config c3 --no-cpu --trained-steps 0 > $O/bench_c3shard.json 2>/dev/null; echo "c3 rc=$?"
-  timeout -k 10 300 python3 bench.py --config c4 --no-cpu --trained-steps 0 > $O/bench_c4.json 2>/dev/null; echo "c4 rc=$?"
-  timeout -k 10 300 python3 bench.py --config c5 --no-cpu --trained-steps 0 > $O/bench_c5shard.json 2>/dev/null; echo "c5 rc=$?"
-  timeout -k 10 300 python3 bench.py --offsets hist --no-cpu --trained-steps 0 > $O/bench_c2_hist50.json 2>/dev/null; echo "hist rc=$?"
+  timeout -k 10 500 python3 bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "c2 rc=$?"
+  timeout -k 10 300 python3 bench.py --full --config c1 --no-cpu --trained-steps 0 > $O/bench_c1.json 2>/dev/null; echo "c1 rc=$?"
+  timeout -k 10 300 python3 bench.py --full --config c3 --no-cpu --trained-steps 0 > $O/bench_c3shard.json 2>/dev/null; echo "c3 rc=$?"
+  timeout -k 10 300 python3 bench.py --full --config c4 --no-cpu --trained-steps 0 > $O/bench_c4.json 2>/dev/null; echo "c4 rc=$?"
+  timeout -k 10 300 python3 bench.py --full --config c5 --no-cpu --trained-steps 0 > $O/bench_c5shard.json 2>/dev/null; echo "c5 rc=$?"
+  timeout -k 10 300 python3 bench.py --full --offsets hist --no-cpu --trained-steps 0 > $O/bench_c2_hist50.json 2>/dev/null; echo "hist rc=$?"
   timeout -k 10 300 python3 bench.py --force-dist --quick > $O/bench_c2_forcedist.json 2>/dev/null; echo "forcedist rc=$?"
 fi
 ls -la $O

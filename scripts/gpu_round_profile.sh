@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/round
 mkdir -p $OUT/prof $OUT/pmc
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu > $OUT/bench.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu > $OUT/bench.log 2>&1
 echo "kernel-trace rc=$?"
 grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json
 python3 $R/scripts/prof_summary.py $OUT/prof/bench_kernel_trace.csv > $OUT/kernel_trace_summary.txt 2>&1

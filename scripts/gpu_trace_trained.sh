@@ -7,7 +7,7 @@ O=$R/gpurun_out/${OUTDIR:-trace_trained}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/trace
-timeout -k 10 500 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o bench -- python3 $R/bench.py --no-cpu --steps 20 --blocks 3 --trained-steps ${TRAINED:-4000} > $O/bench_traced.json 2> $O/bench_traced.err
+timeout -k 10 500 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o bench -- python3 $R/bench.py --full --no-cpu --steps 20 --blocks 3 --trained-steps ${TRAINED:-4000} > $O/bench_traced.json 2> $O/bench_traced.err
 echo "trace rc=$?"
 f=$(find $O/trace -name "*kernel_trace.csv" | head -1)
 python3 $R/scripts/prof_summary.py $f --last 60 > $O/kernel_trace_summary_trained.txt
