@@ -89,9 +89,6 @@ __device__ __forceinline__ void tq_site_beta_compact(const tq_cosmos_args& a, co
     c1 = size * (d.p0 - d.lo) * rsc;
     c0 = size * (d.hi - d.p0) * rsc;
     clamped = (d.val <= d.lo + a.eps * sc) || (d.val >= d.hi - a.eps * sc);
-#ifdef TQ_DIAG_NO_BETAGRAD  // (diagnostic builds, scripts/gpu_site_diag.sh: no gradient is evaluated)
-    clamped = true;
-#endif
     if (!clamped) {
       pair = tq_beta_grad_pair_applies((double)t, (double)c1, (double)size - (double)c1);
       if (!pair) {
@@ -108,9 +105,7 @@ __device__ __forceinline__ void tq_site_beta_compact(const tq_cosmos_args& a, co
   if (!wave_mixed) {
     if (pair) {
       double ga = t, gb = c1;
-#ifndef TQ_DIAG_NO_RP
       tq_beta_grad_pair_mid((double)t, (double)c1, (double)size - (double)c1, &ga, &gb);
-#endif
       dd[0] = (float)ga;
       dd[1] = (float)gb;
     }
@@ -173,23 +168,13 @@ __device__ __forceinline__ void tq_site_beta_compact(const tq_cosmos_args& a, co
         const double total = sz;
         if (c == 0) {
           double ga = x, gb = al;
-#ifndef TQ_DIAG_NO_RP  // (diagnostic builds, scripts/gpu_site_diag.sh: one regime's routine compiled out)
           tq_beta_grad_pair_mid((double)x, (double)al, total - (double)al, &ga, &gb);
-#endif
           L.res[2 * dst] = (float)ga;
           L.res[2 * dst + 1] = (float)gb;
         } else if (c == 1) {
-#ifdef TQ_DIAG_NO_R0
-          L.res[2 * dst + code] = x;
-#else
           L.res[2 * dst + code] = (float)tq_beta_grad_alpha_small((double)x, (double)al, total - (double)al);
-#endif
         } else if (c == 2) {
-#ifdef TQ_DIAG_NO_R1
-          L.res[2 * dst + code] = x;
-#else
           L.res[2 * dst + code] = -tq_beta_grad_beta_small_f(1.0f - x, sz - al, al);
-#endif
         } else if (c == 3) {
           double ga = 0.0, gb = 0.0;
           if (!tq_beta_grad_pair_mid<true>((double)x, (double)al, total - (double)al, &ga, &gb)) {
@@ -201,11 +186,7 @@ __device__ __forceinline__ void tq_site_beta_compact(const tq_cosmos_args& a, co
           if (code & 1) L.res[2 * dst] = (float)ga;
           if (code & 2) L.res[2 * dst + 1] = (float)gb;
         } else {
-#ifdef TQ_DIAG_NO_R3
-          L.res[2 * dst + code] = x;
-#else
           L.res[2 * dst + code] = tq_beta_grad_rational(x, al, sz);
-#endif
         }
       }
       wave0 += (n + 63) >> 6;
@@ -225,13 +206,10 @@ __device__ __forceinline__ void tq_site_beta_compact(const tq_cosmos_args& a, co
 
 // one site of one unit per lane; workgroups are uniform in the site (grid.y), AffineBeta sites go through the compaction
 __device__ __forceinline__ void tq_sample_site_wg(const tq_cosmos_args& a, const int site, const int64_t i, const int64_t B) {
-#ifndef TQ_DIAG_NO_COMPACT  // (diagnostic builds: the plain per-lane evaluation everywhere)
   if (site > a.K) {
     __shared__ TqBetaCompactLds s_bc;
     tq_site_beta_compact(a, site, i, i < B, s_bc);
-  } else
-#endif
-  if (i < B) {
+  } else if (i < B) {
     tq_body_site(a, site, i);
   }
 }
@@ -440,13 +418,9 @@ __global__ __launch_bounds__(256) void tq_tail_reduced_kernel(const tq_cosmos_ar
 #include "tq_ksmogn_dev.h"
 #include "tq_ksmogn_il2.h"
 
-// (host) does this step use the rows layout?  TAPQIR_AMD_ROWS=0 keeps the flat layout + tq_aoi_kernel (A/B timing)
+// (host) does this step use the rows layout?  Full batches with the fused Adam; the others keep the flat layout + tq_aoi_kernel
 static bool tq_rows_layout(const tq_cosmos_args& a) {
-  static const bool enabled = [] {
-    const char* e = getenv("TAPQIR_AMD_ROWS");
-    return !(e && e[0] == '0');
-  }();
-  return enabled && a.fuse_adam && !a.ndx && !a.fdx && a.nb == a.Nt && a.fb == a.F && a.F * a.C >= TQ_UNIT_BLOCK;
+  return a.fuse_adam && !a.ndx && !a.fdx && a.nb == a.Nt && a.fb == a.F && a.F * a.C >= TQ_UNIT_BLOCK;
 }
 
 // Units per workgroup (= per row of partial sums) of the single-launch minibatch step: 16, one 16-lane group each -- or 20,
@@ -458,8 +432,7 @@ static bool tq_rows_layout(const tq_cosmos_args& a) {
 // own flag; before that the tail workgroup next to a worker delayed everybody and 20 lost, 55.5 against 53.0).  A pure function
 // of the batch geometry (TAPQIR_AMD_MB_UNITS = 16 / 20 overrides): the launch that runs the pending tail calls it again.
 static int tq_mb_upr(const tq_cosmos_args& a) {
-  const char* e = getenv("TAPQIR_AMD_MB_UNITS");  // (read at every call: tests switch it inside one process)
-  const int forced = e ? atoi(e) : 0;
+  const int forced = tq_env_int("TAPQIR_AMD_MB_UNITS", 0);  // (read at every call: tests switch it inside one process)
   if ((int64_t)a.fb * a.C < 20 || forced == 16) return 16;
   if (forced == 20) return 20;
   const int64_t B = tq_batch_units(a);
@@ -878,8 +851,8 @@ __device__ __forceinline__ bool tq_groups_reduce_globals_body(const tq_cosmos_ar
 
 // AOI-sharded full-batch steps (and tq_cosmos_tail): rows -> per-AOI sites and gsum, what the all-reduce needs.  Workgroup g
 // adds the rows of group g (one wave, one round trip) and publishes the group row; the workgroup whose ticket is the last
-// one finishes the per-AOI sites and the cross-unit sums from the U / 4096 group rows (tq_rows_sums_kernel, one wave per AOI
-// and a last workgroup that walked all 6250 rows, took 38 us at c2 -- on the critical path of every sharded step).
+// one finishes the per-AOI sites and the cross-unit sums from the U / 4096 group rows (one wave per AOI and a last
+// workgroup that walked all 6250 rows took 38 us at c2 -- on the critical path of every sharded step).
 __global__ __launch_bounds__(256) void tq_group_sums_kernel(const tq_cosmos_args a) {
   __shared__ double s_w[4][TQ_MAX_NGSUM];
   __shared__ int s_last;
@@ -892,64 +865,6 @@ __global__ __launch_bounds__(256) void tq_group_sums_kernel(const tq_cosmos_args
   tq_groups_sums_body<false>(a, s_w);
 }
 
-
-// AOI-sharded full-batch steps: rows -> per-AOI sites and gsum (what the all-reduce needs), nothing of the global
-// sites.  One wave per (AOI, channel) adds the rows that overlap the AOI (a single workgroup would walk 400 AOIs x 17 rows
-// of 64 units in sequence, on the critical path of the step); the LAST workgroup to finish -- a device-scope ticket
-// after a release fence -- sums the rows and the per-AOI ELBO parts in fp64, in a fixed order.
-__global__ __launch_bounds__(256) void tq_rows_sums_kernel(const tq_cosmos_args a) {
-  __shared__ double s_w[4][TQ_MAX_NGSUM];
-  __shared__ int s_last;
-  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
-  const int64_t B = tq_batch_units(a);
-  const uint32_t UPR = (uint32_t)tq_rows_upr(a);
-  const int64_t nrows = (B + UPR - 1) / UPR;
-  const uint32_t FC = (uint32_t)(a.fb * a.C);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nac = a.nb * a.C;
-  const int ac = (int)blockIdx.x * 4 + wave;
-  if (ac < nac) {
-    const uint32_t ai = (uint32_t)ac / (uint32_t)a.C;
-    const int c = ac - (int)ai * a.C;
-    const uint32_t r_lo = (ai * FC) / UPR, r_hi = ((ai + 1) * FC - 1) / UPR;
-    float s1 = 0.0f, s2 = 0.0f;
-    for (uint32_t r = r_lo + lane; r <= r_hi; r += 64) {
-      const int slot = (r * UPR) / FC == ai ? 0 : 1;
-      const float* row = a.blk_part + (int64_t)r * ncol + slot * TQ_ROWS_AOICOL + 2 * c;
-      s1 += row[0];
-      s2 += row[1];
-    }
-    s1 = tq_wave_sum(s1);
-    s2 = tq_wave_sum(s2);
-    if (lane == 0) {
-      float e;
-      tq_body_aoi_finish(a, (int)ai, c, s1, s2, &e);
-      a.aoi_part[2 * B + ac] = e;  // (rows 0 and 1 of aoi_part belong to the flat layout; row 2 is scratch, nb*C <= B)
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (threadIdx.x == 0)
-    s_last = __hip_atomic_fetch_add(&a.sync[3], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  double acc[TQ_MAX_NGSUM];
-#pragma unroll
-  for (int j = 0; j < TQ_MAX_NGSUM; ++j) acc[j] = 0.0;
-  tq_rows_column_sums(a, nrows, nq, ncol, acc);
-  for (int r = threadIdx.x; r < nac; r += 256) acc[TQ_GS_ELBO] += (double)a.aoi_part[2 * B + r];
-#pragma unroll
-  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
-    if (j < nq) {
-      const double s = tq_wave_sum_d(acc[j]);
-      if (lane == 0) s_w[wave][j] = s;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < nq) a.gsum[threadIdx.x] = s_w[0][threadIdx.x] + s_w[1][threadIdx.x] + s_w[2][threadIdx.x] + s_w[3][threadIdx.x];
-  if (threadIdx.x == 0) __hip_atomic_store(&a.sync[3], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed
-}
 
 __global__ __launch_bounds__(256) void tq_rows_reduce_globals_kernel(const tq_cosmos_args a, const int upr) {
   __shared__ double s_w[4][TQ_MAX_NGSUM];
@@ -1375,11 +1290,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
     constexpr int NPASS = (NL * U + 255) / 256;
     // a thin last pass is shared out: G lanes per element (tq_adam_replay_split)
     constexpr int XLAST = NL * U - 256 * (NPASS - 1);
-#ifdef TQ_NO_REPLAY_SPLIT
-    constexpr int G = 1;
-#else
     constexpr int G = NPASS == 1 ? 1 : (XLAST <= 32 ? 8 : (XLAST <= 64 ? 4 : (XLAST <= 128 ? 2 : 1)));
-#endif
     int64_t ej[NPASS];
     int es0[NPASS];
     float ep[NPASS], em[NPASS], ev[NPASS];
@@ -1699,22 +1610,14 @@ static int launch_pixel_unit(const tq_cosmos_args* a, void* stream) {
   return check_launch("tq_pixel_unit_kernel");
 }
 
-// per-AOI sites + gsum of a step with rows, for callers that all-reduce gsum before the global sites (tq_rows_sums_kernel)
+// per-AOI sites + gsum of a step with rows, for callers that all-reduce gsum before the global sites (tq_group_sums_kernel)
 static int launch_rows_sums(const tq_cosmos_args* a, hipStream_t st) {
   if (!a->sync || !a->aoi_part || !a->gsum) {
     tq_set_error("tq_cosmos_elbo_grads: the rows layout needs sync, aoi_part and gsum");
     return TQ_ERR_ARG;
   }
-  static const bool groups = [] {
-    const char* e = getenv("TAPQIR_AMD_GROUPS");
-    return !(e && e[0] == '0');
-  }();
-  if (groups) {
-    hipLaunchKernelGGL(tq_group_sums_kernel, dim3((unsigned)tq_grp_count(tq_batch_units(*a))), dim3(256), 0, st, *a);
-    return check_launch("tq_group_sums_kernel");
-  }
-  hipLaunchKernelGGL(tq_rows_sums_kernel, dim3((unsigned)((a->nb * a->C + 3) / 4)), dim3(256), 0, st, *a);
-  return check_launch("tq_rows_sums_kernel");
+  hipLaunchKernelGGL(tq_group_sums_kernel, dim3((unsigned)tq_grp_count(tq_batch_units(*a))), dim3(256), 0, st, *a);
+  return check_launch("tq_group_sums_kernel");
 }
 
 // rows: AOI-aligned per-unit kernel whose tail also finishes the per-AOI sites (tq_unit_rows_kernel; full-batch steps
@@ -1772,7 +1675,7 @@ static int elbo_grads_impl(const tq_cosmos_args* a, void* stream, bool finish_su
 
 extern "C" int tq_cosmos_elbo_grads(const tq_cosmos_args* a, void* stream) {
   // full-batch steps with the Adam of the local parameters fused in take the rows layout here too (the per-AOI sites are
-  // finished by tq_rows_sums_kernel, which also leaves gsum ready for the caller's all-reduce)
+  // finished by tq_group_sums_kernel, which also leaves gsum ready for the caller's all-reduce)
   return elbo_grads_impl(a, stream, true, a && tq_rows_layout(*a) && a->sync && a->aoi_part);
 }
 
@@ -1846,8 +1749,8 @@ static int launch_reduce_globals(const tq_cosmos_args* a, hipStream_t st) {
 extern "C" int tq_cosmos_tail(const tq_cosmos_args* a, void* stream) {
   if (int rc = check_args(a, "tail")) return rc;
   if (a->tail_kind != TQ_TAIL_ROWS16 && tq_rows_layout(*a) && a->fuse_adam && a->sync && a->aoi_part) {
-    // rows of 64 or 256 units: the per-AOI frame sums span up to F C / 64 rows each -- one wave per AOI
-    // (tq_rows_sums_kernel) instead of one workgroup walking all of them, then the global sites + tail Adam
+    // rows of 64 or 256 units: the per-AOI frame sums span up to F C / 64 rows each -- added per group of 4096 units
+    // (tq_group_sums_kernel) instead of by one workgroup walking all of them, then the global sites + tail Adam
     if (int rc = launch_rows_sums(a, (hipStream_t)stream)) return rc;
     return tq_cosmos_tail_reduced(a, nullptr, stream);
   }
@@ -1902,15 +1805,9 @@ extern "C" int tq_cosmos_step_overlapped(const tq_cosmos_args* a, const tq_cosmo
     prev = nullptr;
   }
   int code = prev ? tq_prev_code(*prev) : 0;
-  {
-    // rows of 64 / 256 units: the idle workgroups of the launch's first grid row add them per group (tq_group_reduce_rows)
-    static const bool groups = [] {
-      const char* e = getenv("TAPQIR_AMD_GROUPS");
-      return !(e && e[0] == '0');
-    }();
-    const int64_t gx = (B + 255) / 256;
-    if (groups && code == 3 && prev->sync && tq_grp_count(tq_batch_units(*prev)) + 1 <= gx) code = 6;
-  }
+  // rows of 64 / 256 units: the idle workgroups of the launch's first grid row add them per group (tq_group_reduce_rows);
+  // code 3 stays for grids too small for that
+  if (code == 3 && prev->sync && tq_grp_count(tq_batch_units(*prev)) + 1 <= (B + 255) / 256) code = 6;
   hipLaunchKernelGGL(tq_sample_locals_tail_kernel, dim3((unsigned)((B + 255) / 256), (unsigned)(2 + 4 * a->K)), dim3(256), 0,
                      (hipStream_t)stream, *a, prev ? *prev : *a, code, B, 0);
   if (int rc = check_launch("tq_sample_locals_tail_kernel")) return rc;
@@ -1950,8 +1847,7 @@ extern "C" int tq_cosmos_minibatch_step(const tq_cosmos_args* a, const tq_cosmos
   // one workgroup per 16 (or 20: tq_mb_upr) units + the one that runs the tail and the global draws
   const int upr = tq_mb_upr(*a);
   const dim3 grid((unsigned)((B + upr - 1) / upr) + 1), block(256);
-  const char* tl = getenv("TAPQIR_AMD_MB_TAIL_LAST");
-  const int tail_last = !(tl && tl[0] == '0') && grid.x > 1 && (grid.x - 1) % 256 == 0 && grid.x <= 513;  // (<= 2 workgroups per CU: all resident)
+  const int tail_last = tq_env_int("TAPQIR_AMD_MB_TAIL_LAST", 1) != 0 && grid.x > 1 && (grid.x - 1) % 256 == 0 && grid.x <= 513;  // (<= 2 workgroups per CU: all resident)
   size_t lds = sizeof(float) * tq_tile16_lds_floats(a->P, a->K, a->O);
   if (a->next_ndx || a->next_fdx) {
     if ((a->next_ndx && a->Nt > TQ_SUBSAMPLE_MAX) || (a->next_fdx && a->F > TQ_SUBSAMPLE_MAX)) {

@@ -755,20 +755,12 @@ static int launch_kb(const tq_ksmogn_args& a, int64_t B, hipStream_t st) {
       const dim3 grid1((unsigned)((B + 63) / 64)), block1(64);
       // a.pixel_mode: 1 = persistent waves (two per SIMD walk over the tiles), 0 = one wave per tile.  Which is faster
       // depends on the box (wave-launch and memory latencies; measured 114-151 us vs 120-131 us at 400 000 units across
-      // the pool): the host times both once and says (CosmosEngine); TAPQIR_AMD_PERSIST=0/1 overrides for A/B runs
-      static const int forced = [] {
-        const char* e = getenv("TAPQIR_AMD_PERSIST");
-        return e ? atoi(e) : -1;
-      }();
-      const int persist = forced >= 0 ? forced : a.pixel_mode;
-      if (bwd && !a.gout && persist > 0 && K <= 2) {  // (K = 3 spills in this form)
+      // the pool): the host times both once and says (CosmosEngine.autotune_pixel)
+      if (bwd && !a.gout && a.pixel_mode > 0 && K <= 2) {  // (K = 3 spills in this form)
         int ntiles = (int)((B + 63) / 64);
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        static const int waves_forced = [] {  // tests: few resident waves = many tiles per wave
-          const char* e = getenv("TAPQIR_AMD_PERSIST_WAVES");
-          return e ? atoi(e) : 0;
-        }();
+        static const int waves_forced = tq_env_int("TAPQIR_AMD_PERSIST_WAVES", 0);  // tests: few resident waves = many tiles per wave
         const int waves = waves_forced > 0 ? waves_forced : cus * 4 * TQ_P_WAVES;
         const int64_t Bn = B;
         ntiles = (int)((Bn + 63) / 64);
@@ -807,18 +799,12 @@ static int launch_kb(const tq_ksmogn_args& a, int64_t B, hipStream_t st) {
   if (!ONE && a.O >= 8) {
     // offset histograms: a wave per unit (the offset loop makes a unit ~O times the work of the single-offset form, and a
     // gathered batch is small: at 16 lanes per unit a 10 x 512 minibatch fills 1.25 waves per SIMD)
-    static const bool wide = [] {
-      const char* e = getenv("TAPQIR_AMD_WIDE_HIST");
-      return !(e && e[0] == '0');
-    }();
-    if (wide) {
-      constexpr int UNITS = TQ_BLOCK / 64;
-      const dim3 gridw((unsigned)((B + UNITS - 1) / UNITS)), blockw(TQ_BLOCK);
-      const size_t ldsw = sizeof(float) * tq_tile16_lds_floats(a.P, K, a.O, UNITS);
-      if (bwd) hipLaunchKernelGGL((tq_ksmogn_kernel<K, false, true, 64>), gridw, blockw, ldsw, st, a, B);
-      else hipLaunchKernelGGL((tq_ksmogn_kernel<K, false, false, 64>), gridw, blockw, ldsw, st, a, B);
-      return launch_status("tq_ksmogn_kernel (64 lanes per unit)");
-    }
+    constexpr int UNITS = TQ_BLOCK / 64;
+    const dim3 gridw((unsigned)((B + UNITS - 1) / UNITS)), blockw(TQ_BLOCK);
+    const size_t ldsw = sizeof(float) * tq_tile16_lds_floats(a.P, K, a.O, UNITS);
+    if (bwd) hipLaunchKernelGGL((tq_ksmogn_kernel<K, false, true, 64>), gridw, blockw, ldsw, st, a, B);
+    else hipLaunchKernelGGL((tq_ksmogn_kernel<K, false, false, 64>), gridw, blockw, ldsw, st, a, B);
+    return launch_status("tq_ksmogn_kernel (64 lanes per unit)");
   }
   const dim3 grid((unsigned)((B + TQ_UNITS_PER_BLOCK - 1) / TQ_UNITS_PER_BLOCK)), block(TQ_BLOCK);
   const size_t lds = sizeof(float) * tq_tile16_lds_floats(a.P, K, a.O);

@@ -4,6 +4,7 @@
 // See tq_ksmogn.hip for the kernels and tq_pixel.h for the arithmetic.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
 
 #include "../../include/tapqir_hip.h"
 #include "tq_dpp.h"
@@ -12,6 +13,13 @@
 #define TQ_LANES_PER_UNIT 16
 #define TQ_UNITS_PER_BLOCK 16
 #define TQ_BLOCK (TQ_LANES_PER_UNIT * TQ_UNITS_PER_BLOCK)
+
+// (host) integer value of a test hook's environment variable, `fallback` where it is not set: the hooks force a launch
+// geometry the inputs of the oracle tests would not reach by themselves (TAPQIR_AMD_MB_UNITS, _MB_TAIL_LAST, _PERSIST_WAVES)
+static inline int tq_env_int(const char* name, int fallback) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : fallback;
+}
 
 __device__ __forceinline__ float tq_fast_sigmoid(float u) { return TQ_FRCP(1.0f + TQ_FEXP(-u)); }
 

@@ -720,11 +720,7 @@ TQ_HD_NOINLINE void tq_beta_grad_pair_rest(float t, float c1, float c0, float si
   dd[0] = dd[1] = 0.0f;
   // saddle-point regime of ONE direction (both: tq_beta_grad_pair_mid has returned true and this routine is not
   // called): the pair routine once, keeping the direction(s) that asked for it
-#if defined(TQ_DIAG_NO_R2)
-  if (false) {
-#else
   if (regime[0] == 2 || regime[1] == 2) {
-#endif
     double ga = 0.0, gb = 0.0;
     if (tq_beta_grad_pair_mid<true>((double)t, (double)c1, total - (double)c1, &ga, &gb)) {
       if (regime[0] == 2) dd[0] = (float)ga;
@@ -747,16 +743,8 @@ TQ_HD_NOINLINE void tq_beta_grad_pair_rest(float t, float c1, float c0, float si
         const bool first = pass == 0 && n0;
         const float xs = first ? xf[0] : xf[1], as = first ? af[0] : af[1];
         float g;
-#if defined(TQ_DIAG_NO_R0)  // (diagnostic builds: scripts/gpu_site_diag.sh)
-        if (r == 0) g = xs;
-#else
         if (r == 0) g = (float)tq_beta_grad_alpha_small((double)xs, (double)as, total - (double)as);
-#endif
-#if defined(TQ_DIAG_NO_R1)
-        else g = as;
-#else
         else g = -tq_beta_grad_beta_small_f(1.0f - xs, size - as, as);
-#endif
         if (first) dd[0] = g;
         else dd[1] = g;
       }
@@ -764,9 +752,5 @@ TQ_HD_NOINLINE void tq_beta_grad_pair_rest(float t, float c1, float c0, float si
   }
 #pragma nounroll
   for (int j = 0; j < 2; ++j)
-#if defined(TQ_DIAG_NO_R3)
-    if (regime[j] == 3) dd[j] = xf[j];
-#else
     if (regime[j] == 3) dd[j] = tq_beta_grad_rational(xf[j], af[j], size);
-#endif
 }

@@ -43,6 +43,7 @@ class CosmosEngine:
     pipelined_tail = True      # tq_cosmos_step_overlapped: the tail of step t inside the sampling launch of step t+1
     split_sampling = True      # tq_cosmos_sample_locals_range: sampling split around an in-flight all-reduce
     lazy_adam_default = True   # tq_cosmos_adam_catchup
+    fused_minibatch = True     # tq_cosmos_minibatch_step: a minibatch step (or a small full batch) as ONE launch
 
     def __init__(self, data, K=2, priors=None, device="cuda", eps=None, seed=0, n_offset=0, Nt_global=None,
                  crosstalk=False, hbm_budget=None):
@@ -111,9 +112,9 @@ class CosmosEngine:
         self._exp_avg = torch.zeros(n, dtype=f32, device=dev)
         self._exp_avg_sq = torch.zeros(n, dtype=f32, device=dev)
         # lazy Adam of minibatch steps (include/tapqir_hip.h: tq_cosmos_adam_catchup): per-unit clock of the last update;
-        # meaningful only while `_stale` (some unit's local parameters lag behind adam_step).  TAPQIR_AMD_LAZY_ADAM=0:
+        # meaningful only while `_stale` (some unit's local parameters lag behind adam_step).  lazy_adam = False (tests):
         # every minibatch step streams the whole buffers through the dense Adam kernel instead
-        self.lazy_adam = self.lazy_adam_default and os.environ.get("TAPQIR_AMD_LAZY_ADAM", "1") != "0"
+        self.lazy_adam = self.lazy_adam_default
         self._last_step = torch.zeros(self.Nt * self.F * self.C, dtype=torch.int32, device=dev)
         self._stale = False
         gsz, bsz = self.struct_sizes()
@@ -130,9 +131,11 @@ class CosmosEngine:
         # contiguous batches at least this large use the lane-per-unit pixel kernel (64 units per wave):
         # 65536 units = one wave per SIMD of an MI355X
         self.il_min_units = 65536
+        # full batches of at most this many units (BASELINE config c1: 5000) take the one-launch step of the minibatches
+        # (_route)
+        self.small_full_max_units = 10240
         # full-batch single-GPU steps leave their single-workgroup tail pending and run it inside the next step's
-        # sampling launch (include/tapqir_hip.h: tq_cosmos_step_overlapped); TAPQIR_AMD_OVERLAP=0 turns it off
-        self.overlap_tail = os.environ.get("TAPQIR_AMD_OVERLAP", "1") != "0"
+        # sampling launch (include/tapqir_hip.h: tq_cosmos_step_overlapped)
         self._tail_args = None  # arguments of the step whose tail is pending
         # form of the backward pixel kernel for contiguous batches (include/tapqir_hip.h: pixel_mode): None = not chosen
         # yet -> the first full-batch step times both forms on this box (autotune_pixel)
@@ -146,9 +149,6 @@ class CosmosEngine:
         # TAPQIR_AMD_FUSE_UNIT=auto brings the timing back (three interleaved rounds, best of each).
         fu = os.environ.get("TAPQIR_AMD_FUSE_UNIT", "1")
         self.fuse_unit = None if fu == "auto" else fu != "0"
-        # minibatch steps with the lazy Adam clock run as ONE launch (include/tapqir_hip.h: tq_cosmos_minibatch_step);
-        # TAPQIR_AMD_MB_FUSED=0 keeps the five-launch sequence
-        self.fused_minibatch = self.pipelined_tail and os.environ.get("TAPQIR_AMD_MB_FUSED", "1") != "0"
         self._sync = torch.zeros(64, dtype=torch.int32, device=dev)  # TQ_SYNC_WORDS (tickets, flags; diagnostic stamps of a TQ_MB_STAMPS build)
         self._sync_value = 0
 
@@ -405,10 +405,9 @@ class CosmosEngine:
         B = nb * fb * self.C
         dev, f32 = self.device, torch.float32
         self.lat = torch.zeros((1 + 4 * K) * B, dtype=f32, device=dev)
-        self.site = torch.zeros(int(os.environ.get("TAPQIR_AMD_SITE_ROWS", 5)) * (1 + 4 * K) * B, dtype=f32, device=dev)  # TQ_NSITE_STORED rows (the switch: A/B runs against older builds of the library)
+        self.site = torch.zeros(5 * (1 + 4 * K) * B, dtype=f32, device=dev)  # TQ_NSITE_STORED rows (tq_site.h)
         self.pix = torch.zeros((M + 2 + 4 * K + (1 + self.C if self.crosstalk else 0)) * B, dtype=f32, device=dev)
         self.aoi_part = torch.zeros(3 * B, dtype=f32, device=dev)
-        nblk = (B + 255) // 256
         self.blk_part = torch.zeros(self._blk_floats(B), dtype=f32, device=dev)
         self._ws_key = key
 
@@ -632,8 +631,7 @@ class CosmosEngine:
         """Can a full-batch step of this engine run pixel + per-unit kernel in one launch?  (tq_cosmos.hip:
         tq_fused_pixel_unit -- same conditions.)"""
         return (self.pipelined_tail and not self.crosstalk and self.K <= 2 and self.O == 1 and self.P in (14, 20)
-                and self.Nt * self.F * self.C >= self.il_min_units and self.F * self.C >= 256
-                and os.environ.get("TAPQIR_AMD_ROWS", "1") != "0")
+                and self.Nt * self.F * self.C >= self.il_min_units and self.F * self.C >= 256)
 
     def autotune_fused(self, steps=6, rounds=3):
         """Choose between two launches (pixel kernel, per-unit kernel) and the fused launch for the full-batch steps of
@@ -666,6 +664,37 @@ class CosmosEngine:
         self.step_times_ms = times
         return self.fuse_unit
 
+    def _route(self, nb, fb, allreduce):
+        """The launch sequence of a step of nb AOIs x fb frames (step() and step_subsampled() both ask here):
+
+        * ``"streamed"``: the images do not fit the device, the step's AOIs go through in groups (_step_streamed);
+        * ``"one_launch"``: catch-up, site draws, likelihood, per-unit terms + Adam in ONE launch that also runs the pending
+          tail of the previous step (tq_cosmos_minibatch_step): minibatches with the lazy Adam clock, and SMALL full batches
+          (BASELINE config c1: 5000 units), whose few hundred workgroups are latency in every phase as a minibatch's are;
+        * ``"overlapped"``: the pipelined step, its tail runs inside the next step's sampling launch
+          (tq_cosmos_step_overlapped): full batches, and the lazy-clock minibatches the single launch does not take
+          (crosstalk, fb C < 16);
+        * ``"staged"``: the launches one after the other (tq_cosmos_step): minibatches with the dense Adam;
+        * ``"sharded"``: the staged launches with the cross-unit sums all-reduced between them (AOI sharding), also the
+          route of engines without the pipelined tail.
+
+        Attribute reads and integer tests only: at the default 10 x 512 minibatch the host bounds ``Model.run``."""
+        if self.streamed:
+            return "streamed"
+        if allreduce is not None or not self.pipelined_tail:
+            return "sharded"
+        minibatch = nb < self.Nt or fb < self.F
+        if self.fused_minibatch and not self.crosstalk:
+            # (offset histograms stay in the single launch: the staged sequence with the wave-per-unit likelihood kernel
+            # measured 0.150 against 0.162 ms at O = 50 -- not worth a second path through the step)
+            if minibatch and self.lazy_adam and fb * self.C >= 16:
+                return "one_launch"
+            B = self.Nt * self.F * self.C
+            if (not minibatch and B <= self.small_full_max_units and B < self.il_min_units
+                    and self.F * self.C >= 16):
+                return "one_launch"
+        return "overlapped" if not minibatch or self.lazy_adam else "staged"
+
     def step_subsampled(self, nb, fb, generator=None):
         """A minibatch step on a subsample the DEVICE has drawn: the single-launch minibatch step also draws the next step's
         `randperm(Nt)[:nb]`, `randperm(F)[:fb]` (include/tapqir_hip.h: next_ndx / next_fdx) into the other of two index
@@ -674,8 +703,8 @@ class CosmosEngine:
         step whose batch sizes differ from what the previous launch prepared) takes a host draw from ``generator``.  Returns
         False if this engine cannot run that path (the caller then passes its own subsample to ``step``)."""
         nb, fb = min(int(nb), self.Nt), min(int(fb), self.F)
-        if not (self.fused_minibatch and self.lazy_adam and self.pipelined_tail and not self.crosstalk and not self.streamed
-                and (nb < self.Nt or fb < self.F) and fb * self.C >= 16 and max(self.Nt, self.F) <= 2048  # TQ_SUBSAMPLE_MAX
+        if not ((nb < self.Nt or fb < self.F) and max(self.Nt, self.F) <= 2048  # TQ_SUBSAMPLE_MAX
+                and self._route(nb, fb, None) == "one_launch"
                 and os.environ.get("TAPQIR_AMD_DEVICE_SUBSAMPLE", "1") != "0"):
             return False
         st = self.__dict__.get("_sub")
@@ -703,7 +732,10 @@ class CosmosEngine:
         sites, Adam of the per-AOI and global parameters) is deferred: it runs after the NEXT step's local guide
         sampling, which needs local parameters only, so the collective's latency hides behind that kernel.  ``join()``
         (called by every read-out) completes a deferred tail."""
-        if self.streamed:
+        nb = self.Nt if ndx is None else int(ndx.numel())
+        fb = self.F if fdx is None else int(fdx.numel())
+        route = self._route(nb, fb, allreduce)
+        if route == "streamed":
             if allreduce is not None:
                 raise NotImplementedError("AOI sharding of a streamed data set: shard first, each rank then streams its own AOIs "
                                           "(not built: a rank's shard of every BASELINE config fits its 288 GB many times over)")
@@ -716,30 +748,18 @@ class CosmosEngine:
         minibatch = bool(a.zero_grad)
         # Adam on the local block is fused into the unit kernel: full batches, and minibatches with the lazy clock
         a.fuse_adam = int(not minibatch or self.lazy_adam)
-        # (offset histograms stay in the single launch: the staged sequence with the wave-per-unit likelihood kernel measured
-        # 0.150 against 0.162 ms at O = 50 -- TAPQIR_AMD_MB_HIST_STAGED=1 -- not worth a second path through the step)
-        one_launch = (minibatch and self.lazy_adam and self.fused_minibatch and allreduce is None and not self.crosstalk
-                      and a.fb * self.C >= 16 and not (self.O >= 8 and os.environ.get("TAPQIR_AMD_MB_HIST_STAGED") == "1"))
-        # a SMALL full batch (BASELINE config c1: 5000 units) is the same case as a minibatch -- a few hundred workgroups
-        # whose every phase is latency: the one-launch step with no subsample and no lazy clock instead of the two launches
-        # of the pipelined full-batch step (TAPQIR_AMD_SMALL_FULL=0: the two launches)
-        B_full = self.Nt * self.F * self.C
-        if (not minibatch and self.fused_minibatch and self.pipelined_tail and allreduce is None and not self.crosstalk
-                and B_full <= 10240 and B_full < self.il_min_units and self.F * self.C >= 16
-                and os.environ.get("TAPQIR_AMD_SMALL_FULL", "1") != "0"):
-            one_launch = True
         if minibatch and self.lazy_adam:
             if not self._stale:
                 self._last_step.fill_(self.adam_step)  # every unit is current: start the clock here
                 self._stale = True
-            if not one_launch:
+            if route != "one_launch":
                 self._adam_catchup(a, 0)
         else:
             self._catch_up_all()
             a.last_step = None  # full batch: no unit falls behind
-        if allreduce is None and self.pipelined_tail:
+        if route != "sharded":
             self._finish_pending()
-            if one_launch:
+            if route == "one_launch":
                 # catch-up, site draws, likelihood, per-unit terms + Adam of this step and the pending tail of the
                 # previous one in a single launch; the tail of this step stays pending
                 prev = self._tail_args
@@ -751,17 +771,17 @@ class CosmosEngine:
                                                               self._stream()), "tq_cosmos_minibatch_step")
                 a.tail_kind = 1  # TQ_TAIL_ROWS16
                 self._tail_args = a
-            elif self.overlap_tail and a.fuse_adam:
+            elif route == "overlapped":
                 if self.fuse_unit and not minibatch and self._fusable():
                     a.pixel_mode = 2  # TQ_PIXEL_FUSED_UNIT
                 prev = self._tail_args
                 _lib.check(self.lib.tq_cosmos_step_overlapped(C.byref(a), None if prev is None else C.byref(prev),
                                                               self._stream()), "tq_cosmos_step_overlapped")
                 self._tail_args = a
-            else:
+            else:  # "staged"
                 self._finish_tail()
                 self.call("cosmos_step", a)
-        else:
+        else:  # "sharded"
             self._finish_tail()
             pending = self._pending
             if pending is not None and not a.fuse_adam:

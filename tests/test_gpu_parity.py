@@ -293,7 +293,7 @@ def test_autotune_fused_restores_the_state():
 @pytest.mark.parametrize("fuse", [False, True], ids=["two_launches", "fused"])
 def test_sharded_launch_sequence_with_rows_matches_the_pipelined_step(handle, fuse):
     """The launch sequence of an AOI-sharded full-batch step (tq_cosmos_elbo_grads with the rows layout -- per-AOI sites and
-    gsum finished by tq_rows_sums_kernel -- then the all-reduce, here of one rank, then tq_cosmos_tail_reduced inside the
+    gsum finished by tq_group_sums_kernel -- then the all-reduce, here of one rank, then tq_cosmos_tail_reduced inside the
     next step's split sampling) against the pipelined single-GPU step on the same data."""
 
     class Done:

@@ -4,7 +4,7 @@ drive the STAGED calls; a real fit goes through ``CosmosEngine.step`` which pick
 
   * ``tq_pixel_unit_kernel<K,P>``      -- full-batch single-GPU steps (pixel + per-unit phase + Adam in one launch),
   * ``tq_minibatch_kernel<K,ONE>``     -- minibatch steps in one launch, ONE = single camera offset or offset histogram,
-  * the AOI-sharded launch sequence (tq_cosmos_elbo_grads with rows + tq_rows_sums_kernel + tq_cosmos_tail_reduced),
+  * the AOI-sharded launch sequence (tq_cosmos_elbo_grads with rows + tq_group_sums_kernel + tq_cosmos_tail_reduced),
   * the small-batch sequence (16-lane pixel kernel + tq_unit_kernel + tq_aoi_kernel) -- BASELINE config c1.
 
 Every test below runs complete device steps (device guide draws, fused Adam), then hands the device's own draws to the
@@ -100,7 +100,7 @@ MB_CASES = [
 @pytest.mark.parametrize("name,K,dkw,nb,fb", MB_CASES, ids=[c[0] for c in MB_CASES])
 def test_single_launch_minibatch_kernel_against_oracle(name, K, dkw, nb, fb):
     d, o, eng = setup(K, dkw)
-    assert eng.fused_minibatch and eng.lazy_adam
+    assert eng.fused_minibatch and eng.lazy_adam and eng._route(nb, fb, None) == "one_launch"
     calls = []
     real = eng.lib.tq_cosmos_minibatch_step
 
@@ -138,7 +138,7 @@ MB_U20_CASES = [
 def test_single_launch_minibatch_kernel_20_units_per_workgroup(name, K, dkw, nb, fb, monkeypatch):
     monkeypatch.setenv("TAPQIR_AMD_MB_UNITS", "20")
     d, o, eng = setup(K, dkw)
-    assert eng.fused_minibatch and eng.lazy_adam and fb * eng.C >= 20
+    assert eng.fused_minibatch and eng.lazy_adam and fb * eng.C >= 20 and eng._route(nb, fb, None) == "one_launch"
     replay(eng, o, dkw["N"], dkw["F"], nb=nb, fb=fb)
     eng.join()  # (the pending tail is sized by the same environment variable)
 
@@ -221,12 +221,13 @@ def test_c1_full_size_steps(minibatch):
     assert len(calls) == 3
 
 
-def test_c1_full_size_steps_two_launches(monkeypatch):
+def test_c1_full_size_steps_two_launches():
     """The same whole-batch steps through the pipelined two-launch sequence (16-lane pixel kernel, flat per-unit kernel,
-    per-AOI kernel, tail inside the next sampling launch), which TAPQIR_AMD_SMALL_FULL=0 keeps available."""
-    monkeypatch.setenv("TAPQIR_AMD_SMALL_FULL", "0")
+    per-AOI kernel, tail inside the next sampling launch), which full batches of more than small_full_max_units take."""
     K, N, F = 1, 50, 100
     d, o, eng = setup(K, dict(N=N, F=F))
+    eng.small_full_max_units = 0
+    assert eng._route(N, F, None) == "overlapped"
     replay(eng, o, N, F)
 
 
@@ -240,7 +241,7 @@ class _Done:
 @pytest.mark.parametrize("fuse", [False, True], ids=["two_launches", "fused"])
 def test_sharded_launch_sequence_against_oracle(handle, fuse):
     """tq_cosmos_elbo_grads with the rows layout (pixel_mode 2 = fused pixel + per-unit launch, or pixel + tq_unit_rows_kernel)
-    -> tq_rows_sums_kernel -> all-reduce (one rank: identity) -> tq_cosmos_tail_reduced, inside the split sampling of the
+    -> tq_group_sums_kernel -> all-reduce (one rank: identity) -> tq_cosmos_tail_reduced, inside the split sampling of the
     next step when the collective is left in flight."""
     N, F = 3, 300
     d, o, eng = setup(2, dict(N=N, F=F), perturb=0.3)

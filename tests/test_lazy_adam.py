@@ -34,6 +34,8 @@ def test_lazy_minibatch_adam_follows_the_dense_trajectory(crosstalk, F, fb):
     likelihood, per-unit terms, pending tail), the dense engine's as the staged launches + dense Adam kernel."""
     dense, lazy = engines(C=2 if crosstalk else 1, crosstalk=crosstalk, F=F)
     assert lazy.fused_minibatch
+    assert lazy._route(2, fb, None) == ("one_launch" if fb * lazy.C >= 16 and not crosstalk else "overlapped")
+    assert dense._route(2, fb, None) == "staged"
     gen = torch.Generator().manual_seed(0)
     touched = torch.zeros(6, F, dtype=torch.bool)
     losses = []
@@ -147,3 +149,45 @@ def test_lazy_adam_on_the_host_build():
                 assert close(getattr(lazy, name), getattr(dense, name), tol), (it, name)
             assert not lazy._stale
     assert dense.adam_step == lazy.adam_step == 14
+
+
+@pytest.mark.parametrize("route,nb,fb,dkw,setup", [
+    ("one_launch", 2, 17, {}, {}),
+    ("one_launch", 2, 17, dict(offsets="hist"), {}),  # offset histograms keep the single launch too
+    ("one_launch", 6, 40, {}, {}),  # a small full batch
+    ("overlapped", 6, 40, {}, dict(small_full_max_units=0)),
+    ("overlapped", 2, 5, {}, {}),  # fb C < 16
+    ("overlapped", 2, 17, dict(C=2), dict(crosstalk=True)),
+    ("staged", 2, 17, {}, dict(lazy_adam=False)),
+    ("sharded", 2, 17, {}, dict(allreduce=True)),
+], ids=["minibatch", "minibatch_hist", "small_full", "full", "narrow_minibatch", "crosstalk", "dense_adam", "allreduce"])
+def test_step_and_step_subsampled_follow_route(route, nb, fb, dkw, setup, monkeypatch):
+    """step() launches what _route() says, and step_subsampled() -- whose next subsample only the single launch draws --
+    accepts exactly the minibatches that step() runs as one launch.  Host build, launches recorded and not run."""
+    from helpers import HostCheckEngine
+
+    monkeypatch.delenv("TAPQIR_AMD_DEVICE_SUBSAMPLE", raising=False)
+    setup = dict(setup)
+    allreduce = (lambda g: None) if setup.pop("allreduce", False) else None
+    d = make_dataset(N=6, F=40, K=2, seed=5, **dkw)
+    eng = HostCheckEngine(d, K=2, device=torch.device("cpu"), crosstalk=setup.pop("crosstalk", False))
+    eng.pipelined_tail, eng.lazy_adam, eng.pixel_mode, eng.fuse_unit = True, True, 0, True
+    for k, v in setup.items():
+        setattr(eng, k, v)
+    calls = []
+
+    class Record:
+        def __getattr__(self, n):
+            return lambda *a: calls.append(n) or 0
+
+    eng.lib = Record()
+    assert eng._route(nb, fb, allreduce) == route
+    last = {"one_launch": "tq_cosmos_minibatch_step", "overlapped": "tq_cosmos_step_overlapped", "staged": "hc_cosmos_step",
+            "sharded": "hc_cosmos_tail_reduced"}[route]
+    gen = torch.Generator().manual_seed(0)
+    eng.step(torch.randperm(6, generator=gen)[:nb], torch.randperm(40, generator=gen)[:fb], allreduce=allreduce)
+    assert calls[-1] == last
+    calls.clear()
+    subsampled = eng.step_subsampled(nb, fb, gen)  # (a single-GPU step: no all-reduce)
+    assert subsampled == (eng._route(nb, fb, None) == "one_launch" and (nb, fb) != (6, 40))
+    assert calls[-1:] == (["tq_cosmos_minibatch_step"] if subsampled else [])
