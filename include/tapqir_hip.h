@@ -429,6 +429,55 @@ typedef struct {
 int tq_snr_chi2(const tq_snr_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Time-to-first-binding kinetics (`tapqir ttfb`, tapqir/main.py:926-1147).
+ *
+ * tq_ttfb_sample replaces time_to_first_binding(z_sample(num_samples)) (tapqir/utils/imscroll.py:187-196,
+ * tapqir/models/cosmos.py:706-709) without drawing the S x N x F Bernoullis: the frames are independent under q, so
+ *   L[n, f] = sum_{j <= f} log1p(-p[n, j])        (double, left to right: log P(tau > f))
+ *   tau[s, n] = first f with L[n, f] < log u[s, n], or F if there is none,
+ * with u[s, n] the uniform of Philox stream (seed, s, site 0xA00, n) (tq_math.h).  Two launches: the prefix (one wave
+ * per AOI) and the search (one lane per (s, n)).
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const float* p;              /* (N, F) p(z = 1) of each AOI-frame, in [0, 1] */
+  double* log_surv;            /* (N, F) out / workspace: L */
+  float* tau;                  /* (S, N) out: integer-valued first-binding frames in [0, F] */
+  int32_t N, F, S;
+  uint64_t seed;
+} tq_ttfb_sample_args;
+
+int tq_ttfb_sample(const tq_ttfb_sample_args* a, void* stream);
+
+/* tq_ttfb_fit replaces train(ttfb_model, ttfb_guide, lr, n_steps) of tapqir/utils/mle_analysis.py:11-105 (pyro SVI,
+ * TraceEnum_ELBO, optim.Adam): S independent maximum-likelihood fits of the censored two-exponential mixture of Friedman
+ * & Gelles (2015), one per row of `tau`.  Per row the unconstrained parameters are (log ka, log kns, logit Af); with
+ * k0 = kns, k1 = ka + kns the log-likelihood is the sum of
+ *   0 < tau < T: logaddexp(log Af + log k1 - k1 tau, log(1 - Af) + log k0 - k0 tau)
+ *   tau == T:    logaddexp(log Af - k1 T, log(1 - Af) - k0 T)
+ *   control:     0 < tauc < T: log kns - kns tauc;  tauc == T: -kns T
+ * (tau == 0 contributes nothing) and Adam (torch.optim.Adam semantics, float32) descends on its negative.
+ * `state` carries parameters and moments between launches: a launch runs Adam steps step0 + 1 .. step0 + n_steps, so a
+ * fit in chunks is bitwise equal to one launch.  The caller initialises state (torch: log 0.001, log 0.001, logit 0.9,
+ * zero moments).  One wave per row: tau is staged in LDS when N <= TQ_TTFB_LDS_POINTS and stage_lds != 0, read from
+ * L2 every step otherwise. */
+typedef struct {
+  const float* tau;            /* (S, N) integer-valued data */
+  const float* tauc;           /* (S, Nc) control data, or NULL (Nc = 0) */
+  float* state;                /* (S, 9) in/out: log ka, log kns, logit Af, exp_avg[3], exp_avg_sq[3] */
+  float* loss;                 /* (S) out or NULL: loss (-log-likelihood) at the last step of the launch, before its update */
+  int32_t S, N, Nc;
+  int32_t step0;               /* Adam steps completed before this launch */
+  int32_t n_steps;             /* Adam steps of this launch (>= 1) */
+  int32_t stage_lds;           /* 1: stage tau in LDS when it fits; 0: always read it from L2 */
+  float Tmax;                  /* observation interval T */
+  double lr, beta1, beta2, eps;
+} tq_ttfb_fit_args;
+#define TQ_TTFB_LDS_POINTS 8192
+#define TQ_TTFB_STATE 9
+
+int tq_ttfb_fit(const tq_ttfb_fit_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame
  * decode of GlimpseDataset.__getitem__ (168-186: big-endian int16 + 2^15) and the offset-region value counts

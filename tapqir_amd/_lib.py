@@ -132,6 +132,30 @@ class GlimpseArgs(C.Structure):
     ]
 
 
+class TtfbSampleArgs(C.Structure):
+    """``tq_ttfb_sample_args`` (include/tapqir_hip.h)."""
+
+    _fields_ = [
+        ("p", C.c_void_p), ("log_surv", C.c_void_p), ("tau", C.c_void_p),
+        ("N", C.c_int32), ("F", C.c_int32), ("S", C.c_int32), ("seed", C.c_uint64),
+    ]
+
+
+class TtfbFitArgs(C.Structure):
+    """``tq_ttfb_fit_args`` (include/tapqir_hip.h)."""
+
+    _fields_ = [
+        ("tau", C.c_void_p), ("tauc", C.c_void_p), ("state", C.c_void_p), ("loss", C.c_void_p),
+        ("S", C.c_int32), ("N", C.c_int32), ("Nc", C.c_int32), ("step0", C.c_int32), ("n_steps", C.c_int32),
+        ("stage_lds", C.c_int32), ("Tmax", C.c_float),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+    ]
+
+
+TTFB_LDS_POINTS = 8192  # TQ_TTFB_LDS_POINTS
+TTFB_STATE = 9          # TQ_TTFB_STATE
+
+
 # every symbol include/tapqir_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "tq_version", "tq_last_error", "tq_ksmogn_log_prob", "tq_ksmogn_crosstalk_log_prob", "tq_crosstalk_param_count",
@@ -140,7 +164,7 @@ EXPORTS = [
     "tq_cosmos_sample_globals", "tq_cosmos_sample_locals", "tq_cosmos_elbo_grads",
     "tq_cosmos_globals_grad", "tq_cosmos_adam", "tq_cosmos_adam_catchup", "tq_cosmos_step", "tq_cosmos_step_overlapped", "tq_cosmos_tail", "tq_cosmos_tail_reduced", "tq_cosmos_sample_locals_range",
     "tq_cosmos_blk_floats", "tq_cosmos_minibatch_step", "tq_cosmos_pixel_unit",
-    "tq_cosmos_probs", "tq_glimpse_extract", "tq_ksmogn_rsample", "tq_snr_chi2",
+    "tq_cosmos_probs", "tq_glimpse_extract", "tq_ksmogn_rsample", "tq_snr_chi2", "tq_ttfb_sample", "tq_ttfb_fit",
 ]
 
 _lib = None
@@ -208,6 +232,10 @@ def load():
     lib.tq_snr_chi2.restype = C.c_int
     lib.tq_glimpse_extract.argtypes = [C.POINTER(GlimpseArgs), C.c_void_p]
     lib.tq_glimpse_extract.restype = C.c_int
+    lib.tq_ttfb_sample.argtypes = [C.POINTER(TtfbSampleArgs), C.c_void_p]
+    lib.tq_ttfb_sample.restype = C.c_int
+    lib.tq_ttfb_fit.argtypes = [C.POINTER(TtfbFitArgs), C.c_void_p]
+    lib.tq_ttfb_fit.restype = C.c_int
     _lib = lib
     return lib
 

@@ -1,10 +1,11 @@
 """
-Command line of the MI355X build: the ``glimpse`` / ``fit`` / ``stats`` / ``log`` commands of ``tapqir``
-(tapqir/main.py:66-318, 321-576, 873-884, 1387-1488) over the same workspace (``<cd>/.tapqir/config.yaml``, ``loginfo``, ``<model>_model.tpqr``,
+Command line of the MI355X build: the ``glimpse`` / ``fit`` / ``stats`` / ``ttfb`` / ``log`` commands of ``tapqir``
+(tapqir/main.py:66-318, 321-576, 873-884, 926-1147, 1387-1488) over the same workspace (``<cd>/.tapqir/config.yaml``, ``loginfo``, ``<model>_model.tpqr``,
 ``<model>_params.tpqr``, ``<model>_summary.csv``).  Options, defaults and exit codes (0 / 1) follow the reference;
 ``--cpu`` exits with 1 because the SVI step has no CPU path here.  ``glimpse`` takes its inputs from flags or from
-``config.yaml`` (there are no interactive prompts).  Plotting (``show``) and the kinetics commands are outside the
-hot-path scope of this build.
+``config.yaml`` (there are no interactive prompts).  ``ttfb`` (tapqir/main.py:926-1147) samples first-binding times and
+fits the association kinetics on the GPU from ``data.tpqr`` and ``<model>_params.tpqr``.  Plotting (``show``) and
+``dwelltime`` are outside the scope of this build.
 
     python -m tapqir_amd --cd <dir> fit --model cosmos --cuda --num-iter 0 --no-input
 """
@@ -237,6 +238,145 @@ def stats(
         logger.exception("Failed to compute stats")
         raise typer.Exit(1)
     logger.info("Computing stats: Done")
+
+
+def _ttfb_plots(cd, name, c, z_masked, sdx, r_type, Tmax, fb_mean, fb_ll, fb_ul, best_fit, logger):
+    """Rastergram and cumulative-fraction plot of one channel (main.py:988-1005, 1108-1147)."""
+    try:
+        import matplotlib as mpl
+
+        mpl.use("Agg")
+        import matplotlib.pyplot as plt
+    except Exception:
+        logger.warning("matplotlib is not available: the ttfb plots are not drawn")
+        return
+    mpl.rcParams["font.family"] = "sans-serif"
+    mpl.rcParams.update({"font.size": 8})
+    fig, ax = plt.subplots()
+    ax.imshow(z_masked[sdx].numpy(), norm=mpl.colors.Normalize(vmin=0, vmax=1), aspect="equal", interpolation="none")
+    ax.set_xlabel("Time (frame)")
+    ax.set_ylabel("AOI")
+    ax.set_title(f"Channel {c}")
+    plt.savefig(cd / f"{name}_ttfb-rastergram-channel{c}.png", dpi=600)
+    plt.close(fig)
+    logger.info(f"Saved a {r_type} rastergram in {name}_ttfb-rastergram-channel{c}.png file")
+
+    t = range(Tmax)
+    fig, ax = plt.subplots()
+    ax.fill_between(t, fb_ll, fb_ul, alpha=0.3, color="C2")
+    ax.plot(t, fb_mean, color="C2")
+    ax.plot(t, best_fit, color="k")
+    plt.minorticks_on()
+    ax.tick_params(direction="in", which="minor", length=1, bottom=True, top=True, left=True, right=True)
+    ax.tick_params(direction="in", which="major", length=2, bottom=True, top=True, left=True, right=True)
+    ax.set_yticks([0, 0.2, 0.4, 0.6, 0.8, 1])
+    ax.set_yticklabels([r"$0$", r"$0.2$", r"$0.4$", r"$0.6$", r"$0.8$", r"$1$"])
+    ax.set_xlabel("Time (frame)")
+    ax.set_ylabel("Cumulative fraction")
+    ax.set_title(f"Channel {c}")
+    ax.set_ylim(-0.05, 1.05)
+    plt.savefig(cd / f"{name}_ttfb-plot-channel{c}.png", dpi=600)
+    plt.close(fig)
+    logger.info(f"Saved data plots in {name}_ttfb-plot-channel{c}.png file")
+
+
+@app.command()
+def ttfb(
+    model: avail_models = typer.Option("cosmos", help="Tapqir model"),
+    binary: bool = typer.Option(False, "--binary/--probabilistic", help="Plot a binary or probabilistic rastergram"),
+    cuda: bool = typer.Option(_default("cuda"), "--cuda/--cpu", help="Run computations on GPU or CPU", show_default=False),
+    num_samples: int = typer.Option(2000, "--num-samples", "-n", min=1, help="Number of posterior samples"),
+    num_iter: int = typer.Option(15000, "--num-iter", "-it", min=1, help="Number of iterations"),
+    no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
+    progress_bar=None,
+):
+    """
+    Time-to-first-binding analysis (tapqir/main.py:926-1147): posterior samples of the first-binding frame of every
+    on-target AOI, one censored two-exponential fit (ka, kns, Af) per sample, and the cumulative fraction bound.
+    Needs ``data.tpqr`` and ``<model>_params.tpqr`` of a cosmos fit.
+    """
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.exceptions import HipExtensionError, TapqirFileNotFoundError
+    from tapqir_amd.models import models
+    from tapqir_amd.utils.imscroll import time_to_first_binding
+    from tapqir_amd.utils.mle_analysis import fraction_bound, fraction_bound_fit, hpdi_columns, ttfb_fit, ttfb_sample
+    from tapqir_amd.utils.stats import hpdi
+
+    cd = DEFAULTS["cd"]
+    logger = logging.getLogger("tapqir")
+    if model.value != "cosmos":
+        # the reference has no z_sample for crosstalk, and cosmos+hmm is not part of this build
+        logger.error(f"ttfb is not available for the {model.value} model (cosmos only)")
+        raise typer.Exit(1)
+    if not cuda:
+        logger.error("ttfb runs on the AMD GPU only (--cuda): the sampler and the fits have no CPU path")
+        raise typer.Exit(1)
+    m = models[model.value](device="cpu", dtype="float")
+    try:
+        m.load(cd, data_only=False)
+    except TapqirFileNotFoundError as err:
+        logger.exception(f"Failed to load {err.name} file")
+        raise typer.Exit(1)
+    if "z_probs" not in m.params:
+        logger.error(f"{m.name}_params.tpqr has no z_probs: run `fit` first")
+        raise typer.Exit(1)
+    if not torch.cuda.is_available():
+        logger.error("ttfb needs an AMD GPU (--cuda): no HIP device is visible")
+        raise typer.Exit(1)
+    if progress_bar is None:
+        try:
+            from tqdm import tqdm as progress_bar
+        except Exception:  # pragma: no cover
+            progress_bar = None
+
+    data = m.data
+    mask = data.mask[: data.N].cpu().bool()
+    if not bool(mask.any()):
+        logger.error("ttfb: no on-target AOI is selected by the data mask")
+        raise typer.Exit(1)
+    p_specific = m.params["p_specific"][: data.N].float()
+    z = (p_specific > 0.5).float() if binary else p_specific
+    r_type = "binary" if binary else "probabilistic"
+    Tmax = data.F
+    try:
+        dev = torch.device("cuda")
+        for c in range(data.C):
+            logger.info(f"Channel #{c} ({data.channels[c]})")
+            z_masked = z[:, :, c][mask]
+            sdx = torch.argsort(time_to_first_binding(z_masked), descending=True)
+
+            p_bound = m.params["z_probs"][: data.N, :, c, 1][mask].float().to(dev)
+            tau = ttfb_sample(p_bound, num_samples, seed=c)
+            tau_host = tau.cpu()
+            pd.DataFrame(data=tau_host.numpy()).to_csv(cd / f"{m.name}_ttfb-data-points-channel{c}.csv")
+            logger.info(f"Saved time-to-first-binding values in {m.name}_ttfb-data-points-channel{c}.csv file")
+
+            fit = ttfb_fit(tau, Tmax, lr=5e-3, n_steps=num_iter, progress_bar=progress_bar)
+            results = pd.DataFrame(columns=["Mean", "95% LL", "95% UL"], dtype=float)
+            for name in ("ka", "kns", "Af"):
+                values = fit[name].squeeze(-1).cpu()
+                ll, ul = hpdi(values, 0.95)
+                results.loc[name] = [values.mean().item(), ll.item(), ul.item()]
+            results.to_csv(cd / f"{m.name}_ttfb-params-channel{c}.csv")
+            logger.info(f"Saved fit parameters in {m.name}_ttfb-params-channel{c}.csv file")
+
+            fb = fraction_bound(tau_host, Tmax)
+            fb_ll, fb_ul = hpdi_columns(fb, 0.95)
+            fb_mean = fb.mean(0)
+            best_fit = fraction_bound_fit(tau_host, Tmax, results.loc["ka", "Mean"], results.loc["kns", "Mean"],
+                                          results.loc["Af", "Mean"])
+            pd.DataFrame(data={"time": torch.arange(Tmax).numpy(), "best fit": best_fit.numpy(),
+                               "fraction bound mean": fb_mean.numpy(), "fraction bound 95% ll": fb_ll.numpy(),
+                               "fraction bound 95% ul": fb_ul.numpy()}).to_csv(
+                cd / f"{m.name}_ttfb-fraction-bound-channel{c}.csv")
+            logger.info(f"Saved fit data in {m.name}_ttfb-fraction-bound-channel{c}.csv file")
+            _ttfb_plots(cd, m.name, c, z_masked.cpu(), sdx.cpu(), r_type, Tmax, fb_mean.numpy(), fb_ll.numpy(),
+                        fb_ul.numpy(), best_fit.numpy(), logger)
+    except HipExtensionError:
+        logger.exception("ttfb failed: it needs an AMD GPU (--cuda) and the built HIP library")
+        raise typer.Exit(1)
 
 
 @app.command()

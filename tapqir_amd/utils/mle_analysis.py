@@ -1,0 +1,126 @@
+"""
+Time-to-first-binding analysis on the HIP device (tapqir/utils/mle_analysis.py:11-105 and the ``ttfb`` command,
+tapqir/main.py:926-1147):
+
+* ``ttfb_sample``: posterior samples of the first-binding frame of each AOI (``tq_ttfb_sample``);
+* ``ttfb_fit``: one maximum-likelihood fit of the censored two-exponential model (Friedman & Gelles 2015) per sample,
+  ``train(ttfb_model, ttfb_guide, lr, n_steps)`` of the reference (``tq_ttfb_fit``);
+* ``fraction_bound`` / ``fraction_bound_fit``: the per-time statistics the command writes.
+
+There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
+"""
+
+import ctypes as C
+
+import torch
+
+from tapqir_amd import _lib
+from tapqir_amd.exceptions import HipExtensionError
+
+ADAM_BETAS = (0.9, 0.999)
+ADAM_EPS = 1e-8
+
+
+def _device_tensor(x, what):
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+        raise HipExtensionError(f"{what} runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    return x.detach().to(torch.float32).contiguous()
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def ttfb_sample(p_bound, num_samples, seed=0):
+    """``num_samples`` posterior draws of the first-binding frame of each AOI.
+
+    ``p_bound`` (N, F): q(z = 1) of each AOI-frame (``z_probs[..., c, 1]`` of the params file).  Returns ``tau``
+    (num_samples, N), float32 on the device: the first frame with z = 1 of each sampled raster, or F if there is none
+    -- ``time_to_first_binding(z_sample(num_samples))`` of the reference, drawn from the exact law of that index."""
+    p = _device_tensor(p_bound, "ttfb_sample")
+    if p.ndim != 2 or p.shape[0] < 1 or p.shape[1] < 1 or num_samples < 1:
+        raise ValueError(f"ttfb_sample: p_bound must be (N, F) with N, F >= 1 and num_samples >= 1, got {tuple(p.shape)}")
+    p = p.clamp(0.0, 1.0)
+    N, F = p.shape
+    L = torch.empty(N, F, dtype=torch.float64, device=p.device)
+    tau = torch.empty(num_samples, N, dtype=torch.float32, device=p.device)
+    a = _lib.TtfbSampleArgs(p=_lib.ptr(p), log_surv=_lib.ptr(L), tau=_lib.ptr(tau), N=N, F=F, S=int(num_samples),
+                            seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib.load().tq_ttfb_sample(C.byref(a), _stream(p.device)), "tq_ttfb_sample")
+    return tau
+
+
+def ttfb_init_state(S, device):
+    """Adam state of ``S`` fits at the reference's initial values (mle_analysis.py:50-64: ka = kns = 0.001, Af = 0.9,
+    stored unconstrained by pyro as log / logit, float32), zero moments."""
+    init = torch.tensor([0.001, 0.001, 0.9], dtype=torch.float32)
+    unc = torch.stack([init[0].log(), init[1].log(), init[2].logit()])
+    state = torch.zeros(S, _lib.TTFB_STATE, dtype=torch.float32)
+    state[:, :3] = unc
+    return state.to(device)
+
+
+def ttfb_fit_steps(state, data, Tmax, control=None, lr=5e-3, step0=0, n_steps=1, loss=None, stage_lds=True):
+    """One launch of ``tq_ttfb_fit``: Adam steps ``step0 + 1 .. step0 + n_steps`` of every fit, in place on ``state``
+    (S, 9).  ``loss`` (S,) receives the loss of the last step (before its update) if given."""
+    tau = _device_tensor(data, "ttfb_fit")
+    S, N = tau.shape
+    tauc = None if control is None else _device_tensor(control, "ttfb_fit")
+    if tauc is not None and tauc.shape[0] != S:
+        raise ValueError(f"ttfb_fit: control has {tauc.shape[0]} rows, data {S}")
+    a = _lib.TtfbFitArgs(tau=_lib.ptr(tau), tauc=_lib.ptr(tauc), state=_lib.ptr(state), loss=_lib.ptr(loss), S=S, N=N,
+                         Nc=0 if tauc is None else tauc.shape[1], step0=int(step0), n_steps=int(n_steps),
+                         stage_lds=1 if stage_lds else 0, Tmax=float(Tmax), lr=float(lr), beta1=ADAM_BETAS[0],
+                         beta2=ADAM_BETAS[1], eps=ADAM_EPS)
+    _lib.check(_lib.load().tq_ttfb_fit(C.byref(a), _stream(tau.device)), "tq_ttfb_fit")
+    return state
+
+
+def ttfb_fit(data, Tmax, control=None, lr=5e-3, n_steps=15000, progress_bar=None, chunk=1000, stage_lds=True):
+    """Maximum-likelihood fit of ka, kns, Af to every row of ``data`` (S, N) of first-binding times.
+
+    ``control`` (S, Nc): first-binding times at control locations, or None.  Runs ``n_steps`` Adam steps (lr, betas
+    (0.9, 0.999), eps 1e-8) in launches of ``chunk`` steps; the result does not depend on ``chunk``.  Returns
+    ``{"ka", "kns", "Af"}``, each (S, 1) float32 on the device, and ``"loss"`` (S,): the loss of the last step."""
+    tau = _device_tensor(data, "ttfb_fit")
+    if tau.ndim != 2:
+        raise ValueError(f"ttfb_fit: data must be (S, N), got {tuple(tau.shape)}")
+    S = tau.shape[0]
+    state = ttfb_init_state(S, tau.device)
+    loss = torch.full((S,), float("nan"), dtype=torch.float32, device=tau.device)
+    starts = range(0, n_steps, max(1, int(chunk)))
+    for step0 in (progress_bar(starts) if progress_bar is not None else starts):
+        ttfb_fit_steps(state, tau, Tmax, control, lr, step0, min(chunk, n_steps - step0), loss, stage_lds)
+    return {"ka": state[:, 0:1].exp(), "kns": state[:, 1:2].exp(), "Af": torch.sigmoid(state[:, 2:3]), "loss": loss}
+
+
+def fraction_bound(data, Tmax):
+    """``fraction_bound[s, t] = mean_n(data[s, n] < t)`` for t = 0 .. Tmax - 1 (main.py:1073), from per-sample counts
+    and a cumulative sum instead of an S x N x T comparison."""
+    tau = data.to(torch.int64).clamp(0, Tmax)
+    S, N = tau.shape
+    counts = torch.zeros(S, Tmax + 1, dtype=torch.float64, device=tau.device)
+    counts.scatter_add_(1, tau, torch.ones_like(tau, dtype=torch.float64))
+    below = torch.cumsum(counts, dim=1) - counts  # below[s, t] = #{n : tau < t}
+    return (below[:, :Tmax] / N).to(torch.float32)
+
+
+def hpdi_columns(x, prob):
+    """Narrowest interval holding ``prob`` of the samples along dim 0, per column (pyro.ops.stats.hpdi(x, prob, dim=0))."""
+    xs = torch.sort(x, dim=0)[0]
+    n = xs.shape[0]
+    k = int(prob * n)
+    left, right = xs[: n - k], xs[k:]
+    i = torch.argmin(right - left, dim=0, keepdim=True)
+    return left.gather(0, i)[0], right.gather(0, i)[0]
+
+
+def fraction_bound_fit(data, Tmax, ka, kns, Af):
+    """Best-fit cumulative fraction bound at t = 0 .. Tmax - 1 (main.py:1079-1096): the share of AOIs bound at t = 0
+    plus the fitted two-exponential curve over the rest, averaged over samples."""
+    data = data.to(torch.float32)
+    N = data.shape[1]
+    nz = (data == 0).sum(1, keepdim=True).to(torch.float32)
+    t = torch.arange(Tmax, dtype=torch.float32, device=data.device)
+    curve = Af * (1 - torch.exp(-(ka + kns) * t)) + (1 - Af) * (1 - torch.exp(-kns * t))
+    return (nz / N + (1 - nz / N) * curve).mean(0)
