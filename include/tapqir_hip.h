@@ -478,6 +478,63 @@ typedef struct {
 int tq_ttfb_fit(const tq_ttfb_fit_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Dwell-time kinetics (`tapqir dwelltime`, tapqir/main.py:1150-1384).
+ *
+ * tq_dwell_sample replaces count_intervals(z_sample(num_samples)[:, mask, :, c]) (tapqir/utils/imscroll.py:14-110,
+ * tapqir/main.py:1222-1226) and the per-sample tables of bound_dwell_times / unbound_dwell_times (imscroll.py:113-141)
+ * without storing the S x N x F raster: frame f of (s, n) is z = (u < p[n, f]) with u the f-th uniform of Philox stream
+ * (seed, s, site 0xA01, n) (tq_math.h), and each row is walked into runs of equal labels as it is drawn.
+ *   mode TQ_DWELL_COUNT: counts[s, n] = number of intervals of the row; every interior interval (low_or_high 0 / 1) of
+ *     dwell time d adds 1 to hist_unbound[s, d] / hist_bound[s, d] (the caller zeroes both histograms).
+ *   mode TQ_DWELL_EMIT: the same draws again; the intervals of row (s, n) are written at offsets[s, n] (the exclusive scan
+ *     of counts in row-major (s, n) order) into the columns of `intervals` (TQ_DWELL_COLS, total) int32: posterior_sample,
+ *     aoi, start_frame, stop_frame, dwell_time, low_or_high, z -- count_intervals' rows in its torch.nonzero order.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const float* p;              /* (N, F) p(z = 1) of each AOI-frame, in [0, 1] */
+  int32_t* counts;             /* (S, N) out (COUNT) */
+  int32_t* hist_bound;         /* (S, F) in/out (COUNT): interior bound runs by dwell time */
+  int32_t* hist_unbound;       /* (S, F) in/out (COUNT): interior unbound runs by dwell time */
+  const int64_t* offsets;      /* (S, N) in (EMIT): exclusive scan of counts */
+  int32_t* intervals;          /* (TQ_DWELL_COLS, total) out (EMIT) */
+  int64_t total;               /* EMIT: number of intervals (the column stride); writes beyond it are dropped */
+  int32_t N, F, S;
+  int32_t mode;                /* TQ_DWELL_COUNT or TQ_DWELL_EMIT */
+  uint64_t seed;
+} tq_dwell_sample_args;
+#define TQ_DWELL_COUNT 0
+#define TQ_DWELL_EMIT 1
+#define TQ_DWELL_COLS 7
+
+int tq_dwell_sample(const tq_dwell_sample_args* a, void* stream);
+
+/* tq_dwell_fit replaces train(exp_model, exp_guide, lr, n_steps, data, K) of tapqir/utils/mle_analysis.py:11-35, 107-130
+ * (pyro SVI, TraceEnum_ELBO, optim.Adam): S independent maximum-likelihood fits of a K-exponential mixture, one per
+ * posterior sample.  Row s of the data is the CSR list (values[i], weights[i]), row_ptr[s] <= i < row_ptr[s + 1], of dwell
+ * times t > 0 with their multiplicities; its log-likelihood is sum_i w_i log sum_j A_j k_j exp(-k_j t_i).  Per row the
+ * unconstrained parameters are log k_j and softmax logits a_j (A = softmax(a)), and Adam (torch.optim.Adam semantics,
+ * float32) descends on the negative log-likelihood.  `state` carries parameters and moments between launches: a launch runs
+ * Adam steps step0 + 1 .. step0 + n_steps, so a fit in chunks is bitwise equal to one launch.  The caller initialises state
+ * (the reference: k = logspace(-K + 1, 0, K), A = 1 / K, zero moments).  One wave per row: a row of at most
+ * TQ_DWELL_LDS_PAIRS pairs is staged in LDS when stage_lds != 0, a longer one is read from L2 every step. */
+typedef struct {
+  const float* values;         /* (nnz) dwell times > 0 */
+  const float* weights;        /* (nnz) multiplicities */
+  const int64_t* row_ptr;      /* (S + 1) */
+  float* state;                /* (S, 6 K) in/out: log k[K], a[K], exp_avg[2K], exp_avg_sq[2K] */
+  float* loss;                 /* (S) out or NULL: loss (-log-likelihood) at the last step of the launch, before its update */
+  int32_t S, K;                /* 1 <= K <= TQ_DWELL_KMAX */
+  int32_t step0;               /* Adam steps completed before this launch */
+  int32_t n_steps;             /* Adam steps of this launch (>= 1) */
+  int32_t stage_lds;           /* 1: stage rows in LDS when they fit; 0: always read them from L2 */
+  double lr, beta1, beta2, eps;
+} tq_dwell_fit_args;
+#define TQ_DWELL_KMAX 8
+#define TQ_DWELL_LDS_PAIRS 2048
+
+int tq_dwell_fit(const tq_dwell_fit_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame
  * decode of GlimpseDataset.__getitem__ (168-186: big-endian int16 + 2^15) and the offset-region value counts

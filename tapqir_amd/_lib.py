@@ -156,6 +156,32 @@ TTFB_LDS_POINTS = 8192  # TQ_TTFB_LDS_POINTS
 TTFB_STATE = 9          # TQ_TTFB_STATE
 
 
+class DwellSampleArgs(C.Structure):
+    """``tq_dwell_sample_args`` (include/tapqir_hip.h)."""
+
+    _fields_ = [
+        ("p", C.c_void_p), ("counts", C.c_void_p), ("hist_bound", C.c_void_p), ("hist_unbound", C.c_void_p),
+        ("offsets", C.c_void_p), ("intervals", C.c_void_p), ("total", C.c_int64),
+        ("N", C.c_int32), ("F", C.c_int32), ("S", C.c_int32), ("mode", C.c_int32), ("seed", C.c_uint64),
+    ]
+
+
+class DwellFitArgs(C.Structure):
+    """``tq_dwell_fit_args`` (include/tapqir_hip.h)."""
+
+    _fields_ = [
+        ("values", C.c_void_p), ("weights", C.c_void_p), ("row_ptr", C.c_void_p), ("state", C.c_void_p),
+        ("loss", C.c_void_p), ("S", C.c_int32), ("K", C.c_int32), ("step0", C.c_int32), ("n_steps", C.c_int32),
+        ("stage_lds", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+    ]
+
+
+DWELL_COUNT, DWELL_EMIT = 0, 1  # TQ_DWELL_COUNT, TQ_DWELL_EMIT
+DWELL_COLS = 7                  # TQ_DWELL_COLS
+DWELL_KMAX = 8                  # TQ_DWELL_KMAX
+DWELL_LDS_PAIRS = 2048          # TQ_DWELL_LDS_PAIRS
+
+
 # every symbol include/tapqir_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "tq_version", "tq_last_error", "tq_ksmogn_log_prob", "tq_ksmogn_crosstalk_log_prob", "tq_crosstalk_param_count",
@@ -165,6 +191,7 @@ EXPORTS = [
     "tq_cosmos_globals_grad", "tq_cosmos_adam", "tq_cosmos_adam_catchup", "tq_cosmos_step", "tq_cosmos_step_overlapped", "tq_cosmos_tail", "tq_cosmos_tail_reduced", "tq_cosmos_sample_locals_range",
     "tq_cosmos_blk_floats", "tq_cosmos_minibatch_step", "tq_cosmos_pixel_unit",
     "tq_cosmos_probs", "tq_glimpse_extract", "tq_ksmogn_rsample", "tq_snr_chi2", "tq_ttfb_sample", "tq_ttfb_fit",
+    "tq_dwell_sample", "tq_dwell_fit",
 ]
 
 _lib = None
@@ -236,6 +263,10 @@ def load():
     lib.tq_ttfb_sample.restype = C.c_int
     lib.tq_ttfb_fit.argtypes = [C.POINTER(TtfbFitArgs), C.c_void_p]
     lib.tq_ttfb_fit.restype = C.c_int
+    lib.tq_dwell_sample.argtypes = [C.POINTER(DwellSampleArgs), C.c_void_p]
+    lib.tq_dwell_sample.restype = C.c_int
+    lib.tq_dwell_fit.argtypes = [C.POINTER(DwellFitArgs), C.c_void_p]
+    lib.tq_dwell_fit.restype = C.c_int
     _lib = lib
     return lib
 

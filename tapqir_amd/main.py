@@ -1,11 +1,12 @@
 """
-Command line of the MI355X build: the ``glimpse`` / ``fit`` / ``stats`` / ``ttfb`` / ``log`` commands of ``tapqir``
-(tapqir/main.py:66-318, 321-576, 873-884, 926-1147, 1387-1488) over the same workspace (``<cd>/.tapqir/config.yaml``, ``loginfo``, ``<model>_model.tpqr``,
+Command line of the MI355X build: the ``glimpse`` / ``fit`` / ``stats`` / ``ttfb`` / ``dwelltime`` / ``log`` commands
+of ``tapqir`` (tapqir/main.py:66-318, 321-576, 873-884, 926-1147, 1150-1384, 1387-1488) over the same workspace (``<cd>/.tapqir/config.yaml``, ``loginfo``, ``<model>_model.tpqr``,
 ``<model>_params.tpqr``, ``<model>_summary.csv``).  Options, defaults and exit codes (0 / 1) follow the reference;
 ``--cpu`` exits with 1 because the SVI step has no CPU path here.  ``glimpse`` takes its inputs from flags or from
 ``config.yaml`` (there are no interactive prompts).  ``ttfb`` (tapqir/main.py:926-1147) samples first-binding times and
-fits the association kinetics on the GPU from ``data.tpqr`` and ``<model>_params.tpqr``.  Plotting (``show``) and
-``dwelltime`` are outside the scope of this build.
+fits the association kinetics on the GPU from ``data.tpqr`` and ``<model>_params.tpqr``; ``dwelltime``
+(tapqir/main.py:1150-1384) samples bound and unbound intervals and fits the dissociation and association rates there too.
+Plotting (``show``) is outside the scope of this build.
 
     python -m tapqir_amd --cd <dir> fit --model cosmos --cuda --num-iter 0 --no-input
 """
@@ -376,6 +377,155 @@ def ttfb(
                         fb_ul.numpy(), best_fit.numpy(), logger)
     except HipExtensionError:
         logger.exception("ttfb failed: it needs an AMD GPU (--cuda) and the built HIP library")
+        raise typer.Exit(1)
+
+
+def _dwell_plot(cd, name, c, kind, map_dt, A, k, t_max, logger):
+    """Dwell-time histogram of the MAP raster with the fitted mixture (main.py:1266-1296, 1350-1381)."""
+    try:
+        import matplotlib as mpl
+
+        mpl.use("Agg")
+        import matplotlib.pyplot as plt
+    except Exception:
+        logger.warning("matplotlib is not available: the dwelltime plots are not drawn")
+        return
+    import numpy as np
+
+    mpl.rcParams["font.family"] = "sans-serif"
+    mpl.rcParams.update({"font.size": 8})
+    fig, ax = plt.subplots()
+    if map_dt.size:
+        ax.hist(map_dt[0], bins=100, density=True)
+    t = np.arange(t_max)
+    y = 0
+    for a_i, k_i in zip(A, k):
+        comp = a_i * k_i * np.exp(-k_i * t)
+        y = y + comp
+        ax.plot(comp, "k--")
+    ax.plot(y, "k-")
+    ax.set_xlabel("Time interval (frame)")
+    ax.set_ylabel("Density")
+    ax.set_title(f"{kind.capitalize()} dwell times channel {c}")
+    plt.savefig(cd / f"{name}_dwelltime-{kind}-histogram-channel{c}.png", dpi=600)
+    plt.close(fig)
+    logger.info(f"Saved {kind} dwell-time histograms in {name}_dwelltime-{kind}-histogram-channel{c}.png file")
+
+
+@app.command()
+def dwelltime(
+    model: avail_models = typer.Option("cosmos", help="Tapqir model"),
+    K: int = typer.Option(3, "-K", help="Number of exponentials"),
+    cuda: bool = typer.Option(_default("cuda"), "--cuda/--cpu", help="Run computations on GPU or CPU", show_default=False),
+    num_samples: int = typer.Option(500, "--num-samples", "-n", min=1, help="Number of posterior samples"),
+    num_iter: int = typer.Option(10000, "--num-iter", "-it", min=1, help="Number of iterations"),
+    no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
+    progress_bar=None,
+):
+    """
+    Dwell-time analysis (tapqir/main.py:1150-1384): the bound and unbound intervals of posterior samples of every
+    on-target AOI's z raster, and one K-exponential fit per sample of the interior bound (koff) and unbound (kon) dwell
+    times.  Needs ``data.tpqr`` and ``<model>_params.tpqr`` of a cosmos fit.
+
+    Unlike the reference, a sample without an interior interval of a kind is left out of that kind's fit and statistics
+    (the count is logged), and a kind that no sample has is skipped with a warning.
+    """
+    import pandas as pd
+    import torch
+
+    from tapqir_amd import _lib
+    from tapqir_amd.exceptions import HipExtensionError, TapqirFileNotFoundError
+    from tapqir_amd.models import models
+    from tapqir_amd.utils.imscroll import bound_dwell_times, count_intervals, unbound_dwell_times
+    from tapqir_amd.utils.mle_analysis import dwell_csr_from_hist, dwell_fit, dwell_intervals, dwell_sample
+    from tapqir_amd.utils.stats import hpdi
+
+    cd = DEFAULTS["cd"]
+    logger = logging.getLogger("tapqir")
+    if model.value != "cosmos":
+        # the reference has no z_sample for crosstalk, and cosmos+hmm is not part of this build
+        logger.error(f"dwelltime is not available for the {model.value} model (cosmos only)")
+        raise typer.Exit(1)
+    if not 1 <= K <= _lib.DWELL_KMAX:
+        logger.error(f"dwelltime: -K must be between 1 and {_lib.DWELL_KMAX}, got {K}")
+        raise typer.Exit(1)
+    if not cuda:
+        logger.error("dwelltime runs on the AMD GPU only (--cuda): the sampler and the fits have no CPU path")
+        raise typer.Exit(1)
+    m = models[model.value](device="cpu", dtype="float")
+    try:
+        m.load(cd, data_only=False)
+    except TapqirFileNotFoundError as err:
+        logger.exception(f"Failed to load {err.name} file")
+        raise typer.Exit(1)
+    if "z_probs" not in m.params:
+        logger.error(f"{m.name}_params.tpqr has no z_probs: run `fit` first")
+        raise typer.Exit(1)
+    if not torch.cuda.is_available():
+        logger.error("dwelltime needs an AMD GPU (--cuda): no HIP device is visible")
+        raise typer.Exit(1)
+    if progress_bar is None:
+        try:
+            from tqdm import tqdm as progress_bar
+        except Exception:  # pragma: no cover
+            progress_bar = None
+    try:
+        from scipy.io import savemat
+    except Exception:
+        savemat = None
+
+    data = m.data
+    mask = data.mask[: data.N].cpu().bool()
+    if not bool(mask.any()):
+        logger.error("dwelltime: no on-target AOI is selected by the data mask")
+        raise typer.Exit(1)
+    z_map = m.params["z_map"][: data.N] if "z_map" in m.params else None
+    kinds = (("bound", "koff", "Off-rate", bound_dwell_times), ("unbound", "kon", "On-rate", unbound_dwell_times))
+    try:
+        dev = torch.device("cuda")
+        for c in range(data.C):
+            logger.info(f"Channel #{c} ({data.channels[c]})")
+            p_bound = m.params["z_probs"][: data.N, :, c, 1][mask].float().to(dev)
+            sample = dwell_sample(p_bound, num_samples, seed=c)
+            intervals = dwell_intervals(p_bound, num_samples, seed=c, sample=sample)
+            intervals.to_pickle(cd / f"{m.name}_dwelltime-intervals-channel{c}.pkl")
+            logger.info(f"Saved time intervals in {m.name}_dwelltime-intervals-channel{c}.pkl file")
+            if savemat is not None:
+                savemat(cd / f"{m.name}_dwelltime-intervals-channel{c}.mat", intervals.to_dict("list"))
+                logger.info(f"Saved time intervals in {m.name}_dwelltime-intervals-channel{c}.mat file")
+            else:
+                logger.info("scipy is not available: the .mat file of the intervals is not written")
+
+            for kind, rate, title, host_dwell_times in kinds:
+                logger.info(f"{title} calculation ...")
+                hist = sample[f"hist_{kind}"]
+                keep = hist.sum(1) > 0
+                n_out = int((~keep).sum())
+                if n_out == hist.shape[0]:
+                    logger.warning(f"dwelltime: no posterior sample has an interior {kind} interval: {rate} is not fitted")
+                    continue
+                if n_out:
+                    logger.info(f"{n_out} of {hist.shape[0]} posterior samples have no interior {kind} interval and "
+                                f"are left out of the {rate} fit")
+                hist = hist[keep]
+                fit = dwell_fit(dwell_csr_from_hist(hist), K, lr=5e-3, n_steps=num_iter, progress_bar=progress_bar)
+                results = pd.DataFrame(columns=["Mean", "95% LL", "95% UL"], dtype=float)
+                A_mean, k_mean = [], []
+                for i in range(K):
+                    for label, values in ((f"A{i}", fit["A"][:, i].cpu()), (f"{rate}{i}", fit["k"][:, i].cpu())):
+                        ll, ul = hpdi(values, 0.95)
+                        results.loc[label] = [values.mean().item(), ll.item(), ul.item()]
+                    A_mean.append(results.loc[f"A{i}", "Mean"])
+                    k_mean.append(results.loc[f"{rate}{i}", "Mean"])
+                results.to_csv(cd / f"{m.name}_dwelltime-{rate}-channel{c}.csv")
+                logger.info(f"Saved {title.lower()} parameters in {m.name}_dwelltime-{rate}-channel{c}.csv file")
+
+                t_max = int(torch.nonzero(hist.sum(0)).max().item())  # the largest sampled dwell time
+                map_dt = (host_dwell_times(count_intervals(z_map[None, mask, :, c].cpu().numpy()))
+                          if z_map is not None else torch.zeros(0).numpy())
+                _dwell_plot(cd, m.name, c, kind, map_dt, A_mean, k_mean, t_max, logger)
+    except HipExtensionError:
+        logger.exception("dwelltime failed: it needs an AMD GPU (--cuda) and the built HIP library")
         raise typer.Exit(1)
 
 

@@ -1,11 +1,15 @@
 """
-Time-to-first-binding analysis on the HIP device (tapqir/utils/mle_analysis.py:11-105 and the ``ttfb`` command,
-tapqir/main.py:926-1147):
+Kinetics analysis on the HIP device (tapqir/utils/mle_analysis.py and the ``ttfb`` / ``dwelltime`` commands,
+tapqir/main.py:926-1384):
 
 * ``ttfb_sample``: posterior samples of the first-binding frame of each AOI (``tq_ttfb_sample``);
 * ``ttfb_fit``: one maximum-likelihood fit of the censored two-exponential model (Friedman & Gelles 2015) per sample,
   ``train(ttfb_model, ttfb_guide, lr, n_steps)`` of the reference (``tq_ttfb_fit``);
-* ``fraction_bound`` / ``fraction_bound_fit``: the per-time statistics the command writes.
+* ``fraction_bound`` / ``fraction_bound_fit``: the per-time statistics the command writes;
+* ``dwell_sample`` / ``dwell_intervals``: interior dwell-time histograms and the interval table of posterior rasters
+  drawn and walked on the device (``count_intervals(z_sample)`` of the ``dwelltime`` command, ``tq_dwell_sample``);
+* ``dwell_fit``: one maximum-likelihood fit of the K-exponential mixture per sample, ``train(exp_model, exp_guide, lr,
+  n_steps, data, K)`` of the reference (``tq_dwell_fit``).
 
 There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
 """
@@ -124,3 +128,143 @@ def fraction_bound_fit(data, Tmax, ka, kns, Af):
     t = torch.arange(Tmax, dtype=torch.float32, device=data.device)
     curve = Af * (1 - torch.exp(-(ka + kns) * t)) + (1 - Af) * (1 - torch.exp(-kns * t))
     return (nz / N + (1 - nz / N) * curve).mean(0)
+
+
+# ---- dwell times (`dwelltime`, tapqir/main.py:1150-1384) ---------------------------------------------------------------
+def dwell_sample(p_bound, num_samples, seed=0):
+    """Launch A of the interval sampler: ``num_samples`` posterior rasters of each AOI, drawn and walked on the device.
+
+    ``p_bound`` (N, F): q(z = 1) of each AOI-frame.  Returns ``{"hist_bound", "hist_unbound"}``, (num_samples, F) int32:
+    the number of interior bound / unbound runs of each dwell time per sample, and ``"counts"`` (num_samples, N) int32:
+    the number of intervals (of any kind) of each sampled row.  Nothing of size S x N x F is stored."""
+    p = _device_tensor(p_bound, "dwell_sample")
+    if p.ndim != 2 or p.shape[0] < 1 or p.shape[1] < 1 or num_samples < 1:
+        raise ValueError(f"dwell_sample: p_bound must be (N, F) with N, F >= 1 and num_samples >= 1, got {tuple(p.shape)}")
+    p = p.clamp(0.0, 1.0)
+    N, F = p.shape
+    S = int(num_samples)
+    counts = torch.empty(S, N, dtype=torch.int32, device=p.device)
+    hb = torch.zeros(S, F, dtype=torch.int32, device=p.device)
+    hu = torch.zeros(S, F, dtype=torch.int32, device=p.device)
+    a = _lib.DwellSampleArgs(p=_lib.ptr(p), counts=_lib.ptr(counts), hist_bound=_lib.ptr(hb), hist_unbound=_lib.ptr(hu),
+                             N=N, F=F, S=S, mode=_lib.DWELL_COUNT, seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib.load().tq_dwell_sample(C.byref(a), _stream(p.device)), "tq_dwell_sample")
+    return {"hist_bound": hb, "hist_unbound": hu, "counts": counts}
+
+
+def dwell_intervals(p_bound, num_samples, seed=0, sample=None):
+    """The interval table of ``num_samples`` posterior rasters (``count_intervals(z_sample)`` of the reference): launch A
+    (or its result ``sample`` from ``dwell_sample`` with the same arguments), an exclusive scan of the row counts, and
+    launch B, which draws the same bits again and writes every row's intervals at its offset.  Returns a DataFrame with
+    the columns of ``tapqir_amd.utils.imscroll.INTERVAL_COLUMNS``, int64, in (sample, AOI, frame) order."""
+    import pandas as pd
+
+    from tapqir_amd.utils.imscroll import INTERVAL_COLUMNS
+
+    p = _device_tensor(p_bound, "dwell_intervals").clamp(0.0, 1.0)
+    if sample is None:
+        sample = dwell_sample(p, num_samples, seed)
+    counts = sample["counts"]
+    N, F = p.shape
+    S = counts.shape[0]
+    csum = torch.cumsum(counts.reshape(-1).to(torch.int64), 0)
+    offsets = (csum - counts.reshape(-1)).contiguous()
+    total = int(csum[-1].item())
+    cols = torch.empty(_lib.DWELL_COLS, max(total, 1), dtype=torch.int32, device=p.device)
+    a = _lib.DwellSampleArgs(p=_lib.ptr(p), offsets=_lib.ptr(offsets), intervals=_lib.ptr(cols), total=total, N=N, F=F,
+                             S=S, mode=_lib.DWELL_EMIT, seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib.load().tq_dwell_sample(C.byref(a), _stream(p.device)), "tq_dwell_sample")
+    host = cols[:, :total].to(torch.int64).cpu().numpy()
+    return pd.DataFrame({name: host[i] for i, name in enumerate(INTERVAL_COLUMNS)})
+
+
+def dwell_csr_from_hist(hist):
+    """(values, weights, row_ptr) of the nonzero bins of per-sample histograms ``hist`` (S, F): value = dwell time (the
+    bin index), weight = its count.  Bin 0 is ignored (a dwell time is at least one frame)."""
+    h = hist.to(torch.float32)
+    h = torch.cat([torch.zeros_like(h[:, :1]), h[:, 1:]], 1)
+    nz = h > 0
+    t = torch.arange(h.shape[1], dtype=torch.float32, device=h.device).expand_as(h)
+    return _csr(t[nz], h[nz], nz.sum(1))
+
+
+def dwell_csr_from_padded(data):
+    """(values, weights, row_ptr) of zero-padded per-sample dwell times ``data`` (S, M), the reference's ``exp_model``
+    input: the entries > 0, each with weight 1."""
+    nz = data > 0
+    vals = data[nz].to(torch.float32)
+    return _csr(vals, torch.ones_like(vals), nz.sum(1))
+
+
+def _csr(values, weights, row_len):
+    row_ptr = torch.zeros(row_len.shape[0] + 1, dtype=torch.int64, device=values.device)
+    row_ptr[1:] = torch.cumsum(row_len.to(torch.int64), 0)
+    if values.numel() == 0:  # keep valid pointers for an all-empty data set
+        values = torch.zeros(1, dtype=torch.float32, device=row_ptr.device)
+        weights = torch.zeros(1, dtype=torch.float32, device=row_ptr.device)
+    return values.contiguous(), weights.contiguous(), row_ptr
+
+
+def dwell_init_state(S, K, device):
+    """Adam state (S, 6K) of ``S`` fits at the reference's initial values (mle_analysis.py:108-116: k = logspace(-K + 1, 0,
+    K), A = ones, stored unconstrained by pyro through transform_to: log k, and softmax logits log 1 = 0, i.e. A = 1 / K;
+    float32), zero moments."""
+    state = torch.zeros(S, 6 * K, dtype=torch.float32)
+    state[:, :K] = torch.logspace(-K + 1, 0, K, dtype=torch.float32).log()
+    return state.to(device)
+
+
+def _check_K(K):
+    if not 1 <= int(K) <= _lib.DWELL_KMAX:
+        raise ValueError(f"dwell_fit: K must be in 1 .. {_lib.DWELL_KMAX}, got {K}")
+    return int(K)
+
+
+def dwell_fit_steps(state, csr, K, lr=5e-3, step0=0, n_steps=1, loss=None, stage_lds=True):
+    """One launch of ``tq_dwell_fit``: Adam steps ``step0 + 1 .. step0 + n_steps`` of every fit, in place on ``state``
+    (S, 6K).  ``csr`` = (values, weights, row_ptr) on the device; ``loss`` (S,) receives the loss of the last step."""
+    K = _check_K(K)
+    values, weights, row_ptr = csr
+    values = _device_tensor(values, "dwell_fit")
+    weights = _device_tensor(weights, "dwell_fit")
+    if not isinstance(row_ptr, torch.Tensor) or row_ptr.device.type != "cuda":
+        raise HipExtensionError("dwell_fit runs on the HIP device only (no CPU fallback): pass cuda tensors")
+    row_ptr = row_ptr.to(torch.int64).contiguous()
+    S = row_ptr.shape[0] - 1
+    if state.shape != (S, 6 * K) or state.dtype != torch.float32 or not state.is_contiguous():
+        raise ValueError(f"dwell_fit: state must be contiguous float32 ({S}, {6 * K}), got {tuple(state.shape)}")
+    a = _lib.DwellFitArgs(values=_lib.ptr(values), weights=_lib.ptr(weights), row_ptr=_lib.ptr(row_ptr),
+                          state=_lib.ptr(state), loss=_lib.ptr(loss), S=S, K=K, step0=int(step0), n_steps=int(n_steps),
+                          stage_lds=1 if stage_lds else 0, lr=float(lr), beta1=ADAM_BETAS[0], beta2=ADAM_BETAS[1],
+                          eps=ADAM_EPS)
+    _lib.check(_lib.load().tq_dwell_fit(C.byref(a), _stream(values.device)), "tq_dwell_fit")
+    return state
+
+
+def dwell_fit(data, K=3, lr=5e-3, n_steps=10000, chunk=1000, progress_bar=None, stage_lds=True):
+    """Maximum-likelihood fit of a K-exponential mixture to every posterior sample's dwell times (``train(exp_model,
+    exp_guide, lr, n_steps, data, K)`` of the reference).
+
+    ``data``: zero-padded dwell times (S, M) (entries > 0 count, as ``bound_dwell_times`` returns them), or a
+    ``(values, weights, row_ptr)`` CSR triple such as ``dwell_csr_from_hist(hist)``; cuda tensors either way.  Runs
+    ``n_steps`` Adam steps (lr, betas (0.9, 0.999), eps 1e-8) in launches of ``chunk`` steps; the result does not depend
+    on ``chunk``.  Returns ``{"k", "A"}``, each (S, K) float32 on the device, and ``"loss"`` (S,): the loss of the last
+    step.  A sample without data keeps its initial values."""
+    K = _check_K(K)
+    if isinstance(data, (tuple, list)):
+        csr = tuple(data)
+    else:
+        d = _device_tensor(data, "dwell_fit")
+        if d.ndim != 2:
+            raise ValueError(f"dwell_fit: data must be (S, M), got {tuple(d.shape)}")
+        csr = dwell_csr_from_padded(d)
+    if not isinstance(csr[2], torch.Tensor) or csr[2].device.type != "cuda":
+        raise HipExtensionError("dwell_fit runs on the HIP device only (no CPU fallback): pass cuda tensors")
+    S = csr[2].shape[0] - 1
+    dev = csr[2].device
+    state = dwell_init_state(S, K, dev)
+    loss = torch.full((S,), float("nan"), dtype=torch.float32, device=dev)
+    starts = range(0, n_steps, max(1, int(chunk)))
+    for step0 in (progress_bar(starts) if progress_bar is not None else starts):
+        dwell_fit_steps(state, csr, K, lr, step0, min(max(1, int(chunk)), n_steps - step0), loss, stage_lds)
+    return {"k": state[:, :K].exp(), "A": torch.softmax(state[:, K:2 * K], dim=1), "loss": loss}
