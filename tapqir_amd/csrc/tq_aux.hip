@@ -5,19 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tq_aux.h"
-
-void tq_set_error(const char* msg);
-
-static int aux_launch_status(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    tq_set_error(buf);
-    return TQ_ERR_LAUNCH;
-  }
-  return TQ_OK;
-}
+#include "tq_host.h"
 
 // one lane per pixel; consecutive lanes write consecutive pixels of the (B, P, P) output
 __global__ __launch_bounds__(256) void tq_rsample_kernel(const tq_rsample_args a, const int64_t total, const int npix) {
@@ -46,7 +34,7 @@ extern "C" int tq_ksmogn_rsample(const tq_rsample_args* a, void* stream) {
   const int npix = a->P * a->P;
   const int64_t total = a->B * npix;
   hipLaunchKernelGGL(tq_rsample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a, total, npix);
-  return aux_launch_status("tq_rsample_kernel");
+  return tq_launch_status("tq_rsample_kernel");
 }
 
 extern "C" int tq_snr_chi2(const tq_snr_args* a, void* stream) {
@@ -59,5 +47,5 @@ extern "C" int tq_snr_chi2(const tq_snr_args* a, void* stream) {
     return TQ_ERR_ARG;
   }
   hipLaunchKernelGGL(tq_snr_chi2_kernel, dim3((unsigned)((a->U + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a);
-  return aux_launch_status("tq_snr_chi2_kernel");
+  return tq_launch_status("tq_snr_chi2_kernel");
 }

@@ -13,8 +13,7 @@
 
 #include "tq_bodies.h"
 #include "tq_dpp.h"
-
-void tq_set_error(const char* msg);
+#include "tq_host.h"
 
 #define TQ_UNIT_BLOCK 256
 #define TQ_MAX_NGSUM (3 + 3 * TQ_MAXQ)  // >= 3 + 3*2 + 2*2 of the crosstalk model
@@ -22,7 +21,9 @@ void tq_set_error(const char* msg);
 // sum over the wave (every lane active), in every lane: DPP adds inside the four rows of 16 lanes, then the four row sums
 // read as scalars -- no LDS crossbar (six ds_bpermute per sum in the shuffle form; the fused pixel + per-unit kernel ends
 // every wave with 22 such sums)
-__device__ __forceinline__ float tq_wave_sum(float v) {
+// Deliberately not tq_fit_wave_sum (tq_fit.h): that one crosses the rows with two __shfl_xor through the LDS crossbar, this
+// one adds the four row sums read as scalars, (r0 + r16) + (r32 + r48); the step kernels' code is tuned around this form.
+__device__ __forceinline__ float tq_wave_sum_rows4(float v) {
   v = tq_group_sum16(v);
   const int b = __builtin_bit_cast(int, v);
   return (__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16))) +
@@ -234,7 +235,7 @@ __global__ __launch_bounds__(TQ_UNIT_BLOCK) void tq_unit_kernel(const tq_cosmos_
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
-      const float s = tq_wave_sum(part[j]);
+      const float s = tq_wave_sum_rows4(part[j]);
       if (lane == 0) s_part[wave][j] = s;
     }
   }
@@ -259,8 +260,8 @@ __global__ __launch_bounds__(256) void tq_aoi_kernel(const tq_cosmos_args a, con
     s1 += a.aoi_part[i];
     s2 += a.aoi_part[B + i];
   }
-  s1 = tq_wave_sum(s1);
-  s2 = tq_wave_sum(s2);
+  s1 = tq_wave_sum_rows4(s1);
+  s2 = tq_wave_sum_rows4(s2);
   if (lane == 0) {
     s_sum[wave][0] = s1;
     s_sum[wave][1] = s2;
@@ -306,7 +307,8 @@ __global__ __launch_bounds__(256) void tq_adam_catchup_kernel(const tq_cosmos_ar
 
 // single-GPU step: finish of the cross-unit sums + all global sites + total ELBO in ONE workgroup of 4 waves
 // (one wave per SIMD, so the fp64 site code keeps the full register file); sites are taken round-robin
-__device__ __forceinline__ double tq_wave_sum_d(double v) {
+// Deliberately not an xor butterfly like the sums of the fit kernels: a __shfl_down reduction, complete in lane 0 only.
+__device__ __forceinline__ double tq_wave_sum_d_lane0(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   return v;
@@ -351,7 +353,7 @@ __device__ __forceinline__ void tq_reduce_sums_body(const tq_cosmos_args& a, con
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
-      const double s = tq_wave_sum_d(acc[j]);
+      const double s = tq_wave_sum_d_lane0(acc[j]);
       if (lane == 0) s_w[wave][j] = s;
     }
   }
@@ -483,14 +485,14 @@ __global__ __launch_bounds__(TQ_UNIT_BLOCK) void tq_unit_rows_kernel(const tq_co
 #pragma unroll
   for (int j = 0; j < TQ_ROWS_GCOL; ++j) {
     if ((j % TQ_ROWS_AOICOL) < 2 * a.C) {
-      const float sum = tq_wave_sum(aoi[j]);
+      const float sum = tq_wave_sum_rows4(aoi[j]);
       if (lane == 0) s_part[wave][j] = sum;
     }
   }
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
-      const float sum = tq_wave_sum(part[j]);
+      const float sum = tq_wave_sum_rows4(part[j]);
       if (lane == 0) s_part[wave][TQ_ROWS_GCOL + j] = sum;
     }
   }
@@ -550,7 +552,7 @@ __device__ __forceinline__ int tq_group_reduce_rows(const tq_cosmos_args& a, con
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
-      const double sum = tq_wave_sum_d((double)col[j]);
+      const double sum = tq_wave_sum_d_lane0((double)col[j]);
       if (lane == 0) __hip_atomic_store(&((double*)grow)[j], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
@@ -565,7 +567,7 @@ __device__ __forceinline__ int tq_group_reduce_rows(const tq_cosmos_args& a, con
     for (int j = 0; j < 2 * TQ_MAXQ; ++j) {
       if (j < 2 * a.C) {
         const float v = (n0 == n) ? s0[j] : ((n0 + 1 == n) ? s1[j] : 0.0f);
-        const float sum = tq_wave_sum(v);
+        const float sum = tq_wave_sum_rows4(v);
         if (lane == 0) __hip_atomic_store(&out[j], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
@@ -617,13 +619,13 @@ __global__ __launch_bounds__(64, 2) void tq_pixel_unit_kernel(const tq_ksmogn_ar
 #pragma unroll
   for (int j = 0; j < TQ_ROWS_GCOL; ++j) {
     const bool used = (j % TQ_ROWS_AOICOL) < 2 * a.C;
-    const float sum = used ? tq_wave_sum(aoi[j]) : 0.0f;
+    const float sum = used ? tq_wave_sum_rows4(aoi[j]) : 0.0f;
     if (threadIdx.x == 0) row[j] = sum;
   }
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
-      const float sum = tq_wave_sum(part[j]);
+      const float sum = tq_wave_sum_rows4(part[j]);
       if (threadIdx.x == 0) row[TQ_ROWS_GCOL + j] = sum;
     }
   }
@@ -750,7 +752,7 @@ __device__ __forceinline__ void tq_rows_reduce_globals_body(const tq_cosmos_args
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
-      const double s = tq_wave_sum_d(acc[j]);
+      const double s = tq_wave_sum_d_lane0(acc[j]);
       if (lane == 0) s_w[wave][j] = s;
     }
   }
@@ -829,7 +831,7 @@ __device__ __forceinline__ bool tq_groups_sums_body(const tq_cosmos_args& a, dou
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
-      const double s = tq_wave_sum_d(acc[j]);
+      const double s = tq_wave_sum_d_lane0(acc[j]);
       if (lane == 0) s_w[wave][j] = s;
     }
   }
@@ -1441,14 +1443,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
 #pragma unroll
   for (int j = 0; j < TQ_ROWS_GCOL; ++j) {
     if ((j % TQ_ROWS_AOICOL) < 2 * a.C) {
-      const float sum = tq_wave_sum(aoi[j]);
+      const float sum = tq_wave_sum_rows4(aoi[j]);
       if (lane == 0) s_part[wave][j] = sum;
     }
   }
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
-      const float sum = tq_wave_sum(part[j]);
+      const float sum = tq_wave_sum_rows4(part[j]);
       if (lane == 0) s_part[wave][TQ_ROWS_GCOL + j] = sum;
     }
   }
@@ -1465,17 +1467,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
 
 
 // ---------------------------------------------------------------------------------------------------------
-static int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    tq_set_error(buf);
-    return TQ_ERR_LAUNCH;
-  }
-  return TQ_OK;
-}
-
 static int check_args(const tq_cosmos_args* a, const char* who) {
   if (!a || !a->params || !a->globals || !a->gbase) {
     tq_set_error("tq_cosmos_*: NULL args/params/globals/gbase");
@@ -1515,7 +1506,7 @@ extern "C" int64_t tq_crosstalk_param_count(int32_t Nt, int32_t F, int32_t C, in
 extern "C" int tq_cosmos_sample_globals(const tq_cosmos_args* a, void* stream) {
   if (int rc = check_args(a, "sample_globals")) return rc;
   hipLaunchKernelGGL(tq_sample_globals_kernel, dim3(tq_num_gsites(*a)), dim3(64), 0, (hipStream_t)stream, *a);
-  return check_launch("tq_sample_globals_kernel");
+  return tq_launch_status("tq_sample_globals_kernel");
 }
 
 extern "C" int tq_cosmos_sample_locals(const tq_cosmos_args* a, void* stream) {
@@ -1527,7 +1518,7 @@ extern "C" int tq_cosmos_sample_locals(const tq_cosmos_args* a, void* stream) {
   const int64_t B = tq_batch_units(*a);
   hipLaunchKernelGGL(tq_sample_locals_kernel, dim3((unsigned)((B + 255) / 256), (unsigned)(1 + 4 * a->K)), dim3(256), 0,
                      (hipStream_t)stream, *a, B, 0);
-  return check_launch("tq_sample_locals_kernel");
+  return tq_launch_status("tq_sample_locals_kernel");
 }
 
 // argument block of the likelihood kernel of a cosmos step
@@ -1607,7 +1598,7 @@ static int launch_pixel_unit(const tq_cosmos_args* a, void* stream) {
     if (a->P == 14) hipLaunchKernelGGL((tq_pixel_unit_kernel<2, 14>), grid, block, 0, st, k, *a, B);
     else hipLaunchKernelGGL((tq_pixel_unit_kernel<2, 20>), grid, block, 0, st, k, *a, B);
   }
-  return check_launch("tq_pixel_unit_kernel");
+  return tq_launch_status("tq_pixel_unit_kernel");
 }
 
 // per-AOI sites + gsum of a step with rows, for callers that all-reduce gsum before the global sites (tq_group_sums_kernel)
@@ -1617,7 +1608,7 @@ static int launch_rows_sums(const tq_cosmos_args* a, hipStream_t st) {
     return TQ_ERR_ARG;
   }
   hipLaunchKernelGGL(tq_group_sums_kernel, dim3((unsigned)tq_grp_count(tq_batch_units(*a))), dim3(256), 0, st, *a);
-  return check_launch("tq_group_sums_kernel");
+  return tq_launch_status("tq_group_sums_kernel");
 }
 
 // rows: AOI-aligned per-unit kernel whose tail also finishes the per-AOI sites (tq_unit_rows_kernel; full-batch steps
@@ -1652,7 +1643,7 @@ static int elbo_grads_impl(const tq_cosmos_args* a, void* stream, bool finish_su
       case 3: hipLaunchKernelGGL((tq_unit_rows_kernel<3>), grid, block, 0, st, *a, B); break;
       default: hipLaunchKernelGGL((tq_unit_rows_kernel<4>), grid, block, 0, st, *a, B); break;
     }
-    if (int rc = check_launch("tq_unit_rows_kernel")) return rc;
+    if (int rc = tq_launch_status("tq_unit_rows_kernel")) return rc;
     return finish_sums ? launch_rows_sums(a, st) : TQ_OK;
   }
   const int64_t nblk = tq_cosmos_nblk(B);
@@ -1663,14 +1654,14 @@ static int elbo_grads_impl(const tq_cosmos_args* a, void* stream, bool finish_su
     case 3: hipLaunchKernelGGL((tq_unit_kernel<3>), grid, block, 0, st, *a, B); break;
     default: hipLaunchKernelGGL((tq_unit_kernel<4>), grid, block, 0, st, *a, B); break;
   }
-  if (int rc = check_launch("tq_unit_kernel")) return rc;
+  if (int rc = tq_launch_status("tq_unit_kernel")) return rc;
   // 3. per-AOI sites
   hipLaunchKernelGGL(tq_aoi_kernel, dim3((unsigned)(a->nb * a->C)), dim3(256), 0, st, *a, B);
-  if (int rc = check_launch("tq_aoi_kernel")) return rc;
+  if (int rc = tq_launch_status("tq_aoi_kernel")) return rc;
   // 4. cross-unit sums
   if (!finish_sums) return TQ_OK;
   hipLaunchKernelGGL(tq_reduce_kernel, dim3(1), dim3(256), 0, st, *a, nblk, B);
-  return check_launch("tq_reduce_kernel");
+  return tq_launch_status("tq_reduce_kernel");
 }
 
 extern "C" int tq_cosmos_elbo_grads(const tq_cosmos_args* a, void* stream) {
@@ -1698,9 +1689,9 @@ extern "C" int tq_cosmos_globals_grad(const tq_cosmos_args* a, void* stream) {
   // caller allocates TQ_GSUM_LEN doubles)
   double* site_elbo = a->gsum + tq_num_gsum(*a);
   hipLaunchKernelGGL(tq_globals_grad_kernel, dim3(tq_num_gsites(*a)), dim3(64), 0, (hipStream_t)stream, *a, site_elbo);
-  if (int rc = check_launch("tq_globals_grad_kernel")) return rc;
+  if (int rc = tq_launch_status("tq_globals_grad_kernel")) return rc;
   hipLaunchKernelGGL(tq_elbo_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *a, (const double*)site_elbo);
-  return check_launch("tq_elbo_finish_kernel");
+  return tq_launch_status("tq_elbo_finish_kernel");
 }
 
 extern "C" int tq_cosmos_adam(const tq_cosmos_args* a, void* stream) {
@@ -1715,7 +1706,7 @@ extern "C" int tq_cosmos_adam(const tq_cosmos_args* a, void* stream) {
   int64_t nblk = (total - first + 255) / 256;
   if (nblk > 256 * 16) nblk = 256 * 16;  // grid-stride: 16 workgroups per CU
   hipLaunchKernelGGL(tq_adam_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, *a, first, total);
-  return check_launch("tq_adam_kernel");
+  return tq_launch_status("tq_adam_kernel");
 }
 
 extern "C" int tq_cosmos_adam_catchup(const tq_cosmos_args* a, int32_t all_units, void* stream) {
@@ -1727,7 +1718,7 @@ extern "C" int tq_cosmos_adam_catchup(const tq_cosmos_args* a, int32_t all_units
   const int64_t n = all_units ? tq_num_units(*a) : tq_batch_units(*a);
   const dim3 grid((unsigned)((n + 255) / 256), (unsigned)TQ_NLOCAL(a->K));
   hipLaunchKernelGGL(tq_adam_catchup_kernel, grid, dim3(256), 0, (hipStream_t)stream, *a, n, (int)all_units);
-  return check_launch("tq_adam_catchup_kernel");
+  return tq_launch_status("tq_adam_catchup_kernel");
 }
 
 // ---- whole steps ---------------------------------------------------------------------------------------------
@@ -1739,11 +1730,11 @@ static int launch_reduce_globals(const tq_cosmos_args* a, hipStream_t st) {
   // no all-reduce on this path: sums, (per-AOI sites,) global sites and the total ELBO finish in one launch
   if (a->tail_kind == TQ_TAIL_ROWS16 || tq_rows_layout(*a)) {
     hipLaunchKernelGGL(tq_rows_reduce_globals_kernel, dim3(1), dim3(256), 0, st, *a, a->tail_kind == TQ_TAIL_ROWS16 ? tq_mb_upr(*a) : TQ_UNIT_BLOCK);
-    return check_launch("tq_rows_reduce_globals_kernel");
+    return tq_launch_status("tq_rows_reduce_globals_kernel");
   }
   const int64_t B = tq_batch_units(*a);
   hipLaunchKernelGGL(tq_reduce_globals_kernel, dim3(1), dim3(256), 0, st, *a, tq_cosmos_nblk(B), B);
-  return check_launch("tq_reduce_globals_kernel");
+  return tq_launch_status("tq_reduce_globals_kernel");
 }
 
 extern "C" int tq_cosmos_tail(const tq_cosmos_args* a, void* stream) {
@@ -1771,7 +1762,7 @@ extern "C" int tq_cosmos_tail_reduced(const tq_cosmos_args* a, const tq_cosmos_a
     return TQ_ERR_ARG;
   }
   hipLaunchKernelGGL(tq_tail_reduced_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *a, next ? *next : *a, next ? 1 : 0);
-  if (int rc = check_launch("tq_tail_reduced_kernel")) return rc;
+  if (int rc = tq_launch_status("tq_tail_reduced_kernel")) return rc;
   return a->fuse_adam ? TQ_OK : tq_cosmos_adam(a, stream);
 }
 
@@ -1810,7 +1801,7 @@ extern "C" int tq_cosmos_step_overlapped(const tq_cosmos_args* a, const tq_cosmo
   if (code == 3 && prev->sync && tq_grp_count(tq_batch_units(*prev)) + 1 <= (B + 255) / 256) code = 6;
   hipLaunchKernelGGL(tq_sample_locals_tail_kernel, dim3((unsigned)((B + 255) / 256), (unsigned)(2 + 4 * a->K)), dim3(256), 0,
                      (hipStream_t)stream, *a, prev ? *prev : *a, code, B, 0);
-  if (int rc = check_launch("tq_sample_locals_tail_kernel")) return rc;
+  if (int rc = tq_launch_status("tq_sample_locals_tail_kernel")) return rc;
   return elbo_grads_impl(a, stream, false, tq_rows_layout(*a));
 }
 
@@ -1875,7 +1866,7 @@ extern "C" int tq_cosmos_minibatch_step(const tq_cosmos_args* a, const tq_cosmos
     default: TQ_MB_LAUNCH(4) break;
   }
 #undef TQ_MB_LAUNCH
-  return check_launch("tq_minibatch_kernel");
+  return tq_launch_status("tq_minibatch_kernel");
 }
 
 // AOI-sharded pipeline: the local sites [site_begin, site_begin + site_count) of `a`; with `prev` (whose gsum the caller
@@ -1900,11 +1891,11 @@ extern "C" int tq_cosmos_sample_locals_range(const tq_cosmos_args* a, int32_t si
   if (prev) {
     hipLaunchKernelGGL(tq_sample_locals_tail_kernel, dim3(gx, (unsigned)(site_count + 1)), dim3(256), 0, (hipStream_t)stream, *a,
                        *prev, 2, B, (int)site_begin);
-    return check_launch("tq_sample_locals_tail_kernel");
+    return tq_launch_status("tq_sample_locals_tail_kernel");
   }
   hipLaunchKernelGGL(tq_sample_locals_kernel, dim3(gx, (unsigned)site_count), dim3(256), 0, (hipStream_t)stream, *a, B,
                      (int)site_begin);
-  return check_launch("tq_sample_locals_kernel");
+  return tq_launch_status("tq_sample_locals_kernel");
 }
 
 // ---- posterior read-out (cosmos.compute_probs) -------------------------------------------------------------
@@ -1930,7 +1921,7 @@ extern "C" int tq_cosmos_probs(const tq_probs_args* a, void* stream) {
   }
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(tq_probs_globals_kernel, dim3(TQ_NGSITES(a->C), a->particles), dim3(64), 0, st, *a);
-  if (int rc = check_launch("tq_probs_globals_kernel")) return rc;
+  if (int rc = tq_launch_status("tq_probs_globals_kernel")) return rc;
   const int64_t U = (int64_t)a->Nt * a->F * a->C;
   const dim3 grid((unsigned)((U + 255) / 256)), block(256);
   switch (a->K) {
@@ -1939,5 +1930,5 @@ extern "C" int tq_cosmos_probs(const tq_probs_args* a, void* stream) {
     case 3: hipLaunchKernelGGL((tq_probs_kernel<3>), grid, block, 0, st, *a, U); break;
     default: hipLaunchKernelGGL((tq_probs_kernel<4>), grid, block, 0, st, *a, U); break;
   }
-  return check_launch("tq_probs_kernel");
+  return tq_launch_status("tq_probs_kernel");
 }

@@ -5,7 +5,8 @@
 //     one independent 2K-parameter fit per posterior sample.
 // The __global__ wrappers are in tq_dwell.hip; the test suite runs the same bodies from a g++ build.
 #pragma once
-#include "tq_kinetics.h"  // tq_ttfb_adam, tq_ttfb_pow: the same torch Adam arithmetic
+#include "../../include/tapqir_hip.h"
+#include "tq_fit.h"
 
 #define TQ_DWELL_SITE 0xA01u  // Philox site id of the raster uniforms: stream (seed, step = s, site, elem = n)
 

@@ -2,21 +2,8 @@
 // emit launches) and the batched K-exponential mixture MLE, one wave per posterior sample.
 #include <hip/hip_runtime.h>
 
-#include "tq_dpp.h"
 #include "tq_dwell.h"
-
-void tq_set_error(const char* msg);
-
-static int dwell_launch_status(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    tq_set_error(buf);
-    return TQ_ERR_LAUNCH;
-  }
-  return TQ_OK;
-}
+#include "tq_host.h"
 
 // ---- sampler: one wave per (AOI n, block of 64 samples), one lane per sample ---------------------------------------------
 // Every lane draws its own row (s, n) frame by frame and walks it in registers; the row of p is staged 64 frames at a time
@@ -108,16 +95,10 @@ extern "C" int tq_dwell_sample(const tq_dwell_sample_args* a, void* stream) {
     if (a->total == 0) return TQ_OK;
     hipLaunchKernelGGL(tq_dwell_sample_kernel<true>, grid, dim3(64), 0, (hipStream_t)stream, *a);
   }
-  return dwell_launch_status("tq_dwell_sample_kernel");
+  return tq_launch_status("tq_dwell_sample_kernel");
 }
 
 // ---- batched MLE: one wave (= one workgroup) per posterior sample -----------------------------------------------------
-__device__ __forceinline__ float dwell_wave_sum(float v) {
-  // the same bits in every lane (each DPP / shuffle step adds a pair in either order), then made wave-uniform
-  v = tq_group_sum<64>(v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
 // A row of at most TQ_DWELL_LDS_PAIRS pairs is staged in LDS once per launch (when stage_lds) and every step reads it
 // there; a longer row, or stage_lds = 0, is read from global memory (L2) every step.
 template <int K>
@@ -135,7 +116,7 @@ __global__ __launch_bounds__(64) void tq_dwell_fit_kernel(const tq_dwell_fit_arg
     n += wt;
     if (staged) pairs[i] = make_float2(t, wt);
   }
-  n = dwell_wave_sum(n);
+  n = tq_fit_wave_sum(n);
   __syncthreads();
 
   constexpr int P = 2 * K;
@@ -147,7 +128,7 @@ __global__ __launch_bounds__(64) void tq_dwell_fit_kernel(const tq_dwell_fit_arg
     m[j] = st[P + j];
     v[j] = st[2 * P + j];
   }
-  const float w1 = (float)(1.0 - a.beta1), b2 = (float)a.beta2, w2 = (float)(1.0 - a.beta2), eps = (float)a.eps;
+  const TqFitAdam adam(a.lr, a.beta1, a.beta2, a.eps);
   const int last = a.step0 + a.n_steps;
   for (int t = a.step0 + 1; t <= last; ++t) {
     const TqDwellK<K> q = tq_dwell_consts<K>(p);
@@ -166,8 +147,8 @@ __global__ __launch_bounds__(64) void tq_dwell_fit_kernel(const tq_dwell_fit_arg
     }
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-      R[j] = dwell_wave_sum(R[j]);
-      RT[j] = dwell_wave_sum(RT[j]);
+      R[j] = tq_fit_wave_sum(R[j]);
+      RT[j] = tq_fit_wave_sum(RT[j]);
     }
     if (t == last && a.loss) {  // loss at the parameters this step starts from (what svi.step() returns)
       float ll = 0.0f, r[K];
@@ -175,15 +156,14 @@ __global__ __launch_bounds__(64) void tq_dwell_fit_kernel(const tq_dwell_fit_arg
         const float2 x = staged ? pairs[i] : make_float2(vals[i], wts[i]);
         ll = fmaf(x.y, tq_dwell_resp<K>(q, x.x, r, true), ll);
       }
-      ll = dwell_wave_sum(ll);
+      ll = tq_fit_wave_sum(ll);
       if (lane == 0) a.loss[s] = -ll;
     }
     float g[P];
     tq_dwell_grad<K>(q, R, RT, n, g);
-    const float step_size = (float)(a.lr / (1.0 - tq_ttfb_pow(a.beta1, (uint32_t)t)));
-    const float bc2s = (float)sqrt(1.0 - tq_ttfb_pow(a.beta2, (uint32_t)t));
+    const float step_size = adam.step_size(t), bc2s = adam.bc2s(t);
 #pragma unroll
-    for (int j = 0; j < P; ++j) tq_ttfb_adam(p[j], m[j], v[j], g[j], w1, b2, w2, step_size, bc2s, eps);
+    for (int j = 0; j < P; ++j) tq_fit_adam(p[j], m[j], v[j], g[j], adam.w1, adam.b2, adam.w2, step_size, bc2s, adam.eps);
   }
   if (lane == 0) {
     float* out = a.state + (int64_t)s * 3 * P;
@@ -211,8 +191,7 @@ extern "C" int tq_dwell_fit(const tq_dwell_fit_args* a, void* stream) {
     tq_set_error("tq_dwell_fit: K must be in 1 .. TQ_DWELL_KMAX");
     return TQ_ERR_ARG;
   }
-  if (a->S < 1 || a->step0 < 0 || a->n_steps < 1 || !(a->lr > 0.0) || !(a->beta1 >= 0.0 && a->beta1 < 1.0) ||
-      !(a->beta2 >= 0.0 && a->beta2 < 1.0) || !(a->eps >= 0.0)) {
+  if (a->S < 1 || a->step0 < 0 || a->n_steps < 1 || !tq_adam_settings_ok(a->lr, a->beta1, a->beta2, a->eps)) {
     tq_set_error("tq_dwell_fit: unsupported S/step0/n_steps or Adam settings");
     return TQ_ERR_ARG;
   }
@@ -227,5 +206,5 @@ extern "C" int tq_dwell_fit(const tq_dwell_fit_args* a, void* stream) {
     case 7: dwell_fit_launch<7>(a, st); break;
     default: dwell_fit_launch<8>(a, st); break;
   }
-  return dwell_launch_status("tq_dwell_fit_kernel");
+  return tq_launch_status("tq_dwell_fit_kernel");
 }

@@ -9,9 +9,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../../include/tapqir_hip.h"
-
-void tq_set_error(const char* msg);
+#include "tq_host.h"
 
 #define TQ_HIST_BINS 65536
 #define TQ_HIST_WINDOW 8192  // LDS window of the per-frame offset histogram (camera offsets spread over a few hundred ADU)
@@ -185,12 +183,5 @@ extern "C" int tq_glimpse_extract(const tq_glimpse_args* a, void* stream) {
     if (rows > 0 && cols > 0)
       hipLaunchKernelGGL(tq_glimpse_hist_kernel, dim3((unsigned)a->nf), dim3(256), 0, st, *a, rows, cols);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "tq_glimpse_extract: %s", hipGetErrorString(e));
-    tq_set_error(buf);
-    return TQ_ERR_LAUNCH;
-  }
-  return TQ_OK;
+  return tq_launch_status("tq_glimpse_extract");
 }

@@ -144,26 +144,6 @@ TQ_HD float tq_ttfb_loss(const TqTtfbK& k, const TqTtfbData& d, float SP) {
   return -ll;
 }
 
-// torch.optim.Adam (betas, eps, bias correction; no weight decay / amsgrad) on one parameter, float32 as torch does it:
-// m.lerp_(g, 1 - beta1); v = v beta2 + (1 - beta2) g^2; p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
-TQ_HD void tq_ttfb_adam(float& p, float& m, float& v, float g, float w1, float b2, float w2, float step_size,
-                        float bc2s, float eps) {
-  m = m + w1 * (g - m);
-  v = v * b2 + (g * g) * w2;
-  p = p - step_size * (m / (sqrtf(v) / bc2s + eps));
-}
-
-// beta^t by binary powering in double: the same bits for a given t however the steps are split over launches
-TQ_HD double tq_ttfb_pow(double b, uint32_t t) {
-  double r = 1.0;
-  while (t) {
-    if (t & 1u) r *= b;
-    b *= b;
-    t >>= 1;
-  }
-  return r;
-}
-
 // one data point alone: log-likelihood term and its gradient (of the log-likelihood) in (log ka, log kns, logit Af),
 // through the same consts / accumulate / grad / loss code as the kernel (host tests)
 TQ_HD void tq_ttfb_point(const float* par, float tau, float T, int control, float* out) {

@@ -2,21 +2,9 @@
 // (prefix + search) and the batched censored-mixture MLE, one wave per posterior sample.
 #include <hip/hip_runtime.h>
 
-#include "tq_dpp.h"
+#include "tq_fit.h"
+#include "tq_host.h"
 #include "tq_kinetics.h"
-
-void tq_set_error(const char* msg);
-
-static int kin_launch_status(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    tq_set_error(buf);
-    return TQ_ERR_LAUNCH;
-  }
-  return TQ_OK;
-}
 
 // ---- sampler, launch 1: log-survival prefix, one wave per AOI ---------------------------------------------------------
 // The lanes form log1p(-p) of 64 frames at a time; lane 0 adds them up in frame order (the host build's order, so the
@@ -65,21 +53,17 @@ extern "C" int tq_ttfb_sample(const tq_ttfb_sample_args* a, void* stream) {
   }
   hipLaunchKernelGGL(tq_ttfb_prefix_kernel, dim3((unsigned)a->N), dim3(64), 0, (hipStream_t)stream, a->p, a->log_surv,
                      a->F);
-  int rc = kin_launch_status("tq_ttfb_prefix_kernel");
+  int rc = tq_launch_status("tq_ttfb_prefix_kernel");
   if (rc != TQ_OK) return rc;
   const int64_t total = (int64_t)a->S * a->N;
   hipLaunchKernelGGL(tq_ttfb_search_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      a->log_surv, a->tau, a->N, a->F, total, a->seed);
-  return kin_launch_status("tq_ttfb_search_kernel");
+  return tq_launch_status("tq_ttfb_search_kernel");
 }
 
 // ---- batched MLE: one wave (= one workgroup) per posterior sample -----------------------------------------------------
-__device__ __forceinline__ float tq_wave_sum(float v) {
-  // the same bits in every lane (each DPP / shuffle step adds a pair in either order), then made wave-uniform
-  v = tq_group_sum<64>(v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ double tq_wave_sum_d(double v) {
+// double sum of a data constant over the wave, in every lane (xor butterfly); the steps' float sums are tq_fit_wave_sum
+__device__ __forceinline__ double ttfb_data_sum(double v) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
@@ -121,18 +105,18 @@ __global__ __launch_bounds__(64) void tq_ttfb_fit_kernel(const tq_ttfb_fit_args 
     }
   }
   TqTtfbData d;
-  d.n_int = (float)tq_wave_sum_d(n_int);
-  d.sum_tau = (float)tq_wave_sum_d(sum_tau);
-  d.n_cens = (float)tq_wave_sum_d(n_cens);
-  d.nc_int = (float)tq_wave_sum_d(nc_int);
-  d.sum_tauc = (float)tq_wave_sum_d(sum_tauc);
-  d.nc_cens = (float)tq_wave_sum_d(nc_cens);
+  d.n_int = (float)ttfb_data_sum(n_int);
+  d.sum_tau = (float)ttfb_data_sum(sum_tau);
+  d.n_cens = (float)ttfb_data_sum(n_cens);
+  d.nc_int = (float)ttfb_data_sum(nc_int);
+  d.sum_tauc = (float)ttfb_data_sum(sum_tauc);
+  d.nc_cens = (float)ttfb_data_sum(nc_cens);
   d.T = T;
   if (STAGED) __syncthreads();
 
   const float* st = a.state + (int64_t)s * TQ_TTFB_STATE;
   float p[3] = {st[0], st[1], st[2]}, m[3] = {st[3], st[4], st[5]}, v[3] = {st[6], st[7], st[8]};
-  const float w1 = (float)(1.0 - a.beta1), b2 = (float)a.beta2, w2 = (float)(1.0 - a.beta2), eps = (float)a.eps;
+  const TqFitAdam adam(a.lr, a.beta1, a.beta2, a.eps);
   const int last = a.step0 + a.n_steps;
   for (int t = a.step0 + 1; t <= last; ++t) {
     const TqTtfbK k = tq_ttfb_consts(p[0], p[1], p[2]);
@@ -147,8 +131,8 @@ __global__ __launch_bounds__(64) void tq_ttfb_fit_kernel(const tq_ttfb_fit_args 
         if (x > 0.0f && x < T) tq_ttfb_accumulate(k, x, W1, W1tau);
       }
     }
-    W1 = tq_wave_sum(W1);
-    W1tau = tq_wave_sum(W1tau);
+    W1 = tq_fit_wave_sum(W1);
+    W1tau = tq_fit_wave_sum(W1tau);
     if (t == last && a.loss) {  // loss at the parameters this step starts from (what svi.step() returns)
       float SP = 0.0f;
       if (STAGED) {
@@ -159,15 +143,14 @@ __global__ __launch_bounds__(64) void tq_ttfb_fit_kernel(const tq_ttfb_fit_args 
           if (x > 0.0f && x < T) SP += tq_ttfb_softplus_d(k, x);
         }
       }
-      SP = tq_wave_sum(SP);
+      SP = tq_fit_wave_sum(SP);
       if (lane == 0) a.loss[s] = tq_ttfb_loss(k, d, SP);
     }
     float g[3];
     tq_ttfb_grad(k, d, W1, W1tau, g);
-    const float step_size = (float)(a.lr / (1.0 - tq_ttfb_pow(a.beta1, (uint32_t)t)));
-    const float bc2s = (float)sqrt(1.0 - tq_ttfb_pow(a.beta2, (uint32_t)t));
+    const float step_size = adam.step_size(t), bc2s = adam.bc2s(t);
 #pragma unroll
-    for (int j = 0; j < 3; ++j) tq_ttfb_adam(p[j], m[j], v[j], g[j], w1, b2, w2, step_size, bc2s, eps);
+    for (int j = 0; j < 3; ++j) tq_fit_adam(p[j], m[j], v[j], g[j], adam.w1, adam.b2, adam.w2, step_size, bc2s, adam.eps);
   }
   if (lane == 0) {
     float* out = a.state + (int64_t)s * TQ_TTFB_STATE;
@@ -186,8 +169,7 @@ extern "C" int tq_ttfb_fit(const tq_ttfb_fit_args* a, void* stream) {
     return TQ_ERR_ARG;
   }
   if (a->S < 1 || a->N < 1 || a->Nc < 0 || (a->tauc && a->Nc < 1) || a->step0 < 0 || a->n_steps < 1 ||
-      !(a->Tmax > 0.0f) || !(a->lr > 0.0) || !(a->beta1 >= 0.0 && a->beta1 < 1.0) ||
-      !(a->beta2 >= 0.0 && a->beta2 < 1.0) || !(a->eps >= 0.0)) {
+      !(a->Tmax > 0.0f) || !tq_adam_settings_ok(a->lr, a->beta1, a->beta2, a->eps)) {
     tq_set_error("tq_ttfb_fit: unsupported S/N/Nc/step0/n_steps/Tmax or Adam settings");
     return TQ_ERR_ARG;
   }
@@ -197,5 +179,5 @@ extern "C" int tq_ttfb_fit(const tq_ttfb_fit_args* a, void* stream) {
     hipLaunchKernelGGL(tq_ttfb_fit_kernel<true>, dim3((unsigned)a->S), dim3(64), (size_t)a->N * sizeof(float),
                        (hipStream_t)stream, *a);
   }
-  return kin_launch_status("tq_ttfb_fit_kernel");
+  return tq_launch_status("tq_ttfb_fit_kernel");
 }

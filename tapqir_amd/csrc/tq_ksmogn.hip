@@ -26,6 +26,7 @@
 
 #include "../../include/tapqir_hip.h"
 #include "tq_dpp.h"
+#include "tq_host.h"
 #include "tq_pixel.h"
 
 #include "tq_ksmogn_dev.h"
@@ -734,17 +735,6 @@ extern "C" const char* tq_last_error(void) { return g_err; }
 extern "C" int tq_version(void) { return 101; }
 void tq_set_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
 
-static int launch_status(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    tq_set_error(buf);
-    return TQ_ERR_LAUNCH;
-  }
-  return TQ_OK;
-}
-
 template <int K, bool ONE>
 static int launch_kb(const tq_ksmogn_args& a, int64_t B, hipStream_t st) {
   const bool bwd = a.g_background != nullptr;
@@ -767,7 +757,7 @@ static int launch_kb(const tq_ksmogn_args& a, int64_t B, hipStream_t st) {
         const dim3 gridp((unsigned)(ntiles < waves ? ntiles : waves));
         if (a.P == 14) hipLaunchKernelGGL((tq_ksmogn_il2p_kernel<K, 14, true>), gridp, block1, 0, st, a, B, Bn, ntiles);
         else hipLaunchKernelGGL((tq_ksmogn_il2p_kernel<K, 20, true>), gridp, block1, 0, st, a, B, Bn, ntiles);
-        return launch_status("tq_ksmogn_il2p_kernel");
+        return tq_launch_status("tq_ksmogn_il2p_kernel");
       }
       if (a.P == 14) {
         if (bwd) hipLaunchKernelGGL((tq_ksmogn_il2_kernel<K, 14, true>), grid1, block1, 0, st, a, B);
@@ -776,7 +766,7 @@ static int launch_kb(const tq_ksmogn_args& a, int64_t B, hipStream_t st) {
         if (bwd) hipLaunchKernelGGL((tq_ksmogn_il2_kernel<K, 20, true>), grid1, block1, 0, st, a, B);
         else hipLaunchKernelGGL((tq_ksmogn_il2_kernel<K, 20, false>), grid1, block1, 0, st, a, B);
       }
-      return launch_status("tq_ksmogn_il2_kernel");
+      return tq_launch_status("tq_ksmogn_il2_kernel");
     }
     if (!ONE && (a.P % 2) == 0 && a.O <= TQ_MO_MAX_O) {
       if constexpr (K <= 2) {
@@ -786,11 +776,11 @@ static int launch_kb(const tq_ksmogn_args& a, int64_t B, hipStream_t st) {
         if (bwd) hipLaunchKernelGGL((tq_ksmogn_il2m_wide_kernel<K, true>), grid, block, 0, st, a, B);
         else hipLaunchKernelGGL((tq_ksmogn_il2m_wide_kernel<K, false>), grid, block, 0, st, a, B);
       }
-      return launch_status("tq_ksmogn_il2m_kernel");
+      return tq_launch_status("tq_ksmogn_il2m_kernel");
     }
     if (bwd) hipLaunchKernelGGL((tq_ksmogn_il_kernel<K, ONE, true>), grid, block, 0, st, a, B);
     else hipLaunchKernelGGL((tq_ksmogn_il_kernel<K, ONE, false>), grid, block, 0, st, a, B);
-    return launch_status("tq_ksmogn_il_kernel");
+    return tq_launch_status("tq_ksmogn_il_kernel");
   }
   if (!a.images) {
     tq_set_error("tq_ksmogn_log_prob: images is NULL and the interleaved kernel does not apply to this batch");
@@ -804,13 +794,13 @@ static int launch_kb(const tq_ksmogn_args& a, int64_t B, hipStream_t st) {
     const size_t ldsw = sizeof(float) * tq_tile16_lds_floats(a.P, K, a.O, UNITS);
     if (bwd) hipLaunchKernelGGL((tq_ksmogn_kernel<K, false, true, 64>), gridw, blockw, ldsw, st, a, B);
     else hipLaunchKernelGGL((tq_ksmogn_kernel<K, false, false, 64>), gridw, blockw, ldsw, st, a, B);
-    return launch_status("tq_ksmogn_kernel (64 lanes per unit)");
+    return tq_launch_status("tq_ksmogn_kernel (64 lanes per unit)");
   }
   const dim3 grid((unsigned)((B + TQ_UNITS_PER_BLOCK - 1) / TQ_UNITS_PER_BLOCK)), block(TQ_BLOCK);
   const size_t lds = sizeof(float) * tq_tile16_lds_floats(a.P, K, a.O);
   if (bwd) hipLaunchKernelGGL((tq_ksmogn_kernel<K, ONE, true>), grid, block, lds, st, a, B);
   else hipLaunchKernelGGL((tq_ksmogn_kernel<K, ONE, false>), grid, block, lds, st, a, B);
-  return launch_status("tq_ksmogn_kernel");
+  return tq_launch_status("tq_ksmogn_kernel");
 }
 
 template <int K>
@@ -861,7 +851,7 @@ extern "C" int tq_images_interleave_n(const float* images, float* images_il, int
   const int64_t total4 = tq_interleaved_floats_n(U, npix) / 4;
   hipLaunchKernelGGL(tq_interleave_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      images, images_il, U, npix, total4);
-  return launch_status("tq_interleave_kernel");
+  return tq_launch_status("tq_interleave_kernel");
 }
 
 extern "C" int tq_images_interleave(const float* images, float* images_il, int64_t U, int32_t P, void* stream) {
@@ -872,7 +862,7 @@ extern "C" int tq_images_interleave(const float* images, float* images_il, int64
   const int64_t total4 = tq_interleaved_floats(U, P) / 4;
   hipLaunchKernelGGL(tq_interleave_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      images, images_il, U, P * P, total4);
-  return launch_status("tq_interleave_kernel");
+  return tq_launch_status("tq_interleave_kernel");
 }
 
 extern "C" int tq_image_stats(const float* images, const float* offset, float* pixstats, int64_t U, int32_t P,
@@ -884,5 +874,5 @@ extern "C" int tq_image_stats(const float* images, const float* offset, float* p
   const int64_t threads = U * 64;
   hipLaunchKernelGGL(tq_image_stats_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      images, offset, pixstats, U, P * P);
-  return launch_status("tq_image_stats_kernel");
+  return tq_launch_status("tq_image_stats_kernel");
 }

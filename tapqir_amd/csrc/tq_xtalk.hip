@@ -4,9 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include "tq_dpp.h"
+#include "tq_host.h"
 #include "tq_xtalk.h"
-
-void tq_set_error(const char* msg);
 
 template <int K, bool BWD>
 __global__ __launch_bounds__(256) void tq_xtalk_kernel(const tq_xtalk_args a, const int64_t Bg) {
@@ -291,14 +290,7 @@ extern "C" int tq_ksmogn_crosstalk_log_prob(const tq_xtalk_args* a, void* stream
     const dim3 gridl((unsigned)((Bg + 255) / 256)), blockl(256);
     if (bwd) hipLaunchKernelGGL((tq_xtalk_il_kernel<true>), gridl, blockl, 0, st, *a, Bg);
     else hipLaunchKernelGGL((tq_xtalk_il_kernel<false>), gridl, blockl, 0, st, *a, Bg);
-    const hipError_t el = hipGetLastError();
-    if (el != hipSuccess) {
-      char buf[200];
-      snprintf(buf, sizeof(buf), "tq_xtalk_il_kernel: %s", hipGetErrorString(el));
-      tq_set_error(buf);
-      return TQ_ERR_LAUNCH;
-    }
-    return TQ_OK;
+    return tq_launch_status("tq_xtalk_il_kernel");
   }
   const dim3 grid((unsigned)((Bg + 15) / 16)), block(256);
   if (a->K == 1) {
@@ -308,12 +300,5 @@ extern "C" int tq_ksmogn_crosstalk_log_prob(const tq_xtalk_args* a, void* stream
     if (bwd) hipLaunchKernelGGL((tq_xtalk_kernel<2, true>), grid, block, 0, st, *a, Bg);
     else hipLaunchKernelGGL((tq_xtalk_kernel<2, false>), grid, block, 0, st, *a, Bg);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "tq_xtalk_kernel: %s", hipGetErrorString(e));
-    tq_set_error(buf);
-    return TQ_ERR_LAUNCH;
-  }
-  return TQ_OK;
+  return tq_launch_status("tq_xtalk_kernel");
 }

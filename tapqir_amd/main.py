@@ -241,18 +241,80 @@ def stats(
     logger.info("Computing stats: Done")
 
 
-def _ttfb_plots(cd, name, c, z_masked, sdx, r_type, Tmax, fb_mean, fb_ll, fb_ul, best_fit, logger):
-    """Rastergram and cumulative-fraction plot of one channel (main.py:988-1005, 1108-1147)."""
+def _kinetics_inputs(command, model, cuda, progress_bar):
+    """The checks `ttfb` and `dwelltime` share, in the order the exit-status tests rely on (``--cpu`` fails before any file
+    is read).  Returns the loaded model, the mask of the on-target AOIs and the progress bar."""
+    import torch
+
+    from tapqir_amd.exceptions import TapqirFileNotFoundError
+    from tapqir_amd.models import models
+
+    cd = DEFAULTS["cd"]
+    logger = logging.getLogger("tapqir")
+    if model.value != "cosmos":
+        # the reference has no z_sample for crosstalk, and cosmos+hmm is not part of this build
+        logger.error(f"{command} is not available for the {model.value} model (cosmos only)")
+        raise typer.Exit(1)
+    if not cuda:
+        logger.error(f"{command} runs on the AMD GPU only (--cuda): the sampler and the fits have no CPU path")
+        raise typer.Exit(1)
+    m = models[model.value](device="cpu", dtype="float")
+    try:
+        m.load(cd, data_only=False)
+    except TapqirFileNotFoundError as err:
+        logger.exception(f"Failed to load {err.name} file")
+        raise typer.Exit(1)
+    if "z_probs" not in m.params:
+        logger.error(f"{m.name}_params.tpqr has no z_probs: run `fit` first")
+        raise typer.Exit(1)
+    if not torch.cuda.is_available():
+        logger.error(f"{command} needs an AMD GPU (--cuda): no HIP device is visible")
+        raise typer.Exit(1)
+    if progress_bar is None:
+        try:
+            from tqdm import tqdm as progress_bar
+        except Exception:  # pragma: no cover
+            progress_bar = None
+    mask = m.data.mask[: m.data.N].cpu().bool()
+    if not bool(mask.any()):
+        logger.error(f"{command}: no on-target AOI is selected by the data mask")
+        raise typer.Exit(1)
+    return m, mask, progress_bar
+
+
+def _summary_table(rows):
+    """Mean and 95% highest-density interval of each ``(label, values)`` pair, one row per label."""
+    import pandas as pd
+
+    from tapqir_amd.utils.stats import hpdi
+
+    results = pd.DataFrame(columns=["Mean", "95% LL", "95% UL"], dtype=float)
+    for label, values in rows:
+        ll, ul = hpdi(values, 0.95)
+        results.loc[label] = [values.mean().item(), ll.item(), ul.item()]
+    return results
+
+
+def _pyplot():
+    """(matplotlib, pyplot) on the Agg backend with the commands' font settings, or (None, None) without matplotlib."""
     try:
         import matplotlib as mpl
 
         mpl.use("Agg")
         import matplotlib.pyplot as plt
     except Exception:
-        logger.warning("matplotlib is not available: the ttfb plots are not drawn")
-        return
+        return None, None
     mpl.rcParams["font.family"] = "sans-serif"
     mpl.rcParams.update({"font.size": 8})
+    return mpl, plt
+
+
+def _ttfb_plots(cd, name, c, z_masked, sdx, r_type, Tmax, fb_mean, fb_ll, fb_ul, best_fit, logger):
+    """Rastergram and cumulative-fraction plot of one channel (main.py:988-1005, 1108-1147)."""
+    mpl, plt = _pyplot()
+    if plt is None:
+        logger.warning("matplotlib is not available: the ttfb plots are not drawn")
+        return
     fig, ax = plt.subplots()
     ax.imshow(z_masked[sdx].numpy(), norm=mpl.colors.Normalize(vmin=0, vmax=1), aspect="equal", interpolation="none")
     ax.set_xlabel("Time (frame)")
@@ -299,44 +361,14 @@ def ttfb(
     import pandas as pd
     import torch
 
-    from tapqir_amd.exceptions import HipExtensionError, TapqirFileNotFoundError
-    from tapqir_amd.models import models
+    from tapqir_amd.exceptions import HipExtensionError
     from tapqir_amd.utils.imscroll import time_to_first_binding
     from tapqir_amd.utils.mle_analysis import fraction_bound, fraction_bound_fit, hpdi_columns, ttfb_fit, ttfb_sample
-    from tapqir_amd.utils.stats import hpdi
 
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
-    if model.value != "cosmos":
-        # the reference has no z_sample for crosstalk, and cosmos+hmm is not part of this build
-        logger.error(f"ttfb is not available for the {model.value} model (cosmos only)")
-        raise typer.Exit(1)
-    if not cuda:
-        logger.error("ttfb runs on the AMD GPU only (--cuda): the sampler and the fits have no CPU path")
-        raise typer.Exit(1)
-    m = models[model.value](device="cpu", dtype="float")
-    try:
-        m.load(cd, data_only=False)
-    except TapqirFileNotFoundError as err:
-        logger.exception(f"Failed to load {err.name} file")
-        raise typer.Exit(1)
-    if "z_probs" not in m.params:
-        logger.error(f"{m.name}_params.tpqr has no z_probs: run `fit` first")
-        raise typer.Exit(1)
-    if not torch.cuda.is_available():
-        logger.error("ttfb needs an AMD GPU (--cuda): no HIP device is visible")
-        raise typer.Exit(1)
-    if progress_bar is None:
-        try:
-            from tqdm import tqdm as progress_bar
-        except Exception:  # pragma: no cover
-            progress_bar = None
-
+    m, mask, progress_bar = _kinetics_inputs("ttfb", model, cuda, progress_bar)
     data = m.data
-    mask = data.mask[: data.N].cpu().bool()
-    if not bool(mask.any()):
-        logger.error("ttfb: no on-target AOI is selected by the data mask")
-        raise typer.Exit(1)
     p_specific = m.params["p_specific"][: data.N].float()
     z = (p_specific > 0.5).float() if binary else p_specific
     r_type = "binary" if binary else "probabilistic"
@@ -355,11 +387,7 @@ def ttfb(
             logger.info(f"Saved time-to-first-binding values in {m.name}_ttfb-data-points-channel{c}.csv file")
 
             fit = ttfb_fit(tau, Tmax, lr=5e-3, n_steps=num_iter, progress_bar=progress_bar)
-            results = pd.DataFrame(columns=["Mean", "95% LL", "95% UL"], dtype=float)
-            for name in ("ka", "kns", "Af"):
-                values = fit[name].squeeze(-1).cpu()
-                ll, ul = hpdi(values, 0.95)
-                results.loc[name] = [values.mean().item(), ll.item(), ul.item()]
+            results = _summary_table((name, fit[name].squeeze(-1).cpu()) for name in ("ka", "kns", "Af"))
             results.to_csv(cd / f"{m.name}_ttfb-params-channel{c}.csv")
             logger.info(f"Saved fit parameters in {m.name}_ttfb-params-channel{c}.csv file")
 
@@ -382,18 +410,12 @@ def ttfb(
 
 def _dwell_plot(cd, name, c, kind, map_dt, A, k, t_max, logger):
     """Dwell-time histogram of the MAP raster with the fitted mixture (main.py:1266-1296, 1350-1381)."""
-    try:
-        import matplotlib as mpl
-
-        mpl.use("Agg")
-        import matplotlib.pyplot as plt
-    except Exception:
+    mpl, plt = _pyplot()
+    if plt is None:
         logger.warning("matplotlib is not available: the dwelltime plots are not drawn")
         return
     import numpy as np
 
-    mpl.rcParams["font.family"] = "sans-serif"
-    mpl.rcParams.update({"font.size": 8})
     fig, ax = plt.subplots()
     if map_dt.size:
         ax.hist(map_dt[0], bins=100, density=True)
@@ -430,55 +452,26 @@ def dwelltime(
     Unlike the reference, a sample without an interior interval of a kind is left out of that kind's fit and statistics
     (the count is logged), and a kind that no sample has is skipped with a warning.
     """
-    import pandas as pd
     import torch
 
     from tapqir_amd import _lib
-    from tapqir_amd.exceptions import HipExtensionError, TapqirFileNotFoundError
-    from tapqir_amd.models import models
+    from tapqir_amd.exceptions import HipExtensionError
     from tapqir_amd.utils.imscroll import bound_dwell_times, count_intervals, unbound_dwell_times
     from tapqir_amd.utils.mle_analysis import dwell_csr_from_hist, dwell_fit, dwell_intervals, dwell_sample
-    from tapqir_amd.utils.stats import hpdi
 
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
-    if model.value != "cosmos":
-        # the reference has no z_sample for crosstalk, and cosmos+hmm is not part of this build
-        logger.error(f"dwelltime is not available for the {model.value} model (cosmos only)")
-        raise typer.Exit(1)
-    if not 1 <= K <= _lib.DWELL_KMAX:
+    # the -K range is checked after the model and before --cpu: a model other than cosmos is left to _kinetics_inputs
+    if model.value == "cosmos" and not 1 <= K <= _lib.DWELL_KMAX:
         logger.error(f"dwelltime: -K must be between 1 and {_lib.DWELL_KMAX}, got {K}")
         raise typer.Exit(1)
-    if not cuda:
-        logger.error("dwelltime runs on the AMD GPU only (--cuda): the sampler and the fits have no CPU path")
-        raise typer.Exit(1)
-    m = models[model.value](device="cpu", dtype="float")
-    try:
-        m.load(cd, data_only=False)
-    except TapqirFileNotFoundError as err:
-        logger.exception(f"Failed to load {err.name} file")
-        raise typer.Exit(1)
-    if "z_probs" not in m.params:
-        logger.error(f"{m.name}_params.tpqr has no z_probs: run `fit` first")
-        raise typer.Exit(1)
-    if not torch.cuda.is_available():
-        logger.error("dwelltime needs an AMD GPU (--cuda): no HIP device is visible")
-        raise typer.Exit(1)
-    if progress_bar is None:
-        try:
-            from tqdm import tqdm as progress_bar
-        except Exception:  # pragma: no cover
-            progress_bar = None
+    m, mask, progress_bar = _kinetics_inputs("dwelltime", model, cuda, progress_bar)
     try:
         from scipy.io import savemat
     except Exception:
         savemat = None
 
     data = m.data
-    mask = data.mask[: data.N].cpu().bool()
-    if not bool(mask.any()):
-        logger.error("dwelltime: no on-target AOI is selected by the data mask")
-        raise typer.Exit(1)
     z_map = m.params["z_map"][: data.N] if "z_map" in m.params else None
     kinds = (("bound", "koff", "Off-rate", bound_dwell_times), ("unbound", "kon", "On-rate", unbound_dwell_times))
     try:
@@ -509,14 +502,10 @@ def dwelltime(
                                 f"are left out of the {rate} fit")
                 hist = hist[keep]
                 fit = dwell_fit(dwell_csr_from_hist(hist), K, lr=5e-3, n_steps=num_iter, progress_bar=progress_bar)
-                results = pd.DataFrame(columns=["Mean", "95% LL", "95% UL"], dtype=float)
-                A_mean, k_mean = [], []
-                for i in range(K):
-                    for label, values in ((f"A{i}", fit["A"][:, i].cpu()), (f"{rate}{i}", fit["k"][:, i].cpu())):
-                        ll, ul = hpdi(values, 0.95)
-                        results.loc[label] = [values.mean().item(), ll.item(), ul.item()]
-                    A_mean.append(results.loc[f"A{i}", "Mean"])
-                    k_mean.append(results.loc[f"{rate}{i}", "Mean"])
+                results = _summary_table(pair for i in range(K) for pair in (
+                    (f"A{i}", fit["A"][:, i].cpu()), (f"{rate}{i}", fit["k"][:, i].cpu())))
+                A_mean = [results.loc[f"A{i}", "Mean"] for i in range(K)]
+                k_mean = [results.loc[f"{rate}{i}", "Mean"] for i in range(K)]
                 results.to_csv(cd / f"{m.name}_dwelltime-{rate}-channel{c}.csv")
                 logger.info(f"Saved {title.lower()} parameters in {m.name}_dwelltime-{rate}-channel{c}.csv file")
 

@@ -35,21 +35,33 @@ def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def _sampler_inputs(who, p_bound, num_samples, seed):
+    """What the samplers share: ``p_bound`` as a clamped (N, F) float32 device tensor, N, F, and the seed as the uint64
+    of the argument block."""
+    p = _device_tensor(p_bound, who)
+    if p.ndim != 2 or p.shape[0] < 1 or p.shape[1] < 1 or num_samples < 1:
+        raise ValueError(f"{who}: p_bound must be (N, F) with N, F >= 1 and num_samples >= 1, got {tuple(p.shape)}")
+    return p.clamp(0.0, 1.0), p.shape[0], p.shape[1], int(seed) & (2**64 - 1)
+
+
+def _run_chunks(fit_steps, n_steps, chunk, progress_bar):
+    """``fit_steps(step0, n)`` for launches of ``max(1, int(chunk))`` steps (the last one shorter) up to ``n_steps``."""
+    chunk = max(1, int(chunk))
+    starts = range(0, n_steps, chunk)
+    for step0 in (progress_bar(starts) if progress_bar is not None else starts):
+        fit_steps(step0, min(chunk, n_steps - step0))
+
+
 def ttfb_sample(p_bound, num_samples, seed=0):
     """``num_samples`` posterior draws of the first-binding frame of each AOI.
 
     ``p_bound`` (N, F): q(z = 1) of each AOI-frame (``z_probs[..., c, 1]`` of the params file).  Returns ``tau``
     (num_samples, N), float32 on the device: the first frame with z = 1 of each sampled raster, or F if there is none
     -- ``time_to_first_binding(z_sample(num_samples))`` of the reference, drawn from the exact law of that index."""
-    p = _device_tensor(p_bound, "ttfb_sample")
-    if p.ndim != 2 or p.shape[0] < 1 or p.shape[1] < 1 or num_samples < 1:
-        raise ValueError(f"ttfb_sample: p_bound must be (N, F) with N, F >= 1 and num_samples >= 1, got {tuple(p.shape)}")
-    p = p.clamp(0.0, 1.0)
-    N, F = p.shape
+    p, N, F, seed = _sampler_inputs("ttfb_sample", p_bound, num_samples, seed)
     L = torch.empty(N, F, dtype=torch.float64, device=p.device)
     tau = torch.empty(num_samples, N, dtype=torch.float32, device=p.device)
-    a = _lib.TtfbSampleArgs(p=_lib.ptr(p), log_surv=_lib.ptr(L), tau=_lib.ptr(tau), N=N, F=F, S=int(num_samples),
-                            seed=int(seed) & (2**64 - 1))
+    a = _lib.TtfbSampleArgs(p=_lib.ptr(p), log_surv=_lib.ptr(L), tau=_lib.ptr(tau), N=N, F=F, S=int(num_samples), seed=seed)
     _lib.check(_lib.load().tq_ttfb_sample(C.byref(a), _stream(p.device)), "tq_ttfb_sample")
     return tau
 
@@ -92,9 +104,8 @@ def ttfb_fit(data, Tmax, control=None, lr=5e-3, n_steps=15000, progress_bar=None
     S = tau.shape[0]
     state = ttfb_init_state(S, tau.device)
     loss = torch.full((S,), float("nan"), dtype=torch.float32, device=tau.device)
-    starts = range(0, n_steps, max(1, int(chunk)))
-    for step0 in (progress_bar(starts) if progress_bar is not None else starts):
-        ttfb_fit_steps(state, tau, Tmax, control, lr, step0, min(chunk, n_steps - step0), loss, stage_lds)
+    _run_chunks(lambda step0, n: ttfb_fit_steps(state, tau, Tmax, control, lr, step0, n, loss, stage_lds), n_steps, chunk,
+                progress_bar)
     return {"ka": state[:, 0:1].exp(), "kns": state[:, 1:2].exp(), "Af": torch.sigmoid(state[:, 2:3]), "loss": loss}
 
 
@@ -137,17 +148,13 @@ def dwell_sample(p_bound, num_samples, seed=0):
     ``p_bound`` (N, F): q(z = 1) of each AOI-frame.  Returns ``{"hist_bound", "hist_unbound"}``, (num_samples, F) int32:
     the number of interior bound / unbound runs of each dwell time per sample, and ``"counts"`` (num_samples, N) int32:
     the number of intervals (of any kind) of each sampled row.  Nothing of size S x N x F is stored."""
-    p = _device_tensor(p_bound, "dwell_sample")
-    if p.ndim != 2 or p.shape[0] < 1 or p.shape[1] < 1 or num_samples < 1:
-        raise ValueError(f"dwell_sample: p_bound must be (N, F) with N, F >= 1 and num_samples >= 1, got {tuple(p.shape)}")
-    p = p.clamp(0.0, 1.0)
-    N, F = p.shape
+    p, N, F, seed = _sampler_inputs("dwell_sample", p_bound, num_samples, seed)
     S = int(num_samples)
     counts = torch.empty(S, N, dtype=torch.int32, device=p.device)
     hb = torch.zeros(S, F, dtype=torch.int32, device=p.device)
     hu = torch.zeros(S, F, dtype=torch.int32, device=p.device)
     a = _lib.DwellSampleArgs(p=_lib.ptr(p), counts=_lib.ptr(counts), hist_bound=_lib.ptr(hb), hist_unbound=_lib.ptr(hu),
-                             N=N, F=F, S=S, mode=_lib.DWELL_COUNT, seed=int(seed) & (2**64 - 1))
+                             N=N, F=F, S=S, mode=_lib.DWELL_COUNT, seed=seed)
     _lib.check(_lib.load().tq_dwell_sample(C.byref(a), _stream(p.device)), "tq_dwell_sample")
     return {"hist_bound": hb, "hist_unbound": hu, "counts": counts}
 
@@ -161,18 +168,18 @@ def dwell_intervals(p_bound, num_samples, seed=0, sample=None):
 
     from tapqir_amd.utils.imscroll import INTERVAL_COLUMNS
 
-    p = _device_tensor(p_bound, "dwell_intervals").clamp(0.0, 1.0)
+    given = num_samples if sample is None else sample["counts"].shape[0]
+    p, N, F, seed = _sampler_inputs("dwell_intervals", p_bound, given, seed)
     if sample is None:
         sample = dwell_sample(p, num_samples, seed)
     counts = sample["counts"]
-    N, F = p.shape
     S = counts.shape[0]
     csum = torch.cumsum(counts.reshape(-1).to(torch.int64), 0)
     offsets = (csum - counts.reshape(-1)).contiguous()
     total = int(csum[-1].item())
     cols = torch.empty(_lib.DWELL_COLS, max(total, 1), dtype=torch.int32, device=p.device)
     a = _lib.DwellSampleArgs(p=_lib.ptr(p), offsets=_lib.ptr(offsets), intervals=_lib.ptr(cols), total=total, N=N, F=F,
-                             S=S, mode=_lib.DWELL_EMIT, seed=int(seed) & (2**64 - 1))
+                             S=S, mode=_lib.DWELL_EMIT, seed=seed)
     _lib.check(_lib.load().tq_dwell_sample(C.byref(a), _stream(p.device)), "tq_dwell_sample")
     host = cols[:, :total].to(torch.int64).cpu().numpy()
     return pd.DataFrame({name: host[i] for i, name in enumerate(INTERVAL_COLUMNS)})
@@ -264,7 +271,6 @@ def dwell_fit(data, K=3, lr=5e-3, n_steps=10000, chunk=1000, progress_bar=None, 
     dev = csr[2].device
     state = dwell_init_state(S, K, dev)
     loss = torch.full((S,), float("nan"), dtype=torch.float32, device=dev)
-    starts = range(0, n_steps, max(1, int(chunk)))
-    for step0 in (progress_bar(starts) if progress_bar is not None else starts):
-        dwell_fit_steps(state, csr, K, lr, step0, min(max(1, int(chunk)), n_steps - step0), loss, stage_lds)
+    _run_chunks(lambda step0, n: dwell_fit_steps(state, csr, K, lr, step0, n, loss, stage_lds), n_steps, chunk,
+                progress_bar)
     return {"k": state[:, :K].exp(), "A": torch.softmax(state[:, K:2 * K], dim=1), "loss": loss}

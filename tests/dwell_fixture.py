@@ -4,11 +4,12 @@ torch.optim.Adam)."""
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pandas as pd
 import torch
+
+from helpers import adam64, build_host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "hostcheck", "dwell_check.cpp")
@@ -18,7 +19,7 @@ COLUMNS = ["posterior_sample", "aoi", "start_frame", "stop_frame", "dwell_time",
 def build_dwell_check(out_dir):
     """Compile tests/hostcheck/dwell_check.cpp into ``out_dir`` and bind it."""
     so = os.path.join(str(out_dir), "libtq_dwell_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", so, SRC])
+    build_host_check(SRC, so)
     lib = C.CDLL(so)
     vp = C.c_void_p
     lib.hk_dwell_walk.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int64]
@@ -92,12 +93,5 @@ def loglik64(par, data, K):
 def torch_fit64(data, K, n_steps=300, lr=5e-3):
     """The reference's fit restated in float64 torch: autograd + torch.optim.Adam from the same initial values."""
     data = data.double().cpu()
-    par = init_par(data.shape[0], K).requires_grad_(True)
-    opt = torch.optim.Adam([par], lr=lr, betas=(0.9, 0.999), eps=1e-8)
-    for _ in range(n_steps):
-        opt.zero_grad()
-        loss = -loglik64(par, data, K).sum()
-        loss.backward()
-        opt.step()
-    p = par.detach()
+    p = adam64(init_par(data.shape[0], K), lambda par: loglik64(par, data, K), n_steps, lr)
     return {"k": p[:, :K].exp(), "A": torch.softmax(p[:, K:], dim=1), "par": p}

@@ -24,6 +24,24 @@ _hc = None
 GIVEN_STAGES = ("cosmos_sample_globals", "cosmos_sample_locals", "cosmos_elbo_grads", "cosmos_globals_grad")
 
 
+def build_host_check(src, so_path):
+    """g++ build of one tests/hostcheck source (the kernels' host+device headers on host memory) into ``so_path``."""
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", so_path, src])
+
+
+def adam64(par0, loglik, n_steps, lr):
+    """``n_steps`` of torch.optim.Adam (betas (0.9, 0.999), eps 1e-8) on ``-loglik(par).sum()`` from ``par0`` (float64):
+    the optimiser of the reference's fits.  Returns the final parameters, detached."""
+    par = par0.clone().requires_grad_(True)
+    opt = torch.optim.Adam([par], lr=lr, betas=(0.9, 0.999), eps=1e-8)
+    for _ in range(n_steps):
+        opt.zero_grad()
+        loss = -loglik(par).sum()
+        loss.backward()
+        opt.step()
+    return par.detach()
+
+
 def load_hostcheck():
     """g++ build of the kernels' inline math, driven on host memory (tests only)."""
     global _hc
@@ -34,8 +52,7 @@ def load_hostcheck():
     hdrs = [os.path.join(ROOT, "tapqir_amd", "csrc", f) for f in os.listdir(os.path.join(ROOT, "tapqir_amd", "csrc"))
             if f.endswith(".h")] + [os.path.join(ROOT, "include", "tapqir_hip.h"), src]
     if not os.path.exists(so) or any(os.path.getmtime(h) > os.path.getmtime(so) for h in hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas",
-                               "-o", so, src])
+        build_host_check(src, so)
     lib = C.CDLL(so)
     lib.hc_globals_size.restype = C.c_int64
     lib.hc_gbase_size.restype = C.c_int64

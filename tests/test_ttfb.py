@@ -175,6 +175,32 @@ def test_mle_entry_points_refuse_cpu_tensors():
         ttfb_fit(torch.rand(3, 5), 5)
 
 
+def test_fit_launches_chunks_of_max_1_int_chunk(monkeypatch):
+    """The fits run their steps in launches of ``max(1, int(chunk))`` steps: ``chunk = 0`` and a float ``chunk`` behave as
+    that integer.  The launches are recorded by a fake ``ttfb_fit_steps``; the fake ``dwell_fit_steps`` is driven through the
+    chunk loop ``dwell_fit`` shares with ``ttfb_fit``."""
+    from tapqir_amd.utils import mle_analysis as mle
+
+    calls = []
+    monkeypatch.setattr(mle, "_device_tensor", lambda x, what: x)
+    monkeypatch.setattr(mle, "ttfb_fit_steps", lambda state, tau, Tmax, control, lr, step0, n_steps, loss, stage_lds:
+                        calls.append((step0, n_steps)))
+    for chunk, want in ((0, [(0, 1), (1, 1), (2, 1)]), (2.9, [(0, 2), (2, 1)]), (0.5, [(0, 1), (1, 1), (2, 1)]),
+                        (3, [(0, 3)]), (10, [(0, 3)])):
+        calls.clear()
+        mle.ttfb_fit(torch.rand(2, 5), 5, n_steps=3, chunk=chunk)
+        assert calls == want, (chunk, calls)
+        assert all(type(n) is int for _, n in calls)
+
+    def dwell_fit_steps(step0, n_steps):
+        calls.append((step0, n_steps))
+
+    for chunk, want in ((0, [(0, 1), (1, 1)]), (1.5, [(0, 1), (1, 1)]), (2.0, [(0, 2)])):
+        calls.clear()
+        mle._run_chunks(dwell_fit_steps, 2, chunk, None)
+        assert calls == want, (chunk, calls)
+
+
 def test_fraction_bound_counts():
     from tapqir_amd.utils.mle_analysis import fraction_bound, hpdi_columns
 

@@ -3,9 +3,10 @@ of the reference's censored-mixture MLE (tapqir/utils/mle_analysis.py:49-101 wit
 
 import ctypes as C
 import os
-import subprocess
 
 import torch
+
+from helpers import adam64, build_host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "hostcheck", "kinetics_check.cpp")
@@ -14,7 +15,7 @@ SRC = os.path.join(ROOT, "tests", "hostcheck", "kinetics_check.cpp")
 def build_kinetics_check(out_dir):
     """Compile tests/hostcheck/kinetics_check.cpp into ``out_dir`` and bind it."""
     so = os.path.join(str(out_dir), "libtq_kinetics_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", so, SRC])
+    build_host_check(SRC, so)
     lib = C.CDLL(so)
     fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
     lib.hk_ttfb_point.argtypes = [fp, C.c_float, C.c_float, C.c_int, fp]
@@ -81,12 +82,5 @@ def torch_fit64(data, Tmax, control=None, n_steps=300, lr=5e-3):
     S = data.shape[0]
     init = torch.tensor([0.001, 0.001, 0.9], dtype=torch.float32)
     par0 = torch.stack([init[0].log(), init[1].log(), init[2].logit()]).double()
-    par = par0.expand(S, 3).clone().requires_grad_(True)
-    opt = torch.optim.Adam([par], lr=lr, betas=(0.9, 0.999), eps=1e-8)
-    for _ in range(n_steps):
-        opt.zero_grad()
-        loss = -loglik64(par, data, Tmax, control).sum()
-        loss.backward()
-        opt.step()
-    p = par.detach()
+    p = adam64(par0.expand(S, 3), lambda par: loglik64(par, data, Tmax, control), n_steps, lr)
     return {"ka": p[:, 0:1].exp(), "kns": p[:, 1:2].exp(), "Af": torch.sigmoid(p[:, 2:3])}
