@@ -12,5 +12,5 @@ done
 wait
 for blk in "$@"; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tapqir_amd/libtapqir_hip_stamps_$blk${SITES:+_s$SITES}.so tapqir_amd/build/tq_ksmogn.o \
-    tapqir_amd/build/tq_xtalk.o tapqir_amd/build/tq_cosmos_stamps_$blk${SITES:+_s$SITES}.o tapqir_amd/build/tq_glimpse.o tapqir_amd/build/tq_aux.o
+    tapqir_amd/build/tq_xtalk.o tapqir_amd/build/tq_cosmos_stamps_$blk${SITES:+_s$SITES}.o tapqir_amd/build/tq_glimpse.o tapqir_amd/build/tq_aux.o tapqir_amd/build/tq_kinetics.o tapqir_amd/build/tq_dwell.o
 done

@@ -68,6 +68,13 @@ class CosmosArgs(C.Structure):
     ]
 
 
+TAIL_ROWS16 = 1       # TQ_TAIL_ROWS16 (tail_kind)
+PIXEL_FUSED_UNIT = 2  # TQ_PIXEL_FUSED_UNIT (pixel_mode)
+SYNC_WORDS = 64       # TQ_SYNC_WORDS
+SUBSAMPLE_MAX = 2048  # TQ_SUBSAMPLE_MAX
+GSUM_LEN = 32         # TQ_GSUM_LEN
+
+
 class XtalkArgs(C.Structure):
     """``tq_xtalk_args`` (include/tapqir_hip.h)."""
 

@@ -18,6 +18,81 @@
 #define TQ_UNIT_BLOCK 256
 #define TQ_MAX_NGSUM (3 + 3 * TQ_MAXQ)  // >= 3 + 3*2 + 2*2 of the crosstalk model
 
+// ---- words of tq_cosmos_args.sync (TQ_SYNC_WORDS int32) -------------------------------------------------------------
+// [0] tickets, [1] first flag and [2] count-out of a minibatch launch; from word 4 the 64-bit stamp slots of a diagnostic
+// build (below); and:
+#define TQ_SYNC_LOST 63    /* workgroups that gave up waiting for a flag, ever (diagnostics; never observed) */
+#define TQ_SYNC_GAIN 62    /* the gain of a minibatch launch (float bits), published with the first flag */
+#define TQ_SYNC_FLAG2 61   /* second flag of a minibatch launch: the global draws after the gain */
+#define TQ_SYNC_CLAIM 60   /* word that names the workgroup running the tail of a minibatch launch (tail_last) */
+#define TQ_SYNC_GROUPS 40  /* counts the finished groups of the group rows */
+
+// Diagnostic stamps (scripts/build_stamps.sh: -DTQ_MB_STAMPS=<workgroup> -DTQ_MB_STAMPS_SITES=<0|1>): thread 0 of a workgroup
+// writes the 100 MHz clock into a 64-bit slot behind word 4 of `sync`.  The macros are empty in the normal build.  Slots, as
+// the readers index them (scripts/mb_dev_time.py: minibatch launch; scripts/fb_tail_time.py: sampling launch of a full batch;
+// scripts/mb_timeline.py reads a kernel trace, no slot):
+enum TqStampSlot {
+  // workgroup TQ_MB_STAMPS of tq_minibatch_kernel (mb_dev_time.py: differences of 0..5, 6 and 7 against 0)
+  TQ_ST_START = 0, TQ_ST_CATCHUP = 1, TQ_ST_SITES = 2, TQ_ST_GAIN = 3, TQ_ST_PIXEL = 4, TQ_ST_UNIT = 5, TQ_ST_TICKET = 6,
+  TQ_ST_PHASE1 = 7,
+  // the tail workgroup.  mb_dev_time.py: start / sums + global gradients / Adam / second flag.  fb_tail_time.py: start / group
+  // rows read / (about) the last sampling workgroup / global draws done
+  TQ_ST_TAIL_START = 8, TQ_ST_TAIL_SUMS = 9, TQ_ST_TAIL_ADAM = 10, TQ_ST_TAIL_DRAWN = 11,
+  TQ_ST_GSUM = 12,        // gsum complete (both readers)
+  TQ_ST_AOI = 13,         // mb_dev_time.py: per-AOI sites of rows of 16 / 20 done; fb_tail_time.py: Adam done, global draws start
+  TQ_ST_FB_GLOBALS = 7,   // fb_tail_time.py: global sites of the pending step done (the sampling launch has no TQ_ST_PHASE1)
+  TQ_ST_MAXIMA = 16,      // 16..21 maxima over the grid of the phase times and the total, 22 (time << 32 | tq_where) of the slowest
+  TQ_ST_TAIL_WHERE = 23,  // tq_where of the tail workgroup of a minibatch launch
+  TQ_ST_DETAIL = 24,      // 24..27: inside the catch-up (mb_dev_time.py CATCHUP=1) or, with TQ_MB_STAMPS_SITES=1, gradient of
+};                        // global site 0..3 done (SITES=1)
+#ifdef TQ_MB_STAMPS
+#define TQ_STAMP_SLOTS(a) ((uint64_t*)((a).sync + 4))
+// (diagnostic) where a workgroup runs: XCC (4 bits) | SE, SH, CU of HW_ID (8 bits) | block (10 bits) | ticket (10 bits)
+__device__ __forceinline__ unsigned long long tq_where(unsigned block, int ticket) {
+  uint32_t hw, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  return ((unsigned long long)(xcc & 15) << 28) | (((hw >> 8) & 0xff) << 20) | ((block & 1023) << 10) | ((unsigned)ticket & 1023);
+}
+// any kernel: thread 0 stamps `slot` (if `cond`); TQ_STAMP_BARRIER: a barrier only the stamped build needs before a stamp
+#define TQ_STAMP_IF(cond, a, slot) \
+  do { if ((cond) && threadIdx.x == 0 && (a).sync) TQ_STAMP_SLOTS(a)[slot] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define TQ_STAMP_BARRIER() __syncthreads()
+// lane 0 of a wave of the tail workgroup: gradient of global site s done
+#define TQ_STAMP_SITE(a, s) \
+  do { if (TQ_MB_STAMPS_SITES == 1 && (a).sync && (s) < 4) TQ_STAMP_SLOTS(a)[TQ_ST_DETAIL + (s)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+// tq_minibatch_kernel (they use its `a`, `tid`, `s_ticket`): every worker keeps its own stamps, workgroup TQ_MB_STAMPS
+// writes them out, and at the last one all add to the maxima over the grid
+#define TQ_MB_STAMP_LOCALS uint64_t tq_tloc[8]
+#define TQ_MB_STAMP(n)                                                                             \
+  do { if (tid == 0) {                                                                             \
+    tq_tloc[n] = __builtin_amdgcn_s_memrealtime();                                                 \
+    if (blockIdx.x == TQ_MB_STAMPS) TQ_STAMP_SLOTS(a)[n] = tq_tloc[n];                             \
+    if (n == TQ_ST_UNIT) {                                                                         \
+      unsigned long long* mx = (unsigned long long*)TQ_STAMP_SLOTS(a) + TQ_ST_MAXIMA;              \
+      for (int ph = 0; ph < 5; ++ph) atomicMax(mx + ph, (unsigned long long)(tq_tloc[ph + 1] - tq_tloc[ph])); \
+      atomicMax(mx + 5, (unsigned long long)(tq_tloc[5] - tq_tloc[0]));                            \
+      atomicMax(mx + 6, ((unsigned long long)(tq_tloc[5] - tq_tloc[0]) << 32) | tq_where(blockIdx.x, s_ticket)); \
+    }                                                                                              \
+  } } while (0)
+#define TQ_MB_STAMP_DETAIL(n) \
+  do { if (tid == 0 && blockIdx.x == TQ_MB_STAMPS) TQ_STAMP_SLOTS(a)[TQ_ST_DETAIL + n] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define TQ_MB_TAIL_STAMP(n)                                                                        \
+  do { if (tid == 0) {                                                                             \
+    TQ_STAMP_SLOTS(a)[n] = __builtin_amdgcn_s_memrealtime();                                       \
+    if (n == TQ_ST_TAIL_START) TQ_STAMP_SLOTS(a)[TQ_ST_TAIL_WHERE] = tq_where(blockIdx.x, s_ticket); \
+  } } while (0)
+#else
+#define TQ_STAMP_IF(cond, a, slot) do {} while (0)
+#define TQ_STAMP_BARRIER() do {} while (0)
+#define TQ_STAMP_SITE(a, s) do {} while (0)
+#define TQ_MB_STAMP_LOCALS do {} while (0)
+#define TQ_MB_STAMP(n) do {} while (0)
+#define TQ_MB_STAMP_DETAIL(n) do {} while (0)
+#define TQ_MB_TAIL_STAMP(n) do {} while (0)
+#endif
+#define TQ_STAMP_AT(a, slot) TQ_STAMP_IF(true, a, slot)
+
 // sum over the wave (every lane active), in every lane: DPP adds inside the four rows of 16 lanes, then the four row sums
 // read as scalars -- no LDS crossbar (six ds_bpermute per sum in the shuffle form; the fused pixel + per-unit kernel ends
 // every wave with 22 such sums)
@@ -321,9 +396,7 @@ __device__ __forceinline__ void tq_globals_from_gsum_body(const tq_cosmos_args& 
   if (lane == 0)
     for (int s = wave; s < ns; s += 4) {
       s_e[s] = tq_body_globals_grad(a, s);
-#if defined(TQ_MB_STAMPS) && TQ_MB_STAMPS_SITES == 1
-      if (a.sync && s < 4) ((uint64_t*)(a.sync + 4))[24 + s] = __builtin_amdgcn_s_memrealtime();
-#endif
+      TQ_STAMP_SITE(a, s);
     }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -441,16 +514,6 @@ static int tq_mb_upr(const tq_cosmos_args& a) {
   const int64_t r16 = ((B + 15) / 16 + 255) / 256, r20 = ((B + 19) / 20 + 255) / 256;
   return 17 * r20 < 13 * r16 ? 20 : 16;
 }
-// has_prev code of a pending step for the kernels that run its tail
-static int tq_prev_code(const tq_cosmos_args& prev) {
-  if (prev.tail_kind == TQ_TAIL_ROWS16) return tq_mb_upr(prev) == 20 ? 7 : 4;
-  return tq_rows_layout(prev) ? 3 : 1;
-}
-// units per row of a step with rows (codes 3 / 4): 16 (single-launch minibatch step), 64 (fused pixel + per-unit
-// kernel), TQ_UNIT_BLOCK (tq_unit_rows_kernel)
-__host__ __device__ __forceinline__ int tq_rows_upr(const tq_cosmos_args& a) {
-  return a.tail_kind == TQ_TAIL_ROWS16 ? 16 : (a.pixel_mode == TQ_PIXEL_FUSED_UNIT ? 64 : TQ_UNIT_BLOCK);
-}
 
 template <int K>
 __global__ __launch_bounds__(TQ_UNIT_BLOCK) void tq_unit_rows_kernel(const tq_cosmos_args a, const int64_t B) {
@@ -519,14 +582,39 @@ __global__ __launch_bounds__(TQ_UNIT_BLOCK) void tq_unit_rows_kernel(const tq_co
 #define TQ_GRP_UNITS 4096
 #define TQ_GRP_AOIS (TQ_GRP_UNITS / TQ_UNIT_BLOCK + 1)   /* AOIs a group can touch (F * C >= TQ_UNIT_BLOCK) */
 #define TQ_GGROW (2 * 16 + TQ_GRP_AOIS * 2 * TQ_MAXQ)    /* floats of a group row: 16 doubles, then 2 * TQ_MAXQ floats per AOI */
-#define TQ_SYNC_LOST 63                                  /* workgroups that gave up waiting for a flag, ever (diagnostics; never observed) */
-#define TQ_SYNC_GAIN 62                                  /* the gain of a minibatch launch (float bits), published with the first flag */
-#define TQ_SYNC_FLAG2 61                                 /* second flag of a minibatch launch: the global draws after the gain */
-#define TQ_SYNC_CLAIM 60                                 /* word that names the workgroup running the tail of a minibatch launch (tail_last) */
-#define TQ_SYNC_GROUPS 40                                /* word of tq_cosmos_args.sync that counts the finished groups */
 __host__ __device__ __forceinline__ int64_t tq_grp_count(int64_t B) { return (B + TQ_GRP_UNITS - 1) / TQ_GRP_UNITS; }
 // group rows follow the rows in blk_part (16-byte aligned)
 __host__ __device__ __forceinline__ int64_t tq_grp_base(int64_t nrows, int ncol) { return ((nrows * ncol + 3) / 4) * 4; }
+
+// The pending tail: what a launch that carries the tail of the PREVIOUS step (`prev`, the kernels' `has_prev`) finds in
+// prev's workspace and has to do before prev's global sites, total ELBO and Adam of the per-AOI / global parameters.  The
+// host picks the code (tq_prev_code, tq_prev_code_sampling), tq_sample_locals_tail_kernel and tq_minibatch_kernel act on it.
+enum TqPrevTail : int {
+  TQ_PREV_NONE = 0,     // nothing pending
+  TQ_PREV_FLAT = 1,     // flat partial sums of tq_unit_kernel + per-AOI terms of tq_aoi_kernel: cross-unit sums first
+  TQ_PREV_REDUCED = 2,  // gsum is complete (all-reduced by the caller): global sites onwards
+  TQ_PREV_ROWS = 3,     // rows of 64 / 256 units with the per-AOI sums folded in, added by the tail workgroup itself
+  TQ_PREV_ROWS16 = 4,   // rows of 16 units of a single-launch minibatch step
+  TQ_PREV_GROUPS = 6,   // as ROWS, the rows added per group of 4096 units by the idle workgroups of the sampling launch
+  TQ_PREV_ROWS20 = 7,   // as ROWS16, rows of 20 units (tq_mb_upr)
+};
+static TqPrevTail tq_prev_code(const tq_cosmos_args& prev) {
+  if (prev.tail_kind == TQ_TAIL_ROWS16) return tq_mb_upr(prev) == 20 ? TQ_PREV_ROWS20 : TQ_PREV_ROWS16;
+  return tq_rows_layout(prev) ? TQ_PREV_ROWS : TQ_PREV_FLAT;
+}
+// ... in a sampling launch whose grid rows have `grid_x` workgroups: rows of 64 / 256 units are added per group by the idle
+// workgroups of the first grid row (tq_group_reduce_rows) where that row has one for every group
+static TqPrevTail tq_prev_code_sampling(const tq_cosmos_args* prev, int64_t grid_x) {
+  if (!prev) return TQ_PREV_NONE;
+  const TqPrevTail code = tq_prev_code(*prev);
+  return code == TQ_PREV_ROWS && prev->sync && tq_grp_count(tq_batch_units(*prev)) + 1 <= grid_x ? TQ_PREV_GROUPS : code;
+}
+// units per row of a step with rows: 16 (single-launch minibatch step; its rows hold tq_mb_rows_upr units), 64 (fused pixel
+// + per-unit kernel), TQ_UNIT_BLOCK (tq_unit_rows_kernel)
+__host__ __device__ __forceinline__ int tq_rows_upr(const tq_cosmos_args& a) {
+  return a.tail_kind == TQ_TAIL_ROWS16 ? 16 : (a.pixel_mode == TQ_PIXEL_FUSED_UNIT ? 64 : TQ_UNIT_BLOCK);
+}
+__device__ __forceinline__ int tq_mb_rows_upr(int has_prev) { return has_prev == TQ_PREV_ROWS20 ? 20 : 16; }
 
 // one wave: rows of group g of step `a` -> group row g (published); returns (lane 0) how many groups had been published before
 __device__ __forceinline__ int tq_group_reduce_rows(const tq_cosmos_args& a, const int g) {
@@ -710,9 +798,7 @@ __device__ __forceinline__ void tq_rows_reduce_globals_body(const tq_cosmos_args
         acc[TQ_GS_ELBO] += (double)e;
       }
     }
-#ifdef TQ_MB_STAMPS
-    if (threadIdx.x == 0) ((uint64_t*)(a.sync + 4))[13] = __builtin_amdgcn_s_memrealtime();
-#endif
+    TQ_STAMP_AT(a, TQ_ST_AOI);
   } else {
     for (int ac = threadIdx.x; ac < nac; ac += 256) {
       const uint32_t ai = (uint32_t)ac / (uint32_t)a.C;  // position of the AOI in the batch
@@ -760,9 +846,7 @@ __device__ __forceinline__ void tq_rows_reduce_globals_body(const tq_cosmos_args
   if (threadIdx.x < nq) a.gsum[threadIdx.x] = s_w[0][threadIdx.x] + s_w[1][threadIdx.x] + s_w[2][threadIdx.x] + s_w[3][threadIdx.x];
   __threadfence_block();
   __syncthreads();
-#ifdef TQ_MB_STAMPS
-  if (threadIdx.x == 0 && a.sync) ((uint64_t*)(a.sync + 4))[12] = __builtin_amdgcn_s_memrealtime();
-#endif
+  TQ_STAMP_AT(a, TQ_ST_GSUM);
   if (with_globals) tq_globals_from_gsum_body(a, s_e);
 }
 
@@ -825,9 +909,7 @@ __device__ __forceinline__ bool tq_groups_sums_body(const tq_cosmos_args& a, dou
     for (int j = 0; j < TQ_MAX_NGSUM; ++j)
       if (j < nq) acc[j] += ldd(p + j);
   }
-#ifdef TQ_MB_STAMPS
-  if (threadIdx.x == 0 && a.sync) ((uint64_t*)(a.sync + 4))[9] = __builtin_amdgcn_s_memrealtime();
-#endif
+  TQ_STAMP_AT(a, TQ_ST_TAIL_SUMS);
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
@@ -844,9 +926,7 @@ __device__ __forceinline__ bool tq_groups_reduce_globals_body(const tq_cosmos_ar
   if (!tq_groups_sums_body<true>(a, s_w)) return false;
   __threadfence_block();
   __syncthreads();
-#ifdef TQ_MB_STAMPS
-  if (threadIdx.x == 0 && a.sync) ((uint64_t*)(a.sync + 4))[12] = __builtin_amdgcn_s_memrealtime();
-#endif
+  TQ_STAMP_AT(a, TQ_ST_GSUM);
   tq_globals_from_gsum_body(a, s_e);
   return true;
 }
@@ -886,55 +966,42 @@ __global__ __launch_bounds__(256) void tq_rows_reduce_globals_kernel(const tq_co
 // kernel had to be built for three waves -- c2 step 0.248 -> 0.235 ms, 0.320 -> 0.288 ms in the regime of a converged fit).
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void tq_sample_locals_tail_kernel(
     const tq_cosmos_args a, const tq_cosmos_args prev, const int has_prev, const int64_t B, const int site_begin) {
-  // has_prev: 0 = nothing pending, 1 = the whole tail of `prev` (cross-unit sums first; 3 = the same from rows of 64 / 256 units
-  // with the per-AOI sites folded in; 6 = the same with the rows added per group of 4096 units by the other workgroups of
-  // this grid row), 2 = gsum of `prev` is complete (all-reduced by the caller): global sites onwards
+  // has_prev: a TqPrevTail code
   if (blockIdx.y == 0) {
     if (blockIdx.x != 0) {
-      // has_prev == 6: workgroup 1 + g adds the rows of group g of `prev` for the tail workgroup (one wave; the others leave)
-      if (has_prev == 6 && (int64_t)blockIdx.x <= tq_grp_count(tq_batch_units(prev)) && threadIdx.x < 64)
+      // workgroup 1 + g adds the rows of group g of `prev` for the tail workgroup (one wave; the others leave)
+      if (has_prev == TQ_PREV_GROUPS && (int64_t)blockIdx.x <= tq_grp_count(tq_batch_units(prev)) && threadIdx.x < 64)
         tq_group_reduce_rows(prev, (int)blockIdx.x - 1);
       return;
     }
     __shared__ double s_w[4][TQ_MAX_NGSUM];
     __shared__ double s_e[TQ_NGSITES(TQ_MAXQ)];
-#ifdef TQ_MB_STAMPS  // (diagnostic build, scripts/fb_tail_time.py: how long the tail workgroup of a full-batch step lives)
-    if (threadIdx.x == 0 && a.sync) ((uint64_t*)(a.sync + 4))[8] = __builtin_amdgcn_s_memrealtime();
-#endif
+    TQ_STAMP_AT(a, TQ_ST_TAIL_START);
     if (has_prev) {
       const int64_t Bp = tq_batch_units(prev);
-      if (has_prev == 3) tq_rows_reduce_globals_body<TQ_UNIT_BLOCK>(prev, s_w, s_e);
-      else if (has_prev == 6) {
+      if (has_prev == TQ_PREV_ROWS) tq_rows_reduce_globals_body<TQ_UNIT_BLOCK>(prev, s_w, s_e);
+      else if (has_prev == TQ_PREV_GROUPS) {
         if (!tq_groups_reduce_globals_body(prev, s_w, s_e) && threadIdx.x == 0) prev.elbo_out[0] = __builtin_nan("");
-      } else if (has_prev == 1) tq_reduce_globals_body(prev, (Bp + TQ_UNIT_BLOCK - 1) / TQ_UNIT_BLOCK, Bp, s_w, s_e);
+      } else if (has_prev == TQ_PREV_FLAT) tq_reduce_globals_body(prev, (Bp + TQ_UNIT_BLOCK - 1) / TQ_UNIT_BLOCK, Bp, s_w, s_e);
       else tq_globals_from_gsum_body(prev, s_e);
       __syncthreads();
-#ifdef TQ_MB_STAMPS
-      if (threadIdx.x == 0 && a.sync) ((uint64_t*)(a.sync + 4))[7] = __builtin_amdgcn_s_memrealtime();
-#endif
+      TQ_STAMP_AT(a, TQ_ST_FB_GLOBALS);
       const int64_t total = tq_num_params(prev);
       for (int64_t j = tq_aoi_base(prev) + threadIdx.x; j < total; j += 256) tq_body_adam(prev, j);
       __threadfence();
       __syncthreads();
     }
-#ifdef TQ_MB_STAMPS
-    if (threadIdx.x == 0 && a.sync) ((uint64_t*)(a.sync + 4))[13] = __builtin_amdgcn_s_memrealtime();
-#endif
+    TQ_STAMP_AT(a, TQ_ST_AOI);
     const int ns = tq_num_gsites(a);
     if ((threadIdx.x & 63) == 0)
       for (int s = threadIdx.x >> 6; s < ns; s += 4) tq_body_sample_globals(a, s);
-#ifdef TQ_MB_STAMPS
-    __syncthreads();
-    if (threadIdx.x == 0 && a.sync) ((uint64_t*)(a.sync + 4))[11] = __builtin_amdgcn_s_memrealtime();
-#endif
+    TQ_STAMP_BARRIER();
+    TQ_STAMP_AT(a, TQ_ST_TAIL_DRAWN);
     return;
   }
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   tq_sample_site_wg(a, site_begin + (int)blockIdx.y - 1, i, B);
-#ifdef TQ_MB_STAMPS
-  if (blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1 && threadIdx.x == 0 && a.sync)
-    ((uint64_t*)(a.sync + 4))[10] = __builtin_amdgcn_s_memrealtime();  // (about) the last sampling workgroup
-#endif
+  TQ_STAMP_IF(blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1, a, TQ_ST_TAIL_ADAM);  // (about) the last sampling workgroup
 }
 
 
@@ -1095,15 +1162,6 @@ __device__ __forceinline__ void tq_adam_replay_split(const tq_cosmos_args& a, in
   }
 }
 
-#ifdef TQ_MB_STAMPS
-// (diagnostic) where a workgroup runs: XCC (4 bits) | SE, SH, CU of HW_ID (8 bits) | block (10 bits) | ticket (10 bits)
-__device__ __forceinline__ unsigned long long tq_where(unsigned block, int ticket) {
-  uint32_t hw, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  return ((unsigned long long)(xcc & 15) << 28) | (((hw >> 8) & 0xff) << 20) | ((block & 1023) << 10) | ((unsigned)ticket & 1023);
-}
-#endif
 template <int K, bool ONE, int U>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void tq_minibatch_kernel(
     const tq_cosmos_args a, const tq_cosmos_args prev, const int has_prev, const tq_ksmogn_args k, const int64_t B,
@@ -1112,38 +1170,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
   __shared__ int s_ticket, s_ok, s_role;
   __shared__ float s_part[4][TQ_ROWS_MAXCOL];
   const int tid = threadIdx.x;
-#ifdef TQ_MB_STAMPS
-  uint64_t tq_tloc[8];  // (every workgroup keeps its own stamps too: maxima over the grid at stamp 5, words 16..21)
-#define TQ_STAMP(n)                                                                   \
-  if (tid == 0) {                                                                     \
-    tq_tloc[n] = __builtin_amdgcn_s_memrealtime();                                    \
-    if (blockIdx.x == TQ_MB_STAMPS) ((uint64_t*)(a.sync + 4))[n] = tq_tloc[n];        \
-    if (n == 5) {                                                                     \
-      unsigned long long* mx = (unsigned long long*)(a.sync + 4) + 16;                \
-      atomicMax(mx + 0, (unsigned long long)(tq_tloc[1] - tq_tloc[0]));               \
-      atomicMax(mx + 1, (unsigned long long)(tq_tloc[2] - tq_tloc[1]));               \
-      atomicMax(mx + 2, (unsigned long long)(tq_tloc[3] - tq_tloc[2]));               \
-      atomicMax(mx + 3, (unsigned long long)(tq_tloc[4] - tq_tloc[3]));               \
-      atomicMax(mx + 4, (unsigned long long)(tq_tloc[5] - tq_tloc[4]));               \
-      atomicMax(mx + 5, (unsigned long long)(tq_tloc[5] - tq_tloc[0]));               \
-      atomicMax(mx + 6, ((unsigned long long)(tq_tloc[5] - tq_tloc[0]) << 32) | tq_where(blockIdx.x, s_ticket)); \
-    }                                                                                 \
-  }
-#define TQ_STAMP2(n) if (tid == 0 && blockIdx.x == TQ_MB_STAMPS) ((uint64_t*)(a.sync + 4))[24 + n] = __builtin_amdgcn_s_memrealtime();
-#define TQ_TAIL_STAMP(n)                                                                     \
-  if (tid == 0) {                                                                            \
-    ((uint64_t*)(a.sync + 4))[n] = __builtin_amdgcn_s_memrealtime();                         \
-    if (n == 8) ((uint64_t*)(a.sync + 4))[23] = tq_where(blockIdx.x, s_ticket);              \
-  }
-#else
-#define TQ_STAMP(n)
-#define TQ_STAMP2(n)
-#define TQ_TAIL_STAMP(n)
-#endif
-  TQ_STAMP(0)
+  TQ_MB_STAMP_LOCALS;
+  TQ_MB_STAMP(TQ_ST_START);
   if (tid == 0) s_ticket = __hip_atomic_fetch_add(&a.sync[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
-  TQ_STAMP(6)
+  TQ_MB_STAMP(TQ_ST_TICKET);
   const int ticket = s_ticket;
   const int flag_value = a.sync_value;
   // every workgroup counts itself out exactly once; the last one re-arms the ticket counter for the next launch
@@ -1202,7 +1233,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
   if (is_tail) {  // the extra workgroup of the grid: owns no units
     __shared__ double s_w[4][TQ_MAX_NGSUM];
     __shared__ double s_e[TQ_NGSITES(TQ_MAXQ)];
-    TQ_TAIL_STAMP(8)
+    TQ_MB_TAIL_STAMP(TQ_ST_TAIL_START);
     // The workers need the GAIN of this step before their likelihood phase and the other global draws (tables of pi, lamda,
     // proximity) only in the per-unit phase after it: the gain's chain -- gradient of its site, Adam of its two
     // parameters, the draw -- runs on wave 0 by itself and is published first (sync[1]); the other sites' gradients
@@ -1211,8 +1242,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
     const int lane = tid & 63, wave = tid >> 6;
     if (has_prev) {
       const int64_t Bp = tq_batch_units(prev);
-      if (has_prev == 3) tq_rows_reduce_globals_body<TQ_UNIT_BLOCK>(prev, s_w, s_e, 16, false);
-      else if (has_prev == 4 || has_prev == 7) tq_rows_reduce_globals_body<16>(prev, s_w, s_e, has_prev == 7 ? 20 : 16, false);
+      if (has_prev == TQ_PREV_ROWS) tq_rows_reduce_globals_body<TQ_UNIT_BLOCK>(prev, s_w, s_e, 16, false);
+      else if (has_prev == TQ_PREV_ROWS16 || has_prev == TQ_PREV_ROWS20) tq_rows_reduce_globals_body<16>(prev, s_w, s_e, tq_mb_rows_upr(has_prev), false);
       else tq_reduce_globals_body(prev, (Bp + TQ_UNIT_BLOCK - 1) / TQ_UNIT_BLOCK, Bp, s_w, s_e, false);
       // (the bodies end with gsum stored, a workgroup-scope fence and a barrier)
       if (lane == 0) {
@@ -1241,7 +1272,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
       }
     }
     __syncthreads();
-    TQ_TAIL_STAMP(9)
+    TQ_MB_TAIL_STAMP(TQ_ST_TAIL_SUMS);
     if (has_prev) {
       if (tid == 0) {  // total ELBO of the previous step (as tq_globals_from_gsum_body)
         const int nsp = tq_num_gsites(prev);
@@ -1255,7 +1286,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
       __threadfence_block();
       __syncthreads();
     }
-    TQ_TAIL_STAMP(10)
+    TQ_MB_TAIL_STAMP(TQ_ST_TAIL_ADAM);
     const int ns = tq_num_gsites(a);
     if (lane == 0)
       for (int sg = 1 + wave; sg < ns; sg += 4) tq_body_sample_globals(a, sg);
@@ -1266,7 +1297,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __hip_atomic_store(&a.sync[TQ_SYNC_FLAG2], flag_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    TQ_TAIL_STAMP(11)
+    TQ_MB_TAIL_STAMP(TQ_ST_TAIL_DRAWN);
     // the NEXT step's subsample (nobody waits for it: the next launch reads it)
     if (a.next_ndx && a.nb < a.Nt) {
       tq_draw_subsample((int*)smem, a.seed, a.step + 1, TQ_SITE_SUBSAMPLE_N, a.Nt, a.nb, a.next_ndx);
@@ -1281,7 +1312,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
   const int64_t u0 = wblk * U;
   const int64_t u_end = u0 + U < B ? u0 + U : B;
   constexpr int NL = TQ_NLOCAL(K), NS = 1 + 4 * K;
-  TQ_STAMP(7)
+  TQ_MB_STAMP(TQ_ST_PHASE1);
   if (a.last_step) {
     // per-step bias-correction factors of the last TQ_BIAS_TABLE_STEPS steps, shared by every element of the workgroup
     __shared__ float s_bias[2 * TQ_BIAS_TABLE_STEPS];
@@ -1325,19 +1356,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
         pw2 *= b2_256;
       }
     }
-    TQ_STAMP2(0)
+    TQ_MB_STAMP_DETAIL(0);
     __syncthreads();
-    TQ_STAMP2(1)
+    TQ_MB_STAMP_DETAIL(1);
 #pragma unroll
     for (int q = 0; q < NPASS; ++q) {
       if (G > 1 && q == NPASS - 1) tq_adam_replay_split<G>(a, ej[q], es0[q], s1, s_bias, T0, ep[q], em[q], ev[q], tid % G);
       else if (ej[q] >= 0) tq_adam_replay_tab_given(a, ej[q], es0[q], s1, s_bias, T0, ep[q], em[q], ev[q]);
-      if (q == 0) { TQ_STAMP2(2) }
+      if (q == 0) { TQ_MB_STAMP_DETAIL(2); }
     }
-    TQ_STAMP2(3)
+    TQ_MB_STAMP_DETAIL(3);
     __syncthreads();
   }
-  TQ_STAMP(1)
+  TQ_MB_STAMP(TQ_ST_CATCHUP);
   if constexpr (K <= 3 && (K + 1) * U <= 64) {
     // one KIND of site per wave -- wave 0 the K+1 Gamma sites (background, heights), waves 1..3 the width / x / y sites --
     // so that no wave runs the Gamma code and then the Beta code (with its regimes) for different lanes
@@ -1353,7 +1384,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
     }
   }
   __syncthreads();
-  TQ_STAMP(2)
+  TQ_MB_STAMP(TQ_ST_SITES);
   // ---- wait for the gain of this step (bounded: ~2 s of the 100 MHz wall clock) ----
   __shared__ float s_gain;
   auto wait_flag = [&](int word) {
@@ -1397,7 +1428,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
     step_lost();
     return;
   }
-  TQ_STAMP(3)
+  TQ_MB_STAMP(TQ_ST_GAIN);
   // ---- phase 2: likelihood of the U units (reads the draws of phase 1 and the gain): sixteen of them with 16 lanes each,
   // and of U = 20 the last four with a wave each (tq_mb_upr: why 20)
   tq_ksmogn_args kw = k;
@@ -1413,7 +1444,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
     step_lost();
     return;
   }
-  TQ_STAMP(4)
+  TQ_MB_STAMP(TQ_ST_PIXEL);
   // ---- phase 3: per-unit terms + Adam, one lane per unit; row of partial sums ----
   const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
   float part[TQ_MAX_NGSUM], aoi[TQ_ROWS_GCOL];
@@ -1460,14 +1491,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
     const float sum = used ? (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]) : 0.0f;
     a.blk_part[wblk * ncol + tid] = sum;
   }
-  TQ_STAMP(5)
+  TQ_MB_STAMP(TQ_ST_UNIT);
   // the last workgroup to get here re-arms the ticket counter for the next launch (the flag holds the step number)
   if (tid == 0) count_out();
 }
 
 
 // ---------------------------------------------------------------------------------------------------------
-static int check_args(const tq_cosmos_args* a, const char* who) {
+static int check_args(const tq_cosmos_args* a) {
   if (!a || !a->params || !a->globals || !a->gbase) {
     tq_set_error("tq_cosmos_*: NULL args/params/globals/gbase");
     return TQ_ERR_ARG;
@@ -1489,7 +1520,6 @@ static int check_args(const tq_cosmos_args* a, const char* who) {
     tq_set_error("tq_cosmos_*: the crosstalk model is implemented for Q = C = 2 and K <= 2");
     return TQ_ERR_ARG;
   }
-  (void)who;
   return TQ_OK;
 }
 
@@ -1504,13 +1534,13 @@ extern "C" int64_t tq_crosstalk_param_count(int32_t Nt, int32_t F, int32_t C, in
 }
 
 extern "C" int tq_cosmos_sample_globals(const tq_cosmos_args* a, void* stream) {
-  if (int rc = check_args(a, "sample_globals")) return rc;
+  if (int rc = check_args(a)) return rc;
   hipLaunchKernelGGL(tq_sample_globals_kernel, dim3(tq_num_gsites(*a)), dim3(64), 0, (hipStream_t)stream, *a);
   return tq_launch_status("tq_sample_globals_kernel");
 }
 
 extern "C" int tq_cosmos_sample_locals(const tq_cosmos_args* a, void* stream) {
-  if (int rc = check_args(a, "sample_locals")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (!a->lat || !a->site) {
     tq_set_error("tq_cosmos_sample_locals: lat or site is NULL");
     return TQ_ERR_ARG;
@@ -1521,8 +1551,9 @@ extern "C" int tq_cosmos_sample_locals(const tq_cosmos_args* a, void* stream) {
   return tq_launch_status("tq_sample_locals_kernel");
 }
 
-// argument block of the likelihood kernel of a cosmos step
-static tq_ksmogn_args cosmos_ksmogn_args(const tq_cosmos_args* a) {
+// argument block of the likelihood kernel of a cosmos step: the one place that knows the row order of `lat` and `pix`
+// (pix_end: the first row of `pix` behind the cosmos block, where the crosstalk model's rows follow)
+static tq_ksmogn_args cosmos_ksmogn_args(const tq_cosmos_args* a, float** pix_end = nullptr) {
   const int K = a->K, M = 1 << K;
   const int64_t B = tq_batch_units(*a), U = tq_num_units(*a);
   tq_ksmogn_args k = {};
@@ -1550,6 +1581,7 @@ static tq_ksmogn_args cosmos_ksmogn_args(const tq_cosmos_args* a) {
   k.g_width = a->pix + (int64_t)(M + 2 + K) * B;
   k.g_x = a->pix + (int64_t)(M + 2 + 2 * K) * B;
   k.g_y = a->pix + (int64_t)(M + 2 + 3 * K) * B;
+  if (pix_end) *pix_end = a->pix + (int64_t)(M + 2 + 4 * K) * B;
   k.nb = a->nb; k.fb = a->fb; k.C = a->C; k.F = a->F; k.P = a->P; k.K = K; k.O = a->O;
   k.scale = a->scale;
   k.images_by_slot = a->images_by_slot;
@@ -1558,9 +1590,9 @@ static tq_ksmogn_args cosmos_ksmogn_args(const tq_cosmos_args* a) {
 
 // pixel kernel of a step: fused render + log-likelihood + pathwise gradients, Dice weights from m_probs
 static int launch_likelihood(const tq_cosmos_args* a, void* stream) {
-  const int K = a->K, M = 1 << K;
   const int64_t B = tq_batch_units(*a), U = tq_num_units(*a);
-  tq_ksmogn_args k = cosmos_ksmogn_args(a);
+  float* pix_end;
+  tq_ksmogn_args k = cosmos_ksmogn_args(a, &pix_end);
   if (a->crosstalk) {
     // one data site per AOI-frame, all dyes in every channel: per-dye marginal likelihoods go where the cosmos
     // per-unit routine expects ll, two more row groups follow the cosmos block of pix
@@ -1574,11 +1606,11 @@ static int launch_likelihood(const tq_cosmos_args* a, void* stream) {
     x.offset_samples = a->offset_samples; x.offset_logits = a->offset_logits;
     x.gout = nullptr; x.m_logit = a->params; x.m_kstride = U; x.aoi_mask = a->aoi_mask;
     x.ll_joint = nullptr; x.ll = a->pix;
-    x.ell_excess = a->pix + (int64_t)(M + 2 + 4 * K) * B;
-    x.g_alpha = a->pix + (int64_t)(M + 3 + 4 * K) * B;
+    x.ell_excess = pix_end;  // one row, then C rows of g_alpha
+    x.g_alpha = pix_end + B;
     x.g_background = k.g_background; x.g_gain = k.g_gain;
     x.g_height = k.g_height; x.g_width = k.g_width; x.g_x = k.g_x; x.g_y = k.g_y;
-    x.nb = a->nb; x.fb = a->fb; x.C = a->C; x.F = a->F; x.P = a->P; x.K = K; x.O = a->O;
+    x.nb = a->nb; x.fb = a->fb; x.C = a->C; x.F = a->F; x.P = a->P; x.K = a->K; x.O = a->O;
     x.scale = a->scale;
     return tq_ksmogn_crosstalk_log_prob(&x, stream);
   }
@@ -1587,10 +1619,10 @@ static int launch_likelihood(const tq_cosmos_args* a, void* stream) {
 
 static int launch_pixel_unit(const tq_cosmos_args* a, void* stream) {
   const int64_t B = tq_batch_units(*a);
-
   const tq_ksmogn_args k = cosmos_ksmogn_args(a);
   const dim3 grid((unsigned)((B + 63) / 64)), block(64);
   hipStream_t st = (hipStream_t)stream;
+  // (not TQ_SWITCH_K: the kernel exists for K <= 2 only, tq_fused_pixel_unit)
   if (a->K == 1) {
     if (a->P == 14) hipLaunchKernelGGL((tq_pixel_unit_kernel<1, 14>), grid, block, 0, st, k, *a, B);
     else hipLaunchKernelGGL((tq_pixel_unit_kernel<1, 20>), grid, block, 0, st, k, *a, B);
@@ -1614,14 +1646,13 @@ static int launch_rows_sums(const tq_cosmos_args* a, hipStream_t st) {
 // rows: AOI-aligned per-unit kernel whose tail also finishes the per-AOI sites (tq_unit_rows_kernel; full-batch steps
 // that finish with tq_cosmos_tail or inside the next tq_cosmos_step_overlapped)
 static int elbo_grads_impl(const tq_cosmos_args* a, void* stream, bool finish_sums, bool rows = false) {
-  if (int rc = check_args(a, "elbo_grads")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (!a->images || !a->xy || !a->is_ontarget || !a->offset_samples || !a->offset_logits || !a->grad || !a->lat ||
       !a->site || !a->pix || (!rows && !a->aoi_part) || !a->blk_part || !a->gsum) {
     tq_set_error("tq_cosmos_elbo_grads: NULL required pointer");
     return TQ_ERR_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
-  const int K = a->K;
   const int64_t B = tq_batch_units(*a);
   if (a->pixel_mode == TQ_PIXEL_FUSED_UNIT) {  // pixel + per-unit kernel in one launch (rows of 64 units)
     if (!rows || !tq_fused_pixel_unit(*a)) {
@@ -1637,23 +1668,13 @@ static int elbo_grads_impl(const tq_cosmos_args* a, void* stream, bool finish_su
   // 2. per-unit sites
   if (rows) {
     const dim3 grid((unsigned)tq_cosmos_nblk(B)), block(TQ_UNIT_BLOCK);
-    switch (K) {
-      case 1: hipLaunchKernelGGL((tq_unit_rows_kernel<1>), grid, block, 0, st, *a, B); break;
-      case 2: hipLaunchKernelGGL((tq_unit_rows_kernel<2>), grid, block, 0, st, *a, B); break;
-      case 3: hipLaunchKernelGGL((tq_unit_rows_kernel<3>), grid, block, 0, st, *a, B); break;
-      default: hipLaunchKernelGGL((tq_unit_rows_kernel<4>), grid, block, 0, st, *a, B); break;
-    }
+    TQ_SWITCH_K(a->K, hipLaunchKernelGGL((tq_unit_rows_kernel<KK>), grid, block, 0, st, *a, B));
     if (int rc = tq_launch_status("tq_unit_rows_kernel")) return rc;
     return finish_sums ? launch_rows_sums(a, st) : TQ_OK;
   }
   const int64_t nblk = tq_cosmos_nblk(B);
   const dim3 grid((unsigned)nblk), block(TQ_UNIT_BLOCK);
-  switch (K) {
-    case 1: hipLaunchKernelGGL((tq_unit_kernel<1>), grid, block, 0, st, *a, B); break;
-    case 2: hipLaunchKernelGGL((tq_unit_kernel<2>), grid, block, 0, st, *a, B); break;
-    case 3: hipLaunchKernelGGL((tq_unit_kernel<3>), grid, block, 0, st, *a, B); break;
-    default: hipLaunchKernelGGL((tq_unit_kernel<4>), grid, block, 0, st, *a, B); break;
-  }
+  TQ_SWITCH_K(a->K, hipLaunchKernelGGL((tq_unit_kernel<KK>), grid, block, 0, st, *a, B));
   if (int rc = tq_launch_status("tq_unit_kernel")) return rc;
   // 3. per-AOI sites
   hipLaunchKernelGGL(tq_aoi_kernel, dim3((unsigned)(a->nb * a->C)), dim3(256), 0, st, *a, B);
@@ -1671,7 +1692,7 @@ extern "C" int tq_cosmos_elbo_grads(const tq_cosmos_args* a, void* stream) {
 }
 
 extern "C" int tq_cosmos_pixel_unit(const tq_cosmos_args* a, void* stream) {
-  if (int rc = check_args(a, "pixel_unit")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (a->pixel_mode != TQ_PIXEL_FUSED_UNIT) {
     tq_set_error("tq_cosmos_pixel_unit: pixel_mode must be TQ_PIXEL_FUSED_UNIT");
     return TQ_ERR_ARG;
@@ -1680,7 +1701,7 @@ extern "C" int tq_cosmos_pixel_unit(const tq_cosmos_args* a, void* stream) {
 }
 
 extern "C" int tq_cosmos_globals_grad(const tq_cosmos_args* a, void* stream) {
-  if (int rc = check_args(a, "globals_grad")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (!a->grad || !a->gsum || !a->elbo_out) {
     tq_set_error("tq_cosmos_globals_grad: NULL required pointer");
     return TQ_ERR_ARG;
@@ -1695,7 +1716,7 @@ extern "C" int tq_cosmos_globals_grad(const tq_cosmos_args* a, void* stream) {
 }
 
 extern "C" int tq_cosmos_adam(const tq_cosmos_args* a, void* stream) {
-  if (int rc = check_args(a, "adam")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (!a->grad || !a->exp_avg || !a->exp_avg_sq) {
     tq_set_error("tq_cosmos_adam: NULL required pointer");
     return TQ_ERR_ARG;
@@ -1710,7 +1731,7 @@ extern "C" int tq_cosmos_adam(const tq_cosmos_args* a, void* stream) {
 }
 
 extern "C" int tq_cosmos_adam_catchup(const tq_cosmos_args* a, int32_t all_units, void* stream) {
-  if (int rc = check_args(a, "adam_catchup")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (!a->last_step || !a->exp_avg || !a->exp_avg_sq) {
     tq_set_error("tq_cosmos_adam_catchup: NULL required pointer (last_step, exp_avg, exp_avg_sq)");
     return TQ_ERR_ARG;
@@ -1738,7 +1759,7 @@ static int launch_reduce_globals(const tq_cosmos_args* a, hipStream_t st) {
 }
 
 extern "C" int tq_cosmos_tail(const tq_cosmos_args* a, void* stream) {
-  if (int rc = check_args(a, "tail")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (a->tail_kind != TQ_TAIL_ROWS16 && tq_rows_layout(*a) && a->fuse_adam && a->sync && a->aoi_part) {
     // rows of 64 or 256 units: the per-AOI frame sums span up to F C / 64 rows each -- added per group of 4096 units
     // (tq_group_sums_kernel) instead of by one workgroup walking all of them, then the global sites + tail Adam
@@ -1750,9 +1771,9 @@ extern "C" int tq_cosmos_tail(const tq_cosmos_args* a, void* stream) {
 }
 
 extern "C" int tq_cosmos_tail_reduced(const tq_cosmos_args* a, const tq_cosmos_args* next, void* stream) {
-  if (int rc = check_args(a, "tail_reduced")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (next)
-    if (int rc = check_args(next, "tail_reduced (next)")) return rc;
+    if (int rc = check_args(next)) return rc;
   if (!a->grad || !a->gsum || !a->elbo_out || !a->exp_avg || !a->exp_avg_sq) {
     tq_set_error("tq_cosmos_tail_reduced: NULL required pointer");
     return TQ_ERR_ARG;
@@ -1767,7 +1788,7 @@ extern "C" int tq_cosmos_tail_reduced(const tq_cosmos_args* a, const tq_cosmos_a
 }
 
 extern "C" int tq_cosmos_step(const tq_cosmos_args* a, void* stream) {
-  if (int rc = check_args(a, "step")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (int rc = tq_cosmos_sample_globals(a, stream)) return rc;
   if (int rc = tq_cosmos_sample_locals(a, stream)) return rc;
   if (int rc = elbo_grads_impl(a, stream, false, tq_rows_layout(*a))) return rc;
@@ -1775,9 +1796,9 @@ extern "C" int tq_cosmos_step(const tq_cosmos_args* a, void* stream) {
 }
 
 extern "C" int tq_cosmos_step_overlapped(const tq_cosmos_args* a, const tq_cosmos_args* prev, void* stream) {
-  if (int rc = check_args(a, "step_overlapped")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (prev)
-    if (int rc = check_args(prev, "step_overlapped (prev)")) return rc;
+    if (int rc = check_args(prev)) return rc;
   if (!a->fuse_adam || (prev && !prev->fuse_adam)) {
     tq_set_error("tq_cosmos_step_overlapped: full-batch steps with fuse_adam only (the next step's local sampling must not depend on the pending tail)");
     return TQ_ERR_ARG;
@@ -1795,12 +1816,9 @@ extern "C" int tq_cosmos_step_overlapped(const tq_cosmos_args* a, const tq_cosmo
     if (int rc = tq_cosmos_tail(prev, stream)) return rc;
     prev = nullptr;
   }
-  int code = prev ? tq_prev_code(*prev) : 0;
-  // rows of 64 / 256 units: the idle workgroups of the launch's first grid row add them per group (tq_group_reduce_rows);
-  // code 3 stays for grids too small for that
-  if (code == 3 && prev->sync && tq_grp_count(tq_batch_units(*prev)) + 1 <= (B + 255) / 256) code = 6;
-  hipLaunchKernelGGL(tq_sample_locals_tail_kernel, dim3((unsigned)((B + 255) / 256), (unsigned)(2 + 4 * a->K)), dim3(256), 0,
-                     (hipStream_t)stream, *a, prev ? *prev : *a, code, B, 0);
+  const int64_t gx = (B + 255) / 256;
+  hipLaunchKernelGGL(tq_sample_locals_tail_kernel, dim3((unsigned)gx, (unsigned)(2 + 4 * a->K)), dim3(256), 0,
+                     (hipStream_t)stream, *a, prev ? *prev : *a, (int)tq_prev_code_sampling(prev, gx), B, 0);
   if (int rc = tq_launch_status("tq_sample_locals_tail_kernel")) return rc;
   return elbo_grads_impl(a, stream, false, tq_rows_layout(*a));
 }
@@ -1818,9 +1836,9 @@ extern "C" int64_t tq_cosmos_blk_floats(int32_t Nt, int32_t F, int32_t C, int32_
 
 
 extern "C" int tq_cosmos_minibatch_step(const tq_cosmos_args* a, const tq_cosmos_args* prev, void* stream) {
-  if (int rc = check_args(a, "minibatch_step")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (prev)
-    if (int rc = check_args(prev, "minibatch_step (prev)")) return rc;
+    if (int rc = check_args(prev)) return rc;
   if (a->crosstalk || !a->fuse_adam || (prev && !prev->fuse_adam) || (int64_t)a->fb * a->C < TQ_UNITS_PER_BLOCK) {
     tq_set_error("tq_cosmos_minibatch_step: cosmos steps with fuse_adam and at least 16 units per AOI only");
     return TQ_ERR_ARG;
@@ -1828,7 +1846,7 @@ extern "C" int tq_cosmos_minibatch_step(const tq_cosmos_args* a, const tq_cosmos
   if (!a->images || !a->xy || !a->is_ontarget || !a->offset_samples || !a->offset_logits || !a->lat || !a->site || !a->pix ||
       !a->blk_part || !a->gsum || !a->elbo_out || !a->exp_avg || !a->exp_avg_sq || !a->grad || !a->sync ||
       (prev && (!prev->grad || !prev->gsum || !prev->elbo_out || !prev->exp_avg || !prev->exp_avg_sq || !prev->blk_part ||
-                (tq_prev_code(*prev) == 1 && !prev->aoi_part)))) {
+                (tq_prev_code(*prev) == TQ_PREV_FLAT && !prev->aoi_part)))) {
     tq_set_error("tq_cosmos_minibatch_step: NULL required pointer");
     return TQ_ERR_ARG;
   }
@@ -1848,24 +1866,17 @@ extern "C" int tq_cosmos_minibatch_step(const tq_cosmos_args* a, const tq_cosmos
     const size_t sel = sizeof(int) * (2048 + 8);  // tq_draw_subsample: histogram of 2048 bins + scan / boundary words
     if (lds < sel) lds = sel;
   }
-  const int code = prev ? tq_prev_code(*prev) : 0;
+  const int code = prev ? tq_prev_code(*prev) : TQ_PREV_NONE;
   const tq_cosmos_args& pv = prev ? *prev : *a;
   hipStream_t st = (hipStream_t)stream;
-#define TQ_MB_LAUNCH(KK)                                                                                                 \
-  if (upr == 20) {                                                                                                       \
-    if (one) hipLaunchKernelGGL((tq_minibatch_kernel<KK, true, 20>), grid, block, lds, st, *a, pv, code, k, B, tail_last);         \
-    else hipLaunchKernelGGL((tq_minibatch_kernel<KK, false, 20>), grid, block, lds, st, *a, pv, code, k, B, tail_last);            \
-  } else {                                                                                                               \
-    if (one) hipLaunchKernelGGL((tq_minibatch_kernel<KK, true, 16>), grid, block, lds, st, *a, pv, code, k, B, tail_last);         \
-    else hipLaunchKernelGGL((tq_minibatch_kernel<KK, false, 16>), grid, block, lds, st, *a, pv, code, k, B, tail_last);            \
-  }
-  switch (a->K) {
-    case 1: TQ_MB_LAUNCH(1) break;
-    case 2: TQ_MB_LAUNCH(2) break;
-    case 3: TQ_MB_LAUNCH(3) break;
-    default: TQ_MB_LAUNCH(4) break;
-  }
-#undef TQ_MB_LAUNCH
+  TQ_SWITCH_K(a->K,
+    if (upr == 20) {
+      if (one) hipLaunchKernelGGL((tq_minibatch_kernel<KK, true, 20>), grid, block, lds, st, *a, pv, code, k, B, tail_last);
+      else hipLaunchKernelGGL((tq_minibatch_kernel<KK, false, 20>), grid, block, lds, st, *a, pv, code, k, B, tail_last);
+    } else {
+      if (one) hipLaunchKernelGGL((tq_minibatch_kernel<KK, true, 16>), grid, block, lds, st, *a, pv, code, k, B, tail_last);
+      else hipLaunchKernelGGL((tq_minibatch_kernel<KK, false, 16>), grid, block, lds, st, *a, pv, code, k, B, tail_last);
+    });
   return tq_launch_status("tq_minibatch_kernel");
 }
 
@@ -1875,9 +1886,9 @@ extern "C" int tq_cosmos_minibatch_step(const tq_cosmos_args* a, const tq_cosmos
 // all-reduce of step t is in flight, waits for it, and calls this with `prev` for the remaining sites.
 extern "C" int tq_cosmos_sample_locals_range(const tq_cosmos_args* a, int32_t site_begin, int32_t site_count,
                                              const tq_cosmos_args* prev, void* stream) {
-  if (int rc = check_args(a, "sample_locals_range")) return rc;
+  if (int rc = check_args(a)) return rc;
   if (prev)
-    if (int rc = check_args(prev, "sample_locals_range (prev)")) return rc;
+    if (int rc = check_args(prev)) return rc;
   if (!a->lat || !a->site || site_begin < 0 || site_count < 1 || site_begin + site_count > 1 + 4 * a->K) {
     tq_set_error("tq_cosmos_sample_locals_range: bad site range or NULL lat/site");
     return TQ_ERR_ARG;
@@ -1890,7 +1901,7 @@ extern "C" int tq_cosmos_sample_locals_range(const tq_cosmos_args* a, int32_t si
   const unsigned gx = (unsigned)((B + 255) / 256);
   if (prev) {
     hipLaunchKernelGGL(tq_sample_locals_tail_kernel, dim3(gx, (unsigned)(site_count + 1)), dim3(256), 0, (hipStream_t)stream, *a,
-                       *prev, 2, B, (int)site_begin);
+                       *prev, (int)TQ_PREV_REDUCED, B, (int)site_begin);
     return tq_launch_status("tq_sample_locals_tail_kernel");
   }
   hipLaunchKernelGGL(tq_sample_locals_kernel, dim3(gx, (unsigned)site_count), dim3(256), 0, (hipStream_t)stream, *a, B,
@@ -1924,11 +1935,6 @@ extern "C" int tq_cosmos_probs(const tq_probs_args* a, void* stream) {
   if (int rc = tq_launch_status("tq_probs_globals_kernel")) return rc;
   const int64_t U = (int64_t)a->Nt * a->F * a->C;
   const dim3 grid((unsigned)((U + 255) / 256)), block(256);
-  switch (a->K) {
-    case 1: hipLaunchKernelGGL((tq_probs_kernel<1>), grid, block, 0, st, *a, U); break;
-    case 2: hipLaunchKernelGGL((tq_probs_kernel<2>), grid, block, 0, st, *a, U); break;
-    case 3: hipLaunchKernelGGL((tq_probs_kernel<3>), grid, block, 0, st, *a, U); break;
-    default: hipLaunchKernelGGL((tq_probs_kernel<4>), grid, block, 0, st, *a, U); break;
-  }
+  TQ_SWITCH_K(a->K, hipLaunchKernelGGL((tq_probs_kernel<KK>), grid, block, 0, st, *a, U));
   return tq_launch_status("tq_probs_kernel");
 }

@@ -120,7 +120,7 @@ class CosmosEngine:
         gsz, bsz = self.struct_sizes()
         self.globals = torch.zeros(gsz // 4, dtype=f32, device=dev)
         self.gbase = torch.zeros(bsz // 8, dtype=torch.float64, device=dev)
-        self._gsum_buf = torch.zeros(32, dtype=torch.float64, device=dev)  # TQ_GSUM_LEN
+        self._gsum_buf = torch.zeros(_lib.GSUM_LEN, dtype=torch.float64, device=dev)
         self.n_gsum = 3 + 3 * self.C + (self.C * self.C if self.crosstalk else 0)
         self.gsum = self._gsum_buf[: self.n_gsum]  # the part that crosses ranks
         self.elbo_out = torch.zeros(1, dtype=torch.float64, device=dev)
@@ -149,7 +149,7 @@ class CosmosEngine:
         # TAPQIR_AMD_FUSE_UNIT=auto brings the timing back (three interleaved rounds, best of each).
         fu = os.environ.get("TAPQIR_AMD_FUSE_UNIT", "1")
         self.fuse_unit = None if fu == "auto" else fu != "0"
-        self._sync = torch.zeros(64, dtype=torch.int32, device=dev)  # TQ_SYNC_WORDS (tickets, flags; diagnostic stamps of a TQ_MB_STAMPS build)
+        self._sync = torch.zeros(_lib.SYNC_WORDS, dtype=torch.int32, device=dev)  # tickets, flags; diagnostic stamps of a TQ_MB_STAMPS build
         self._sync_value = 0
 
     # -- the library --------------------------------------------------------------------------------
@@ -214,7 +214,7 @@ class CosmosEngine:
         else:  # window by window (whole AOIs): the same kernel on slices of every array
             fc = self.F * self.C
             xy2 = self.xy.reshape(U, 2)
-            for aois in self._groups(None):
+            for aois in self._groups(None):  # (upload, then wait: one window in flight -- not _windows, which prefetches)
                 wi, n0, n = self._upload_group(aois), int(aois[0]), aois.numel()
                 torch.cuda.current_stream(self.device).wait_event(self._win_ready[wi])
                 u0, u1 = n0 * fc, (n0 + n) * fc
@@ -224,9 +224,7 @@ class CosmosEngine:
                 launch(self._win[wi], xy2[u0:u1].contiguous(), *parts, b[u0:u1].contiguous(), snr_g, chi2_g, u1 - u0)
                 snr[:, u0:u1] = snr_g
                 chi2[u0:u1] = chi2_g
-                ev = torch.cuda.Event()
-                ev.record()
-                self._win_free[wi] = ev
+                self._release_window(wi)
         return snr.view(self.K, self.Nt, self.F, self.C), chi2.view(self.Nt, self.F, self.C)
 
     def run_probs(self, a):
@@ -273,22 +271,34 @@ class CosmosEngine:
         aois = torch.arange(self.Nt) if ndx is None else ndx.detach().to("cpu", torch.int64).reshape(-1)
         return [aois[i:i + self.window_aois] for i in range(0, aois.numel(), self.window_aois)]
 
-    def _image_stats_streamed(self):
-        U, fc = self.Nt * self.F * self.C, self.F * self.C
-        groups = self._groups(None)
+    def _release_window(self, w):
+        """The launches that read window `w` have been issued on the current stream: the copy stream may refill it after them."""
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._win_free[w] = ev
+
+    def _windows(self, groups):
+        """Yields (window index, AOIs) for every group, the window filled as far as the current stream is concerned (it
+        waits for the upload) and the NEXT group's upload already issued, so that it travels while this group computes; the
+        window is released when the consumer comes back for the next group."""
+        cur = torch.cuda.current_stream(self.device)
         nxt = self._upload_group(groups[0])
         for g, aois in enumerate(groups):
-            w, n0, n = nxt, int(aois[0]), aois.numel()
-            torch.cuda.current_stream(self.device).wait_event(self._win_ready[w])
+            w = nxt
+            cur.wait_event(self._win_ready[w])
             if g + 1 < len(groups):
                 nxt = self._upload_group(groups[g + 1])
+            yield w, aois
+            self._release_window(w)
+
+    def _image_stats_streamed(self):
+        U, fc = self.Nt * self.F * self.C, self.F * self.C
+        for w, aois in self._windows(self._groups(None)):
+            n0, n = int(aois[0]), aois.numel()
             tmp = torch.empty(3, n * fc, dtype=torch.float32, device=self.device)
             _lib.check(self.lib.tq_image_stats(_lib.ptr(self._win[w]), _lib.ptr(self.offset_samples), _lib.ptr(tmp), n * fc, self.P,
                                                self._stream()), "tq_image_stats")
             self.pixstats.view(3, U)[:, n0 * fc:(n0 + n) * fc] = tmp
-            ev = torch.cuda.Event()
-            ev.record()
-            self._win_free[w] = ev
 
     def _step_streamed(self, ndx, fdx):
         """One SVI step of a streamed data set: the step's AOIs in groups of at most `window_aois`; per group the staged
@@ -303,44 +313,27 @@ class CosmosEngine:
         nb_total = sum(g.numel() for g in groups)
         fb = self.F if fdx is None else int(fdx.numel())
         minibatch = nb_total < self.Nt or fb < self.F
-        lazy = minibatch and self.lazy_adam
         self._workspace(min(self.window_aois, nb_total), fb)  # (a new workspace joins first: before the lazy clock is started)
         ws_key = self._ws_key
-        if lazy:
-            if not self._stale:
-                self._last_step.fill_(self.adam_step)
-                self._stale = True
-        else:
-            self._catch_up_all()
         fdx_dev = None if fdx is None else self._index_to_device(fdx, 1)
         gtot = torch.zeros_like(self.gsum)
-        cur = torch.cuda.current_stream(self.device)
-        nxt = self._upload_group(groups[0])
         a = None
-        for g, aois in enumerate(groups):
-            w = nxt
+        for w, aois in self._windows(groups):
+            first = a is None
             nd = aois.to(self.device, torch.int32)
             a = self.make_args(nd, fdx_dev, draw_globals=True, _for_step=True, _ws=ws_key)
             a.images, a.images_il, a.images_by_slot = _lib.ptr(self._win[w]), None, 1
             a.scale_n = self.Nt_global / self._nb_global(nb_total)
             a.scale = a.scale_n * self.F / fb
-            a.zero_grad = int(minibatch)
-            a.fuse_adam = int(not minibatch or lazy)
-            if not lazy:
-                a.last_step = None
-            if g == 0:
+            a.zero_grad = int(minibatch)  # (of the step, not of the group)
+            lazy = self._open_step(a)
+            if first:
                 self.call("cosmos_sample_globals", a)
-            cur.wait_event(self._win_ready[w])
-            if g + 1 < len(groups):
-                nxt = self._upload_group(groups[g + 1])  # travels while this group computes
             if lazy:
                 self._adam_catchup(a, 0)
             self.call("cosmos_sample_locals", a)
             self.call("cosmos_elbo_grads", a)
             gtot += self.gsum
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            self._win_free[w] = ev
         self.gsum.copy_(gtot)
         self._tail_reduced(a, None)
         self.adam_step += 1
@@ -367,15 +360,8 @@ class CosmosEngine:
         """Bring the local parameters and moments of every unit to `adam_step` (lazy Adam)."""
         if self._stale:
             self._stale = False
-            a = _lib.CosmosArgs()  # only what the replay reads: buffers, geometry, optimiser constants, step count
-            p = _lib.ptr
-            a.params, a.exp_avg, a.exp_avg_sq, a.last_step = p(self._params), p(self._exp_avg), p(self._exp_avg_sq), p(self._last_step)
-            a.globals, a.gbase = p(self.globals), p(self.gbase)
-            a.Nt, a.F, a.C, a.P, a.K, a.O = self.Nt, self.F, self.C, self.P, self.K, self.O
+            a = self._core_args()  # all the replay reads, with the full geometry and the step count (no join, no workspace)
             a.nb, a.fb = self.Nt, self.F
-            a.lr, a.beta1, a.beta2, a.adam_eps = self.lr, self.betas[0], self.betas[1], self.adam_eps
-            a.beta1_d, a.beta2_d = float(self.betas[0]), float(self.betas[1])
-            a.crosstalk = int(self.crosstalk)
             a.step = self.adam_step
             self._adam_catchup(a, 1)
 
@@ -483,6 +469,18 @@ class CosmosEngine:
         slot[4] = True
         return (dev[:nb] if take_n else None), (dev[Nt:Nt + fb] if take_f else None)
 
+    def _core_args(self):
+        """An argument block with the parameter / optimiser buffers, the geometry of the data set and the optimiser constants."""
+        p = _lib.ptr
+        a = _lib.CosmosArgs()
+        a.params, a.exp_avg, a.exp_avg_sq, a.last_step = p(self._params), p(self._exp_avg), p(self._exp_avg_sq), p(self._last_step)
+        a.globals, a.gbase = p(self.globals), p(self.gbase)
+        a.Nt, a.F, a.C, a.P, a.K, a.O = self.Nt, self.F, self.C, self.P, self.K, self.O
+        a.lr, a.beta1, a.beta2, a.adam_eps = self.lr, self.betas[0], self.betas[1], self.adam_eps
+        a.beta1_d, a.beta2_d = float(self.betas[0]), float(self.betas[1])
+        a.crosstalk = int(self.crosstalk)
+        return a
+
     def make_args(self, ndx=None, fdx=None, draw_globals=True, global_weight=1.0, step=None, draw_locals=None,
                   _for_step=False, _ws=None):
         if not _for_step:
@@ -497,21 +495,18 @@ class CosmosEngine:
         # keep the index tensors alive while kernels run (the previous step's too: its tail may still be pending)
         self._keep_prev, self._keep = getattr(self, "_keep", None), (ndx, fdx)
         p = _lib.ptr
-        a = _lib.CosmosArgs()
+        a = self._core_args()
         a.images, a.xy, a.is_ontarget, a.aoi_mask = p(self.images), p(self.xy), p(self.is_ontarget), p(self._mask_arg)
         a.images_il = p(self.images_il)
         a.pixstats = p(self.pixstats)
         a.ndx, a.fdx = p(ndx), p(fdx)
         a.offset_samples, a.offset_logits = p(self.offset_samples), p(self.offset_logits)
-        a.params, a.grad, a.exp_avg, a.exp_avg_sq = p(self._params), p(self.grad), p(self._exp_avg), p(self._exp_avg_sq)
-        a.last_step = p(self._last_step)
-        a.beta1_d, a.beta2_d = float(self.betas[0]), float(self.betas[1])
+        a.grad = p(self.grad)
         a.lat, a.pix, a.aoi_part, a.blk_part = p(self.lat), p(self.pix), p(self.aoi_part), p(self.blk_part)
         a.site = p(self.site)
         a.draw_locals = int(bool(draw_globals if draw_locals is None else draw_locals))
         a.il_min_units = self.il_min_units
-        a.gsum, a.globals, a.gbase, a.elbo_out = p(self._gsum_buf), p(self.globals), p(self.gbase), p(self.elbo_out)
-        a.Nt, a.F, a.C, a.P, a.K, a.O = self.Nt, self.F, self.C, self.P, self.K, self.O
+        a.gsum, a.elbo_out = p(self._gsum_buf), p(self.elbo_out)
         a.nb, a.fb, a.n_offset, a.draw_globals = nb, fb, self.n_offset, int(bool(draw_globals))
         a.scale_n = self.Nt_global / self._nb_global(nb)
         a.scale = a.scale_n * self.F / fb
@@ -522,12 +517,10 @@ class CosmosEngine:
         a.background_mean_std, a.background_std_std = pr["background_mean_std"], pr["background_std_std"]
         a.gain_std, a.lamda_rate, a.proximity_rate = pr["gain_std"], pr["lamda_rate"], pr["proximity_rate"]
         t = self.adam_step + 1
-        a.lr, a.beta1, a.beta2, a.adam_eps = self.lr, self.betas[0], self.betas[1], self.adam_eps
         a.bias_correction1 = 1.0 - self.betas[0] ** t
         a.bias_correction2 = 1.0 - self.betas[1] ** t
         a.zero_grad = int(nb < self.Nt or fb < self.F)
-        a.fuse_adam = 0  # set by step() for full-batch steps
-        a.crosstalk = int(self.crosstalk)
+        a.fuse_adam = 0  # set by _open_step()
         a.seed = self.seed
         a.step = self.adam_step if step is None else int(step)
         a.pixel_mode = int(self.pixel_mode or 0)
@@ -540,11 +533,10 @@ class CosmosEngine:
         (minibatch steps are launch-bound: the host side of a step must stay well below the ~50 us of its kernels)."""
         nb = self.Nt if ndx is None else int(ndx.numel())
         fb = self.F if fdx is None else int(fdx.numel())
-        key = (nb, fb, self.lr, self.betas, self.adam_eps, self.seed, id(self.priors), self._ws_key)
-        if self.__dict__.get("_tmpl_key") != key or self._ws_key != (nb, fb):
+        key = (nb, fb, self.lr, self.betas, self.adam_eps, self.seed, id(self.priors))
+        if self.__dict__.get("_tmpl_key") != key or self._ws_key != (nb, fb):  # (the template points into the workspace)
             a = self.make_args(ndx, fdx, _for_step=True)
-            self._tmpl, self._tmpl_key = _lib.CosmosArgs.from_buffer_copy(a), (nb, fb, self.lr, self.betas, self.adam_eps,
-                                                                              self.seed, id(self.priors), self._ws_key)
+            self._tmpl, self._tmpl_key = _lib.CosmosArgs.from_buffer_copy(a), key
             return a
         a = _lib.CosmosArgs.from_buffer_copy(self._tmpl)
         ndx, fdx = self._indices_to_device(ndx, fdx)
@@ -703,7 +695,7 @@ class CosmosEngine:
         step whose batch sizes differ from what the previous launch prepared) takes a host draw from ``generator``.  Returns
         False if this engine cannot run that path (the caller then passes its own subsample to ``step``)."""
         nb, fb = min(int(nb), self.Nt), min(int(fb), self.F)
-        if not ((nb < self.Nt or fb < self.F) and max(self.Nt, self.F) <= 2048  # TQ_SUBSAMPLE_MAX
+        if not ((nb < self.Nt or fb < self.F) and max(self.Nt, self.F) <= _lib.SUBSAMPLE_MAX
                 and self._route(nb, fb, None) == "one_launch"
                 and os.environ.get("TAPQIR_AMD_DEVICE_SUBSAMPLE", "1") != "0"):
             return False
@@ -735,7 +727,7 @@ class CosmosEngine:
         nb = self.Nt if ndx is None else int(ndx.numel())
         fb = self.F if fdx is None else int(fdx.numel())
         route = self._route(nb, fb, allreduce)
-        if route == "streamed":
+        if route == "streamed":  # (its groups have an argument block each)
             if allreduce is not None:
                 raise NotImplementedError("AOI sharding of a streamed data set: shard first, each rank then streams its own AOIs "
                                           "(not built: a rank's shard of every BASELINE config fits its 288 GB many times over)")
@@ -745,84 +737,111 @@ class CosmosEngine:
         if self.fuse_unit is None and ndx is None and fdx is None and allreduce is None and self.pipelined_tail:
             self.autotune_fused()
         a = self._step_args(ndx, fdx)
+        self._open_step(a)
+        if route == "one_launch":
+            self._step_one_launch(a, _next_sub)
+        elif route == "overlapped":
+            self._step_overlapped(a)
+        elif route == "staged":
+            self._step_staged(a)
+        else:
+            self._step_sharded(a, allreduce)
+        self.adam_step += 1
+
+    def _open_step(self, a):
+        """The optimiser side of a step's start, for its argument block `a` (a streamed step: of every group): Adam of the local
+        block fused into the per-unit kernel for full batches and for minibatches with the lazy clock, which starts here if
+        it is not running; any other step first brings every unit to the current Adam step and carries no clock.  Returns
+        whether the step is a lazy one: its route then catches up the units of the batch before it samples."""
         minibatch = bool(a.zero_grad)
-        # Adam on the local block is fused into the unit kernel: full batches, and minibatches with the lazy clock
-        a.fuse_adam = int(not minibatch or self.lazy_adam)
-        if minibatch and self.lazy_adam:
+        lazy = minibatch and self.lazy_adam
+        a.fuse_adam = int(not minibatch or lazy)
+        if lazy:
             if not self._stale:
                 self._last_step.fill_(self.adam_step)  # every unit is current: start the clock here
                 self._stale = True
-            if route != "one_launch":
-                self._adam_catchup(a, 0)
         else:
             self._catch_up_all()
-            a.last_step = None  # full batch: no unit falls behind
-        if route != "sharded":
-            self._finish_pending()
-            if route == "one_launch":
-                # catch-up, site draws, likelihood, per-unit terms + Adam of this step and the pending tail of the
-                # previous one in a single launch; the tail of this step stays pending
-                prev = self._tail_args
-                self._sync_value = self._sync_value % 0x3FFFFFFF + 1  # never 0, never the same value twice in a row
-                a.sync_value = self._sync_value
-                if _next_sub is not None:
-                    a.next_ndx, a.next_fdx = _lib.ptr(_next_sub[0]), _lib.ptr(_next_sub[1])
-                _lib.check(self.lib.tq_cosmos_minibatch_step(C.byref(a), None if prev is None else C.byref(prev),
-                                                              self._stream()), "tq_cosmos_minibatch_step")
-                a.tail_kind = 1  # TQ_TAIL_ROWS16
-                self._tail_args = a
-            elif route == "overlapped":
-                if self.fuse_unit and not minibatch and self._fusable():
-                    a.pixel_mode = 2  # TQ_PIXEL_FUSED_UNIT
-                prev = self._tail_args
-                _lib.check(self.lib.tq_cosmos_step_overlapped(C.byref(a), None if prev is None else C.byref(prev),
-                                                              self._stream()), "tq_cosmos_step_overlapped")
-                self._tail_args = a
-            else:  # "staged"
-                self._finish_tail()
-                self.call("cosmos_step", a)
-        else:  # "sharded"
-            self._finish_tail()
-            pending = self._pending
-            if pending is not None and not a.fuse_adam:
-                self._finish_pending()  # a minibatch step samples after the dense Adam of the previous one
-                pending = None
-            if pending is not None and self.split_sampling and getattr(pending[1], "in_stream", False):
-                # the collective was issued on this stream (tapqir_amd.rccl.RcclDirect): stream order is the dependency.  ONE
-                # sampling launch that carries the pending step's post-all-reduce tail and this step's global draws
-                prev, _ = self._pending
-                self._pending = None
-                _lib.check(self.lib.tq_cosmos_sample_locals_range(C.byref(a), 0, 1 + 4 * self.K, C.byref(prev), self._stream()),
-                           "tq_cosmos_sample_locals_range")
-            elif pending is not None and self.split_sampling:
-                # first half of the local sites while the all-reduce is in flight; the rest in a launch that also
-                # carries the pending step's post-all-reduce tail and this step's global draws
-                nsites = 1 + 4 * self.K
-                n1 = nsites // 2
-                prev, handle = self._pending
-                self._pending = None
-                _lib.check(self.lib.tq_cosmos_sample_locals_range(C.byref(a), 0, n1, None, self._stream()),
-                           "tq_cosmos_sample_locals_range")
-                handle.wait()  # the current stream waits for the collective
-                _lib.check(self.lib.tq_cosmos_sample_locals_range(C.byref(a), n1, nsites - n1, C.byref(prev), self._stream()),
-                           "tq_cosmos_sample_locals_range")
+            a.last_step = None  # no unit falls behind
+        return lazy
+
+    def _step_one_launch(self, a, next_sub):
+        """Catch-up, site draws, likelihood, per-unit terms + Adam of this step and the pending tail of the previous one in
+        a single launch; the tail of this step stays pending."""
+        self._finish_pending()
+        prev = self._tail_args
+        self._sync_value = self._sync_value % 0x3FFFFFFF + 1  # never 0, never the same value twice in a row
+        a.sync_value = self._sync_value
+        if next_sub is not None:
+            a.next_ndx, a.next_fdx = _lib.ptr(next_sub[0]), _lib.ptr(next_sub[1])
+        _lib.check(self.lib.tq_cosmos_minibatch_step(C.byref(a), None if prev is None else C.byref(prev), self._stream()),
+                   "tq_cosmos_minibatch_step")
+        a.tail_kind = _lib.TAIL_ROWS16
+        self._tail_args = a
+
+    def _step_overlapped(self, a):
+        """The pipelined step: the pending tail of the previous step inside this step's sampling launch; its own stays pending."""
+        if a.last_step:
+            self._adam_catchup(a, 0)
+        self._finish_pending()
+        if self.fuse_unit and not a.zero_grad and self._fusable():
+            a.pixel_mode = _lib.PIXEL_FUSED_UNIT
+        prev = self._tail_args
+        _lib.check(self.lib.tq_cosmos_step_overlapped(C.byref(a), None if prev is None else C.byref(prev), self._stream()),
+                   "tq_cosmos_step_overlapped")
+        self._tail_args = a
+
+    def _step_staged(self, a):
+        """The launches one after the other, nothing left pending."""
+        self._finish_pending()
+        self._finish_tail()
+        self.call("cosmos_step", a)
+
+    def _step_sharded(self, a, allreduce):
+        """The staged launches with the cross-unit sums all-reduced between them; a full-batch step whose collective is
+        asynchronous leaves its global tail pending for the next step's sampling."""
+        if a.last_step:
+            self._adam_catchup(a, 0)
+        self._finish_tail()
+        pending = self._pending
+        if pending is not None and not a.fuse_adam:
+            self._finish_pending()  # a minibatch step samples after the dense Adam of the previous one
+            pending = None
+        if pending is not None and self.split_sampling and getattr(pending[1], "in_stream", False):
+            # the collective was issued on this stream (tapqir_amd.rccl.RcclDirect): stream order is the dependency.  ONE
+            # sampling launch that carries the pending step's post-all-reduce tail and this step's global draws
+            prev, _ = self._pending
+            self._pending = None
+            _lib.check(self.lib.tq_cosmos_sample_locals_range(C.byref(a), 0, 1 + 4 * self.K, C.byref(prev), self._stream()),
+                       "tq_cosmos_sample_locals_range")
+        elif pending is not None and self.split_sampling:
+            # first half of the local sites while the all-reduce is in flight; the rest in a launch that also
+            # carries the pending step's post-all-reduce tail and this step's global draws
+            nsites = 1 + 4 * self.K
+            n1 = nsites // 2
+            prev, handle = self._pending
+            self._pending = None
+            _lib.check(self.lib.tq_cosmos_sample_locals_range(C.byref(a), 0, n1, None, self._stream()),
+                       "tq_cosmos_sample_locals_range")
+            handle.wait()  # the current stream waits for the collective
+            _lib.check(self.lib.tq_cosmos_sample_locals_range(C.byref(a), n1, nsites - n1, C.byref(prev), self._stream()),
+                       "tq_cosmos_sample_locals_range")
+        else:
+            self.call("cosmos_sample_locals", a)
+            if pending is not None:
+                self._finish_pending(next_args=a)  # ... and draws this step's global sites in the same launch
             else:
-                self.call("cosmos_sample_locals", a)
-                if pending is not None:
-                    self._finish_pending(next_args=a)  # ... and draws this step's global sites in the same launch
-                else:
-                    self.call("cosmos_sample_globals", a)
-            if a.fuse_adam and not minibatch and self.fuse_unit is not False and self._fusable():
-                a.pixel_mode = 2  # TQ_PIXEL_FUSED_UNIT (not timed against the two-launch form on this path)
-            self.call("cosmos_elbo_grads", a)
-            handle = allreduce(self.gsum) if allreduce is not None else None
-            if handle is not None and hasattr(handle, "wait") and a.fuse_adam:
-                self._pending = (a, handle)
-            else:
-                if handle is not None and hasattr(handle, "wait"):
-                    handle.wait()
-                self._tail_reduced(a, None)
-        self.adam_step += 1
+                self.call("cosmos_sample_globals", a)
+        if a.fuse_adam and not a.zero_grad and self.fuse_unit is not False and self._fusable():
+            a.pixel_mode = _lib.PIXEL_FUSED_UNIT  # (not timed against the two-launch form on this path)
+        self.call("cosmos_elbo_grads", a)
+        handle = allreduce(self.gsum) if allreduce is not None else None
+        if handle is not None and hasattr(handle, "wait") and a.fuse_adam:
+            self._pending = (a, handle)
+        else:
+            if handle is not None and hasattr(handle, "wait"):
+                handle.wait()
+            self._tail_reduced(a, None)
 
     def _tail_reduced(self, a, next_args):
         """Everything of step `a` after the all-reduce (one launch), plus the global draws of `next_args`."""

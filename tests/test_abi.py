@@ -62,6 +62,22 @@ int main(void) {
     assert got == want
 
 
+# the constants of the header that the binding mirrors: every upper-case integer of tapqir_amd._lib
+MIRRORED = sorted(n for n, v in vars(_lib).items() if n.isupper() and type(v) is int)
+
+
+@pytest.mark.parametrize("name", MIRRORED)
+def test_mirrored_constants_match_the_c_header(name):
+    text = open(os.path.join(ROOT, "include", "tapqir_hip.h")).read()
+    found = re.findall(r"^#define TQ_%s\s+(\d+)\b" % name, text, flags=re.M)
+    assert len(found) == 1, "TQ_%s is not #defined (once, as an integer) in include/tapqir_hip.h" % name
+    assert int(found[0]) == getattr(_lib, name)
+
+
+def test_the_engine_constants_are_mirrored():
+    assert {"TAIL_ROWS16", "PIXEL_FUSED_UNIT", "SYNC_WORDS", "SUBSAMPLE_MAX", "GSUM_LEN"} <= set(MIRRORED)
+
+
 def test_argument_validation_returns_error_codes_without_a_gpu():
     lib = _lib.load()
     a = _lib.KsmognArgs()

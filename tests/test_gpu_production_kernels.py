@@ -19,6 +19,7 @@ import torch
 from helpers import (GIVEN_STAGES, CosmosEngine, fp32_latents, make_dataset, make_oracle, oracle_grads, oracle_to_engine,
                      put_latents, read_engine_latents, rel_err)
 
+from tapqir_amd import _lib
 from tapqir_amd.models.cosmos import initial_values
 
 pytestmark = pytest.mark.gpu
@@ -75,7 +76,7 @@ def test_fused_pixel_unit_kernel_against_oracle(K, P, perturb):
     assert eng._fusable()
 
     def expect(e):
-        assert e._tail_args is not None and e._tail_args.pixel_mode == 2  # TQ_PIXEL_FUSED_UNIT, tail pending
+        assert e._tail_args is not None and e._tail_args.pixel_mode == _lib.PIXEL_FUSED_UNIT  # tail pending
 
     replay(eng, o, N, F, expect=expect)
 
