@@ -1,5 +1,5 @@
 // tq_bodies.h -- per-work-item bodies of the cosmos step kernels (host+device inline).
-// The __global__ wrappers in tq_cosmos.hip call these with the work-item index; the CPU test
+// The __global__ wrappers of tq_cosmos.hip (its tq_step_*.h) call these with the work-item index; the CPU test
 // harness (tests/hostcheck) calls the same bodies in plain loops on host memory.
 #pragma once
 #include "../../include/tapqir_hip.h"
@@ -83,7 +83,7 @@ TQ_HD void tq_body_sample_globals(const tq_cosmos_args& a, int s) {
 // terms (tq_site.h: TQ_NSITE_TERMS per site).  Lanes of a wave share the site kind (site-major
 // order), so the Gamma and Beta code paths do not diverge inside a wave.
 // The body in three parts (the sampling kernels put a workgroup-wide regime compaction between the draw and the terms of
-// the AffineBeta sites, tq_cosmos.hip: tq_site_beta_compact):
+// the AffineBeta sites, tq_beta_compact.h: tq_site_beta_compact):
 //   tq_site_draw   parameters -> draw (or the given value), everything the terms need
 //   tq_site_terms  log q, its derivatives, implicit gradients (dd: the pair of tq_dirichlet_grad values if the caller
 //                  has them already)

@@ -72,7 +72,7 @@ struct TqGlobalSite {
 
 // Global guide sites are numbered s = 0: gain, 1: proximity, 2+q: lamda_q, 2+Q+q: pi_q.  Each site
 // has its own Philox stream, draws its own base variates and fills its own fields of TqGlobals, so
-// the device runs one site per wave (tq_cosmos.hip) and the host loops over s.
+// the device runs one site per wave (tq_step_staged.h) and the host loops over s.
 #define TQ_NGSITES(Q) (2 + 2 * (Q))
 #define TQ_NGSITES_X(Q, xt) (2 + 2 * (Q) + ((xt) ? (Q) : 0))   // crosstalk: 2+2Q+q = alpha_q
 

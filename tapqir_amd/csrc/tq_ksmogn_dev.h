@@ -1,5 +1,5 @@
 // tq_ksmogn_dev.h -- device-side building blocks of the KSMOGN likelihood kernels shared by tq_ksmogn.hip and
-// tq_cosmos.hip: per-lane accumulators, the per-pixel routines, assembly / store of a unit's outputs, the Dice weights,
+// tq_cosmos.hip (tq_step_rows.h, tq_step_minibatch.h): per-lane accumulators, the per-pixel routines, assembly / store of a unit's outputs, the Dice weights,
 // and the 16-lanes-per-unit tile routine (LDS-staged tile, separable Gaussian factors in LDS, DPP row sums).
 // See tq_ksmogn.hip for the kernels and tq_pixel.h for the arithmetic.
 #pragma once
@@ -300,7 +300,7 @@ __device__ __forceinline__ void tq_pixel_loop(TqPixAcc<K>& A, const tq_ksmogn_ar
 #endif
 // The 16 units [blk * 16, blk * 16 + 16) of the batch by one workgroup of 256 threads; `smem` holds
 // tq_tile16_lds_floats(P, K) floats.  Called by tq_ksmogn_kernel (tq_ksmogn.hip) and by the single-launch minibatch step
-// (tq_cosmos.hip), which runs it between its sampling and per-unit phases.
+// (tq_step_minibatch.h), which runs it between its sampling and per-unit phases.
 #define TQ_OFFTAB_MAX 2048  /* offsets whose table the workgroup keeps in LDS (16 B each: 32 KB); longer histograms read global memory */
 __host__ __device__ inline size_t tq_tile16_lds_floats(int P, int K, int O = 1, int units = TQ_UNITS_PER_BLOCK) {
   return (size_t)units * (tq_tile_stride(P * P) + 2 * K * TQ_MAX_P) + ((O > 1 && O <= TQ_OFFTAB_MAX) ? 4 + 4 * (size_t)O : 0);

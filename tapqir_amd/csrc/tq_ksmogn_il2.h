@@ -1,5 +1,5 @@
 // Packed lane-per-unit pixel routine (single offset, P in {14, 20}), shared by tq_ksmogn_il2_kernel (tq_ksmogn.hip)
-// and the fused pixel + per-unit kernel of full-batch steps (tq_cosmos.hip).  See tq_ksmogn.hip for the description.
+// and the fused pixel + per-unit kernel of full-batch steps (tq_step_rows.h).  See tq_ksmogn.hip for the description.
 #pragma once
 #include <type_traits>
 

@@ -566,7 +566,7 @@ TQ_HD float tq_beta_grad_window_f(float x, float alpha, float beta) {
 // only ONE of the two directions is in the saddle-point regime (the other one is in a series regime); the caller
 // keeps the direction it needs (tq_beta_grad_pair_rest).
 // (does tq_beta_grad_pair_mid<false> apply?  The sampling kernels sort the draws of a workgroup by regime before they
-// evaluate anything: tq_cosmos.hip, tq_site_beta_compact)
+// evaluate anything: tq_beta_compact.h, tq_site_beta_compact)
 TQ_HD bool tq_beta_grad_pair_applies(double x, double alpha, double beta) {
   const double total = alpha + beta;
   const double y = 1.0 - x;

@@ -1,5 +1,5 @@
 // tq_site.h -- everything in one SVI step of the cosmos model that is per unit (AOI n, frame f,
-// channel c) but NOT per pixel (host+device inline; used by tq_cosmos.hip and tests/hostcheck).
+// channel c) but NOT per pixel (host+device inline; used by the kernels of tq_cosmos.hip and tests/hostcheck).
 //
 // Reference semantics (tapqir/models/cosmos.py:82-462 under pyro TraceEnum_ELBO; SURVEY.md
 // Appendix A.3).  For one unit, with Dice weights W(m) = prod_k q(m_k), m in {0,1}^K:

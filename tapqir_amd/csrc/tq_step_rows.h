@@ -1,0 +1,500 @@
+// tq_step_rows.h -- part of the translation unit tq_cosmos.hip, included from there only (it defines __global__ kernels):
+// the rows layout of full-batch steps and everything that writes or reads it -- the two per-unit kernels that leave
+// rows, the group rows, the single-workgroup tail bodies, and the sampling launch that carries a pending tail.
+// =============================================================================================================
+// Per-unit kernel of full-batch steps (tq_cosmos_step_overlapped / tq_cosmos_step) with the per-AOI frame sums folded in.
+//
+// The units (f, c) of an AOI are contiguous, so a workgroup of 256 consecutive units touches at most TWO AOIs (when
+// F * C >= 256): its row of partial sums carries, next to the cross-unit sums, the sums of
+// d/d(background_mean_loc, background_std_loc) over its units of the first AOI (slot 0) and of the second (slot 1).  The
+// single-workgroup tail adds the few rows that overlap an AOI itself, so there is no per-AOI kernel (5 us + a launch
+// boundary at 400 000 units) and no aoi_part round trip (16 B per unit).  Workgroups stay 1 KiB-aligned in every
+// parameter row (AOI-aligned workgroups start at n * F * C and straddle cache lines: 9 % slower, measured).
+// Row layout: [2 slots][2 * TQ_MAXQ per-channel AOI partials][nq cross-unit sums]; fixed offsets keep every
+// register-array index a compile-time constant.
+//
+// Group rows: the tail's sums, spread over the otherwise idle workgroups of the sampling launch.
+// At c2 the fused launch leaves 6250 rows (one per wave).  The single-workgroup tail that adds them is a guest of the next
+// step's sampling launch, and under that launch's memory traffic each of its ~17 dependent round trips (per-AOI frame
+// sums: 16 rows per AOI, two AOIs per thread; cross-unit sums: 25 rows per thread) takes ~2.5 us: the sums alone kept it
+// busy for 50 of its 84 us, which made it the last workgroup of the launch.  The grid row of that launch that holds the
+// tail workgroup has B / 256 workgroups of which only the first did anything: now workgroup 1 + g of that row adds the rows
+// of GROUP g (4096 units: 64 rows of 64 units or 16 of 256) -- one lane per row, one round trip -- and leaves a group row:
+// the cross-unit sums in double and the per-AOI frame sums of the (at most 17) AOIs the group touches, published with
+// write-through (`sc1`) stores, a drained store queue and an agent-scope counter (MI355X_MICROARCH.md, inter-workgroup
+// visibility).  The tail workgroup polls the counter, then reads U / 4096 group rows with `sc1` loads: one round trip for
+// the cross-unit sums, one for the per-AOI sums (stamps build: sums complete 9 us after its start instead of 50).  The
+// reducers never wait, so the polling workgroup cannot deadlock.
+// =============================================================================================================
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "tq_beta_compact.h"
+#include "tq_bodies.h"
+#include "tq_ksmogn_dev.h"
+#include "tq_ksmogn_il2.h"
+#include "tq_stamps.h"
+#include "tq_step_staged.h"
+
+#define TQ_ROWS_AOICOL (2 * TQ_MAXQ)
+#define TQ_ROWS_GCOL (2 * TQ_ROWS_AOICOL)
+#define TQ_ROWS_MAXCOL (TQ_ROWS_GCOL + TQ_MAX_NGSUM)
+
+template <int K>
+__global__ __launch_bounds__(TQ_UNIT_BLOCK) void tq_unit_rows_kernel(const tq_cosmos_args a, const int64_t B) {
+  __shared__ float s_part[TQ_UNIT_BLOCK / 64][TQ_ROWS_MAXCOL];
+  const int64_t i = (int64_t)blockIdx.x * TQ_UNIT_BLOCK + threadIdx.x;
+  const bool live = i < B;
+  const uint32_t FC = (uint32_t)(a.F * a.C);
+  const uint32_t n0 = ((uint32_t)blockIdx.x * TQ_UNIT_BLOCK) / FC;  // AOI of the workgroup's first unit
+  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
+  float part[TQ_MAX_NGSUM], aoi[TQ_ROWS_GCOL];
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) part[j] = 0.0f;
+#pragma unroll
+  for (int j = 0; j < TQ_ROWS_GCOL; ++j) aoi[j] = 0.0f;
+  if (live) {
+    float aoi2[2];
+    tq_body_unit<K>(a, i, part, aoi2);
+    const uint32_t n = (uint32_t)i / FC;
+    const int c = (int)((uint32_t)i % (uint32_t)a.C);
+    const int slot = n == n0 ? 0 : 1;
+#pragma unroll
+    for (int sl = 0; sl < 2; ++sl) {
+#pragma unroll
+      for (int q = 0; q < TQ_MAXQ; ++q) {
+        const bool mine = sl == slot && q == c;
+        aoi[sl * TQ_ROWS_AOICOL + 2 * q] = mine ? aoi2[0] : 0.0f;
+        aoi[sl * TQ_ROWS_AOICOL + 2 * q + 1] = mine ? aoi2[1] : 0.0f;
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < TQ_ROWS_GCOL; ++j) {
+    if ((j % TQ_ROWS_AOICOL) < 2 * a.C) {
+      const float sum = tq_wave_sum_rows4(aoi[j]);
+      if (lane == 0) s_part[wave][j] = sum;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
+    if (j < nq) {
+      const float sum = tq_wave_sum_rows4(part[j]);
+      if (lane == 0) s_part[wave][TQ_ROWS_GCOL + j] = sum;
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < ncol) {
+    const bool used = (int)threadIdx.x >= TQ_ROWS_GCOL || ((int)threadIdx.x % TQ_ROWS_AOICOL) < 2 * a.C;
+    const float sum = used ? (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]) : 0.0f;
+    a.blk_part[(int64_t)blockIdx.x * ncol + threadIdx.x] = sum;
+  }
+}
+
+// ---- group rows: the rows added per group of 4096 units for the tail workgroup (see the top of this file) ---------------
+#define TQ_GRP_UNITS 4096
+#define TQ_GRP_AOIS (TQ_GRP_UNITS / TQ_UNIT_BLOCK + 1)   /* AOIs a group can touch (F * C >= TQ_UNIT_BLOCK) */
+#define TQ_GGROW (2 * 16 + TQ_GRP_AOIS * 2 * TQ_MAXQ)    /* floats of a group row: 16 doubles, then 2 * TQ_MAXQ floats per AOI */
+__host__ __device__ __forceinline__ int64_t tq_grp_count(int64_t B) { return (B + TQ_GRP_UNITS - 1) / TQ_GRP_UNITS; }
+// group rows follow the rows in blk_part (16-byte aligned)
+__host__ __device__ __forceinline__ int64_t tq_grp_base(int64_t nrows, int ncol) { return ((nrows * ncol + 3) / 4) * 4; }
+
+// The pending tail: what a launch that carries the tail of the PREVIOUS step (`prev`, the kernels' `has_prev`) finds in
+// prev's workspace and has to do before prev's global sites, total ELBO and Adam of the per-AOI / global parameters.  The
+// host picks the code (tq_prev_code, tq_prev_code_sampling), tq_sample_locals_tail_kernel and tq_minibatch_kernel act on it.
+enum TqPrevTail : int {
+  TQ_PREV_NONE = 0,     // nothing pending
+  TQ_PREV_FLAT = 1,     // flat partial sums of tq_unit_kernel + per-AOI terms of tq_aoi_kernel: cross-unit sums first
+  TQ_PREV_REDUCED = 2,  // gsum is complete (all-reduced by the caller): global sites onwards
+  TQ_PREV_ROWS = 3,     // rows of 64 / 256 units with the per-AOI sums folded in, added by the tail workgroup itself
+  TQ_PREV_ROWS16 = 4,   // rows of 16 units of a single-launch minibatch step
+  TQ_PREV_GROUPS = 6,   // as ROWS, the rows added per group of 4096 units by the idle workgroups of the sampling launch
+  TQ_PREV_ROWS20 = 7,   // as ROWS16, rows of 20 units (tq_mb_upr)
+};
+
+// units per row of a step with rows: 16 (single-launch minibatch step; its rows hold tq_mb_rows_upr units), 64 (fused pixel
+// + per-unit kernel), TQ_UNIT_BLOCK (tq_unit_rows_kernel)
+__host__ __device__ __forceinline__ int tq_rows_upr(const tq_cosmos_args& a) {
+  return a.tail_kind == TQ_TAIL_ROWS16 ? 16 : (a.pixel_mode == TQ_PIXEL_FUSED_UNIT ? 64 : TQ_UNIT_BLOCK);
+}
+__device__ __forceinline__ int tq_mb_rows_upr(int has_prev) { return has_prev == TQ_PREV_ROWS20 ? 20 : 16; }
+
+// one wave: rows of group g of step `a` -> group row g (published); returns (lane 0) how many groups had been published before
+__device__ __forceinline__ int tq_group_reduce_rows(const tq_cosmos_args& a, const int g) {
+  const int lane = threadIdx.x & 63;
+  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
+  const int64_t B = tq_batch_units(a);
+  const uint32_t UPR = (uint32_t)tq_rows_upr(a), RPG = TQ_GRP_UNITS / UPR;
+  const int64_t nrows = (B + UPR - 1) / UPR;
+  const int64_t r0 = (int64_t)g * RPG;
+  const int nw = (int)((nrows - r0) < (int64_t)RPG ? (nrows - r0) : (int64_t)RPG);
+  const bool have = lane < nw;
+  const float* my = a.blk_part + (r0 + (have ? lane : 0)) * ncol;
+  float s0[2 * TQ_MAXQ], s1[2 * TQ_MAXQ], col[TQ_MAX_NGSUM];
+#pragma unroll
+  for (int j = 0; j < 2 * TQ_MAXQ; ++j) {
+    const bool used = j < 2 * a.C;
+    s0[j] = (have && used) ? my[j] : 0.0f;
+    s1[j] = (have && used) ? my[TQ_ROWS_AOICOL + j] : 0.0f;
+  }
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) col[j] = (have && j < nq) ? my[TQ_ROWS_GCOL + j] : 0.0f;
+  float* grow = a.blk_part + tq_grp_base(nrows, ncol) + (int64_t)g * TQ_GGROW;
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
+    if (j < nq) {
+      const double sum = tq_wave_sum_d_lane0((double)col[j]);
+      if (lane == 0) __hip_atomic_store(&((double*)grow)[j], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  const uint32_t FC = (uint32_t)(a.fb * a.C);
+  const uint32_t u_first = (uint32_t)g * TQ_GRP_UNITS;
+  const uint32_t u_last = (uint32_t)(((int64_t)u_first + TQ_GRP_UNITS - 1 < B - 1) ? u_first + TQ_GRP_UNITS - 1 : B - 1);
+  const uint32_t n_lo = u_first / FC, n_hi = u_last / FC;
+  const uint32_t n0 = (u_first + UPR * (uint32_t)lane) / FC;  // AOI of this row's first unit (slot 0; slot 1 is the next AOI)
+  for (uint32_t n = n_lo; n <= n_hi; ++n) {
+    float* out = grow + 32 + (n - n_lo) * (2 * TQ_MAXQ);
+#pragma unroll
+    for (int j = 0; j < 2 * TQ_MAXQ; ++j) {
+      if (j < 2 * a.C) {
+        const float v = (n0 == n) ? s0[j] : ((n0 + 1 == n) ? s1[j] : 0.0f);
+        const float sum = tq_wave_sum_rows4(v);
+        if (lane == 0) __hip_atomic_store(&out[j], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the group row has left
+  int ticket = 0;
+  if (lane == 0) ticket = __hip_atomic_fetch_add(a.sync + TQ_SYNC_GROUPS, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return ticket;
+}
+
+// Fused pixel + per-unit kernel of full-batch steps (pixel_mode = TQ_PIXEL_FUSED_UNIT): a wave renders its tile of 64
+// units (tq_il2_lane, the routine of tq_ksmogn_il2_kernel) and goes straight on to the per-unit terms + Adam of the same
+// 64 units, lane for lane.  The pixel phase is bound by VALU issue (PMC: ~75 % busy) and the per-unit phase by HBM
+// (4.3 TB/s of traffic at 33 % VALU busy): as two launches they run one after the other, here the waves of a SIMD are in
+// different phases most of the time.  The pixel results go from one phase to the next in registers (56 B per unit
+// neither written nor read), a launch boundary is gone, and the row of partial sums is per wave (rows of 64 units).
+template <int K, int P>
+__global__ __launch_bounds__(64, 2) void tq_pixel_unit_kernel(const tq_ksmogn_args k, const tq_cosmos_args a, const int64_t B) {
+  float pixv[TQ_PIXOUT(K)];
+#pragma unroll
+  for (int j = 0; j < TQ_PIXOUT(K); ++j) pixv[j] = 0.0f;
+  tq_il2_lane<K, P, true>(k, B, pixv);
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  const uint32_t FC = (uint32_t)(a.F * a.C);
+  const uint32_t n0 = ((uint32_t)blockIdx.x * 64u) / FC;  // AOI of the wave's first unit
+  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
+  float part[TQ_MAX_NGSUM], aoi[TQ_ROWS_GCOL];
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) part[j] = 0.0f;
+#pragma unroll
+  for (int j = 0; j < TQ_ROWS_GCOL; ++j) aoi[j] = 0.0f;
+  if (i < B) {
+    float aoi2[2];
+    tq_body_unit<K, false, true>(a, i, part, aoi2, pixv);
+    const uint32_t n = (uint32_t)i / FC;
+    const int c = (int)((uint32_t)i % (uint32_t)a.C);
+    const int slot = n == n0 ? 0 : 1;
+#pragma unroll
+    for (int sl = 0; sl < 2; ++sl) {
+#pragma unroll
+      for (int q = 0; q < TQ_MAXQ; ++q) {
+        const bool mine = sl == slot && q == c;
+        aoi[sl * TQ_ROWS_AOICOL + 2 * q] = mine ? aoi2[0] : 0.0f;
+        aoi[sl * TQ_ROWS_AOICOL + 2 * q + 1] = mine ? aoi2[1] : 0.0f;
+      }
+    }
+  }
+  float* row = a.blk_part + (int64_t)blockIdx.x * ncol;
+#pragma unroll
+  for (int j = 0; j < TQ_ROWS_GCOL; ++j) {
+    const bool used = (j % TQ_ROWS_AOICOL) < 2 * a.C;
+    const float sum = used ? tq_wave_sum_rows4(aoi[j]) : 0.0f;
+    if (threadIdx.x == 0) row[j] = sum;
+  }
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
+    if (j < nq) {
+      const float sum = tq_wave_sum_rows4(part[j]);
+      if (threadIdx.x == 0) row[TQ_ROWS_GCOL + j] = sum;
+    }
+  }
+}
+
+// acc[j] += sum over this thread's rows (r = threadIdx.x, + 256, ...) of column j of the cross-unit sums.  Four rows are
+// REQUESTED before any is added: with one row in flight at a time the 25 rows per thread of a c2-sized step with rows of
+// 64 units were 25 memory latencies in sequence (~25 us, which made the tail workgroup the last one of the sampling
+// launch it hides in).  Same order of additions per thread as the plain loop.
+__device__ __forceinline__ void tq_rows_column_sums(const tq_cosmos_args& a, int64_t nrows, int nq, int ncol, double* acc) {
+  for (int64_t r0 = threadIdx.x; r0 < nrows; r0 += 4 * 256) {
+    float v[4][TQ_MAX_NGSUM];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t r = r0 + 256 * u;
+#pragma unroll
+      for (int j = 0; j < TQ_MAX_NGSUM; ++j) v[u][j] = (r < nrows && j < nq) ? a.blk_part[r * ncol + TQ_ROWS_GCOL + j] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+      for (int j = 0; j < TQ_MAX_NGSUM; ++j)
+        if (j < nq) acc[j] += (double)v[u][j];
+    }
+  }
+}
+
+// Tail of a step whose per-unit kernel wrote such rows (ONE workgroup of 256 threads): per-AOI sites from the rows that
+// overlap the AOI, cross-unit sums in fp64, global sites and the total ELBO.
+// UPR = units per row: TQ_UNIT_BLOCK (tq_unit_rows_kernel) or 16 (the single-launch minibatch step, whose rows hold `mb_upr`
+// = 16 or 20 units: the host's tq_mb_upr)
+template <int UPR_T>
+__device__ __forceinline__ void tq_rows_reduce_globals_body(const tq_cosmos_args& a, double (*s_w)[TQ_MAX_NGSUM], double* s_e,
+                                                            const int mb_upr = 16, const bool with_globals = true) {
+  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
+  const int64_t B = tq_batch_units(a);
+  const uint32_t UPR = UPR_T == 16 ? (uint32_t)mb_upr : (uint32_t)tq_rows_upr(a);  // (one instance serves rows of 64 and of 256)
+  const int64_t nrows = (B + UPR - 1) / UPR;
+  const uint32_t FC = (uint32_t)(a.fb * a.C);  // units of one AOI of the batch
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double acc[TQ_MAX_NGSUM];
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) acc[j] = 0.0;
+  // per-AOI sites: frame sums = sums over the rows that overlap the AOI; prior terms; gradient of the AOI parameters
+  const int nac = a.nb * a.C;
+  if constexpr (UPR_T == 16) {
+    // rows of 16 units: an AOI of the minibatch spans fb C / 16 rows (32 at the default 10 x 512) and this workgroup is
+    // the critical path of the step -- 16 lanes share the rows of one (AOI, channel), so the loads of an AOI are two
+    // round trips instead of 32 in sequence
+    const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
+    for (int ac0 = 0; ac0 < nac; ac0 += 16) {
+      const int ac = ac0 + grp;
+      const bool on = ac < nac;
+      const uint32_t ai = on ? (uint32_t)ac / (uint32_t)a.C : 0u;
+      const int c = on ? ac - (int)ai * a.C : 0;
+      float s1 = 0.0f, s2 = 0.0f;
+      if (on) {
+        const uint32_t r_lo = (ai * FC) / UPR, r_hi = ((ai + 1) * FC - 1) / UPR;
+        for (uint32_t r = r_lo + gl; r <= r_hi; r += 16) {
+          const int slot = (r * UPR) / FC == ai ? 0 : 1;
+          const float* row = a.blk_part + (int64_t)r * ncol + slot * TQ_ROWS_AOICOL + 2 * c;
+          s1 += row[0];
+          s2 += row[1];
+        }
+      }
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) {
+        s1 += __shfl_xor(s1, o, 16);
+        s2 += __shfl_xor(s2, o, 16);
+      }
+      if (on && gl == 0) {
+        float e;
+        tq_body_aoi_finish(a, (int)ai, c, s1, s2, &e);
+        acc[TQ_GS_ELBO] += (double)e;
+      }
+    }
+    TQ_STAMP_AT(a, TQ_ST_AOI);
+  } else {
+    for (int ac = threadIdx.x; ac < nac; ac += 256) {
+      const uint32_t ai = (uint32_t)ac / (uint32_t)a.C;  // position of the AOI in the batch
+      const int c = ac - (int)ai * a.C;
+      const uint32_t r_lo = (ai * FC) / UPR, r_hi = ((ai + 1) * FC - 1) / UPR;
+      float s1 = 0.0f, s2 = 0.0f;
+      for (uint32_t rb = r_lo; rb <= r_hi; rb += 4) {  // four rows requested before any is added (see tq_rows_column_sums)
+        float p1[4], p2[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const uint32_t r = rb + u;
+          const int slot = (r * UPR) / FC == ai ? 0 : 1;
+          const float* row = a.blk_part + (int64_t)r * ncol + slot * TQ_ROWS_AOICOL + 2 * c;
+          p1[u] = r <= r_hi ? row[0] : 0.0f;
+          p2[u] = r <= r_hi ? row[1] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          s1 += p1[u];
+          s2 += p2[u];
+        }
+      }
+      float e;
+      tq_body_aoi_finish(a, (int)ai, c, s1, s2, &e);
+      acc[TQ_GS_ELBO] += (double)e;
+    }
+  }
+  if constexpr (UPR_T == 16) {  // a few hundred rows: the plain loop (and no extra registers in the minibatch kernel)
+    for (int64_t r = threadIdx.x; r < nrows; r += 256) {
+#pragma unroll
+      for (int j = 0; j < TQ_MAX_NGSUM; ++j)
+        if (j < nq) acc[j] += (double)a.blk_part[r * ncol + TQ_ROWS_GCOL + j];
+    }
+  } else {
+    tq_rows_column_sums(a, nrows, nq, ncol, acc);
+  }
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
+    if (j < nq) {
+      const double s = tq_wave_sum_d_lane0(acc[j]);
+      if (lane == 0) s_w[wave][j] = s;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < nq) a.gsum[threadIdx.x] = s_w[0][threadIdx.x] + s_w[1][threadIdx.x] + s_w[2][threadIdx.x] + s_w[3][threadIdx.x];
+  __threadfence_block();
+  __syncthreads();
+  TQ_STAMP_AT(a, TQ_ST_GSUM);
+  if (with_globals) tq_globals_from_gsum_body(a, s_e);
+}
+
+// Sums of a step from the group rows that other workgroups publish (ONE workgroup of 256 threads): WAIT: polls the counter of
+// published groups first (the tail workgroup inside a sampling launch; returns false after ~2 s without them: never
+// observed, the caller leaves a NaN loss) -- else the caller knows they are all there (the last workgroup of
+// tq_group_sums_kernel).  Then per-AOI sites from the one or two groups that overlap the AOI and the cross-unit sums -> gsum.
+template <bool WAIT>
+__device__ __forceinline__ bool tq_groups_sums_body(const tq_cosmos_args& a, double (*s_w)[TQ_MAX_NGSUM]) {
+  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
+  const int64_t B = tq_batch_units(a);
+  const uint32_t UPR = (uint32_t)tq_rows_upr(a);
+  const int64_t nrows = (B + UPR - 1) / UPR;
+  const int ngroups = (int)tq_grp_count(B);
+  const float* grows = a.blk_part + tq_grp_base(nrows, ncol);
+  const uint32_t FC = (uint32_t)(a.fb * a.C);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int s_ok;
+  if (threadIdx.x == 0) {
+    int ok = 1;
+    if (WAIT) {
+      const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+      while (__hip_atomic_load(a.sync + TQ_SYNC_GROUPS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ngroups) {
+        __builtin_amdgcn_s_sleep(8);
+        if (__builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {
+          ok = 0;
+          break;
+        }
+      }
+    }
+    __hip_atomic_store(a.sync + TQ_SYNC_GROUPS, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next launch
+    s_ok = ok;
+  }
+  __syncthreads();
+  if (!s_ok) return false;
+  auto ld = [](const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  auto ldd = [](const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  double acc[TQ_MAX_NGSUM];
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) acc[j] = 0.0;
+  const int nac = a.nb * a.C;
+  for (int ac = threadIdx.x; ac < nac; ac += 256) {
+    const uint32_t ai = (uint32_t)ac / (uint32_t)a.C;
+    const int c = ac - (int)ai * a.C;
+    const uint32_t g_lo = (ai * FC) / TQ_GRP_UNITS, g_hi = ((ai + 1) * FC - 1) / TQ_GRP_UNITS;
+    float s1 = 0.0f, s2 = 0.0f;
+    for (uint32_t g = g_lo; g <= g_hi; ++g) {
+      const uint32_t m = ai - (g * TQ_GRP_UNITS) / FC;
+      const float* p = grows + (int64_t)g * TQ_GGROW + 32 + m * (2 * TQ_MAXQ) + 2 * c;
+      s1 += ld(p);
+      s2 += ld(p + 1);
+    }
+    float e;
+    tq_body_aoi_finish(a, (int)ai, c, s1, s2, &e);
+    acc[TQ_GS_ELBO] += (double)e;
+  }
+  for (int g = threadIdx.x; g < ngroups; g += 256) {
+    const double* p = (const double*)(grows + (int64_t)g * TQ_GGROW);
+#pragma unroll
+    for (int j = 0; j < TQ_MAX_NGSUM; ++j)
+      if (j < nq) acc[j] += ldd(p + j);
+  }
+  TQ_STAMP_AT(a, TQ_ST_TAIL_SUMS);
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
+    if (j < nq) {
+      const double s = tq_wave_sum_d_lane0(acc[j]);
+      if (lane == 0) s_w[wave][j] = s;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < nq) a.gsum[threadIdx.x] = s_w[0][threadIdx.x] + s_w[1][threadIdx.x] + s_w[2][threadIdx.x] + s_w[3][threadIdx.x];
+  return true;
+}
+// ... and the global sites + total ELBO (the tail workgroup of a sampling launch)
+__device__ __forceinline__ bool tq_groups_reduce_globals_body(const tq_cosmos_args& a, double (*s_w)[TQ_MAX_NGSUM], double* s_e) {
+  if (!tq_groups_sums_body<true>(a, s_w)) return false;
+  __threadfence_block();
+  __syncthreads();
+  TQ_STAMP_AT(a, TQ_ST_GSUM);
+  tq_globals_from_gsum_body(a, s_e);
+  return true;
+}
+
+// AOI-sharded full-batch steps (and tq_cosmos_tail): rows -> per-AOI sites and gsum, what the all-reduce needs.  Workgroup g
+// adds the rows of group g (one wave, one round trip) and publishes the group row; the workgroup whose ticket is the last
+// one finishes the per-AOI sites and the cross-unit sums from the U / 4096 group rows (one wave per AOI and a last
+// workgroup that walked all 6250 rows took 38 us at c2 -- on the critical path of every sharded step).
+__global__ __launch_bounds__(256) void tq_group_sums_kernel(const tq_cosmos_args a) {
+  __shared__ double s_w[4][TQ_MAX_NGSUM];
+  __shared__ int s_last;
+  if (threadIdx.x < 64) {
+    const int ticket = tq_group_reduce_rows(a, (int)blockIdx.x);
+    if (threadIdx.x == 0) s_last = ticket == (int)gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  tq_groups_sums_body<false>(a, s_w);
+}
+
+__global__ __launch_bounds__(256) void tq_rows_reduce_globals_kernel(const tq_cosmos_args a, const int upr) {
+  __shared__ double s_w[4][TQ_MAX_NGSUM];
+  __shared__ double s_e[TQ_NGSITES(TQ_MAXQ)];
+  if (upr <= 20) tq_rows_reduce_globals_body<16>(a, s_w, s_e, upr);
+  else tq_rows_reduce_globals_body<TQ_UNIT_BLOCK>(a, s_w, s_e);
+}
+
+// Full-batch pipeline (tq_cosmos_step_overlapped): the local guide sampling of step t, with ONE extra workgroup (block (0, 0),
+// dispatched first) that runs the single-workgroup tail of step t-1 -- cross-unit sums, global sites, total ELBO, Adam
+// of the per-AOI / global parameters -- and then draws the global sites of step t from the updated parameters.  The
+// sampling of the local sites reads local parameters only (already updated by the Adam fused into the unit kernel of
+// step t-1), so the ~35 us latency chain of the tail hides behind the ~14 000 sampling workgroups of the same launch.
+// Compiled for the occupancy of the SAMPLING path (five waves per SIMD, 96 registers; the fp64 code of the global sites
+// spills ~800 registers to scratch at that cap, which the one tail workgroup can afford now that the other workgroups of
+// its grid row add the rows for it: with the tail adding all rows itself it was the last workgroup of the launch and the
+// kernel had to be built for three waves -- c2 step 0.248 -> 0.235 ms, 0.320 -> 0.288 ms in the regime of a converged fit).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void tq_sample_locals_tail_kernel(
+    const tq_cosmos_args a, const tq_cosmos_args prev, const int has_prev, const int64_t B, const int site_begin) {
+  // has_prev: a TqPrevTail code
+  if (blockIdx.y == 0) {
+    if (blockIdx.x != 0) {
+      // workgroup 1 + g adds the rows of group g of `prev` for the tail workgroup (one wave; the others leave)
+      if (has_prev == TQ_PREV_GROUPS && (int64_t)blockIdx.x <= tq_grp_count(tq_batch_units(prev)) && threadIdx.x < 64)
+        tq_group_reduce_rows(prev, (int)blockIdx.x - 1);
+      return;
+    }
+    __shared__ double s_w[4][TQ_MAX_NGSUM];
+    __shared__ double s_e[TQ_NGSITES(TQ_MAXQ)];
+    TQ_STAMP_AT(a, TQ_ST_TAIL_START);
+    if (has_prev) {
+      const int64_t Bp = tq_batch_units(prev);
+      if (has_prev == TQ_PREV_ROWS) tq_rows_reduce_globals_body<TQ_UNIT_BLOCK>(prev, s_w, s_e);
+      else if (has_prev == TQ_PREV_GROUPS) {
+        if (!tq_groups_reduce_globals_body(prev, s_w, s_e) && threadIdx.x == 0) prev.elbo_out[0] = __builtin_nan("");
+      } else if (has_prev == TQ_PREV_FLAT) tq_reduce_globals_body(prev, (Bp + TQ_UNIT_BLOCK - 1) / TQ_UNIT_BLOCK, Bp, s_w, s_e);
+      else tq_globals_from_gsum_body(prev, s_e);
+      __syncthreads();
+      TQ_STAMP_AT(a, TQ_ST_FB_GLOBALS);
+      const int64_t total = tq_num_params(prev);
+      for (int64_t j = tq_aoi_base(prev) + threadIdx.x; j < total; j += 256) tq_body_adam(prev, j);
+      __threadfence();
+      __syncthreads();
+    }
+    TQ_STAMP_AT(a, TQ_ST_AOI);
+    const int ns = tq_num_gsites(a);
+    if ((threadIdx.x & 63) == 0)
+      for (int s = threadIdx.x >> 6; s < ns; s += 4) tq_body_sample_globals(a, s);
+    TQ_STAMP_BARRIER();
+    TQ_STAMP_AT(a, TQ_ST_TAIL_DRAWN);
+    return;
+  }
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  tq_sample_site_wg(a, site_begin + (int)blockIdx.y - 1, i, B);
+  TQ_STAMP_IF(blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1, a, TQ_ST_TAIL_ADAM);  // (about) the last sampling workgroup
+}

@@ -620,8 +620,8 @@ class CosmosEngine:
         return self.pixel_mode
 
     def _fusable(self):
-        """Can a full-batch step of this engine run pixel + per-unit kernel in one launch?  (tq_cosmos.hip:
-        tq_fused_pixel_unit -- same conditions.)"""
+        """Can a full-batch step of this engine run pixel + per-unit kernel in one launch?  (The host predicate
+        tq_fused_pixel_unit of tq_cosmos.hip asks the same of a step's arguments.)"""
         return (self.pipelined_tail and not self.crosstalk and self.K <= 2 and self.O == 1 and self.P in (14, 20)
                 and self.Nt * self.F * self.C >= self.il_min_units and self.F * self.C >= 256)
 
