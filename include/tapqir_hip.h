@@ -429,6 +429,33 @@ typedef struct {
 int tq_snr_chi2(const tq_snr_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Credible intervals of the per-unit variational posteriors: the central interval of probability `ci` of
+ *   TQ_INTERVAL_GAMMA        Gamma(concentration = p0 p1, rate = p1)                     p0 = loc,  p1 = beta
+ *   TQ_INTERVAL_AFFINE_BETA  low + (high - low) Beta(c1, c0),                            p0 = mean, p1 = size
+ *                            c1 = p1 (p0 - low) / (high - low), c0 = p1 (high - p0) / (high - low)
+ * i.e. ll = quantile((1 - ci) / 2), ul = quantile((1 + ci) / 2), element by element, in double.
+ * Replaces the LL / UL of background, height, width, x, y in compute_params (tapqir/models/cosmos.py:740-776), which
+ * the reference takes on the host through torch_to_scipy_dist(...).interval (scipy.stats.gamma / beta).
+ * The Gamma concentration is the fp32 product p0 * p1 upcast, as the reference forms it; everything after is double.
+ * Elements outside the domain (non-finite, concentration <= 0, mean outside (low, high)) give NaN.
+ * ------------------------------------------------------------------------------------- */
+#define TQ_INTERVAL_GAMMA 0
+#define TQ_INTERVAL_AFFINE_BETA 1
+
+typedef struct {
+  int32_t kind;     /* TQ_INTERVAL_* */
+  const float* p0;  /* [n] loc  | mean */
+  const float* p1;  /* [n] beta | size */
+  double* ll;       /* [n] out (float64) */
+  double* ul;       /* [n] out (float64) */
+  int64_t n;
+  double ci;        /* in (0, 1) */
+  double low, high; /* TQ_INTERVAL_AFFINE_BETA only: finite, low < high */
+} tq_interval_args;
+
+int tq_credible_intervals(const tq_interval_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Time-to-first-binding kinetics (`tapqir ttfb`, tapqir/main.py:926-1147).
  *
  * tq_ttfb_sample replaces time_to_first_binding(z_sample(num_samples)) (tapqir/utils/imscroll.py:187-196,

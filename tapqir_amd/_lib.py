@@ -127,6 +127,18 @@ class SnrArgs(C.Structure):
     ]
 
 
+class IntervalArgs(C.Structure):
+    """``tq_interval_args`` (include/tapqir_hip.h)."""
+
+    _fields_ = [
+        ("kind", C.c_int32), ("p0", C.c_void_p), ("p1", C.c_void_p), ("ll", C.c_void_p), ("ul", C.c_void_p),
+        ("n", C.c_int64), ("ci", C.c_double), ("low", C.c_double), ("high", C.c_double),
+    ]
+
+
+INTERVAL_GAMMA, INTERVAL_AFFINE_BETA = 0, 1  # TQ_INTERVAL_GAMMA, TQ_INTERVAL_AFFINE_BETA
+
+
 class GlimpseArgs(C.Structure):
     """``tq_glimpse_args`` (include/tapqir_hip.h)."""
 
@@ -198,7 +210,7 @@ EXPORTS = [
     "tq_cosmos_globals_grad", "tq_cosmos_adam", "tq_cosmos_adam_catchup", "tq_cosmos_step", "tq_cosmos_step_overlapped", "tq_cosmos_tail", "tq_cosmos_tail_reduced", "tq_cosmos_sample_locals_range",
     "tq_cosmos_blk_floats", "tq_cosmos_minibatch_step", "tq_cosmos_pixel_unit",
     "tq_cosmos_probs", "tq_glimpse_extract", "tq_ksmogn_rsample", "tq_snr_chi2", "tq_ttfb_sample", "tq_ttfb_fit",
-    "tq_dwell_sample", "tq_dwell_fit",
+    "tq_dwell_sample", "tq_dwell_fit", "tq_credible_intervals",
 ]
 
 _lib = None
@@ -264,6 +276,8 @@ def load():
     lib.tq_ksmogn_rsample.restype = C.c_int
     lib.tq_snr_chi2.argtypes = [C.POINTER(SnrArgs), C.c_void_p]
     lib.tq_snr_chi2.restype = C.c_int
+    lib.tq_credible_intervals.argtypes = [C.POINTER(IntervalArgs), C.c_void_p]
+    lib.tq_credible_intervals.restype = C.c_int
     lib.tq_glimpse_extract.argtypes = [C.POINTER(GlimpseArgs), C.c_void_p]
     lib.tq_glimpse_extract.restype = C.c_int
     lib.tq_ttfb_sample.argtypes = [C.POINTER(TtfbSampleArgs), C.c_void_p]

@@ -732,7 +732,7 @@ __global__ __launch_bounds__(256) void tq_image_stats_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
 extern "C" const char* tq_last_error(void) { return g_err; }
-extern "C" int tq_version(void) { return 101; }
+extern "C" int tq_version(void) { return 102; }
 void tq_set_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
 
 template <int K, bool ONE>

@@ -253,6 +253,7 @@ class cosmos(Model):
     def compute_params(self, CI):
         """Credible intervals / means of the variational posteriors and the spot probabilities
         (cosmos.py:711-784; same keys, tensors on the CPU)."""
+        from tapqir_amd.utils import stats
         from tapqir_amd.utils.stats import affine_beta_interval, dirichlet_interval, gamma_interval
 
         cp = {n: v.detach() for n, v in self.engine.layout.constrained(self.engine.params).items()}
@@ -263,15 +264,20 @@ class cosmos(Model):
         def put(name, tup):
             out[name] = {"LL": tup[0], "UL": tup[1], "Mean": tup[2]}
 
+        # the per-unit posteriors on the device that holds them (tq_credible_intervals), the few global scalars by scipy;
+        # an engine that is not on a HIP device (the host-check engine of the CPU tests) takes scipy for both
+        on_device = cp["b_loc"].device.type == "cuda"
+        local_gamma = stats.gamma_interval_device if on_device else gamma_interval
+        local_beta = stats.affine_beta_interval_device if on_device else affine_beta_interval
         put("gain", gamma_interval(cp["gain_loc"], cp["gain_beta"], CI))
         put("pi", dirichlet_interval(cp["pi_mean"] * cp["pi_size"], CI))
         put("lamda", gamma_interval(cp["lamda_loc"], cp["lamda_beta"], CI))
         put("proximity", affine_beta_interval(cp["proximity_loc"], cp["proximity_size"], 0.0, (P + 1) / math.sqrt(12), CI))
-        put("background", gamma_interval(cp["b_loc"], cp["b_beta"], CI))
-        put("height", gamma_interval(cp["h_loc"], cp["h_beta"], CI))
-        put("width", affine_beta_interval(cp["w_mean"], cp["w_size"], pr["width_min"], pr["width_max"], CI))
-        put("x", affine_beta_interval(cp["x_mean"], cp["size"], -H, H, CI))
-        put("y", affine_beta_interval(cp["y_mean"], cp["size"], -H, H, CI))
+        put("background", local_gamma(cp["b_loc"], cp["b_beta"], CI))
+        put("height", local_gamma(cp["h_loc"], cp["h_beta"], CI))
+        put("width", local_beta(cp["w_mean"], cp["w_size"], pr["width_min"], pr["width_max"], CI))
+        put("x", local_beta(cp["x_mean"], cp["size"], -H, H, CI))
+        put("y", local_beta(cp["y_mean"], cp["size"], -H, H, CI))
         out["m_probs"] = self.m_probs.cpu()
         out["z_probs"] = self.z_probs.cpu()
         out["theta_probs"] = self.theta_probs.cpu()

@@ -1,9 +1,10 @@
 """
 Post-fit statistics (the part of tapqir/utils/stats.py:89-259 that `tapqir fit` needs): credible
-intervals of the variational posteriors (scipy), spot probabilities, classification scores against
+intervals of the variational posteriors, spot probabilities, classification scores against
 simulated labels, ``<name>_params.tpqr`` / ``<name>_summary.csv`` (/ ``.mat``).
 
-Runs once per fit: credible intervals (scipy, host), SNR and chi2 (stats.py:29-86, 166-193; ``tq_snr_chi2`` on the device
+Runs once per fit: credible intervals (the per-unit posteriors by ``tq_credible_intervals`` on the device through
+``gamma_interval_device`` / ``affine_beta_interval_device``; the handful of global parameters by scipy on the host), SNR and chi2 (stats.py:29-86, 166-193; ``tq_snr_chi2`` on the device
 through ``CosmosEngine.snr_chi2``), plot ranges, classification scores and p(specific) (194-226).  The rastergram PNGs of the
 reference (105-124) are not drawn.
 """
@@ -40,6 +41,46 @@ def dirichlet_interval(conc, CI):
     d = sps.beta(a=conc.numpy(), b=(conc.sum(-1, keepdim=True) - conc).numpy())
     ll, ul = d.interval(CI)
     return torch.as_tensor(ll), torch.as_tensor(ul), conc / conc.sum(-1, keepdim=True)
+
+
+def _device_intervals(kind, p0, p1, low, high, CI):
+    """``tq_credible_intervals`` on two same-shaped tensors of the HIP device: (LL, UL) as float64 CPU tensors."""
+    import ctypes as C
+
+    from tapqir_amd import _lib
+    from tapqir_amd.exceptions import HipExtensionError
+
+    if p0.device.type != "cuda" or p1.device != p0.device:
+        raise HipExtensionError("credible intervals of the per-unit posteriors run on the HIP device only (no CPU fallback)")
+    shape, dev = torch.broadcast_shapes(p0.shape, p1.shape), p0.device
+    a0 = p0.detach().to(torch.float32).expand(shape).contiguous()
+    a1 = p1.detach().to(torch.float32).expand(shape).contiguous()
+    ll = torch.empty(shape, dtype=torch.float64, device=dev)
+    ul = torch.empty(shape, dtype=torch.float64, device=dev)
+    if ll.numel():
+        a = _lib.IntervalArgs()
+        a.kind, a.p0, a.p1, a.ll, a.ul = kind, _lib.ptr(a0), _lib.ptr(a1), _lib.ptr(ll), _lib.ptr(ul)
+        a.n, a.ci, a.low, a.high = a0.numel(), float(CI), float(low), float(high)
+        _lib.check(_lib.load().tq_credible_intervals(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "tq_credible_intervals")
+    return ll.cpu(), ul.cpu()  # the copies synchronise with the kernel
+
+
+def gamma_interval_device(loc, beta, CI):
+    """``gamma_interval`` for tensors of any shape on the HIP device: the quantiles by ``tq_credible_intervals``
+    (LL, UL: float64 CPU tensors of the input's shape), the mean as the host helper forms it."""
+    from tapqir_amd import _lib
+
+    ll, ul = _device_intervals(_lib.INTERVAL_GAMMA, loc, beta, 0.0, 0.0, CI)
+    return ll, ul, loc.double().cpu()
+
+
+def affine_beta_interval_device(mean, size, low, high, CI):
+    """``affine_beta_interval`` for tensors of any shape on the HIP device (see ``gamma_interval_device``)."""
+    from tapqir_amd import _lib
+
+    ll, ul = _device_intervals(_lib.INTERVAL_AFFINE_BETA, mean, size, low, high, CI)
+    return ll, ul, mean.double().cpu()
 
 
 def quantile(x, q):
