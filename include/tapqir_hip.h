@@ -374,6 +374,8 @@ typedef struct {
   int32_t draw;                /* 1: draw latents from the guide; 0: use gbase_p / xy_given (parity tests) */
   float eps;
   uint64_t seed;
+  int32_t n_offset;            /* global index of local AOI 0 (AOI sharding: the per-unit RNG streams use global unit ids,
+                                * as the step's do); >= 0, 0 for an unsharded read-out */
 } tq_probs_args;
 
 int tq_cosmos_probs(const tq_probs_args* a, void* stream);

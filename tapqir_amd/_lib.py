@@ -103,6 +103,7 @@ class ProbsArgs(C.Structure):
         ("xy_given", C.c_void_p), ("z_probs", C.c_void_p), ("theta_probs", C.c_void_p),
         ("Nt", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("P", C.c_int32), ("K", C.c_int32),
         ("particles", C.c_int32), ("draw", C.c_int32), ("eps", C.c_float), ("seed", C.c_uint64),
+        ("n_offset", C.c_int32),
     ]
 
 

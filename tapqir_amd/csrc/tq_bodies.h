@@ -501,6 +501,8 @@ TQ_HD void tq_body_probs_unit(const tq_probs_args& a, int64_t u) {
   const int64_t U = (int64_t)a.Nt * a.F * a.C;
   const int c = (int)((uint32_t)u % (uint32_t)a.C);  // U < 2^31 (host-checked)
   const int n = (int)((uint32_t)u / ((uint32_t)a.F * (uint32_t)a.C));
+  // the streams of a unit are keyed by its GLOBAL index, like the step's local draws: a shard draws what the whole set draws
+  const uint64_t elem = (uint64_t)u + (uint64_t)a.n_offset * (uint64_t)a.F * (uint64_t)a.C;
   float z1 = 0.0f, th[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) th[k] = 0.0f;
@@ -523,7 +525,7 @@ TQ_HD void tq_body_probs_unit(const tq_probs_args& a, int64_t u) {
 #pragma nounroll
           for (int ax = 0; ax < 2; ++ax) {
             TqPhilox s;
-            tq_philox_init(&s, a.seed, 0x40000000u + (uint32_t)p, 0x800u + 2 * k + ax, (uint64_t)u);
+            tq_philox_init(&s, a.seed, 0x40000000u + (uint32_t)p, 0x800u + 2 * k + ax, elem);
             const float mean = ax ? ym[k] : xm[k];
             const float c1 = sz[k] * (mean + H) / (2.0f * H), c0 = sz[k] - c1;
             const float g1 = tq_sample_std_gamma(&s, c1), g0 = tq_sample_std_gamma(&s, c0);

@@ -536,6 +536,10 @@ extern "C" int tq_cosmos_probs(const tq_probs_args* a, void* stream) {
     tq_set_error("tq_cosmos_probs: unsupported K/C/particles");
     return TQ_ERR_ARG;
   }
+  if (a->n_offset < 0) {
+    tq_set_error("tq_cosmos_probs: n_offset < 0");
+    return TQ_ERR_ARG;
+  }
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(tq_probs_globals_kernel, dim3(TQ_NGSITES(a->C), a->particles), dim3(64), 0, st, *a);
   if (int rc = tq_launch_status("tq_probs_globals_kernel")) return rc;

@@ -56,6 +56,35 @@ def _write_config(cd: Path):
         yaml.dump({k: v for k, v in DEFAULTS.items() if k != "cd"}, f, sort_keys=False)
 
 
+GPUS_HELP = ("Number of GPUs: N > 1 shards the AOIs contiguously over N rank processes, one per GPU (cosmos only).  "
+             "--nbatch-size stays the global number: rank r subsamples max(1, nbatch_size * Nt_r // Nt) of its Nt_r AOIs "
+             "per step (Nt: all AOIs).")
+
+
+def _check_gpus(command, gpus, model, cuda, logger):
+    """The checks `fit` and `stats` share for --gpus, before anything is written or started.  Returns True for a sharded
+    run (N > 1); a one-process run in a directory that holds a sharded fit is refused."""
+    from tapqir_amd.launch import read_world
+
+    if gpus < 1:
+        logger.error(f"{command}: --gpus must be at least 1, got {gpus}")
+        raise typer.Exit(1)
+    if gpus == 1:
+        world = read_world(DEFAULTS["cd"])
+        if world is not None:
+            logger.error(f"{command}: this directory holds a fit sharded over {world} ranks (.tapqir/world, rank "
+                         f"checkpoints under .tapqir/rank<r>): pass --gpus {world}")
+            raise typer.Exit(1)
+        return False
+    if not cuda:
+        logger.error(f"{command}: --gpus {gpus} needs the AMD GPUs (--cuda): the SVI step has no CPU path")
+        raise typer.Exit(1)
+    if model.value != "cosmos":
+        logger.error(f"{command}: --gpus {gpus} is not available for the {model.value} model (cosmos only)")
+        raise typer.Exit(1)
+    return True
+
+
 def _build_model(name: str, logger, **settings):
     from tapqir_amd.exceptions import HipExtensionError
     from tapqir_amd.models import models
@@ -149,6 +178,7 @@ def fit(
     num_iter: int = typer.Option(0, "--num-iter", "-it", help="Number of iterations (0 = until converged)"),
     k_max: int = typer.Option(2, "--k-max", "-k", help="Maximum number of spots per image"),
     matlab: bool = typer.Option(_default("matlab"), "--matlab", help="Save parameters in matlab format"),
+    gpus: int = typer.Option(1, "--gpus", help=GPUS_HELP),
     funsor: bool = typer.Option(False, "--funsor/--pyro", help="Accepted for compatibility; ignored"),
     pykeops: bool = typer.Option(True, "--pykeops/--no-pykeops", help="Accepted for compatibility; ignored"),
     overwrite: bool = typer.Option(True, "--overwrite", "-w", help="Overwrite defaults values."),
@@ -162,12 +192,25 @@ def fit(
 
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
+    sharded = _check_gpus("fit", gpus, model, cuda, logger)
     settings = {"S": S, "K": k_max, "device": "cuda" if cuda else "cpu", "dtype": "double", "use_pykeops": pykeops,
                 "priors": {k: float(v) for k, v in DEFAULTS.get("priors", PRIOR_DEFAULTS).items()}}
     if overwrite:
         DEFAULTS.update({"cuda": cuda, "nbatch-size": nbatch_size, "fbatch-size": fbatch_size,
                          "learning-rate": learning_rate, "matlab": matlab})
         _write_config(cd)
+
+    if sharded:
+        from tapqir_amd.launch import launch_fit
+
+        logger.info(f"Fitting the data on {gpus} GPUs ...")
+        if launch_fit(cd, gpus, settings, {"mode": "fit", "model": model.value, "learning_rate": learning_rate,
+                                            "nbatch_size": nbatch_size, "fbatch_size": fbatch_size, "num_iter": num_iter,
+                                            "matlab": bool(matlab)}):
+            logger.error("Failed to fit the data")
+            raise typer.Exit(1)
+        logger.info("Fitting the data and computing stats: Done")
+        return
 
     logger.info("Fitting the data ...")
     m = _build_model(model.value, logger, **settings)
@@ -205,6 +248,7 @@ def stats(
     nbatch_size: int = typer.Option(_default("nbatch-size"), "--nbatch-size", "-nbs", help="AOI batch size"),
     fbatch_size: int = typer.Option(_default("fbatch-size"), "--fbatch-size", "-fbs", help="Frame batch size"),
     matlab: bool = typer.Option(_default("matlab"), "--matlab", help="Save parameters in matlab format"),
+    gpus: int = typer.Option(1, "--gpus", help=GPUS_HELP),
     funsor: bool = typer.Option(False, "--funsor/--pyro", help="Accepted for compatibility; ignored"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
 ):
@@ -215,6 +259,17 @@ def stats(
 
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
+    if _check_gpus("stats", gpus, model, cuda, logger):
+        from tapqir_amd.launch import launch_fit
+
+        logger.info(f"Computing stats on {gpus} GPUs ...")
+        if launch_fit(cd, gpus, {"device": "cuda", "dtype": "double"},
+                      {"mode": "stats", "model": model.value, "nbatch_size": nbatch_size, "fbatch_size": fbatch_size,
+                       "matlab": bool(matlab)}):
+            logger.error("Failed to compute stats")
+            raise typer.Exit(1)
+        logger.info("Computing stats: Done")
+        return
     logger.info("Computing stats ...")
     m = _build_model(model.value, logger, device="cuda" if cuda else "cpu", dtype="double")
     if m is None:

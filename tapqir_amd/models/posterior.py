@@ -29,6 +29,7 @@ def probs_args(eng, particles, seed, draw=True, gbase_p=None, xy_given=None):
     a.z_probs, a.theta_probs = p(ws["z_probs"]), p(ws["theta_probs"])
     a.Nt, a.F, a.C, a.P, a.K = eng.Nt, eng.F, eng.C, eng.P, eng.K
     a.particles, a.draw, a.eps, a.seed = particles, int(bool(draw)), eng.eps, seed
+    a.n_offset = eng.n_offset  # AOI sharding: the per-unit draws are keyed by the global unit index
     return a, ws
 
 

@@ -134,20 +134,35 @@ def snr_and_chi2(data, height, width, x, y, target_locs, background, gain, offse
     return snr.reshape((K,) + lead), chi2.reshape(lead)
 
 
-def save_stats(model, path, CI=0.95, save_matlab=False):
-    import pandas as pd
-
-    global_params = model._global_params
-    ll_col, ul_col = f"{int(100 * CI)}% LL", f"{int(100 * CI)}% UL"
-    summary = pd.DataFrame(index=global_params, columns=["Mean", ll_col, ul_col])
+def unit_stats(model, CI=0.95):
+    """The per-unit part of the statistics, which needs the engine (its parameters and images): credible intervals and
+    spot probabilities (``model.compute_params``) with chi2 of every fitted image under ``chi2["values"]``, and the
+    signal-to-noise ratio of every spot ``(K, Nt, F, Q)`` (float64, CPU).  A rank of an AOI-sharded fit computes these for
+    its own AOIs; everything that depends on all AOIs is left to ``summarise``."""
     logger.info("- credible intervals & spot probabilities")
     ci_stats = model.compute_params(CI)
+    logger.info("- SNR and Chi2-test")
+    # one kernel over all units on the device that holds the images (stats.py:166-182 loops over the AOIs on the host)
+    snr, chi2 = model.engine.snr_chi2(model.data.offset.mean, model.data.offset.var)
+    ci_stats["chi2"] = {"values": chi2.float().cpu()}
+    return ci_stats, snr.double().cpu()
+
+
+def summarise(ci_stats, snr, data, CI=0.95, global_params=("gain", "proximity", "lamda", "pi")):
+    """Everything that depends on ALL AOIs, from the per-unit statistics of the whole data set (``unit_stats`` of a
+    one-process fit, or the ranks' outputs concatenated by ``tapqir_amd.launch.merge_rank_outputs``) and its labels:
+    the plot ranges ``vmin`` / ``vmax`` (written into ``ci_stats``), the summary rows of the global parameters, the mean
+    SNR per dye, and the classification scores and p(specific) against ``data.labels``.  Returns the summary table."""
+    import pandas as pd
+
+    ll_col, ul_col = f"{int(100 * CI)}% LL", f"{int(100 * CI)}% UL"
+    summary = pd.DataFrame(index=list(global_params), columns=["Mean", ll_col, ul_col])
     for param in global_params:
         for col, key in (("Mean", "Mean"), (ll_col, "LL"), (ul_col, "UL")):
             v = ci_stats[param][key]
             summary.loc[param, col] = v.item() if v.ndim == 0 else v.tolist()
 
-    data = model.data
+    chi2 = ci_stats.pop("chi2")["values"]  # (re-inserted below: the file keeps its key order)
     # plot ranges (stats.py:126-142)
     tmask = ci_stats["theta_probs"] > 0.5
     hmax = float(np.percentile(ci_stats["height"]["Mean"][tmask].numpy(), 99)) if bool(tmask.any()) else 1.0
@@ -159,18 +174,12 @@ def save_stats(model, path, CI=0.95, save_matlab=False):
         ci_stats["time1"] = data.time1
     if getattr(data, "ttb", None) is not None:
         ci_stats["ttb"] = data.ttb
-    model.params = ci_stats
 
-    logger.info("- SNR and Chi2-test")
-    K, Q = model.K, model.Q
-    # one kernel over all units on the device that holds the images (stats.py:166-182 loops over the AOIs on the host)
-    snr, chi2 = model.engine.snr_chi2(data.offset.mean, data.offset.var)
-    snr, chi2 = snr.double().cpu(), chi2.double().cpu()
-    for q in range(Q):
+    for q in range(snr.shape[-1]):
         sel = snr[..., q][ci_stats["theta_probs"][..., q] > 0.5]
         summary.loc[f"SNR_{q}", "Mean"] = float(sel.mean()) if sel.numel() else float("nan")
     cmax = float(quantile(chi2.flatten(), 0.99))
-    ci_stats["chi2"] = {"values": chi2.float(), "vmin": -0.03 * cmax, "vmax": 1.3 * cmax}
+    ci_stats["chi2"] = {"values": chi2, "vmin": -0.03 * cmax, "vmax": 1.3 * cmax}
 
     if data.labels is not None:
         from sklearn.metrics import confusion_matrix, matthews_corrcoef, precision_score, recall_score
@@ -197,21 +206,38 @@ def save_stats(model, path, CI=0.95, save_matlab=False):
             summary.loc["p(specific)", ll_col], summary.loc["p(specific)", ul_col] = float(lo), float(hi)
         else:
             summary.loc["p(specific)", "Mean"] = summary.loc["p(specific)", ll_col] = summary.loc["p(specific)", ul_col] = 0.0
+    return summary
+
+
+def write_stats(ci_stats, summary, path, name, save_matlab=False):
+    """``<path>/<name>_params.tpqr`` (and ``.mat``) and ``<path>/<name>_summary.csv``."""
+    path = Path(path)
+    torch.save(ci_stats, path / f"{name}_params.tpqr")
+    logger.info(f"Parameters were saved in {path / f'{name}_params.tpqr'}")
+    if save_matlab:
+        from scipy.io import savemat
+
+        mat = {}
+        for param, field in ci_stats.items():
+            if isinstance(field, dict):
+                mat[param] = {s: np.asarray(v) for s, v in field.items()}
+            else:
+                mat[param] = np.asarray(field)
+        savemat(path / f"{name}_params.mat", mat)
+    summary.to_csv(path / f"{name}_summary.csv")
+    logger.info(f"Summary statistics were saved in {path / f'{name}_summary.csv'}")
+
+
+SNR_FILE = "{name}_snr.tpqr"  # per-rank side file of an AOI-sharded fit: the per-unit SNR the merged summary needs
+
+
+def save_stats(model, path, CI=0.95, save_matlab=False):
+    ci_stats, snr = unit_stats(model, CI)
+    summary = summarise(ci_stats, snr, model.data, CI, global_params=model._global_params)
+    model.params = ci_stats
     model.summary = summary
-
     if path is not None:
-        path = Path(path)
-        torch.save(ci_stats, path / f"{model.name}_params.tpqr")
-        logger.info(f"Parameters were saved in {path / f'{model.name}_params.tpqr'}")
-        if save_matlab:
-            from scipy.io import savemat
-
-            mat = {}
-            for param, field in ci_stats.items():
-                if isinstance(field, dict):
-                    mat[param] = {s: np.asarray(v) for s, v in field.items()}
-                else:
-                    mat[param] = np.asarray(field)
-            savemat(path / f"{model.name}_params.mat", mat)
-        summary.to_csv(path / f"{model.name}_summary.csv")
-        logger.info(f"Summary statistics were saved in {path / f'{model.name}_summary.csv'}")
+        write_stats(ci_stats, summary, path, model.name, save_matlab)
+        if model.collective is not None:
+            # one rank of an AOI-sharded fit: the files above cover this rank's AOIs; the launcher merges them
+            torch.save({"snr": snr}, Path(path) / SNR_FILE.format(name=model.name))
