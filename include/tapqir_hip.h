@@ -272,9 +272,9 @@ typedef struct {
                                   `randperm(F)[:fb]` of pyro.plate (cosmos.py:194-208), as the nb / fb smallest of Nt / F Philox
                                   keys (stream: seed, step + 1; a radix selection, no sort) in its tail workgroup, after the flags are published: a host that
                                   passes them as ndx / fdx of the next call never draws, stages or copies an index
-                                  (Nt, F <= TQ_SUBSAMPLE_MAX) */
+                                  (Nt, F <= TQ_SUBSAMPLE_MAX: the index is a 16-bit field beside the key) */
 } tq_cosmos_args;
-#define TQ_SUBSAMPLE_MAX 2048
+#define TQ_SUBSAMPLE_MAX 65536
 
 #define TQ_TAIL_AUTO 0
 #define TQ_TAIL_ROWS16 1
@@ -339,6 +339,14 @@ int tq_cosmos_pixel_unit(const tq_cosmos_args* a, void* stream);
  * fb * C >= 16; `sync` must point to TQ_SYNC_WORDS zero-initialised int32 (zeroed again by the host after a launch that was
  * torn down). */
 int tq_cosmos_minibatch_step(const tq_cosmos_args* a, const tq_cosmos_args* prev, void* stream);
+/* The subsample that launch draws, by itself (one workgroup running the same device routine): out[0..take) = the indices of
+ * the `take` smallest of the n Philox keys of (seed, step, axis; element = index), ties broken by the index, listed
+ * ascending by (index mod 256, index div 256).  axis 0: AOIs (what the launch of step `step - 1` writes to next_ndx with
+ * n = Nt, take = nb), 1: frames (next_fdx, n = F, take = fb).  Replaces pyro.plate's subsample (cosmos.py:194-208);
+ * a fit's subsamples can be reproduced from (seed, step) alone.  TQ_ERR_ARG, before anything touches the device, unless
+ * out != NULL, axis in {0, 1} and 1 <= take <= n <= TQ_SUBSAMPLE_MAX. */
+int tq_subsample_draw(uint64_t seed, uint32_t step, int32_t axis /* 0: AOIs, 1: frames */, int32_t n, int32_t take,
+                      int32_t* out /* [take], device */, void* stream);
 
 /* AOI-sharded runs: everything that follows the all-reduce of gsum (tq_cosmos_globals_grad + tq_cosmos_adam) in one
  * single-workgroup launch, plus -- if `next` is given (full-batch steps) -- the global draws of the next step

@@ -71,7 +71,7 @@ class CosmosArgs(C.Structure):
 TAIL_ROWS16 = 1       # TQ_TAIL_ROWS16 (tail_kind)
 PIXEL_FUSED_UNIT = 2  # TQ_PIXEL_FUSED_UNIT (pixel_mode)
 SYNC_WORDS = 64       # TQ_SYNC_WORDS
-SUBSAMPLE_MAX = 2048  # TQ_SUBSAMPLE_MAX
+SUBSAMPLE_MAX = 65536  # TQ_SUBSAMPLE_MAX
 GSUM_LEN = 32         # TQ_GSUM_LEN
 
 
@@ -209,7 +209,7 @@ EXPORTS = [
     "tq_globals_size", "tq_gbase_size", "tq_cosmos_nblk", "tq_cosmos_param_count",
     "tq_cosmos_sample_globals", "tq_cosmos_sample_locals", "tq_cosmos_elbo_grads",
     "tq_cosmos_globals_grad", "tq_cosmos_adam", "tq_cosmos_adam_catchup", "tq_cosmos_step", "tq_cosmos_step_overlapped", "tq_cosmos_tail", "tq_cosmos_tail_reduced", "tq_cosmos_sample_locals_range",
-    "tq_cosmos_blk_floats", "tq_cosmos_minibatch_step", "tq_cosmos_pixel_unit",
+    "tq_cosmos_blk_floats", "tq_cosmos_minibatch_step", "tq_subsample_draw", "tq_cosmos_pixel_unit",
     "tq_cosmos_probs", "tq_glimpse_extract", "tq_ksmogn_rsample", "tq_snr_chi2", "tq_ttfb_sample", "tq_ttfb_fit",
     "tq_dwell_sample", "tq_dwell_fit", "tq_credible_intervals",
 ]
@@ -269,6 +269,8 @@ def load():
         fn.restype = C.c_int
     lib.tq_cosmos_sample_locals_range.argtypes = [C.POINTER(CosmosArgs), C.c_int32, C.c_int32, C.POINTER(CosmosArgs), C.c_void_p]
     lib.tq_cosmos_sample_locals_range.restype = C.c_int
+    lib.tq_subsample_draw.argtypes = [C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.tq_subsample_draw.restype = C.c_int
     lib.tq_cosmos_adam_catchup.argtypes = [C.POINTER(CosmosArgs), C.c_int32, C.c_void_p]
     lib.tq_cosmos_adam_catchup.restype = C.c_int
     lib.tq_cosmos_probs.argtypes = [C.POINTER(ProbsArgs), C.c_void_p]

@@ -469,8 +469,7 @@ extern "C" int tq_cosmos_minibatch_step(const tq_cosmos_args* a, const tq_cosmos
       tq_set_error("tq_cosmos_minibatch_step: next_ndx / next_fdx need Nt, F <= TQ_SUBSAMPLE_MAX");
       return TQ_ERR_ARG;
     }
-    const size_t sel = sizeof(int) * (2048 + 8);  // tq_draw_subsample: histogram of 2048 bins + scan / boundary words
-    if (lds < sel) lds = sel;
+    if (lds < TQ_SUBSAMPLE_LDS) lds = TQ_SUBSAMPLE_LDS;
   }
   const int code = prev ? tq_prev_code(*prev) : TQ_PREV_NONE;
   const tq_cosmos_args& pv = prev ? *prev : *a;
@@ -484,6 +483,32 @@ extern "C" int tq_cosmos_minibatch_step(const tq_cosmos_args* a, const tq_cosmos
       else hipLaunchKernelGGL((tq_minibatch_kernel<KK, false, 16>), grid, block, lds, st, *a, pv, code, k, B, tail_last);
     });
   return tq_launch_status("tq_minibatch_kernel");
+}
+
+// The subsample of a minibatch step by itself: the routine the tail workgroup of tq_minibatch_kernel runs, in a launch of
+// one workgroup.
+__global__ __launch_bounds__(256) void tq_subsample_draw_kernel(const uint64_t seed, const uint32_t step, const uint32_t site, const int n,
+                                                                const int take, int32_t* out) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  tq_draw_subsample((int*)smem, seed, step, site, n, take, out);
+}
+
+extern "C" int tq_subsample_draw(uint64_t seed, uint32_t step, int32_t axis, int32_t n, int32_t take, int32_t* out, void* stream) {
+  if (!out) {
+    tq_set_error("tq_subsample_draw: NULL out");
+    return TQ_ERR_ARG;
+  }
+  if (axis != 0 && axis != 1) {
+    tq_set_error("tq_subsample_draw: axis must be 0 (AOIs) or 1 (frames)");
+    return TQ_ERR_ARG;
+  }
+  if (n < 1 || n > TQ_SUBSAMPLE_MAX || take < 1 || take > n) {
+    tq_set_error("tq_subsample_draw: need 1 <= take <= n <= TQ_SUBSAMPLE_MAX");
+    return TQ_ERR_ARG;
+  }
+  hipLaunchKernelGGL(tq_subsample_draw_kernel, dim3(1), dim3(256), TQ_SUBSAMPLE_LDS, (hipStream_t)stream, seed, step,
+                     axis == 0 ? TQ_SITE_SUBSAMPLE_N : TQ_SITE_SUBSAMPLE_F, (int)n, (int)take, out);
+  return tq_launch_status("tq_subsample_draw_kernel");
 }
 
 // AOI-sharded pipeline: the local sites [site_begin, site_begin + site_count) of `a`; with `prev` (whose gsum the caller

@@ -43,16 +43,26 @@
 #include "tq_step_rows.h"
 #include "tq_step_staged.h"
 
-// The next step's subsample, drawn by the tail workgroup of a minibatch launch: `take` of `n` indices without replacement =
-// the indices of the `take` smallest of n Philox keys (stream: seed, step, site; ties broken by the index).  The law of
-// randperm(n)[:take] (pyro.plate's subsample, cosmos.py:194-208) up to the order of the selected indices, which no sum depends
-// on.  256 threads, n <= TQ_SUBSAMPLE_MAX = 2048 (eight keys per thread, in registers); `hist` holds 2048 + 8 int32 words.
+// The next step's subsample, drawn by the tail workgroup of a minibatch launch (and by tq_subsample_draw, the same routine in
+// a launch of its own): `take` of `n` indices without replacement = the indices of the `take` smallest of n Philox keys
+// (stream: seed, step, site, element = index; ties broken by the index).  The law of randperm(n)[:take] (pyro.plate's
+// subsample, cosmos.py:194-208) up to the order of the selected indices, which no sum depends on.  256 threads,
+// n <= TQ_SUBSAMPLE_MAX = 65536 (the index field of the composite below); `hist` holds 2048 + 8 int32 words of LDS whatever n.
 //
 // Selection by radix instead of a sort (a bitonic sort of 1024 keys in LDS is 55 barrier-separated stages, ~2.5 us of every
-// step): a histogram of the top 11 bits of the 43-bit composite (key << 11 | index), a scan over its bins to the bin that
+// step): a histogram of the top 11 bits of the 48-bit composite (key << 16 | index), a scan over its bins to the bin that
 // holds the take-th smallest, and -- only if that bin is not taken whole -- the same again on the next 11 bits inside it
-// (random keys: the boundary bin holds one or two elements, so one or two levels).  Then the selected indices are
-// compacted in (thread, slot) order through a second scan: the output does not depend on the timing of any atomic.
+// (levels of 11, 11, 11, 11 and 4 bits; random keys: the boundary bin of the second level holds one or two elements, so
+// two levels, seldom three).  Then the selected indices are compacted in (thread, slot) order through a second scan: thread
+// tid owns the indices tid, tid + 256, ..., so the output lists them ascending by (i mod 256, i div 256) and does not depend
+// on the timing of any atomic.
+//
+// Thread tid's composites: up to TQ_SUBSAMPLE_REG = 2048 indices, eight in registers (the default minibatches; fully unrolled).
+// Beyond, the thread walks its ceil(n / 256) indices once per pass -- a pass per level, one to count, one to write -- and
+// recomputes the key of an index in every pass: four interleaved Philox chains per thread measured faster than composites
+// parked in global memory after the first pass and loaded back (by about 6 % at n = 65536, 20 % at 4000).
+#define TQ_SUBSAMPLE_REG 2048
+#define TQ_SUBSAMPLE_LDS (sizeof(int) * (2048 + 8)) /* histogram of 2048 bins + scan / boundary words: what a launch that draws must provide */
 __device__ __forceinline__ int tq_block_exscan(int v, int* s_w) {  // exclusive prefix sum over the 256 threads; s_w: 4 words
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int inc = v;
@@ -70,33 +80,46 @@ __device__ __forceinline__ int tq_block_exscan(int v, int* s_w) {  // exclusive 
     if (w < wave) base += s_w[w];
   return base + inc - v;
 }
-__device__ __forceinline__ void tq_draw_subsample(int* hist, uint64_t seed, uint32_t step, uint32_t site, int n, int take,
-                                                  int32_t* out) {
-  constexpr int PER = TQ_SUBSAMPLE_MAX / 256;
+__device__ __forceinline__ uint64_t tq_subsample_composite(uint64_t seed, uint32_t step, uint32_t site, int i) {
+  TqPhilox s;
+  tq_philox_init(&s, seed, step, site, (uint64_t)i);
+  return ((uint64_t)tq_philox_next(&s) << 16) | (uint32_t)i;
+}
+template <bool REG>
+__device__ __forceinline__ void tq_draw_subsample_impl(int* hist, uint64_t seed, uint32_t step, uint32_t site, int n, int take,
+                                                       int32_t* out) {
+  constexpr int PER = TQ_SUBSAMPLE_REG / 256;
+  constexpr int UNR = REG ? PER : 4;
   int* s_w = hist + 2048;      // 4 words of the scans
   int* s_bnd = hist + 2048 + 4;  // boundary bin, elements below it, elements in it
   const int tid = threadIdx.x;
+  const int per = REG ? PER : (n + 255) >> 8;  // slots of this thread: index tid + 256 j in slot j
   uint64_t c[PER];
+  if constexpr (REG) {
 #pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const int i = tid + 256 * j;
-    c[j] = ~0ull;
-    if (i < n) {
-      TqPhilox s;
-      tq_philox_init(&s, seed, step, site, (uint64_t)i);
-      c[j] = ((uint64_t)tq_philox_next(&s) << 11) | (uint32_t)i;
+    for (int j = 0; j < PER; ++j) {
+      const int i = tid + 256 * j;
+      c[j] = i < n ? tq_subsample_composite(seed, step, site, i) : ~0ull;
     }
   }
+  auto composite = [&](int j) -> uint64_t {  // of slot j, whose index is < n
+    if constexpr (REG) return c[j];
+    return tq_subsample_composite(seed, step, site, tid + 256 * j);
+  };
   uint64_t path = 0, T = 0;
   int need = take;
-  for (int level = 0; level < 4; ++level) {
-    const int shift = level == 0 ? 32 : (level == 1 ? 21 : (level == 2 ? 10 : 0));
-    const int width = level == 3 ? 10 : 11;
+  for (int level = 0; level < 5; ++level) {
+    const int shift = level == 4 ? 0 : 37 - 11 * level;
+    const int width = level == 4 ? 4 : 11;
     for (int b = tid; b < 2048; b += 256) hist[b] = 0;
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < PER; ++j)
-      if (tid + 256 * j < n && (c[j] >> (shift + width)) == path) atomicAdd(&hist[(int)((c[j] >> shift) & ((1u << width) - 1u))], 1);
+#pragma unroll UNR
+    for (int j = 0; j < per; ++j) {
+      if (tid + 256 * j < n) {
+        const uint64_t v = composite(j);
+        if ((v >> (shift + width)) == path) atomicAdd(&hist[(int)((v >> shift) & ((1u << width) - 1u))], 1);
+      }
+    }
     __syncthreads();
     int cnt[8], local = 0;
 #pragma unroll
@@ -125,13 +148,25 @@ __device__ __forceinline__ void tq_draw_subsample(int* hist, uint64_t seed, uint
     __syncthreads();  // (s_bnd is rewritten at the next level)
   }
   int mine = 0;
-#pragma unroll
-  for (int j = 0; j < PER; ++j) mine += (tid + 256 * j < n && c[j] < T) ? 1 : 0;
+#pragma unroll UNR
+  for (int j = 0; j < per; ++j)
+    if (tid + 256 * j < n) mine += composite(j) < T ? 1 : 0;
   int at = tq_block_exscan(mine, s_w);
-#pragma unroll
-  for (int j = 0; j < PER; ++j)
-    if (tid + 256 * j < n && c[j] < T) out[at++] = (int32_t)(tid + 256 * j);
+#pragma unroll UNR
+  for (int j = 0; j < per; ++j)
+    if (tid + 256 * j < n && composite(j) < T) out[at++] = (int32_t)(tid + 256 * j);
   __syncthreads();  // (hist is reused by the next draw)
+}
+// The chunked walk stays out of line: inlined (twice) into tq_minibatch_kernel its Philox chains and level loop took part in
+// the register allocation of the whole launch and moved the spills of the workers' phases.  One call per drawn axis.
+static __device__ __noinline__ void tq_draw_subsample_chunked(int* hist, uint64_t seed, uint32_t step, uint32_t site, int n, int take,
+                                                              int32_t* out) {
+  tq_draw_subsample_impl<false>(hist, seed, step, site, n, take, out);
+}
+__device__ __forceinline__ void tq_draw_subsample(int* hist, uint64_t seed, uint32_t step, uint32_t site, int n, int take,
+                                                  int32_t* out) {
+  if (n <= TQ_SUBSAMPLE_REG) tq_draw_subsample_impl<true>(hist, seed, step, site, n, take, out);
+  else tq_draw_subsample_chunked(hist, seed, step, site, n, take, out);
 }
 #define TQ_SITE_SUBSAMPLE_N 0xA00u
 #define TQ_SITE_SUBSAMPLE_F 0xA01u

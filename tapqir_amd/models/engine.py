@@ -25,6 +25,14 @@ DEFAULT_PRIORS = {  # tapqir/models/cosmos.py:55-64
 }
 
 
+# Most keys CosmosEngine.step_subsampled lets a launch walk for the next step's subsample: the sizes of the axes it actually
+# subsamples, added up (an axis taken whole draws nothing).  The library draws up to _lib.SUBSAMPLE_MAX = 65536 per axis, but
+# the draw is one workgroup walking every key, and where it outlasts the workers of the launch the step is slower than one on
+# indices the host supplies.  400 + 4000 keys (the shard of BASELINE config c3) is the largest draw measured that is not slower;
+# 16384 is slower ("Subsamples beyond 2048 AOIs or frames").  Every data set within 2048 x 2048 is below it.
+DEVICE_SUBSAMPLE_MAX = 4400
+
+
 def merge_offsets(samples, weights):
     """Offset samples with equal value are one mixture component: sum_o w_o f(D - d_o) is
     unchanged when equal d_o are merged (simulate.py:92-103 stores 3 identical samples)."""
@@ -695,7 +703,8 @@ class CosmosEngine:
         step whose batch sizes differ from what the previous launch prepared) takes a host draw from ``generator``.  Returns
         False if this engine cannot run that path (the caller then passes its own subsample to ``step``)."""
         nb, fb = min(int(nb), self.Nt), min(int(fb), self.F)
-        if not ((nb < self.Nt or fb < self.F) and max(self.Nt, self.F) <= _lib.SUBSAMPLE_MAX
+        drawn = (self.Nt if nb < self.Nt else 0) + (self.F if fb < self.F else 0)  # keys the launch would walk
+        if not (0 < drawn <= DEVICE_SUBSAMPLE_MAX
                 and self._route(nb, fb, None) == "one_launch"
                 and os.environ.get("TAPQIR_AMD_DEVICE_SUBSAMPLE", "1") != "0"):
             return False
@@ -715,6 +724,26 @@ class CosmosEngine:
         self.step(ndx, fdx, _next_sub=(nxt[:nb] if nb < self.Nt else None, nxt[Nt:Nt + fb] if fb < self.F else None))
         st["turn"], st["ready"] = 1 - cur, (nb, fb, self.adam_step)
         return True
+
+    def draw_subsample_device(self, nb, fb, step):
+        """The subsample of the minibatch step that starts from ``adam_step == step``, as the device draws it for this engine's
+        seed: ``(ndx, fdx)``, int32 device tensors of nb AOI / fb frame indices, ``None`` where the whole axis is taken.
+        Mind the off-by-one: the launch of step ``s`` draws the subsample of step ``s + 1`` with the key stream
+        ``(seed, s + 1)``, so what this returns is what the launch of step ``step - 1`` writes into its ``next_ndx`` /
+        ``next_fdx`` (``tq_subsample_draw``, the same device routine in a launch of its own) -- the indices
+        ``step_subsampled`` runs step ``step`` on, unless that step opened a sequence with a host draw.  Replaces
+        pyro.plate's subsample (tapqir/models/cosmos.py:194-208); a fit's subsamples are reproducible from (seed, step)."""
+        nb, fb = min(int(nb), self.Nt), min(int(fb), self.F)
+        out = []
+        for axis, (n, take) in enumerate(((self.Nt, nb), (self.F, fb))):
+            if take >= n:
+                out.append(None)
+                continue
+            idx = torch.empty(take, dtype=torch.int32, device=self.device)
+            _lib.check(self.lib.tq_subsample_draw(self.seed & 0xFFFFFFFFFFFFFFFF, int(step), axis, n, take, _lib.ptr(idx), self._stream()),
+                       "tq_subsample_draw")
+            out.append(idx)
+        return tuple(out)
 
     def step(self, ndx=None, fdx=None, allreduce=None, _next_sub=None):
         """One SVI step; returns nothing (the ELBO stays on the device in ``elbo_out``).
