@@ -1,6 +1,7 @@
 """Shared test utilities: problem construction, oracle <-> engine plumbing, host-check loader."""
 
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -150,6 +151,11 @@ def make_dataset(N=4, F=6, C=1, P=14, K=2, seed=0, offsets="sim", mask=None):
         w = torch.exp(-0.5 * ((s - 90.0) / 60.0) ** 2)
         d = CosmosDataset(d.images, d.xy, d.is_ontarget, labels=d.labels, offset_samples=s,
                           offset_weights=(w / w.sum()).float())
+    if offsets == "hist8":  # a histogram narrow enough for the dense oracle at the default 10 x 512 minibatch (5120 units)
+        s = torch.arange(82.0, 98.0, 2.0)
+        w = torch.exp(-0.5 * ((s - 90.0) / 4.0) ** 2)
+        d = CosmosDataset(d.images, d.xy, d.is_ontarget, labels=d.labels, offset_samples=s,
+                          offset_weights=(w / w.sum()).float())
     if mask is not None:
         d.mask = mask
     return d
@@ -244,3 +250,144 @@ def read_engine_latents(eng, nb, fb):
     if getattr(eng, "crosstalk", False):  # float alpha[2][2] follows c[4]
         out["alpha"] = g[21:25].clone().view(2, 2)
     return out
+
+
+# ---- whole device steps against the oracle ---------------------------------------------------------------------------------
+# the tolerances of test_gpu_production_kernels.replay: -ELBO relative, every parameter after the update absolute (2 % of one
+# Adam step of lr = 0.005)
+ELBO_RTOL, PARAM_ATOL = 2e-5, 1e-4
+
+
+def replay_steps(eng, o, step, steps=3):
+    """test_gpu_production_kernels.replay with the device step left to the caller: ``step(eng, it)`` runs step ``it`` on the
+    engine and returns the AOI and frame indices it ran on (host int64 tensors).  The oracle replays each step from the
+    device's draws, the same assertions are made, and the oracle's parameters go back into the engine."""
+    for it in range(steps):
+        nd, fd = step(eng, it)
+        eng.join()
+        torch.cuda.synchronize()
+        lat32 = read_engine_latents(eng, len(nd), len(fd))
+        with torch.no_grad():
+            base = o.base_draws(lat32, o._guide_dists(o.constrained(o.params), nd, fd))
+        loss_o = o.step(nd, fd, base=base)
+        loss_k = -float(eng.elbo_out[0])
+        assert abs(loss_k - loss_o) <= ELBO_RTOL * abs(loss_o), (it, loss_k, loss_o)
+        views = eng.named("params")
+        for n, u in o.params.items():
+            got = views[n].cpu().double().reshape(u.shape)
+            err = float((got - u.detach()).abs().max())
+            assert err < PARAM_ATOL, (it, n, err)
+        oracle_to_engine(o, eng)
+
+
+# ---- free-running trajectories: nothing is copied back into the engine -------------------------------------------------------
+def oracle_twin(o):
+    """A second oracle on the same data with the same parameter values and a fresh Adam state (``o`` has not stepped yet)."""
+    t = type(o)(o.data, K=o.K, priors=o.priors, eps=o.eps)
+    t.params = {n: u.detach().clone().requires_grad_(True) for n, u in o.params.items()}
+    t.make_optim(lr=next(iter(o.optim.values())).param_groups[0]["lr"])
+    return t
+
+
+def oracle_step_from_latents(o, nd, fd, lat32, grad_eps=0.0, generator=None, round32=False):
+    """One oracle step on latent VALUES ``lat32`` (the base draws behind them are recovered with the oracle's own parameters,
+    as replay() does).  ``grad_eps``: every gradient element is multiplied by 1 + grad_eps randn before Adam;
+    ``round32``: the parameters are rounded to float32 after the update.  Returns the loss (-ELBO)."""
+    with torch.no_grad():
+        base = o.base_draws(lat32, o._guide_dists(o.constrained(o.params), nd, fd))
+    for u in o.params.values():
+        u.grad = None
+    loss = -o.elbo(o.params, nd, fd, o.latents_from_base(o.params, nd, fd, base))
+    loss.backward()
+    for n, u in o.params.items():
+        if u.grad is None:
+            u.grad = torch.zeros_like(u)
+        if grad_eps:
+            u.grad.mul_(1.0 + grad_eps * torch.randn(u.shape, generator=generator, dtype=u.dtype))
+        o.optim[n].step()
+        if round32:
+            u.data = u.data.float().double()
+    return float(loss.detach())
+
+
+def _max_diff(a, b):
+    """{family: max |a - b|} of two oracles' parameters."""
+    return {n: float((a.params[n].detach() - u.detach()).abs().max()) for n, u in b.params.items()}
+
+
+def free_run(eng, o, N, F, steps, nb=None, fb=None, seed=5, expect=None, extra_eps=(), check_at=(10, 25)):
+    """``steps`` steps of the engine and of the oracle side by side, each with its OWN parameters and Adam state from a common
+    start: every step the engine's latent draws go to the oracle (read_engine_latents + base_draws, as in replay()), and
+    nothing ever goes back.  A gradient error the step-by-step replays wipe out accumulates here, and so does an error in how
+    the Adam moments or the lazy-Adam clock carry from step to step.  The engine runs as a fit runs it: the tail of a step
+    stays pending and runs inside the next launch (its ELBO is compared then), ``join()`` -- which also brings every unit of a
+    lazy-Adam fit to the current step -- is called only where the parameters are read: after steps ``check_at`` and the last.
+
+    The bound comes from the reference alone.  Two more copies of the oracle take the same latents:
+      * the tolerated-error twin multiplies every gradient element by 1 + 1e-4 randn (fixed generator) before Adam: 1e-4 is
+        the gradient tolerance the suite grants the kernels;
+      * the storage twin rounds its parameters to float32 after every step.
+    drift(twin) = max over all parameters of |twin - oracle|.  At every check, for every parameter family,
+        max |engine - oracle| <= 3 drift(tolerated twin) + drift(storage twin)
+    (3: the twin's noise is random and adds in quadrature, a kernel's error of that size may be systematic); -ELBO agrees to
+    ELBO_RTOL at every step.  ``extra_eps``: further gradient-noise twins, recorded only.  ``eng`` = None: no engine, the
+    latents are the oracle's own float32-rounded guide draws (the twins and the bound by themselves).
+
+    Returns one record per check: step, bound, drift of each twin ("tolerated", "storage", every extra eps) and "engine" =
+    {family: (max |engine - oracle|, flat index of that element)}."""
+    twins = {"tolerated": (oracle_twin(o), 1e-4, False), "storage": (oracle_twin(o), 0.0, True)}
+    for e in extra_eps:
+        twins[e] = (oracle_twin(o), e, False)
+    noise = {k: torch.Generator().manual_seed(100 + i) for i, k in enumerate(twins)}
+    g = torch.Generator().manual_seed(seed)
+    mini = nb is not None
+    cuda = eng is not None and eng.device.type == "cuda"
+    owed = None  # (step, oracle loss) of a step whose device ELBO is still in its pending tail
+    records = []
+
+    def settle(owed):
+        it, loss_o = owed
+        loss_k = -float(eng.elbo_out[0])
+        assert abs(loss_k - loss_o) <= ELBO_RTOL * abs(loss_o), (it, loss_k, loss_o)
+
+    for it in range(steps):
+        nd = torch.randperm(N, generator=g)[:nb] if mini else torch.arange(N)
+        fd = torch.randperm(F, generator=g)[:fb] if mini else torch.arange(F)
+        if eng is None:
+            lat32, _ = fp32_latents(o, nd, fd, seed=seed + it)
+        else:
+            eng.step(nd if mini else None, fd if mini else None)
+            if expect is not None:
+                expect(eng)
+            if cuda:
+                torch.cuda.synchronize()
+            if owed is not None:  # the launch just run carried the tail of the step before
+                settle(owed)
+            lat32 = read_engine_latents(eng, len(nd), len(fd))
+        loss_o = oracle_step_from_latents(o, nd, fd, lat32)
+        for k, (t, e, r32) in twins.items():
+            oracle_step_from_latents(t, nd, fd, lat32, grad_eps=e, generator=noise[k], round32=r32)
+        if eng is not None:
+            owed = (it, loss_o)
+            if eng._tail_args is None and eng._pending is None:  # nothing deferred: the ELBO of this step is out
+                settle(owed)
+                owed = None
+        if it + 1 in check_at or it + 1 == steps:
+            rec = {"step": it + 1}
+            for k, (t, _, _) in twins.items():
+                rec[k] = max(_max_diff(t, o).values())
+            rec["bound"] = 3.0 * rec["tolerated"] + rec["storage"]
+            if eng is not None:
+                views = eng.named("params")  # join(): the pending tail, and every unit at the current Adam step
+                if cuda:
+                    torch.cuda.synchronize()
+                if owed is not None:
+                    settle(owed)
+                    owed = None
+                rec["engine"] = {}
+                for n, u in o.params.items():
+                    diff = (views[n].cpu().double().reshape(u.shape) - u.detach()).abs().reshape(-1)
+                    rec["engine"][n] = (float(diff.max()), int(diff.argmax()))
+                    assert math.isfinite(rec["engine"][n][0]) and rec["engine"][n][0] <= rec["bound"], (n, rec)
+            records.append(rec)
+    return records

@@ -32,34 +32,50 @@ def test_library_exports_every_declared_symbol():
     assert _lib.load().tq_version() >= 100
 
 
+# the ctypes mirrors of the header's argument structs: {C name (from the mirror's docstring): class}
+MIRRORS = {re.search(r"``(tq_\w+)``", c.__doc__).group(1): c for c in vars(_lib).values()
+           if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure}
+
+
+def header_fields(name):
+    """Field names of ``typedef struct { ... } name;`` in include/tapqir_hip.h, in order."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tapqir_hip.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct \{([^{}]*)\}\s*%s;" % name, text).group(1)
+    out = []
+    for decl in body.split(";"):
+        if decl.strip():  # "const float* p" | "int32_t P, K, O" | "double lamda_g[4]": the declarators' identifiers
+            first, *more = decl.split(",")
+            out += [re.search(r"(\w+)\s*(\[[^\]]*\]\s*)*$", d.strip()).group(1) for d in [first] + more]
+    return out
+
+
 def test_struct_sizes_match_the_c_header():
-    """ctypes mirrors of the argument structs have the C compiler's layout."""
+    """ctypes mirrors of the argument structs have the C compiler's layout: sizeof and the offsetof of EVERY field of all
+    twelve, the C generated from each mirror's _fields_; and a mirror names the fields the header declares, in its order (a
+    field added at the end of the C struct can hide in the tail padding, where neither size nor offsets show it)."""
     import subprocess
     import tempfile
 
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "tapqir_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(tq_ksmogn_args), offsetof(tq_ksmogn_args, m_kstride),
-         offsetof(tq_ksmogn_args, scale), sizeof(tq_cosmos_args), offsetof(tq_cosmos_args, Nt),
-         offsetof(tq_cosmos_args, seed), sizeof(tq_xtalk_args), offsetof(tq_xtalk_args, m_kstride),
-         offsetof(tq_xtalk_args, scale), sizeof(tq_probs_args), sizeof(tq_glimpse_args),
-         offsetof(tq_glimpse_args, offset_P));
-  return 0;
-}'''
+    assert len(MIRRORS) == 12 and {"tq_rsample_args", "tq_snr_args", "tq_cosmos_args", "tq_ksmogn_args"} <= set(MIRRORS)
+    lines, want = [], []
+    for cname, cls in sorted(MIRRORS.items()):
+        names = [f[0] for f in cls._fields_]
+        assert names == header_fields(cname), cname
+        lines.append('  printf("%%zu\\n", sizeof(%s));' % cname)
+        want.append((cname, "sizeof", ctypes.sizeof(cls)))
+        for f in names:
+            lines.append('  printf("%%zu\\n", offsetof(%s, %s));' % (cname, f))
+            want.append((cname, f, getattr(cls, f).offset))
+    head = '#include <stdio.h>\n#include <stddef.h>\n#include "tapqir_hip.h"\nint main(void) {\n'
+    src = head + "\n".join(lines) + "\n  return 0;\n}\n"
     with tempfile.TemporaryDirectory() as td:
         c = os.path.join(td, "s.c")
         open(c, "w").write(src)
         exe = os.path.join(td, "s")
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
         got = [int(v) for v in subprocess.check_output([exe]).split()]
-    K, Cs, X = _lib.KsmognArgs, _lib.CosmosArgs, _lib.XtalkArgs
-    want = [ctypes.sizeof(K), K.m_kstride.offset, K.scale.offset, ctypes.sizeof(Cs), Cs.Nt.offset, Cs.seed.offset,
-            ctypes.sizeof(X), X.m_kstride.offset, X.scale.offset, ctypes.sizeof(_lib.ProbsArgs),
-            ctypes.sizeof(_lib.GlimpseArgs), _lib.GlimpseArgs.offset_P.offset]
-    assert got == want
+    assert len(got) == len(want)
+    assert [(n, f, g) for (n, f, _), g in zip(want, got)] == want
 
 
 # the constants of the header that the binding mirrors: every upper-case integer of tapqir_amd._lib

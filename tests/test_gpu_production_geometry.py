@@ -1,0 +1,130 @@
+"""
+The oracle behind what a real `fit` does and the other parity tests reach only through self-comparisons (VERDICT weak #2):
+
+  A. the DEFAULT minibatch launch, 10 AOIs x 512 frames per step with nothing overridden: 5120 units make the library pick
+     20 units per workgroup (tq_mb_upr: one round of 256 workgroups instead of two), the grid is 256 + 1 workgroups, so the
+     block dispatched last claims the tail and ticket 0 takes over its units (tq_minibatch_kernel, `tail_last`); with one
+     offset and with an offset histogram, with host-drawn and with device-drawn subsamples; and 8 x 512 = 4096 units, the
+     same grid of 257 with the 16-unit template.  Three steps, each replayed by the oracle (test_gpu_production_kernels.replay
+     and its tolerances: -ELBO 2e-5 relative, every parameter 1e-4 absolute);
+  C. FREE-RUNNING trajectories (helpers.free_run): tens of steps with nothing copied back into the engine, so that a small
+     systematic gradient error, or an error in how the Adam moments and the lazy-Adam clock carry from step to step,
+     accumulates instead of being wiped out at every step.  The bound is measured inside the test from the oracle alone.
+
+(B, the fused full-batch launch at c2 / c3-shard grid size, is in test_gpu_shards.py.)
+Reference semantics: tapqir/models/cosmos.py:82-462, tapqir/models/model.py:169-183, 210-212; tapqir/main.py:1429-1430.
+"""
+
+import pytest
+import torch
+
+from helpers import free_run, replay_steps
+from test_gpu_production_kernels import replay, setup
+
+from tapqir_amd import _lib
+
+pytestmark = pytest.mark.gpu
+
+
+# ---- A. the default minibatch launch ----------------------------------------------------------------------------------
+def mb_geometry(units):
+    """(units per workgroup, workgroups of the grid) of a single-launch minibatch step, as tq_mb_upr and
+    tq_cosmos_minibatch_step (tq_cosmos.hip) choose them with nothing forced and at least 20 units per AOI."""
+    r16, r20 = ((units + 15) // 16 + 255) // 256, ((units + 19) // 20 + 255) // 256  # rounds of 256 workgroups
+    upr = 20 if 17 * r20 < 13 * r16 else 16
+    return upr, (units + upr - 1) // upr + 1
+
+
+MB_DEFAULT_CASES = [
+    # id, dataset kwargs, nb, fb, units, units per workgroup, one offset, device-drawn subsamples
+    ("10x512_one_offset", dict(N=12, F=600), 10, 512, 5120, 20, True, False),        # tq_minibatch_kernel<2, true, 20>
+    ("10x512_hist8", dict(N=12, F=600, offsets="hist8"), 10, 512, 5120, 20, False, False),  # <2, false, 20>
+    ("8x512_one_offset", dict(N=12, F=600), 8, 512, 4096, 16, True, False),          # <2, true, 16>
+    ("10x512_device_subsampled", dict(N=12, F=600), 10, 512, 5120, 20, True, True),
+]
+
+
+@pytest.mark.parametrize("name,dkw,nb,fb,units,upr,one,device_drawn", MB_DEFAULT_CASES, ids=[c[0] for c in MB_DEFAULT_CASES])
+def test_default_minibatch_launch_against_oracle(name, dkw, nb, fb, units, upr, one, device_drawn, monkeypatch):
+    """Grid 257 = 256 workers + 1 in every case, so `tail_last` is on (grid > 1, (grid - 1) % 256 == 0, grid <= 513)."""
+    monkeypatch.delenv("TAPQIR_AMD_MB_UNITS", raising=False)
+    monkeypatch.delenv("TAPQIR_AMD_MB_TAIL_LAST", raising=False)
+    N, F = dkw["N"], dkw["F"]
+    d, o, eng = setup(2, dkw)
+    assert eng.fused_minibatch and eng.lazy_adam and eng._route(nb, fb, None) == "one_launch"
+    assert nb * fb * eng.C == units and mb_geometry(units) == (upr, 257) and (eng.O == 1) == one
+    if not device_drawn:
+        replay(eng, o, N, F, nb=nb, fb=fb)
+        return
+
+    # step_subsampled: the first step takes a host draw from the generator, every later one the subsample the launch of the
+    # step before drew on the device, which draw_subsample_device gives by itself from (seed, step)
+    gen, twin = torch.Generator().manual_seed(7), torch.Generator().manual_seed(7)
+
+    def step(eng, it):
+        if it == 0:
+            want = (torch.randperm(N, generator=twin)[:nb], torch.randperm(F, generator=twin)[:fb])
+        else:
+            want = tuple(t.cpu().long() for t in eng.draw_subsample_device(nb, fb, eng.adam_step))
+        assert eng.step_subsampled(nb, fb, gen) is True
+        slot = eng._sub["slots"][1 - eng._sub["turn"]].cpu().long()  # the slot the step just launched ran on
+        nd, fd = slot[:nb], slot[eng.Nt:eng.Nt + fb]
+        assert torch.equal(nd, want[0]) and torch.equal(fd, want[1]), it
+        return nd, fd
+
+    replay_steps(eng, o, step)
+    assert eng.adam_step == 3
+
+
+# ---- C. free-running trajectories ---------------------------------------------------------------------------------------
+def _report(capsys, name, records):
+    with capsys.disabled():
+        for r in records:
+            fam, (err, at) = max(r["engine"].items(), key=lambda kv: kv[1][0])
+            print("\nfree run %s: step %d  device %.3g (%s[%d])  bound %.3g  tolerated twin %.3g  storage twin %.3g"
+                  % (name, r["step"], err, fam, at, r["bound"], r["tolerated"], r["storage"]))
+
+
+def test_free_run_full_batch_one_launch(capsys):
+    """N = 4, F = 64: 256 units, whole-batch steps in the single launch of the minibatches, 50 steps.
+    Measured on an MI355X, device against oracle at steps 10 / 25 / 50: 1.6e-6 / 2.8e-6 / 4.0e-6 (worst family w_size, h_loc,
+    w_size), bounds 1.7e-5 / 2.9e-5 / 4.9e-5 (tolerated-error twin 1.5e-5, storage twin 3.9e-6 at step 50)."""
+    N, F = 4, 64
+    d, o, eng = setup(2, dict(N=N, F=F))
+    assert eng._route(N, F, None) == "one_launch"
+    recs = free_run(eng, o, N, F, 50, seed=11)
+    _report(capsys, "full_batch_one_launch", recs)
+    assert [r["step"] for r in recs] == [10, 25, 50]
+
+
+def test_free_run_minibatch_lazy_adam(capsys):
+    """N = 5, F = 64, 3 x 40 of them per step, host-drawn subsamples, 50 steps: the lazy clock and the catch-up replay of
+    the units outside the minibatches against dense torch.optim.Adam, over runs of visits and skips that end only where
+    the parameters are read (steps 10, 25, 50).
+    Measured on an MI355X, device against oracle at steps 10 / 25 / 50: 2.1e-6 / 2.7e-6 / 3.4e-6 (worst family y_mean, h_beta,
+    h_loc), bounds 1.2e-5 / 2.3e-5 / 4.0e-5 (tolerated-error twin 1.2e-5, storage twin 3.3e-6 at step 50)."""
+    N, F, nb, fb = 5, 64, 3, 40
+    d, o, eng = setup(2, dict(N=N, F=F))
+    assert eng.lazy_adam and eng._route(nb, fb, None) == "one_launch"
+    recs = free_run(eng, o, N, F, 50, nb=nb, fb=fb, seed=11)
+    _report(capsys, "minibatch_lazy_adam", recs)
+    assert [r["step"] for r in recs] == [10, 25, 50]
+
+
+def test_free_run_full_batch_fused(capsys):
+    """N = 2, F = 256: the pipelined full-batch step with the fused pixel + per-unit launch (tq_pixel_unit_kernel), its tail
+    inside the next step's sampling launch, 30 steps.
+    Measured on an MI355X, device against oracle at steps 10 / 25 / 30: 5.5e-6 / 6.2e-6 / 6.4e-6 (worst family m_probs each
+    time), bounds 1.5e-5 / 3.0e-5 / 3.4e-5 (tolerated-error twin 1.1e-5, storage twin 2.8e-6 at step 30)."""
+    N, F = 2, 256
+    d, o, eng = setup(2, dict(N=N, F=F))
+    eng.il_min_units = 1
+    eng.pixel_mode, eng.fuse_unit = 0, True
+    assert eng._fusable() and eng._route(N, F, None) == "overlapped"
+
+    def expect(e):
+        assert e._tail_args is not None and e._tail_args.pixel_mode == _lib.PIXEL_FUSED_UNIT  # tail pending
+
+    recs = free_run(eng, o, N, F, 30, seed=11, expect=expect)
+    _report(capsys, "full_batch_fused", recs)
+    assert [r["step"] for r in recs] == [10, 25, 30]

@@ -18,6 +18,7 @@ import torch
 from helpers import EPS32, oracle_grads, rel_err
 from oracle.cosmos import CosmosOracle, OracleData
 from oracle.crosstalk import CrosstalkOracle
+from tapqir_amd import _lib
 from tapqir_amd.models.cosmos import initial_values
 from tapqir_amd.models.crosstalk import crosstalk_initial_values
 from tapqir_amd.models.engine import CosmosEngine
@@ -73,14 +74,15 @@ def _stages(eng, draw=True):
     return eng.gsum.clone(), float(eng.elbo_out[0])
 
 
-def _oracle_for_units(s, eng, nd, fd):
-    """Oracle over the AOIs `nd` x frames `fd` with the engine's parameters and its latent draws of those units."""
+def _oracle_for_units(s, eng, nd, fd, views=None):
+    """Oracle over the AOIs `nd` x frames `fd` with the engine's parameters (or the parameter views `views`: those of a copy
+    taken before a step updated them) and its latent draws of those units."""
     d, K, C = s.data, s.K, s.C
     img = d.images[nd][:, fd]
     od = OracleData(img, d.xy[nd][:, fd], d.is_ontarget[nd], d.offset.samples.cpu(), d.offset.weights.cpu())
     o = (CrosstalkOracle if s.xt else CosmosOracle)(od, K=K, eps=EPS32)
     o.init_parameters()
-    views = eng.named("params")
+    views = eng.named("params") if views is None else views
     for name, u in o.params.items():
         v = views[name].detach().cpu().double()
         if v.dim() == 4:  # (K, Nt, F, Q)
@@ -152,6 +154,63 @@ def test_sampled_units_match_the_oracle(shard, pixel_mode):
             continue  # per-AOI and global parameters sum over units outside the sample
         worst[name] = rel_err(got.reshape(ref.shape), ref)
     assert len(worst) == 10 and max(worst.values()) < 1e-4, worst
+
+
+def test_fused_step_sampled_units_match_the_oracle(shard, capsys):
+    """The fused pixel + per-unit launch (tq_pixel_unit_kernel) at the grid size of c2 and of the c3 shard (6 250 / 25 000
+    tiles of 64 units), through CosmosEngine.step.  The launch writes no gradient, but its first Adam step from zero moments
+    leaves exp_avg = -(1 - beta1) dELBO/dtheta: the gradient of every local parameter is recovered from it (to one fp32
+    rounding) and compared with the oracle on 8 AOIs x 8 frames that hold the first and the last unit -- the first and the
+    last tile of the grid.  On EVERY unit: exp_avg_sq is (1 - beta2) g^2 of that gradient, the updated parameters are the Adam
+    step of the device's own moments evaluated in float64, and exp_avg_sq of h_loc is > 0 (a tile the grid skipped would
+    leave zeros).  The ELBO is not checked here: the dense oracle cannot hold 400 000 units.
+    Measured worst sampled-unit gradient error (MI355X): c2 7.0e-6, c3_shard 3.8e-6, both in m_probs."""
+    s = shard
+    eng = s.engine()
+    if not eng._fusable():
+        pytest.skip("the fused launch covers cosmos K <= 2 with one offset")
+    s.perturb(eng)
+    eng.pixel_mode, eng.fuse_unit = 0, True  # (neither autotuner runs)
+    assert eng.adam_step == 0 and not bool(eng.exp_avg.any()) and not bool(eng.exp_avg_sq.any())
+    p0 = eng.params.clone()
+    eng.step()
+    assert eng._tail_args is not None and eng._tail_args.pixel_mode == _lib.PIXEL_FUSED_UNIT  # tail pending
+    eng.join()
+    torch.cuda.synchronize()
+    g = torch.Generator().manual_seed(3)
+    half = s.N // 2  # on-target AOIs are the first half: 4 of each kind, AOI 0 and AOI N - 1 among them
+    nd = torch.cat([torch.tensor([0]), 1 + torch.randperm(half - 1, generator=g)[:3],
+                    half + torch.randperm(s.N - half - 1, generator=g)[:3], torch.tensor([s.N - 1])])
+    fd = torch.cat([torch.tensor([0]), 1 + torch.randperm(s.F - 2, generator=g)[:6], torch.tensor([s.F - 1])])
+    assert len(set(nd.tolist())) == 8 and len(set(fd.tolist())) == 8
+    o, base, ar_n, ar_f = _oracle_for_units(s, eng, nd, fd, views=eng.layout.views(p0))
+    _, g_o = oracle_grads(o, ar_n, ar_f, base)
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    b1, b2 = f32(eng.betas[0]), f32(eng.betas[1])  # the kernel's fp32 constants; 1 - b is exact in fp32
+    nl = eng.layout.n_local
+    m, v = eng.exp_avg[:nl].cpu().double(), eng.exp_avg_sq[:nl].cpu().double()
+    g_dev = -m / (1.0 - b1)
+    gv = eng.layout.views(torch.cat([g_dev, torch.zeros(eng.layout.total - nl, dtype=torch.float64)]))
+    worst = {}
+    for name, ref in g_o.items():
+        t = gv[name]
+        if t.dim() == 4:
+            got = t[:, nd][:, :, fd]
+        elif t.dim() == 3 and t.shape[1] != 1:
+            got = t[nd][:, fd]
+        else:
+            continue  # per-AOI and global parameters sum over units outside the sample
+        worst[name] = rel_err(got.reshape(ref.shape), ref)
+    with capsys.disabled():
+        print("\nfused step, sampled-unit gradient error:", s.tag, "worst %.3g" % max(worst.values()), worst)
+    assert len(worst) == 10 and max(worst.values()) < 1e-4, worst
+    # ---- every unit ----
+    tiny = float(torch.finfo(torch.float32).tiny)  # below it the fp32 product g g has no 24 bits left
+    assert torch.allclose(v, (1.0 - b2) * g_dev ** 2, rtol=1e-5, atol=tiny)
+    m_hat, v_hat = m / (1.0 - eng.betas[0]), v / (1.0 - eng.betas[1])  # step count 1
+    want = p0[:nl].cpu().double() - eng.lr * m_hat / (v_hat.sqrt() + eng.adam_eps)
+    assert torch.allclose(eng.params[:nl].cpu().double(), want, rtol=1e-5, atol=1e-6)
+    assert bool((eng.layout.views(eng.exp_avg_sq)["h_loc"] > 0).all())
 
 
 def test_elbo_is_additive_over_aoi_shards(shard):

@@ -8,8 +8,8 @@ comparisons run through the C ABI on the GPU in test_gpu_parity.py.
 import pytest
 import torch
 
-from helpers import (GIVEN_STAGES, CosmosEngine, fp32_latents, load_hostcheck, make_dataset, make_oracle, oracle_grads,
-                     oracle_to_engine, put_latents, rel_err)
+from helpers import (GIVEN_STAGES, CosmosEngine, fp32_latents, free_run, load_hostcheck, make_dataset, make_oracle,
+                     oracle_grads, oracle_to_engine, put_latents, rel_err)
 
 CASES = [
     # id, dataset kwargs, K, ndx, fdx
@@ -105,3 +105,38 @@ def test_extreme_gamma_draw_far_below_the_mean():
         got = gv[n].double().reshape(ref.shape)
         assert torch.isfinite(got).all(), n
         assert rel_err(got, ref) < 1e-4, (n, rel_err(got, ref))
+
+
+# ---- free-running trajectories (helpers.free_run): 50 full-batch steps, nothing copied back into the engine ----------------
+def _free_run_problem():
+    K, N, F = 2, 4, 64
+    d = make_dataset(N=N, F=F, K=K)
+    o = make_oracle(d, K, perturb=0.0)
+    o.make_optim(lr=0.005)
+    return d, o, K, N, F
+
+
+def test_free_run_stays_inside_the_reference_bound(capsys):
+    """The g++ build of the kernels' math and the host logic of the engine run 50 steps beside the oracle from a common start
+    (N = 4, F = 64, K = 2, lr 0.005, seed 11) and stay within 3 drift(tolerated twin) + drift(storage twin) of it at steps 10,
+    25 and 50.  Measured: the host build is 1.5e-6 / 2.8e-6 / 4.1e-6 from the oracle after 10 / 25 / 50 steps (worst family
+    w_size, h_loc, size), the bounds there are 1.7e-5 / 2.9e-5 / 4.9e-5."""
+    d, o, K, N, F = _free_run_problem()
+    eng = CosmosEngine(d, K=K, device="cpu", lib=load_hostcheck(), seed=11)
+    oracle_to_engine(o, eng)
+    recs = free_run(eng, o, N, F, 50, seed=11)
+    with capsys.disabled():
+        for r in recs:
+            print("\nfree run, host build:", r["step"], "bound %.3g" % r["bound"],
+                  "worst family", max(r["engine"].items(), key=lambda kv: kv[1][0]))
+    assert [r["step"] for r in recs] == [10, 25, 50]
+
+
+def test_free_run_bound_has_teeth():
+    """The bound of free_run rejects a gradient error of 1e-3, ten times what the suite tolerates, without any code under test:
+    the latents are the oracle's own draws, and a fourth twin with 1 + 1e-3 randn on every gradient element is outside
+    3 drift(1e-4 twin) + drift(storage twin) after 50 steps (measured: 1e-4 twin 1.8e-5, storage twin 3.5e-6, bound 5.7e-5; 1e-3 twin 1.3e-4; a 1e-2 twin is at 1.6e-3)."""
+    d, o, K, N, F = _free_run_problem()
+    last = free_run(None, o, N, F, 50, seed=11, extra_eps=(1e-3,))[-1]
+    assert last["step"] == 50 and last[1e-3] > last["bound"], last
+    assert last["tolerated"] < last["bound"]

@@ -35,9 +35,7 @@ def test_subsample_max_is_the_16_bit_index_field():
 
 _OUT = (ctypes.c_int32 * 4)()  # (kept alive here) never written: every case below is refused on the host
 OUT = ctypes.addressof(_OUT)
-
-
-@pytest.mark.parametrize("axis,n,take,out", [
+BAD_ARGUMENTS = [
     (0, 8, 4, None),       # out == NULL
     (0, 0, 1, OUT),        # n < 1
     (1, -3, 1, OUT),
@@ -48,7 +46,12 @@ OUT = ctypes.addressof(_OUT)
     (0, 2 ** 31 - 1, 4, OUT),
     (2, 8, 4, OUT),        # axis not 0 or 1
     (-1, 8, 4, OUT),
-])
+]
+
+
+# (ids by hand: the address of _OUT differs from process to process, and a test's id must not)
+@pytest.mark.parametrize("axis,n,take,out", BAD_ARGUMENTS,
+                         ids=["%d-%d-%d-%s" % (a, n, t, "None" if o is None else "OUT") for a, n, t, o in BAD_ARGUMENTS])
 def test_bad_arguments_are_refused_without_a_gpu(axis, n, take, out):
     lib = _lib.load()
     lib.tq_cosmos_step(ctypes.byref(_lib.CosmosArgs()), None)  # (leaves another call's text behind)
