@@ -1,5 +1,6 @@
 """
-Oracle restatement of ``tapqir/models/crosstalk.py`` (TEST INFRASTRUCTURE ONLY; float64 dense torch).
+Oracle restatement of ``tapqir/models/crosstalk.py`` (TEST INFRASTRUCTURE ONLY; dense torch in
+``oracle.cosmos.working_dtype``, float64 unless a test or the benchmark asks for the plain float32 pass).
 
 The crosstalk model is the cosmos model with
   * a global Dirichlet site ``alpha`` (Q, C): fraction of dye q's signal seen in channel c
@@ -21,7 +22,7 @@ import torch
 import torch.distributions as D
 from torch.distributions import constraints
 
-from .cosmos import (AffineBeta, CosmosOracle, _DirichletGiven, _abeta_lp, _gamma_lp, _halfnormal_lp, _lg, _t)
+from .cosmos import (_DT, AffineBeta, CosmosOracle, _DirichletGiven, _abeta_lp, _gamma_lp, _halfnormal_lp, _lg, _t)
 from .dist_util import probs_m
 from .ksmogn import ksmogn_crosstalk_log_prob, ksmogn_log_prob_bruteforce
 
@@ -32,7 +33,7 @@ class CrosstalkOracle(CosmosOracle):
         assert self.Q == data.C, "crosstalk.py indexes dyes and channels with the same default (Q = data.C)"
 
     def alpha_prior_conc(self):  # crosstalk.py:84-86
-        return torch.ones(self.Q, self.data.C, dtype=torch.float64) + 9 * torch.eye(self.Q, dtype=torch.float64)
+        return torch.ones(self.Q, self.data.C, dtype=_DT[0]) + 9 * torch.eye(self.Q, dtype=_DT[0])
 
     def _constraints(self):
         c = super()._constraints()
@@ -43,7 +44,7 @@ class CrosstalkOracle(CosmosOracle):
     def init_values(self):  # crosstalk.py:424-455
         v = super().init_values()
         v["alpha_mean"] = self.alpha_prior_conc()
-        v["alpha_size"] = torch.full((self.Q, 1), 2.0, dtype=torch.float64)
+        v["alpha_size"] = torch.full((self.Q, 1), 2.0, dtype=_DT[0])
         return v
 
     def _guide_dists(self, cp, ndx, fdx):
@@ -72,7 +73,7 @@ class CrosstalkOracle(CosmosOracle):
         """(Mj = 2^(K Q), Q, K): joint combination index has bit (q K + k) = m_qk."""
         K, Q = self.K, self.Q
         return torch.tensor([[[(mj >> (q * K + k)) & 1 for k in range(K)] for q in range(Q)]
-                             for mj in range(2 ** (K * Q))], dtype=torch.float64)
+                             for mj in range(2 ** (K * Q))], dtype=_DT[0])
 
     def elbo(self, params, ndx, fdx, lat):
         d, K, Q, pr = self.data, self.K, self.Q, self.priors
@@ -81,13 +82,13 @@ class CrosstalkOracle(CosmosOracle):
         nb, fb = len(ndx), len(fdx)
         s_n = d.Nt / nb
         s = s_n * d.F / fb
-        mask = d.mask[ndx].to(torch.float64)[:, None]
+        mask = d.mask[ndx].to(_DT[0])[:, None]
         n_, f_ = ndx[:, None], fdx[None, :]
 
         # global sites (crosstalk.py:80-103 / 268-305)
         G = D.HalfNormal(_t(pr["gain_std"])).log_prob(lat["gain"]) - g["gain"].log_prob(lat["gain"])
         G = G + (D.Dirichlet(self.alpha_prior_conc()).log_prob(lat["alpha"]) - g["alpha"].log_prob(lat["alpha"])).sum()
-        G = G + (D.Dirichlet(torch.full((Q, 2), 0.5, dtype=torch.float64)).log_prob(lat["pi"])
+        G = G + (D.Dirichlet(torch.full((Q, 2), 0.5, dtype=_DT[0])).log_prob(lat["pi"])
                  - g["pi"].log_prob(lat["pi"])).sum()
         G = G + (D.Exponential(_t(pr["lamda_rate"])).log_prob(lat["lamda"]) - g["lamda"].log_prob(lat["lamda"])).sum()
         G = G + D.Exponential(_t(pr["proximity_rate"])).log_prob(lat["proximity"]) - g["proximity"].log_prob(lat["proximity"])
@@ -107,12 +108,12 @@ class CrosstalkOracle(CosmosOracle):
         W = logq.exp()
 
         T = (D.HalfNormal(_t(pr["height_std"])).log_prob(lat["height"])
-             + AffineBeta(torch.tensor(1.5, dtype=torch.float64), 2.0, pr["width_min"], pr["width_max"]).log_prob(lat["width"])
+             + AffineBeta(torch.tensor(1.5, dtype=_DT[0]), 2.0, pr["width_min"], pr["width_max"]).log_prob(lat["width"])
              - g["height"].log_prob(lat["height"]) - g["width"].log_prob(lat["width"])
              - g["x"].log_prob(lat["x"]) - g["y"].log_prob(lat["y"]))  # (K, nb, fb, Q)
 
         L = self.zt_marginal(lat, ndx)  # (2^K, nb, fb, Q): per-dye marginal over (z_q, theta_q)
-        idx = (mgj * (2.0 ** torch.arange(K, dtype=torch.float64))).sum(-1).long()  # (Mj, Q): per-dye combination
+        idx = (mgj * (2.0 ** torch.arange(K, dtype=_DT[0]))).sum(-1).long()  # (Mj, Q): per-dye combination
         Lj = sum(L[idx[:, q], :, :, q] for q in range(Q))  # (Mj, nb, fb)
         Tj = sum(mgj[:, q, k][:, None, None] * T[k, :, :, q] for q in range(Q) for k in range(K))
 

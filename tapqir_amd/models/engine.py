@@ -125,6 +125,7 @@ class CosmosEngine:
         self.lazy_adam = self.lazy_adam_default
         self._last_step = torch.zeros(self.Nt * self.F * self.C, dtype=torch.int32, device=dev)
         self._stale = False
+        self._grad_dirty = False  # `grad` holds gradients no minibatch step has cleared (_open_step)
         gsz, bsz = self.struct_sizes()
         self.globals = torch.zeros(gsz // 4, dtype=f32, device=dev)
         self.gbase = torch.zeros(bsz // 8, dtype=torch.float64, device=dev)
@@ -495,6 +496,7 @@ class CosmosEngine:
             # staged calls from outside read the parameters of arbitrary units and overwrite globals / gsum / grad: finish
             # a pipelined tail or an in-flight all-reduce first, then bring every unit to the current Adam step
             self.join()
+            self._grad_dirty = True
         nb = self.Nt if ndx is None else int(ndx.numel())
         fb = self.F if fdx is None else int(fdx.numel())
         if _ws is None:
@@ -785,6 +787,16 @@ class CosmosEngine:
         minibatch = bool(a.zero_grad)
         lazy = minibatch and self.lazy_adam
         a.fuse_adam = int(not minibatch or lazy)
+        if not minibatch:
+            self._grad_dirty = True  # a full-batch step writes every element it reads and clears none
+        elif self._grad_dirty:
+            # A minibatch step writes the gradient of its own units and AOIs only and relies on the rest being zero (the Adam
+            # of a minibatch step clears what it read).  After a full-batch step or staged calls from outside the buffer
+            # holds THEIR gradients: the per-AOI parameters of the AOIs outside this minibatch would take them again.
+            self._finish_pending()
+            self._finish_tail()
+            self.grad.zero_()
+            self._grad_dirty = False
         if lazy:
             if not self._stale:
                 self._last_step.fill_(self.adam_step)  # every unit is current: start the clock here

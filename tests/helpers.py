@@ -5,6 +5,7 @@ import math
 import os
 import subprocess
 
+import pytest
 import torch
 
 from oracle.cosmos import CosmosOracle, OracleData
@@ -252,24 +253,182 @@ def read_engine_latents(eng, nb, fb):
     return out
 
 
+# ---- gradients of whole device steps, per element ---------------------------------------------------------------------------
+# A whole step writes no gradient: it leaves Adam moments.  exp_avg across one update is b1 m + (1 - b1) g, so the gradient
+# the step took comes back from the two moments, for every element of every parameter, and is compared with the oracle's
+# element by element.  (Parameters after the update cannot show a gradient error: Adam's update is invariant to a persistent
+# factor on a gradient element, and its first step is lr sign(g).)
+def _f32(v):
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+ADAM_B1, ADAM_B2 = _f32(0.9), _f32(0.999)  # the kernels' fp32 constants (CosmosEngine.betas); 1 - b is exact in fp32
+FLT_MIN = float(torch.finfo(torch.float32).tiny)
+GRAD_RTOL = 1e-4   # the project's gradient tolerance
+FP32_FACTOR = 16   # allowance over the plain-fp32 oracle's own error: 2 (hardware exp2 / log2 / rcp against libm) x 4 (wave-order
+#                    sums of 196-400 pixel terms against torch's pairwise sums) x 2 (fp32 series of the implicit gradients)
+
+
+def oracle_grads32(o, nd, fd, base):
+    """The gradients of ``oracle_grads`` from the reference's plain float32 evaluation: a second oracle built inside
+    ``oracle.cosmos.working_dtype(torch.float32)`` on the same data with the same parameter values, the base draws cast to
+    float32.  Returns float64 tensors.  |oracle_grads32 - oracle_grads| is the error fp32 torch makes on the same formula."""
+    from oracle.cosmos import working_dtype
+
+    with working_dtype(torch.float32):
+        d = o.data
+        od = OracleData(d.images, d.xy, d.is_ontarget, d.offset_samples, d.offset_weights, mask=d.mask)
+        t = type(o)(od, K=o.K, priors=o.priors, eps=o.eps)
+        t.params = {n: u.detach().float().requires_grad_(True) for n, u in o.params.items()}
+        _, g = oracle_grads(t, nd, fd, {k: v.float() for k, v in base.items()})
+    return {n: v.double() for n, v in g.items()}
+
+
+def recover_step_gradient(m_before, m_after, decay_steps=1):
+    """d ELBO / d param of one Adam update from exp_avg before and after it (float64 tensors holding the fp32 moments):
+    m_after = b1**k m_before + (1 - b1) (-g), ``decay_steps`` = k = steps since the element's last Adam update, this one
+    included (a tensor per element under the lazy clock; 1 everywhere after a ``join()``).  Returns (g, R):
+    R = 4 eps32 (|m_before| + |m_after|) / (1 - b1), two fp32 roundings of the moment before and after, amplified by the
+    division, times two -- what the recovery itself cannot resolve."""
+    m_before, m_after = m_before.double(), m_after.double()
+    k = torch.as_tensor(decay_steps, dtype=torch.float64)
+    g = -(m_after - ADAM_B1 ** k * m_before) / (1.0 - ADAM_B1)
+    R = 4.0 * EPS32 * (m_before.abs() + m_after.abs()) / (1.0 - ADAM_B1)
+    return g, R
+
+
+def _unit_of(name, shape, flat):
+    """'(k, n, f, c)' of flat index ``flat`` of a parameter of shape ``shape`` ('-' for the axes it does not have)."""
+    idx = [int(i) for i in torch.unravel_index(torch.tensor(flat), shape)] if len(shape) else []
+    k, n, f, c = "-", "-", "-", "-"
+    if len(shape) == 4:
+        k, n, f, c = idx
+    elif len(shape) == 3:
+        n, f, c = idx
+        if shape[1] == 1:
+            f = "-"
+    elif len(shape):
+        c = tuple(idx) if len(idx) > 1 else idx[0]
+    return "(k=%s, n=%s, f=%s, c=%s)" % (k, n, f, c)
+
+
+def assert_gradients_match(g_dev, g64, g32, R, where, norm_only=()):
+    """Recovered device gradients against the oracle's, per element, for every parameter family n (dicts of tensors of the
+    oracle's shapes; ``R`` the recovery rounding of ``recover_step_gradient``):
+
+      * finite everywhere;
+      * element-wise  |g_dev - g64| <= 1e-4 |g64| + 16 E32_n + R,  E32_n = max |g32_n - g64_n|: the project's gradient
+        tolerance relative to the ELEMENT, plus a fixed multiple of the error plain fp32 torch makes on the same formula;
+      * norm-wise, as the staged tests have it:  max(|g_dev - g64| - R) <= 1e-4 max |g64|;
+      * where the oracle's gradient is exactly zero (units outside the minibatch, per-AOI parameters of AOIs outside it,
+        masked AOIs)  |g_dev| <= R.
+
+    ``norm_only``: families held to the norm-wise check only (a test lists them with the mechanism).  Returns
+    {family: worst (|g_dev - g64| - 1e-4 |g64| - R) / E32_n}: what of the factor 16 the family used (<= 0: none)."""
+    worst = {}
+    for n, ref in g64.items():
+        ref = ref.detach().double()
+        shape = tuple(ref.shape)
+        got, r = g_dev[n].double().reshape(shape), R[n].double().reshape(shape)
+        e32 = float((g32[n].double().reshape(shape) - ref).abs().max())
+        err = (got - ref).abs()
+
+        def fail(what, mask_or_excess):
+            at = int(mask_or_excess.reshape(-1).argmax())
+            return "%s: %s of %s[%d] unit %s: device %.9g oracle %.9g (fp32 oracle %.9g) R %.3g E32 %.3g" % (
+                where, what, n, at, _unit_of(n, shape, at), float(got.reshape(-1)[at]), float(ref.reshape(-1)[at]),
+                float(g32[n].double().reshape(-1)[at]), float(r.reshape(-1)[at]), e32)
+
+        assert bool(torch.isfinite(got).all()), fail("non-finite gradient", (~torch.isfinite(got)).double())
+        zero = ref == 0
+        over = torch.where(zero, got.abs() - r, torch.full_like(err, -1.0))
+        assert not bool((over > 0).any()), fail("gradient where the oracle has none", over)
+        excess = err - GRAD_RTOL * ref.abs() - r
+        top = float(excess.max()) if excess.numel() else 0.0
+        worst[n] = top / e32 if e32 > 0 else (0.0 if top <= 0 else math.inf)
+        if n not in norm_only:
+            assert top <= FP32_FACTOR * e32, fail("element-wise, excess %.3g E32" % worst[n], excess)
+        normwise = err - r
+        assert float(normwise.max()) <= GRAD_RTOL * float(ref.abs().max()), fail("norm-wise", normwise)
+    return worst
+
+
+WORST_RATIOS = {}  # where -> {family: worst excess / E32_n} of the checks run so far (tests print and clear it)
+
+
+def engine_state(eng):
+    """(params, exp_avg, exp_avg_sq) as float64 host copies, every unit at the current Adam step (the reads join())."""
+    return tuple(getattr(eng, n).detach().cpu().double().clone() for n in ("params", "exp_avg", "exp_avg_sq"))
+
+
+def check_step(eng, before, after, g64, g32, where, norm_only=()):
+    """One Adam update of every element between two ``engine_state`` snapshots (every unit current in both, so one decay
+    step everywhere): the recovered gradient against the oracle (assert_gradients_match), the second moment against that
+    gradient, and the parameters against the Adam update evaluated in float64 from the device's own moments at step count
+    ``eng.adam_step``.  Returns the worst excess / E32 per family."""
+    (p0, m0, v0), (p1, m1, v1) = before, after
+    g, R = recover_step_gradient(m0, m1)
+    lay = eng.layout
+    worst = assert_gradients_match(lay.views(g), g64, g32, lay.views(R), where, norm_only)
+    resid = (v1 - ADAM_B2 * v0 - (1.0 - ADAM_B2) * g ** 2).abs()
+    bound = 1e-5 * v1 + 4.0 * EPS32 * (v0 + v1) + FLT_MIN
+    at = int((resid - bound).argmax())
+    assert bool((resid <= bound).all()), "%s: exp_avg_sq[%d] %.9g after %.9g with gradient %.9g: residual %.3g > %.3g" % (
+        where, at, float(v1[at]), float(v0[at]), float(g[at]), float(resid[at]), float(bound[at]))
+    t = eng.adam_step
+    m_hat, v_hat = m1 / (1.0 - eng.betas[0] ** t), v1 / (1.0 - eng.betas[1] ** t)
+    want = p0 - eng.lr * m_hat / (v_hat.sqrt() + eng.adam_eps)
+    ok = torch.isclose(p1, want, rtol=1e-5, atol=1e-6)
+    at = int((p1 - want).abs().argmax())
+    assert bool(ok.all()), "%s: params[%d] %.9g, Adam step %d of the device's own moments gives %.9g" % (
+        where, at, float(p1[at]), t, float(want[at]))
+    rec = WORST_RATIOS.setdefault(where.split(" step ")[0], {})
+    for n, w in worst.items():
+        rec[n] = max(rec.get(n, -math.inf), w)
+    return worst
+
+
+@pytest.fixture
+def gradient_report(capsys, request):
+    """Prints the worst excess / E32_n per family of the gradient checks a test ran (import it into the test module and
+    mark the module's tests with ``pytest.mark.usefixtures("gradient_report")``)."""
+    WORST_RATIOS.clear()
+    yield
+    with capsys.disabled():
+        for where, rec in WORST_RATIOS.items():
+            fam = max(rec, key=rec.get)
+            print("\ngradient check %s [%s]: worst excess / E32 %.3g (%s)  %s" % (
+                request.node.name, where, rec[fam], fam, {n: round(w, 2) for n, w in rec.items() if w > 0}))
+    WORST_RATIOS.clear()
+
+
 # ---- whole device steps against the oracle ---------------------------------------------------------------------------------
-# the tolerances of test_gpu_production_kernels.replay: -ELBO relative, every parameter after the update absolute (2 % of one
-# Adam step of lr = 0.005)
+# -ELBO relative, every parameter after the update absolute (2 % of one Adam step of lr = 0.005)
 ELBO_RTOL, PARAM_ATOL = 2e-5, 1e-4
 
 
-def replay_steps(eng, o, step, steps=3):
-    """test_gpu_production_kernels.replay with the device step left to the caller: ``step(eng, it)`` runs step ``it`` on the
-    engine and returns the AOI and frame indices it ran on (host int64 tensors).  The oracle replays each step from the
-    device's draws, the same assertions are made, and the oracle's parameters go back into the engine."""
+def replay_steps(eng, o, step, steps=3, where="replay", norm_only=()):
+    """``step(eng, it)`` runs step ``it`` on the engine and returns the AOI and frame indices it ran on (host int64 tensors).
+    The oracle replays each step from the device's draws: -ELBO to ELBO_RTOL, every parameter after the update to
+    PARAM_ATOL; and -- what the parameters cannot show -- the gradient of every parameter recovered from the moments,
+    the second moments and the update itself (check_step).  Then the oracle's parameters go back into the engine."""
+    cuda = eng.device.type == "cuda"
     for it in range(steps):
+        before = engine_state(eng)  # (joins: every unit current)
         nd, fd = step(eng, it)
         eng.join()
-        torch.cuda.synchronize()
+        if cuda:
+            torch.cuda.synchronize()
+        after = engine_state(eng)
         lat32 = read_engine_latents(eng, len(nd), len(fd))
         with torch.no_grad():
             base = o.base_draws(lat32, o._guide_dists(o.constrained(o.params), nd, fd))
-        loss_o = o.step(nd, fd, base=base)
+        elbo_o, g64 = oracle_grads(o, nd, fd, base)  # at the pre-step parameters: the gradients the oracle's own step takes
+        g32 = oracle_grads32(o, nd, fd, base)
+        for n, u in o.params.items():  # CosmosOracle.step on those gradients (the loss is -ELBO)
+            u.grad = -g64[n]
+            o.optim[n].step()
+        loss_o = -elbo_o
         loss_k = -float(eng.elbo_out[0])
         assert abs(loss_k - loss_o) <= ELBO_RTOL * abs(loss_o), (it, loss_k, loss_o)
         views = eng.named("params")
@@ -277,7 +436,131 @@ def replay_steps(eng, o, step, steps=3):
             got = views[n].cpu().double().reshape(u.shape)
             err = float((got - u.detach()).abs().max())
             assert err < PARAM_ATOL, (it, n, err)
-        oracle_to_engine(o, eng)
+        check_step(eng, before, after, g64, g32, "%s step %d" % (where, it), norm_only)
+        oracle_to_engine(o, eng)  # identical parameters on both sides for the next step
+
+
+LOCAL_NAMES = ("m_probs", "h_loc", "h_beta", "w_mean", "w_size", "x_mean", "y_mean", "size", "b_loc", "b_beta")
+
+
+def lr0_sequence(eng, o, plan, where, norm_only=()):
+    """Steps with ``eng.lr = 0`` and NO join() between them, so that every tail runs where a fit runs it: inside the next
+    launch.  The parameters never move -- the oracle holds them exactly at every step with nothing read back -- while the
+    moments still accumulate b1 m + (1 - b1) g, and every step's gradient comes back from exp_avg read raw after each launch:
+
+      * local parameters of step t from the local block across launch t; the decay count of every unit comes from a table of
+        last updates kept HERE (a unit of the batch: every step since its last update, the catch-up of the lazy clock
+        included).  Units outside the batch are either bit-unchanged, or -- where the launch brought every unit to the
+        current step first -- decayed with no gradient;
+      * per-AOI and global parameters of step t from the rest of the buffer across the launch that ran tail t: launch t + 1
+        where the step left its tail pending (and then the block is bit-unchanged across launch t), launch t itself otherwise;
+      * -ELBO of step t where free_run reads it.
+    The last tail, and the decay of every unit a lazy step left behind, come after the final join().
+
+    ``plan``: one dict per step with ``nd`` / ``fd`` (host index tensors, None = whole axis) and optionally ``pre(eng)``,
+    ``post(eng)`` (called before / right after the launch) and ``kw`` (keyword arguments of ``step``).  Returns, per step,
+    whether its tail was left pending."""
+    eng.lr = 0.0
+    eng.__dict__.pop("_tmpl_key", None)  # (argument templates carry the learning rate)
+    lay, cuda = eng.layout, eng.device.type == "cuda"
+    nl, Nt, F, C = lay.n_local, eng.Nt, eng.F, eng.C
+    rows = nl // lay.U
+    rest_names = [n for n in o.params if n not in LOCAL_NAMES]
+
+    def raw():
+        if cuda:
+            torch.cuda.synchronize()
+        return eng._exp_avg.detach().cpu().double().clone()
+
+    def rest_views(flat_rest):
+        full = torch.cat([torch.zeros(nl, dtype=torch.float64), flat_rest])
+        return {n: v for n, v in lay.views(full).items() if n in rest_names}
+
+    def local_views(flat_local):
+        full = torch.cat([flat_local.reshape(-1), torch.zeros(lay.total - nl, dtype=torch.float64)])
+        return {n: v for n, v in lay.views(full).items() if n in LOCAL_NAMES}
+
+    def record(worst):
+        rec = WORST_RATIOS.setdefault(where, {})
+        for n, w in worst.items():
+            rec[n] = max(rec.get(n, -math.inf), w)
+
+    def check_rest(m0, m1, tails, tag):
+        """``tails``: (g64, g32) of the tails the launch ran, oldest first: m1 = b1^k m0 + (1 - b1) sum b1^(k-1-i) (-g_i)."""
+        k = len(tails)
+        g, R = recover_step_gradient(m0[nl:], m1[nl:], k)
+        mix = lambda which: {n: sum(ADAM_B1 ** (k - 1 - i) * tl[which][n].detach().double() for i, tl in enumerate(tails))
+                             for n in rest_names}
+        record(assert_gradients_match(rest_views(g), mix(0), mix(1), rest_views(R), "%s %s" % (where, tag), norm_only))
+
+    def check_elbo(it, loss_o):
+        loss_k = -float(eng.elbo_out[0])
+        assert abs(loss_k - loss_o) <= ELBO_RTOL * abs(loss_o), (where, it, loss_k, loss_o)
+
+    eng.join()
+    p0 = eng._params.detach().cpu().clone()
+    m_prev = raw()
+    clock = torch.zeros(Nt, F, dtype=torch.int64) + eng.adam_step  # Adam steps every unit has taken
+    t0 = eng.adam_step
+    owed, pendings = None, []
+    for it, e in enumerate(plan):
+        t = t0 + it
+        if e.get("pre") is not None:
+            e["pre"](eng)
+        nd, fd = e.get("nd"), e.get("fd")
+        eng.step(nd, fd, **e.get("kw", {}))
+        if e.get("post") is not None:
+            e["post"](eng)
+        m_now = raw()
+        pending = eng._tail_args is not None or eng._pending is not None
+        pendings.append(pending)
+        nd_ = torch.arange(Nt) if nd is None else nd
+        fd_ = torch.arange(F) if fd is None else fd
+        lat32 = read_engine_latents(eng, len(nd_), len(fd_))
+        with torch.no_grad():
+            base = o.base_draws(lat32, o._guide_dists(o.constrained(o.params), nd_, fd_))
+        elbo_o, g64 = oracle_grads(o, nd_, fd_, base)
+        g32 = oracle_grads32(o, nd_, fd_, base)
+        # ---- local block across this launch
+        inb = torch.zeros(Nt, F, dtype=torch.bool)
+        inb[nd_[:, None], fd_[None, :]] = True
+        l0, l1 = m_prev[:nl].view(rows, Nt, F, C), m_now[:nl].view(rows, Nt, F, C)
+        out = (~inb)[None, :, :, None].expand_as(l0)
+        caught_up = not torch.equal(l0[out], l1[out])  # the launch brought the units outside the batch to step t first
+        k = torch.where(inb, t + 1 - clock, (t - clock) if caught_up else torch.zeros_like(clock))
+        clock = torch.where(inb, torch.full_like(clock, t + 1), torch.full_like(clock, t) if caught_up else clock)
+        g, R = recover_step_gradient(l0, l1, k[None, :, :, None].expand_as(l0))
+        loc64 = {n: v for n, v in g64.items() if n in LOCAL_NAMES}
+        record(assert_gradients_match(local_views(g), loc64, g32, local_views(R), "%s step %d" % (where, it), norm_only))
+        # ---- the rest of the buffer: the tails this launch ran
+        tails = ([owed[1:]] if owed is not None else []) + ([] if pending else [(g64, g32)])
+        if tails:
+            check_rest(m_prev, m_now, tails, "tail run by launch %d" % it)
+        else:
+            assert torch.equal(m_prev[nl:], m_now[nl:]), (where, it, "a launch that left its tail pending moved per-AOI / global moments")
+        if pending:
+            if owed is not None:
+                check_elbo(it - 1, owed[0])
+            owed = (-elbo_o, g64, g32)
+        else:
+            check_elbo(it, -elbo_o)
+            owed = None
+        m_prev = m_now
+    T = t0 + len(plan)
+    eng.join()
+    m_fin = raw()
+    assert eng.adam_step == T
+    if owed is not None:
+        check_elbo(len(plan) - 1, owed[0])
+        check_rest(m_prev, m_fin, [owed[1:]], "tail after the last join")
+    else:
+        assert torch.equal(m_prev[nl:], m_fin[nl:])
+    l0, l1 = m_prev[:nl].view(rows, Nt, F, C), m_fin[:nl].view(rows, Nt, F, C)
+    g, R = recover_step_gradient(l0, l1, (T - clock)[None, :, :, None].expand_as(l0))
+    zeros = {n: torch.zeros_like(u.detach()) for n, u in o.params.items() if n in LOCAL_NAMES}
+    assert_gradients_match(local_views(g), zeros, zeros, local_views(R), "%s catch-up of the last join" % where)
+    assert torch.equal(eng._params.detach().cpu(), p0), (where, "lr = 0 moved a parameter")
+    return pendings
 
 
 # ---- free-running trajectories: nothing is copied back into the engine -------------------------------------------------------
