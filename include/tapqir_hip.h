@@ -273,6 +273,16 @@ typedef struct {
                                   keys (stream: seed, step + 1; a radix selection, no sort) in its tail workgroup, after the flags are published: a host that
                                   passes them as ndx / fdx of the next call never draws, stages or copies an index
                                   (Nt, F <= TQ_SUBSAMPLE_MAX: the index is a 16-bit field beside the key) */
+  int32_t pu_split;            /* fused launch (TQ_PIXEL_FUSED_UNIT): tiles of 64 units split BY ROWS over four waves each, which are
+                                  dispatched in front of the whole tiles; the wave of a tile that finishes last adds the four
+                                  partial sums in a fixed order and goes on as the wave of a whole tile does, so nobody waits and the
+                                  results do not depend on who arrives when.  -1: the last `ntiles mod slots` tiles where they
+                                  would be a nearly empty last round (tq_cosmos_pu_split_auto; none without pu_scratch); 0: none;
+                                  n > 0: the last n tiles (needs pu_scratch for n tiles) */
+  int32_t pu_scratch_tiles;    /* split tiles that pu_scratch has room for */
+  void* pu_scratch;            /* tq_cosmos_pu_scratch_bytes(pu_scratch_tiles) bytes, or NULL: one ticket counter per split tile,
+                                  zeroed once by the caller and never reset (four tickets per tile and launch), then the
+                                  partial sums [tile][part][value][lane] */
 } tq_cosmos_args;
 #define TQ_SUBSAMPLE_MAX 65536
 
@@ -330,6 +340,14 @@ int tq_cosmos_tail(const tq_cosmos_args* a, void* stream);
  * tq_cosmos_pixel_unit is that launch alone (a stage export like tq_cosmos_elbo_grads: draws and global tables of `a`
  * must be in place; it applies the Adam step of the local parameters and leaves the rows for the tail). */
 int tq_cosmos_pixel_unit(const tq_cosmos_args* a, void* stream);
+/* Split tiles of that launch (tq_cosmos_args.pu_split).  tq_cosmos_pu_slots: waves of the (K, P) instance that the current
+ * device holds at a time (occupancy x compute units; 0 if it cannot be asked).  tq_cosmos_pu_split_auto: the rule of
+ * pu_split = -1 for a launch of `ntiles` tiles -- with r = ntiles mod slots, the last r tiles if ntiles >= slots and
+ * 0 < r <= slots / 8, else none: a batch below one full round of waves is never split.  tq_cosmos_pu_scratch_bytes: size of
+ * pu_scratch for `tiles` split tiles. */
+int32_t tq_cosmos_pu_slots(int32_t K, int32_t P);
+int32_t tq_cosmos_pu_split_auto(int64_t ntiles, int32_t slots);
+int64_t tq_cosmos_pu_scratch_bytes(int32_t tiles);
 /* Minibatch steps (the reference's default operating point is 10 AOIs x 512 frames = 5120 units, main.py:1428-1431) in
  * ONE launch: every workgroup takes 16 units (20 when that saves a round of workgroups on the chip's CUs) through lazy-Adam catch-up, guide-site draws, likelihood and per-unit terms + Adam; one more workgroup runs
  * the pending tail of `prev` (or nothing) and the global draws of `a` -- the gain first, which the others wait for before

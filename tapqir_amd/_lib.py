@@ -65,6 +65,7 @@ class CosmosArgs(C.Structure):
         ("last_step", C.c_void_p), ("beta1_d", C.c_double), ("beta2_d", C.c_double),
         ("pixel_mode", C.c_int32), ("tail_kind", C.c_int32), ("sync", C.c_void_p), ("sync_value", C.c_int32),
         ("images_by_slot", C.c_int32), ("next_ndx", C.c_void_p), ("next_fdx", C.c_void_p),
+        ("pu_split", C.c_int32), ("pu_scratch_tiles", C.c_int32), ("pu_scratch", C.c_void_p),
     ]
 
 
@@ -210,6 +211,7 @@ EXPORTS = [
     "tq_cosmos_sample_globals", "tq_cosmos_sample_locals", "tq_cosmos_elbo_grads",
     "tq_cosmos_globals_grad", "tq_cosmos_adam", "tq_cosmos_adam_catchup", "tq_cosmos_step", "tq_cosmos_step_overlapped", "tq_cosmos_tail", "tq_cosmos_tail_reduced", "tq_cosmos_sample_locals_range",
     "tq_cosmos_blk_floats", "tq_cosmos_minibatch_step", "tq_subsample_draw", "tq_cosmos_pixel_unit",
+    "tq_cosmos_pu_slots", "tq_cosmos_pu_split_auto", "tq_cosmos_pu_scratch_bytes",
     "tq_cosmos_probs", "tq_glimpse_extract", "tq_ksmogn_rsample", "tq_snr_chi2", "tq_ttfb_sample", "tq_ttfb_fit",
     "tq_dwell_sample", "tq_dwell_fit", "tq_credible_intervals",
 ]
@@ -263,6 +265,12 @@ def load():
         fn.restype = C.c_int
     lib.tq_cosmos_blk_floats.argtypes = [C.c_int32] * 4 + [C.c_int64]
     lib.tq_cosmos_blk_floats.restype = C.c_int64
+    lib.tq_cosmos_pu_slots.argtypes = [C.c_int32, C.c_int32]
+    lib.tq_cosmos_pu_slots.restype = C.c_int32
+    lib.tq_cosmos_pu_split_auto.argtypes = [C.c_int64, C.c_int32]
+    lib.tq_cosmos_pu_split_auto.restype = C.c_int32
+    lib.tq_cosmos_pu_scratch_bytes.argtypes = [C.c_int32]
+    lib.tq_cosmos_pu_scratch_bytes.restype = C.c_int64
     for name in ("tq_cosmos_step_overlapped", "tq_cosmos_tail_reduced", "tq_cosmos_minibatch_step"):
         fn = getattr(lib, name)
         fn.argtypes = [C.POINTER(CosmosArgs), C.POINTER(CosmosArgs), C.c_void_p]

@@ -158,11 +158,52 @@ __device__ __forceinline__ void tq_pixel_pair(TqPixAcc2<K, P, COLACC>& A, tq_f2 
 }
 
 
-// One lane = one unit of tile blockIdx.x (64 units).  OUT != nullptr: the results of the unit (TQ_PIXOUT(K) floats:
+// Everything the packed loop leaves is a plain sum over pixels, so the loop bodies of a tile can be shared out and the
+// partial sums added afterwards: f(pair) for every running sum of the loop that outlives it (S0r is per row), in a fixed
+// order.  `sum_gy` (K floats) travels as one more pair.
+template <int K, int P, bool COLACC>
+constexpr int tq_acc2_pairs() { return ((1 << K) - 1) + 1 + (COLACC ? 2 * K + K * (P / 2) : 5 * K) + 1; }
+template <int K, int P, bool COLACC, class F>
+__device__ __forceinline__ void tq_acc2_each(TqPixAcc2<K, P, COLACC>& A, float* sum_gy, F&& f) {
+#pragma unroll
+  for (int mi = 1; mi < (1 << K); ++mi) f(A.T[mi]);
+  f(A.acc_b);
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    f(A.Sy[k]);
+    f(A.Syy[k]);
+    if (COLACC) {
+#pragma unroll
+      for (int ip = 0; ip < P / 2; ++ip) f(A.col[k][ip]);
+    } else {
+      f(A.S0[k]);
+      f(A.Sx[k]);
+      f(A.Sxx[k]);
+    }
+  }
+  tq_f2 gy = (tq_f2){sum_gy[0], K > 1 ? sum_gy[K > 1 ? 1 : 0] : 0.0f};
+  static_assert(K <= 2, "sum_gy travels as one pair");
+  f(gy);
+  sum_gy[0] = gy.x;
+  if (K > 1) sum_gy[K > 1 ? 1 : 0] = gy.y;
+}
+
+// The whole tile in one wave: the loop bodies [0, NB), nothing between the loop and the fold.
+struct TqWholeTile {
+  static constexpr bool SPLIT = false;
+};
+
+// One lane = one unit of tile `tile` (64 units).  OUT != nullptr: the results of the unit (TQ_PIXOUT(K) floats:
 // ll[2^K], g_background, g_gain, g_height[K], g_width[K], g_x[K], g_y[K]) are returned there and NOT stored.
+// Range: TqWholeTile, or (SPLIT) a wave that runs the loop bodies [body_begin, body_end) of the tile only -- wave-uniform,
+// at least one body -- and hands the partial sums to range.combine(A, sum_gy) between the loop and the fold: where that
+// returns false the wave is done and so is this routine (it returns false); where it returns true, A and sum_gy hold the
+// sums of the whole tile and the wave finishes the tile.  The scalar loop of a tile with a small alpha is not shared out:
+// range.whole_tile() says which ONE of the tile's waves runs all of it (the test is the same in all of them).
 #define TQ_PIXOUT(K) ((1 << (K)) + 2 + 4 * (K))
-template <int K, int P, bool BWD>
-__device__ __forceinline__ void tq_il2_lane(const tq_ksmogn_args& a, const int64_t B, float* OUT = nullptr) {
+template <int K, int P, bool BWD, class Range = TqWholeTile>
+__device__ __forceinline__ bool tq_il2_lane(const tq_ksmogn_args& a, const int64_t B, float* OUT = nullptr,
+                                            const int64_t tile = blockIdx.x, const Range range = Range()) {
   static_assert(P % 2 == 0 && (P * P) % 4 == 0, "packed kernel needs an even tile side");
   constexpr int M = 1 << K;
   constexpr int R = ((P / 2) % 2) ? 2 : 1;  // rows per loop body so that the body starts on a float4 boundary
@@ -171,7 +212,8 @@ __device__ __forceinline__ void tq_il2_lane(const tq_ksmogn_args& a, const int64
   constexpr int npix = P * P, npix4 = npix / 4;
   constexpr bool COLACC = BWD && (K * P <= 28);
   constexpr bool PINNED = BWD && K == 2;  // prefetches fenced in place + first body peeled (see run_body)
-  const int64_t i_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;  // one wave per workgroup: no barriers, finest dispatch granularity
+  constexpr bool SPLIT = Range::SPLIT;
+  const int64_t i_raw = tile * 64 + threadIdx.x;  // one wave per workgroup: no barriers, finest dispatch granularity
   const bool live = i_raw < B;
   const int64_t i = live ? i_raw : (B - 1);
   // idle lanes of the last workgroup read the LAST tile too: the interleaved buffer ends with its 64-tile block
@@ -241,9 +283,14 @@ __device__ __forceinline__ void tq_il2_lane(const tq_ksmogn_args& a, const int64
       }
     }
 
+    int body_begin = 0, body_end = NB;  // (compile-time constants for the whole tile)
+    if constexpr (SPLIT) {
+      body_begin = range.body_begin;
+      body_end = range.body_end;
+    }
     float4 ring[G];
 #pragma unroll
-    for (int j = 0; j < G; ++j) ring[j] = src[j * 64];
+    for (int j = 0; j < G; ++j) ring[j] = src[(SPLIT ? body_begin * G : 0) * 64 + j * 64];
     // one loop body = R rows; MORE: the groups of the next body are fetched as those of this one retire
     // (the last body is peeled so that the prefetches are unconditional and stay where they are written)
     auto run_body = [&](const int body, auto more_tag) {
@@ -294,15 +341,24 @@ __device__ __forceinline__ void tq_il2_lane(const tq_ksmogn_args& a, const int64
         }
       }
     };
-    if (PINNED) {  // first body peeled: see above
-      run_body(0, std::true_type{});
+    if constexpr (SPLIT) {  // the same shape relative to the range: first body peeled where there is more than one, last peeled
+      if (body_end - body_begin > 1) run_body(body_begin, std::true_type{});
 #pragma unroll 1
-      for (int body = 1; body < NB - 1; ++body) run_body(body, std::true_type{});
+      for (int body = body_begin + 1; body < body_end - 1; ++body) run_body(body, std::true_type{});
+      run_body(body_end - 1, std::false_type{});
+      // the partial sums of the other ranges of the tile: all but the wave that goes on leave here
+      if (!range.combine(A, sum_gy)) return false;
     } else {
+      if (PINNED) {  // first body peeled: see above
+        run_body(0, std::true_type{});
 #pragma unroll 1
-      for (int body = 0; body < NB - 1; ++body) run_body(body, std::true_type{});
+        for (int body = 1; body < NB - 1; ++body) run_body(body, std::true_type{});
+      } else {
+#pragma unroll 1
+        for (int body = 0; body < NB - 1; ++body) run_body(body, std::true_type{});
+      }
+      run_body(NB - 1, std::false_type{});
     }
-    run_body(NB - 1, std::false_type{});
 
     // fold the two pixel slots, then the common single-offset assembly / store
 #pragma unroll
@@ -337,6 +393,9 @@ __device__ __forceinline__ void tq_il2_lane(const tq_ksmogn_args& a, const int64
     }
   } else {
     // some unit of this wave has a small alpha = background / gain: general (scalar, exact Binet) loop
+    if constexpr (SPLIT) {
+      if (!range.whole_tile()) return false;
+    }
     tq_il_pixel_loop<K, true, BWD, false>(S, a, src, P, npix, b, amph, nl2, cx, cy, g, rg, ln_g, W);
   }
   const float S_v = a.pixstats[i];
@@ -356,4 +415,5 @@ __device__ __forceinline__ void tq_il2_lane(const tq_ksmogn_args& a, const int64
     }
     tq_pixel_store<K, true, BWD>(a, B, i, S, W, b, rg, hk, wk, cxs, cys, (float)npix, S_v, bad, OUT);
   }
+  return true;
 }

@@ -176,15 +176,106 @@ __device__ __forceinline__ int tq_group_reduce_rows(const tq_cosmos_args& a, con
 // (4.3 TB/s of traffic at 33 % VALU busy): as two launches they run one after the other, here the waves of a SIMD are in
 // different phases most of the time.  The pixel results go from one phase to the next in registers (56 B per unit
 // neither written nor read), a launch boundary is gone, and the row of partial sums is per wave (rows of 64 units).
+//
+// Split tiles (nsplit > 0; tq_cosmos_args.pu_split).  The launch holds `slots` waves at a time (2048 on 256 CUs), so the
+// ntiles mod slots tiles of the last round run on a nearly empty chip: 106 of 6250 tiles at c2.  A tile is one wave only
+// because one wave walks all P rows, and everything the pixel loop leaves is a sum over pixels: the last `nsplit` tiles
+// are each run by TQ_PU_PARTS waves that take a range of loop bodies each (tq_il2_lane with a TqSplitPart), in the first
+// blocks of the grid so that they start with the first round.  A part wave writes its partial sums to its slab of
+// pu_scratch with write-through stores, drains its store queue and takes a ticket on the tile's counter (the protocol of
+// tq_group_reduce_rows); the wave that draws the tile's last ticket reads all four slabs (its own too) with device-scope
+// loads, adds them as ((p0 + p1) + p2) + p3 and goes on as the wave of a whole tile does; the others leave.  Nobody waits,
+// and who arrives last does not enter the result.  The counters are never reset: every launch draws TQ_PU_PARTS tickets
+// per split tile, so the last one is the ticket with (ticket & 3) == 3.
+#define TQ_PU_PARTS 4
+#define TQ_PU_PAIRS 24 /* 8-byte values per lane of a slab: the most any instance leaves (K = 2, P = 14: 23) */
+__host__ __device__ __forceinline__ int64_t tq_pu_counter_words(int64_t tiles) { return ((tiles + 63) / 64) * 64; }
+__host__ __device__ __forceinline__ int64_t tq_pu_scratch_bytes(int64_t tiles) {
+  return tq_pu_counter_words(tiles) * 4 + tiles * TQ_PU_PARTS * TQ_PU_PAIRS * 64 * 8;
+}
+
+struct TqSplitPart {
+  static constexpr bool SPLIT = true;
+  int body_begin, body_end;  // loop bodies of this part
+  int part;                  // 0 .. TQ_PU_PARTS - 1
+  int32_t* counter;          // tickets of the tile
+  uint64_t* slabs;           // [TQ_PU_PARTS][TQ_PU_PAIRS][64] of the tile
+
+  // lane 0 draws a ticket: was it the tile's last one?  (wave-uniform)
+  __device__ __forceinline__ bool last_ticket() const {
+    int ticket = 0;
+    if (threadIdx.x == 0) ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ticket = __builtin_amdgcn_readfirstlane(ticket);
+    asm volatile("" ::: "memory");  // the loads of the slabs stay behind the ticket
+    return (ticket & (TQ_PU_PARTS - 1)) == TQ_PU_PARTS - 1;
+  }
+  // a tile of the scalar loop: nothing to hand over, the wave with the last ticket runs all of it
+  __device__ __forceinline__ bool whole_tile() const { return last_ticket(); }
+
+  template <int K, int P, bool COLACC>
+  __device__ __forceinline__ bool combine(TqPixAcc2<K, P, COLACC>& A, float* sum_gy) const {
+    static_assert(tq_acc2_pairs<K, P, COLACC>() <= TQ_PU_PAIRS, "slab too small");
+    static_assert(TQ_PU_PARTS == 4, "the sum below is written out for four parts");
+    uint64_t* mine = slabs + (int64_t)part * (TQ_PU_PAIRS * 64) + threadIdx.x;
+    int v = 0;
+    tq_acc2_each<K, P, COLACC>(A, sum_gy, [&](tq_f2& x) {
+      uint64_t bits;
+      __builtin_memcpy(&bits, &x, 8);
+      __hip_atomic_store(mine + 64 * v, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      ++v;
+    });
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the slab has left
+    if (!last_ticket()) return false;
+    const uint64_t* all = slabs + threadIdx.x;
+    v = 0;
+    tq_acc2_each<K, P, COLACC>(A, sum_gy, [&](tq_f2& x) {
+      tq_f2 p[TQ_PU_PARTS];
+#pragma unroll
+      for (int q = 0; q < TQ_PU_PARTS; ++q) {
+        const uint64_t bits = __hip_atomic_load(all + (q * TQ_PU_PAIRS + v) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_memcpy(&p[q], &bits, 8);
+      }
+      x = ((p[0] + p[1]) + p[2]) + p[3];
+      ++v;
+    });
+    return true;
+  }
+};
+
+// loop bodies [begin, end) of part q of a tile of NB bodies: ceil(NB / 4) each, the last part what is left (P = 14: 2 2 2 1
+// of 7 bodies of two rows, P = 20: 5 5 5 5 of 20 rows); every part has at least one
+template <int P>
+__device__ __forceinline__ void tq_pu_part_bodies(int q, int* begin, int* end) {
+  constexpr int R = ((P / 2) % 2) ? 2 : 1, NB = P / R, PER = (NB + TQ_PU_PARTS - 1) / TQ_PU_PARTS;
+  static_assert(PER * (TQ_PU_PARTS - 1) < NB, "a part without a loop body");
+  *begin = q * PER;
+  *end = (q + 1) * PER < NB ? (q + 1) * PER : NB;
+}
+
 template <int K, int P>
-__global__ __launch_bounds__(64, 2) void tq_pixel_unit_kernel(const tq_ksmogn_args k, const tq_cosmos_args a, const int64_t B) {
+__global__ __launch_bounds__(64, 2) void tq_pixel_unit_kernel(const tq_ksmogn_args k, const tq_cosmos_args a, const int64_t B,
+                                                              const int nsplit) {
   float pixv[TQ_PIXOUT(K)];
 #pragma unroll
   for (int j = 0; j < TQ_PIXOUT(K); ++j) pixv[j] = 0.0f;
-  tq_il2_lane<K, P, true>(k, B, pixv);
-  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  // blocks 0 .. 4 nsplit - 1: the parts of the last nsplit tiles; then the whole tiles 0 .. ntiles - nsplit - 1
+  int64_t tile = (int64_t)blockIdx.x - TQ_PU_PARTS * nsplit;
+  if (tile < 0) {
+    const int s = (int)blockIdx.x / TQ_PU_PARTS;
+    TqSplitPart sp;
+    sp.part = (int)blockIdx.x % TQ_PU_PARTS;
+    tq_pu_part_bodies<P>(sp.part, &sp.body_begin, &sp.body_end);
+    sp.counter = (int32_t*)a.pu_scratch + s;
+    sp.slabs = (uint64_t*)((int32_t*)a.pu_scratch + tq_pu_counter_words(a.pu_scratch_tiles)) +
+               (int64_t)s * (TQ_PU_PARTS * TQ_PU_PAIRS * 64);
+    tile = ((B + 63) >> 6) - nsplit + s;
+    if (!tq_il2_lane<K, P, true, TqSplitPart>(k, B, pixv, tile, sp)) return;
+  } else {
+    tq_il2_lane<K, P, true>(k, B, pixv, tile);
+  }
+  const int64_t i = tile * 64 + threadIdx.x;
   const uint32_t FC = (uint32_t)(a.F * a.C);
-  const uint32_t n0 = ((uint32_t)blockIdx.x * 64u) / FC;  // AOI of the wave's first unit
+  const uint32_t n0 = ((uint32_t)tile * 64u) / FC;  // AOI of the wave's first unit
   const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
   float part[TQ_MAX_NGSUM], aoi[TQ_ROWS_GCOL];
 #pragma unroll
@@ -207,7 +298,7 @@ __global__ __launch_bounds__(64, 2) void tq_pixel_unit_kernel(const tq_ksmogn_ar
       }
     }
   }
-  float* row = a.blk_part + (int64_t)blockIdx.x * ncol;
+  float* row = a.blk_part + tile * ncol;
 #pragma unroll
   for (int j = 0; j < TQ_ROWS_GCOL; ++j) {
     const bool used = (j % TQ_ROWS_AOICOL) < 2 * a.C;

@@ -158,6 +158,12 @@ class CosmosEngine:
         # TAPQIR_AMD_FUSE_UNIT=auto brings the timing back (three interleaved rounds, best of each).
         fu = os.environ.get("TAPQIR_AMD_FUSE_UNIT", "1")
         self.fuse_unit = None if fu == "auto" else fu != "0"
+        # the fused launch can split its last tiles by rows over four waves each, dispatched first, so that a nearly empty
+        # last round of tiles goes (tq_cosmos_args.pu_split): -1 = the library's rule (tq_cosmos_pu_split_auto), 0 = never,
+        # n = the last n tiles.  TAPQIR_AMD_PU_SPLIT=auto|0|n fixes it for A/B timing.
+        ps = os.environ.get("TAPQIR_AMD_PU_SPLIT", "auto")
+        self.pu_split = -1 if ps == "auto" else int(ps)
+        self._pu_scratch, self._pu_scratch_tiles = None, 0
         self._sync = torch.zeros(_lib.SYNC_WORDS, dtype=torch.int32, device=dev)  # tickets, flags; diagnostic stamps of a TQ_MB_STAMPS build
         self._sync_value = 0
 
@@ -387,6 +393,8 @@ class CosmosEngine:
         # reload) must not leave a ticket counter that no later launch can start from
         self._sync.zero_()
         self._sync_value = 0
+        if self._pu_scratch is not None:
+            self._pu_scratch[:self._pu_scratch_tiles].zero_()  # the tickets of the split tiles (four per tile and launch)
         if "_sub" in self.__dict__:
             self._sub["ready"] = None  # a device-drawn subsample belongs to the step count it was drawn for
 
@@ -405,6 +413,30 @@ class CosmosEngine:
         self.aoi_part = torch.zeros(3 * B, dtype=f32, device=dev)
         self.blk_part = torch.zeros(self._blk_floats(B), dtype=f32, device=dev)
         self._ws_key = key
+
+    def _pu_split_tiles(self, nb, fb):
+        """Tiles that a fused full-batch launch of this engine splits by rows (tq_cosmos_args.pu_split): the engine's fixed
+        count, or the library's rule for the wave slots of the instantiated kernel; 0 where no step can be fused."""
+        full = nb == self.Nt and fb == self.F
+        if (not self.pu_split or not full or not self.pipelined_tail or self.crosstalk or self.K > 2 or self.O != 1
+                or self.P not in (14, 20) or self.F * self.C < 256):
+            return 0
+        ntiles = (nb * fb * self.C + 63) // 64
+        if self.pu_split > 0:
+            return min(self.pu_split, ntiles)
+        if "_pu_slots" not in self.__dict__:
+            self._pu_slots = int(self.lib.tq_cosmos_pu_slots(self.K, self.P))
+        return int(self.lib.tq_cosmos_pu_split_auto(ntiles, self._pu_slots))
+
+    def _pu_split_scratch(self, nb, fb):
+        """Tickets and partial sums of the split tiles: grown to what the batch geometry needs, zeroed when allocated (the
+        tickets count four per tile and launch and are never reset)."""
+        tiles = self._pu_split_tiles(nb, fb)
+        if tiles > self._pu_scratch_tiles:
+            words = int(self.lib.tq_cosmos_pu_scratch_bytes(tiles)) // 4
+            self._pu_scratch = torch.zeros(words, dtype=torch.int32, device=self.device)
+            self._pu_scratch_tiles = tiles
+        return self._pu_scratch, self._pu_scratch_tiles
 
     def _index_to_device(self, idx, which):
         """One subsample index vector as a device int32 tensor (see _indices_to_device for the step's fast path)."""
@@ -535,6 +567,9 @@ class CosmosEngine:
         a.step = self.adam_step if step is None else int(step)
         a.pixel_mode = int(self.pixel_mode or 0)
         a.sync, a.tail_kind = p(self._sync), 0
+        a.pu_split = self.pu_split
+        scratch, a.pu_scratch_tiles = self._pu_split_scratch(nb, fb)
+        a.pu_scratch = p(scratch)
         return a
 
     def _step_args(self, ndx, fdx):
@@ -543,7 +578,7 @@ class CosmosEngine:
         (minibatch steps are launch-bound: the host side of a step must stay well below the ~50 us of its kernels)."""
         nb = self.Nt if ndx is None else int(ndx.numel())
         fb = self.F if fdx is None else int(fdx.numel())
-        key = (nb, fb, self.lr, self.betas, self.adam_eps, self.seed, id(self.priors))
+        key = (nb, fb, self.lr, self.betas, self.adam_eps, self.seed, id(self.priors), self.pu_split)
         if self.__dict__.get("_tmpl_key") != key or self._ws_key != (nb, fb):  # (the template points into the workspace)
             a = self.make_args(ndx, fdx, _for_step=True)
             self._tmpl, self._tmpl_key = _lib.CosmosArgs.from_buffer_copy(a), key
