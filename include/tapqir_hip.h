@@ -88,9 +88,8 @@ typedef struct {
   int32_t nb_full;             /* Nt of the dataset behind images_il */
   int32_t il_min_units;        /* use the interleaved kernel only for batches of at least this many units */
   float scale;                 /* plate scale (Nt/nb)(F/fb), used with m_logit */
-  int32_t pixel_mode;          /* backward pass on the interleaved layout (K <= 2, one offset): 1 = persistent waves that walk
-                                  over the tiles with every global read an LDS-DMA request, 0 = one wave per tile.  Same
-                                  results; which is faster depends on the box, so the host times both once */
+  int32_t pixel_mode;          /* must be 0.  (1 used to select a persistent form of the backward kernel on the interleaved
+                                  layout; that form was retired and any other value is now TQ_ERR_ARG) */
   int32_t images_by_slot;      /* 1: `images` holds only the AOIs of THIS batch, AOI number ai of the batch at
                                   images[ai * F * C * P * P] (a window of a data set that does not fit the device: the host
                                   streams the AOIs of a batch in, dataset.py:140-151 does the same per minibatch); every other
@@ -251,7 +250,8 @@ typedef struct {
   /* lazy Adam of minibatch steps (tq_cosmos_adam_catchup) */
   int32_t* last_step;          /* [Nt*F*C] Adam step at which the local parameters of a unit were last updated, or NULL */
   double beta1_d, beta2_d;     /* the Adam betas in double: 1 - beta^s of the replayed steps is formed like the host's */
-  int32_t pixel_mode;          /* 0 / 1: passed on to tq_ksmogn_args.pixel_mode; TQ_PIXEL_FUSED_UNIT (2): see tq_cosmos_pixel_unit */
+  int32_t pixel_mode;          /* 0: pixel kernel and per-unit kernel as two launches; TQ_PIXEL_FUSED_UNIT (2): see
+                                  tq_cosmos_pixel_unit.  Any other value is TQ_ERR_ARG (1, the persistent pixel kernel, was retired) */
   int32_t tail_kind;           /* how the pending tail of THIS step finds its partial sums: TQ_TAIL_AUTO (what tq_cosmos_step /
                                   _step_overlapped / _elbo_grads wrote) or TQ_TAIL_ROWS16 (the step ran as
                                   tq_cosmos_minibatch_step); the host sets it on the struct it later passes as `prev` / to

@@ -50,7 +50,7 @@ if [[ $S == *pmc* ]]; then
   cd /tmp
 fi
 if [[ $S == *pix* ]]; then
-  PIXARGS="--pixel-mode 0" bash $R/scripts/gpu_pix_pmc.sh "FETCH_SIZE" "WRITE_SIZE" > $O/pixpmc.log 2>&1
+  bash $R/scripts/gpu_pix_pmc.sh "FETCH_SIZE" "WRITE_SIZE" > $O/pixpmc.log 2>&1
   cp $R/gpurun_out/pixpmc/summary.txt $O/pmc_summary_logprob.txt
   cd $R; python3 scripts/make_pmc_traffic.py $O/pmc_traffic.json 2 14 400000 $O/pmc_summary_logprob.txt > /dev/null; cd /tmp
 fi

@@ -17,8 +17,6 @@ def main():
     ap.add_argument("--P", type=int, default=14)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--offsets", default="sim")
-    ap.add_argument("--pixel-mode", type=int, default=None,
-                    help="form of the backward pixel kernel (0: one wave per tile, 1: persistent waves); default: autotune_pixel's")
     a = ap.parse_args()
     from tapqir_amd.models.cosmos import initial_values
     from tapqir_amd.models.engine import CosmosEngine
@@ -37,9 +35,6 @@ def main():
         data = CosmosDataset(data.images, data.xy, data.is_ontarget, offset_samples=s, offset_weights=w / w.sum())
     eng = CosmosEngine(data, K=a.K, device=dev, seed=7)
     eng.layout.set_constrained(eng.params, initial_values(eng, data))
-    eng.autotune_pixel()
-    if a.pixel_mode is not None:
-        eng.pixel_mode = a.pixel_mode
     B = a.aois * a.frames
     for bwd in (False, True):
         t = bench.time_pixel_kernel(eng, a.launches, bwd)

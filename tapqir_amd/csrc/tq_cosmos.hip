@@ -106,6 +106,10 @@ static bool tq_fused_pixel_unit(const tq_cosmos_args& a) {
 
 // ---------------------------------------------------------------------------------------------------------
 static int check_args(const tq_cosmos_args* a) {
+  if (a && a->pixel_mode != 0 && a->pixel_mode != TQ_PIXEL_FUSED_UNIT) {  // (first: refused whatever else the block holds)
+    tq_set_error("tq_cosmos_*: pixel_mode must be 0 or TQ_PIXEL_FUSED_UNIT (the persistent form of the pixel kernel, pixel_mode = 1, was retired)");
+    return TQ_ERR_ARG;
+  }
   if (!a || !a->params || !a->globals || !a->gbase) {
     tq_set_error("tq_cosmos_*: NULL args/params/globals/gbase");
     return TQ_ERR_ARG;
@@ -169,7 +173,6 @@ static tq_ksmogn_args cosmos_ksmogn_args(const tq_cosmos_args* a, float** pix_en
   k.pixstats = a->pixstats;
   k.stats_stride = U;
   k.il_min_units = a->il_min_units;
-  k.pixel_mode = a->pixel_mode;
   k.background = a->lat;
   k.height = a->lat + (int64_t)1 * B;
   k.width = a->lat + (int64_t)(1 + K) * B;

@@ -15,7 +15,7 @@
 #define TQ_BLOCK (TQ_LANES_PER_UNIT * TQ_UNITS_PER_BLOCK)
 
 // (host) integer value of a test hook's environment variable, `fallback` where it is not set: the hooks force a launch
-// geometry the inputs of the oracle tests would not reach by themselves (TAPQIR_AMD_MB_UNITS, _MB_TAIL_LAST, _PERSIST_WAVES)
+// geometry the inputs of the oracle tests would not reach by themselves (TAPQIR_AMD_MB_UNITS, _MB_TAIL_LAST)
 static inline int tq_env_int(const char* name, int fallback) {
   const char* e = getenv(name);
   return e ? atoi(e) : fallback;
@@ -142,13 +142,11 @@ __device__ __forceinline__ void tq_pixel_multi_offset(TqPixAcc<K>& A, const tq_k
 template <int K, bool BWD>
 __device__ __forceinline__ void tq_pixel_assemble_one_offset(const tq_ksmogn_args& a, TqPixAcc<K>& A, const float* W,
                                                              float b, float g, float rg, float ln_g, float fnpix,
-                                                             float S_v, float S_lv, const float* logit0 = nullptr) {
-  // logit0: the log-weight of the single offset if the caller has it in a register (the persistent kernel keeps
-  // register-destination loads out of its tile loop)
+                                                             float S_v, float S_lv) {
   constexpr int M = 1 << K;
   TqCombo0 c0;
   tq_combo0_prepare(b, rg, g, ln_g, &c0);
-  const float lw0 = (logit0 ? *logit0 : a.offset_logits[0]) - TQ_LN_SQRT_2PI;
+  const float lw0 = a.offset_logits[0] - TQ_LN_SQRT_2PI;
   const float common = lw0 * fnpix - S_lv;             // sum [ln w - ln sqrt(2pi) - ln v]
   const float S_lvg = S_lv - fnpix * ln_g;             // sum [ln v - ln g]
   const float sl0 = S_lv - fnpix * c0.lnb;             // sum ln(v / b)

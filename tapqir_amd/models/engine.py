@@ -146,18 +146,14 @@ class CosmosEngine:
         # full-batch single-GPU steps leave their single-workgroup tail pending and run it inside the next step's
         # sampling launch (include/tapqir_hip.h: tq_cosmos_step_overlapped)
         self._tail_args = None  # arguments of the step whose tail is pending
-        # form of the backward pixel kernel for contiguous batches (include/tapqir_hip.h: pixel_mode): None = not chosen
-        # yet -> the first full-batch step times both forms on this box (autotune_pixel)
-        self.pixel_mode = None
-        # full-batch single-GPU steps can run the pixel kernel and the per-unit kernel as ONE launch (pixel_mode =
-        # TQ_PIXEL_FUSED_UNIT of tq_cosmos_args): None = not chosen yet -> the first such step times both ways
-        # (autotune_fused); TAPQIR_AMD_FUSE_UNIT=0/1 fixes the choice
-        # Default: fused wherever the step qualifies (_fusable).  Rounds 1-2 timed both ways on the first step, but four steps
-        # each decide by ~2 % of noise while the fused launch has been 7-15 % ahead on every box since its per-unit phase
-        # became scratch-free (round 3: a mis-tuned run of bench.py measured 0.244 instead of 0.227 ms per c2 step).
-        # TAPQIR_AMD_FUSE_UNIT=auto brings the timing back (three interleaved rounds, best of each).
+        # form of the stand-alone pixel kernel: always 0, the one wave per tile form is the only one (bench.py reads this)
+        self.pixel_mode = 0
+        # full-batch steps run the pixel kernel and the per-unit kernel as ONE launch (pixel_mode = TQ_PIXEL_FUSED_UNIT of
+        # tq_cosmos_args) wherever the step qualifies (_fusable); TAPQIR_AMD_FUSE_UNIT=0 keeps the two launches for A/B timing
         fu = os.environ.get("TAPQIR_AMD_FUSE_UNIT", "1")
-        self.fuse_unit = None if fu == "auto" else fu != "0"
+        if fu not in ("0", "1"):
+            raise ValueError(f"TAPQIR_AMD_FUSE_UNIT={fu!r}: expected 0 or 1")
+        self.fuse_unit = fu != "0"
         # the fused launch can split its last tiles by rows over four waves each, dispatched first, so that a nearly empty
         # last round of tiles goes (tq_cosmos_args.pu_split): -1 = the library's rule (tq_cosmos_pu_split_auto), 0 = never,
         # n = the last n tiles.  TAPQIR_AMD_PU_SPLIT=auto|0|n fixes it for A/B timing.
@@ -417,9 +413,7 @@ class CosmosEngine:
     def _pu_split_tiles(self, nb, fb):
         """Tiles that a fused full-batch launch of this engine splits by rows (tq_cosmos_args.pu_split): the engine's fixed
         count, or the library's rule for the wave slots of the instantiated kernel; 0 where no step can be fused."""
-        full = nb == self.Nt and fb == self.F
-        if (not self.pu_split or not full or not self.pipelined_tail or self.crosstalk or self.K > 2 or self.O != 1
-                or self.P not in (14, 20) or self.F * self.C < 256):
+        if not self.pu_split or nb < self.Nt or fb < self.F or not self._fusable():
             return 0
         ntiles = (nb * fb * self.C + 63) // 64
         if self.pu_split > 0:
@@ -565,7 +559,7 @@ class CosmosEngine:
         a.fuse_adam = 0  # set by _open_step()
         a.seed = self.seed
         a.step = self.adam_step if step is None else int(step)
-        a.pixel_mode = int(self.pixel_mode or 0)
+        a.pixel_mode = 0  # (_step_overlapped / _step_sharded ask for the fused launch)
         a.sync, a.tail_kind = p(self._sync), 0
         a.pu_split = self.pu_split
         scratch, a.pu_scratch_tiles = self._pu_split_scratch(nb, fb)
@@ -609,8 +603,8 @@ class CosmosEngine:
         _lib.check(getattr(self.lib, "tq_" + name)(C.byref(args), self._stream()), "tq_" + name)
 
     def ksmogn_args(self, backward=True):
-        """Argument block of ``tq_ksmogn_log_prob`` for the full batch with the latents in the workspace (diagnostics,
-        bench.py's roofline leg and the autotuner)."""
+        """Argument block of ``tq_ksmogn_log_prob`` for the full batch with the latents in the workspace (diagnostics and
+        bench.py's roofline leg)."""
         self._workspace(self.Nt, self.F)
         K, M = self.K, 1 << self.K
         B = self.Nt * self.F * self.C
@@ -632,74 +626,14 @@ class CosmosEngine:
         k.m_kstride = B
         k.nb, k.fb, k.C, k.F, k.P, k.K, k.O = self.Nt, self.F, self.C, self.F, self.P, K, self.O
         k.scale = 1.0
-        k.pixel_mode = int(self.pixel_mode or 0)
+        k.pixel_mode = 0
         return k
-
-    def autotune_pixel(self, launches=8):
-        """Choose the form of the backward pixel kernel for this box and this dataset: the persistent form is insensitive to
-        wave-launch and memory latency, the one-wave-per-tile form is ahead where those are short (120-131 us against
-        114-151 us at 400 000 units across the boxes of one pool).  Both give the same results; a few launches of each on
-        the latents of the workspace (drawn here if the step has not run yet) decide.  Applies to K <= 2 with one offset."""
-        self.pixel_mode = 0
-        if self.crosstalk or self.K > 2 or self.O != 1 or self.P not in (14, 20) or self.Nt * self.F * self.C < self.il_min_units:
-            return 0
-        a = self.make_args()
-        self.call("cosmos_sample_globals", a)
-        self.call("cosmos_sample_locals", a)
-        times = []
-        for mode in (0, 1):
-            self.pixel_mode = mode
-            k = self.ksmogn_args(backward=True)
-            for _ in range(2):
-                _lib.check(self.lib.tq_ksmogn_log_prob(C.byref(k), self._stream()), "tq_ksmogn_log_prob")
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(launches):
-                self.lib.tq_ksmogn_log_prob(C.byref(k), self._stream())
-            e1.record()
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) / launches)
-        self.pixel_mode = int(times[1] < times[0])
-        self.pixel_times_ms = times
-        self.__dict__.pop("_tmpl_key", None)  # argument templates carry the mode
-        return self.pixel_mode
 
     def _fusable(self):
         """Can a full-batch step of this engine run pixel + per-unit kernel in one launch?  (The host predicate
         tq_fused_pixel_unit of tq_cosmos.hip asks the same of a step's arguments.)"""
         return (self.pipelined_tail and not self.crosstalk and self.K <= 2 and self.O == 1 and self.P in (14, 20)
                 and self.Nt * self.F * self.C >= self.il_min_units and self.F * self.C >= 256)
-
-    def autotune_fused(self, steps=6, rounds=3):
-        """Choose between two launches (pixel kernel, per-unit kernel) and the fused launch for the full-batch steps of
-        this box and dataset by timing real steps each way (``rounds`` interleaved rounds of ``steps`` steps, the best round
-        of each counts); parameters, optimiser state and step count are put back afterwards."""
-        if not self._fusable():
-            self.fuse_unit = False
-            return False
-        self.join()
-        saved = (self.params.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.adam_step)
-        times = [float("inf"), float("inf")]
-        for _ in range(rounds):
-            for k, fuse in enumerate((False, True)):
-                self.fuse_unit = fuse
-                self.step()
-                self.step()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(steps):
-                    self.step()
-                e1.record()
-                e1.synchronize()
-                times[k] = min(times[k], e0.elapsed_time(e1) / steps)
-        self.join()
-        self.params.copy_(saved[0])
-        self.exp_avg.copy_(saved[1])
-        self.exp_avg_sq.copy_(saved[2])
-        self.adam_step = saved[3]
-        self.fuse_unit = bool(times[1] < times[0])
-        self.step_times_ms = times
-        return self.fuse_unit
 
     def _route(self, nb, fb, allreduce):
         """The launch sequence of a step of nb AOIs x fb frames (step() and step_subsampled() both ask here):
@@ -798,10 +732,6 @@ class CosmosEngine:
                 raise NotImplementedError("AOI sharding of a streamed data set: shard first, each rank then streams its own AOIs "
                                           "(not built: a rank's shard of every BASELINE config fits its 288 GB many times over)")
             return self._step_streamed(ndx, fdx)
-        if self.pixel_mode is None and ndx is None and fdx is None and self.pipelined_tail:
-            self.autotune_pixel()
-        if self.fuse_unit is None and ndx is None and fdx is None and allreduce is None and self.pipelined_tail:
-            self.autotune_fused()
         a = self._step_args(ndx, fdx)
         self._open_step(a)
         if route == "one_launch":
@@ -908,8 +838,8 @@ class CosmosEngine:
                 self._finish_pending(next_args=a)  # ... and draws this step's global sites in the same launch
             else:
                 self.call("cosmos_sample_globals", a)
-        if a.fuse_adam and not a.zero_grad and self.fuse_unit is not False and self._fusable():
-            a.pixel_mode = _lib.PIXEL_FUSED_UNIT  # (not timed against the two-launch form on this path)
+        if a.fuse_adam and not a.zero_grad and self.fuse_unit and self._fusable():
+            a.pixel_mode = _lib.PIXEL_FUSED_UNIT
         self.call("cosmos_elbo_grads", a)
         handle = allreduce(self.gsum) if allreduce is not None else None
         if handle is not None and hasattr(handle, "wait") and a.fuse_adam:

@@ -210,3 +210,34 @@ def test_abi_rejects_malformed_arguments():
     p = _lib.ProbsArgs()
     assert lib.tq_cosmos_probs(C.byref(p), None) == 1
     assert lib.tq_images_interleave(None, None, 0, 14, None) == 1
+
+
+def test_abi_rejects_the_retired_pixel_mode():
+    """pixel_mode = 1 asked for the persistent form of the pixel kernel, which the library no longer has: TQ_ERR_ARG (= 1)
+    and a message that says so, before anything else is looked at.  The blocks hold nothing but the mode: were the check to
+    go, the NULL-pointer check would answer (another message), not a launch."""
+    lib = _lib.load()
+    k = _lib.KsmognArgs()
+    for mode in (1, _lib.PIXEL_FUSED_UNIT):  # (the fused launch is asked of tq_cosmos_*, not of the pixel kernel)
+        k.pixel_mode = mode
+        assert lib.tq_ksmogn_log_prob(C.byref(k), None) == 1, mode
+        assert b"pixel_mode" in lib.tq_last_error() and b"retired" in lib.tq_last_error()
+    a = _lib.CosmosArgs()
+    for mode in (1, 3):
+        a.pixel_mode = mode
+        for name in ("tq_cosmos_elbo_grads", "tq_cosmos_step", "tq_cosmos_sample_globals"):
+            assert getattr(lib, name)(C.byref(a), None) == 1, (name, mode)
+            assert b"pixel_mode" in lib.tq_last_error() and b"retired" in lib.tq_last_error()
+    a.pixel_mode = _lib.PIXEL_FUSED_UNIT  # accepted as a mode: the NULL pointers are what is refused
+    assert lib.tq_cosmos_elbo_grads(C.byref(a), None) == 1 and b"NULL" in lib.tq_last_error()
+
+
+def test_fuse_unit_takes_0_or_1(monkeypatch):
+    """TAPQIR_AMD_FUSE_UNIT=auto used to time both step forms; an engine now refuses anything but 0 and 1."""
+    d = make_dataset(N=2, F=2, K=1)
+    for value, want in (("0", False), ("1", True)):
+        monkeypatch.setenv("TAPQIR_AMD_FUSE_UNIT", value)
+        assert CosmosEngine(d, K=1, device="cpu", lib=load_hostcheck()).fuse_unit is want
+    monkeypatch.setenv("TAPQIR_AMD_FUSE_UNIT", "auto")
+    with pytest.raises(ValueError, match="0 or 1"):
+        CosmosEngine(d, K=1, device="cpu", lib=load_hostcheck())

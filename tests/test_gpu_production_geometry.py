@@ -122,7 +122,7 @@ def test_free_run_full_batch_fused(capsys):
     N, F = 2, 256
     d, o, eng = setup(2, dict(N=N, F=F))
     eng.il_min_units = 1
-    eng.pixel_mode, eng.fuse_unit = 0, True
+    eng.fuse_unit = True
     assert eng._fusable() and eng._route(N, F, None) == "overlapped"
 
     def expect(e):

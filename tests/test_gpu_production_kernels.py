@@ -69,7 +69,7 @@ def test_fused_pixel_unit_kernel_against_oracle(K, P, perturb):
     N, F = 3, 300
     d, o, eng = setup(K, dict(N=N, F=F, P=P), perturb=perturb)
     eng.il_min_units = 1
-    eng.pixel_mode, eng.fuse_unit = 0, True
+    eng.fuse_unit = True
     assert eng._fusable()
 
     def expect(e):
@@ -269,7 +269,7 @@ def test_sharded_launch_sequence_against_oracle(handle, fuse):
     N, F = 3, 300
     d, o, eng = setup(2, dict(N=N, F=F), perturb=0.3)
     eng.il_min_units = 1
-    eng.pixel_mode, eng.fuse_unit = 0, fuse
+    eng.fuse_unit = fuse
     replay(eng, o, N, F, steps=4, allreduce=(lambda g: _Done()) if handle else (lambda g: None))
 
 

@@ -106,13 +106,14 @@ def _oracle_for_units(s, eng, nd, fd, views=None):
     return o, base, ar_n, ar_f
 
 
-@pytest.mark.parametrize("pixel_mode", [0, 1], ids=["wave_per_tile", "persistent"])
-def test_sampled_units_match_the_oracle(shard, pixel_mode):
+# (the ids of two tests below end in "wave_per_tile", as they did while the pixel kernel had a second, persistent form)
+WAVE_PER_TILE = pytest.mark.parametrize((), [pytest.param(id="wave_per_tile")])
+
+
+@WAVE_PER_TILE
+def test_sampled_units_match_the_oracle(shard):
     s = shard
-    if pixel_mode and (s.xt or s.K > 2):
-        pytest.skip("the persistent form covers cosmos K <= 2")
     eng = s.engine()
-    eng.pixel_mode = pixel_mode
     s.perturb(eng)
     _stages(eng)
     K, M, C = s.K, 1 << s.K, s.C
@@ -170,7 +171,6 @@ def test_fused_step_sampled_units_match_the_oracle(shard, capsys):
     if not eng._fusable():
         pytest.skip("the fused launch covers cosmos K <= 2 with one offset")
     s.perturb(eng)
-    eng.pixel_mode, eng.fuse_unit = 0, True  # (neither autotuner runs)
     assert eng.adam_step == 0 and not bool(eng.exp_avg.any()) and not bool(eng.exp_avg_sq.any())
     p0 = eng.params.clone()
     eng.step()
@@ -237,16 +237,13 @@ def test_elbo_is_additive_over_aoi_shards(shard):
     assert abs(float(total[2]) - float(gs_full[2])) <= 1e-7 * abs(float(gs_full[2]))
 
 
-@pytest.mark.parametrize("pixel_mode", [0, 1], ids=["wave_per_tile", "persistent"])
-def test_pixel_kernels_agree(shard, pixel_mode):
+@WAVE_PER_TILE
+def test_pixel_kernels_agree(shard):
     s = shard
-    if pixel_mode and (s.xt or s.K > 2):
-        pytest.skip("the persistent form covers cosmos K <= 2")
     outs = []
     for il in (1, 1 << 30):
         eng = s.engine()
         eng.il_min_units = il
-        eng.pixel_mode = pixel_mode
         _stages(eng)
         outs.append(eng.pix.view(-1, s.N * s.F * s.C).clone())
         del eng

@@ -39,7 +39,7 @@ FAST_ALPHA = 8.0         # TQ_FAST_ALPHA: below it a tile takes the scalar loop
 def _engine(K, P, perturb=0.3):
     d, o, eng = setup(K, dict(N=N, F=F, P=P), perturb=perturb)
     eng.il_min_units = 1
-    eng.pixel_mode, eng.fuse_unit = 0, True
+    eng.fuse_unit = True
     assert eng._fusable() and NTILES == 15
     return d, o, eng
 

@@ -59,7 +59,6 @@ def test_full_batch_and_minibatch_steps_in_turn():
     N, F = 3, 300
     d, o, eng = setup(2, dict(N=N, F=F), perturb=0.3)
     eng.il_min_units = 1
-    eng.pixel_mode = 0
     mb = _subs(N, F, 2, 40, 3)
 
     def fused(e):
@@ -92,7 +91,6 @@ def test_full_batch_families_carry_each_other_s_tails():
     launches (tq_cosmos_tail of the rows-of-16 tail before the overlapped step) -> single launch -> fused."""
     N, F = 3, 300
     d, o, eng = setup(2, dict(N=N, F=F), perturb=0.3)
-    eng.pixel_mode = 0
 
     def fused(e):
         e.il_min_units, e.fuse_unit = 1, True
@@ -169,7 +167,7 @@ def test_sharded_steps_with_the_collective_in_flight():
     N, F = 3, 300
     d, o, eng = setup(2, dict(N=N, F=F), perturb=0.3)
     eng.il_min_units = 1
-    eng.pixel_mode, eng.fuse_unit = 0, True
+    eng.fuse_unit = True
     plan = [dict(nd=None, fd=None, kw=dict(allreduce=lambda g: _Done()),
                  post=lambda e: None if e._pending is not None else pytest.fail("no pending all-reduce")) for _ in range(5)]
     found = _carried(eng, plan)

@@ -171,7 +171,7 @@ def test_step_and_step_subsampled_follow_route(route, nb, fb, dkw, setup, monkey
     allreduce = (lambda g: None) if setup.pop("allreduce", False) else None
     d = make_dataset(N=6, F=40, K=2, seed=5, **dkw)
     eng = HostCheckEngine(d, K=2, device=torch.device("cpu"), crosstalk=setup.pop("crosstalk", False))
-    eng.pipelined_tail, eng.lazy_adam, eng.pixel_mode, eng.fuse_unit = True, True, 0, True
+    eng.pipelined_tail, eng.lazy_adam, eng.fuse_unit = True, True, True
     for k, v in setup.items():
         setattr(eng, k, v)
     calls = []
