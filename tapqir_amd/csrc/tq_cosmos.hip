@@ -6,8 +6,10 @@
 // and extern "C" entry point, and the posterior read-out.  The kernels are in headers that only this file includes, one
 // per launch family:
 //   tq_step_staged.h     one kernel per stage of a step; the wave sums and single-workgroup bodies every tail shares
-//   tq_step_rows.h       the rows layout of full-batch steps: per-unit kernels that leave rows, group rows, the sampling
-//                        launch that carries the pending tail of the previous step
+//   tq_rows.h            the rows of partial sums in blk_part, the format in which a step with rows hands its sums to its
+//                        tail: widths, the writers of a row, the addresses a reader takes from a row or a group row
+//   tq_step_rows.h       full-batch steps with rows: per-unit kernels that leave rows, group rows, the sampling launch that
+//                        carries the pending tail of the previous step
 //   tq_step_minibatch.h  the single-launch minibatch step
 //   tq_beta_compact.h    one local guide site by one workgroup (all sampling launches), AffineBeta regime compaction
 //   tq_stamps.h          words of tq_cosmos_args.sync, diagnostic stamps (scripts/build_stamps.sh)
@@ -60,12 +62,13 @@
 #include "tq_bodies.h"
 #include "tq_host.h"
 #include "tq_ksmogn_dev.h"
+#include "tq_rows.h"
 #include "tq_step_minibatch.h"
 #include "tq_step_rows.h"
 #include "tq_step_staged.h"
 
 // ---- host predicates: which layout, which launch, which pending tail ------------------------------------------------------
-// Does this step leave its partial sums in the rows layout (tq_step_rows.h)?  Full batches with the fused Adam and at least
+// Does this step leave its partial sums in the rows layout (tq_rows.h)?  Full batches with the fused Adam and at least
 // TQ_UNIT_BLOCK units per AOI; the others keep the flat layout + tq_aoi_kernel.
 static bool tq_rows_layout(const tq_cosmos_args& a) {
   return a.fuse_adam && !a.ndx && !a.fdx && a.nb == a.Nt && a.fb == a.F && a.F * a.C >= TQ_UNIT_BLOCK;
@@ -227,6 +230,16 @@ static int launch_likelihood(const tq_cosmos_args* a, void* stream) {
   return tq_ksmogn_log_prob(&k, stream);
 }
 
+// The (K, P) instances of tq_pixel_unit_kernel: runs `...` with the compile-time constants KK = K (1 or 2) and PP = P (14 or
+// 20), which tq_fused_pixel_unit has checked (not TQ_SWITCH_K: the kernel exists for K <= 2 only)
+#define TQ_SWITCH_PU(K, P, ...)                                             \
+  switch (2 * ((K) != 1) + ((P) != 14)) {                                   \
+    case 0: { constexpr int KK = 1, PP = 14; __VA_ARGS__; } break;          \
+    case 1: { constexpr int KK = 1, PP = 20; __VA_ARGS__; } break;          \
+    case 2: { constexpr int KK = 2, PP = 14; __VA_ARGS__; } break;          \
+    default: { constexpr int KK = 2, PP = 20; __VA_ARGS__; } break;         \
+  }
+
 // Split tiles of the fused launch (tq_step_rows.h).  Waves of the (K, P) instance that the device holds at a time: asked once.
 extern "C" int32_t tq_cosmos_pu_slots(int32_t K, int32_t P) {
   static int cache[2][2] = {{-1, -1}, {-1, -1}};
@@ -235,10 +248,7 @@ extern "C" int32_t tq_cosmos_pu_slots(int32_t K, int32_t P) {
   if (slots < 0) {
     int per_cu = 0, dev = 0, cus = 0;
     hipError_t e;
-    if (K == 1) e = P == 14 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tq_pixel_unit_kernel<1, 14>, 64, 0)
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tq_pixel_unit_kernel<1, 20>, 64, 0);
-    else e = P == 14 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tq_pixel_unit_kernel<2, 14>, 64, 0)
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tq_pixel_unit_kernel<2, 20>, 64, 0);
+    TQ_SWITCH_PU(K, P, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tq_pixel_unit_kernel<KK, PP>, 64, 0));
     if (e == hipSuccess) e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) {
@@ -277,14 +287,7 @@ static int launch_pixel_unit(const tq_cosmos_args* a, void* stream) {
   }
   const dim3 grid((unsigned)(ntiles + (TQ_PU_PARTS - 1) * (int64_t)nsplit)), block(64);
   hipStream_t st = (hipStream_t)stream;
-  // (not TQ_SWITCH_K: the kernel exists for K <= 2 only, tq_fused_pixel_unit)
-  if (a->K == 1) {
-    if (a->P == 14) hipLaunchKernelGGL((tq_pixel_unit_kernel<1, 14>), grid, block, 0, st, k, *a, B, nsplit);
-    else hipLaunchKernelGGL((tq_pixel_unit_kernel<1, 20>), grid, block, 0, st, k, *a, B, nsplit);
-  } else {
-    if (a->P == 14) hipLaunchKernelGGL((tq_pixel_unit_kernel<2, 14>), grid, block, 0, st, k, *a, B, nsplit);
-    else hipLaunchKernelGGL((tq_pixel_unit_kernel<2, 20>), grid, block, 0, st, k, *a, B, nsplit);
-  }
+  TQ_SWITCH_PU(a->K, a->P, hipLaunchKernelGGL((tq_pixel_unit_kernel<KK, PP>), grid, block, 0, st, k, *a, B, nsplit));
   return tq_launch_status("tq_pixel_unit_kernel");
 }
 
@@ -479,11 +482,11 @@ extern "C" int tq_cosmos_step_overlapped(const tq_cosmos_args* a, const tq_cosmo
 }
 
 extern "C" int64_t tq_cosmos_blk_floats(int32_t Nt, int32_t F, int32_t C, int32_t crosstalk, int64_t B) {
-  const int64_t ncol = TQ_ROWS_GCOL + TQ_NGSUM_X(C, crosstalk);
+  const int64_t ncol = tq_row_floats(TQ_NGSUM_X(C, crosstalk));
   const int64_t full = (((int64_t)Nt * F * C + 63) / 64) * ncol;                             // full-batch rows of 256 or 64 units
   const int64_t mini = ((B + TQ_UNITS_PER_BLOCK - 1) / TQ_UNITS_PER_BLOCK) * ncol;          // single-launch minibatch step: rows of 16
   const int64_t flat = tq_cosmos_nblk(B) * TQ_NGSUM_X(C, crosstalk);
-  const int64_t grp = 4 + tq_grp_count((int64_t)Nt * F * C) * TQ_GGROW;                      // group rows behind the full-batch rows
+  const int64_t grp = tq_grp_floats((int64_t)Nt * F * C);                                    // group rows behind the full-batch rows
   const int64_t most = full > mini ? (full > flat ? full : flat) : (mini > flat ? mini : flat);
   return most + grp;
 }

@@ -18,7 +18,7 @@
 //                   last four with a wave each;
 //   (wait 2)      : flag 2 (the per-unit terms need the tables of pi, lamda, proximity: set long before);
 //   phase 3       : per-unit ELBO terms, gradients and Adam (one lane per unit), row of partial sums with the per-AOI
-//                   frame sums folded in (rows of U units, tq_rows_reduce_globals_body<16>).
+//                   frame sums folded in (rows of U units, tq_rows.h; tq_rows_sums_body<16>).
 // Phases hand data over through the step workspace in global memory; a workgroup lives on one CU, whose L1 its waves
 // share, so a workgroup barrier orders those accesses.  The tail workgroup never waits for a workgroup that may not be
 // resident yet, so the waiting workgroups cannot deadlock whatever the dispatch order.  The tail of THIS step runs in the next launch (or in
@@ -39,6 +39,7 @@
 
 #include "tq_bodies.h"
 #include "tq_ksmogn_dev.h"
+#include "tq_rows.h"
 #include "tq_stamps.h"
 #include "tq_step_rows.h"
 #include "tq_step_staged.h"
@@ -291,9 +292,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
     const int lane = tid & 63, wave = tid >> 6;
     if (has_prev) {
       const int64_t Bp = tq_batch_units(prev);
-      if (has_prev == TQ_PREV_ROWS) tq_rows_reduce_globals_body<TQ_UNIT_BLOCK>(prev, s_w, s_e, 16, false);
-      else if (has_prev == TQ_PREV_ROWS16 || has_prev == TQ_PREV_ROWS20) tq_rows_reduce_globals_body<16>(prev, s_w, s_e, tq_mb_rows_upr(has_prev), false);
-      else tq_reduce_globals_body(prev, (Bp + TQ_UNIT_BLOCK - 1) / TQ_UNIT_BLOCK, Bp, s_w, s_e, false);
+      if (has_prev == TQ_PREV_ROWS) tq_rows_sums_body<TQ_UNIT_BLOCK>(prev, s_w);
+      else if (has_prev == TQ_PREV_ROWS16 || has_prev == TQ_PREV_ROWS20) tq_rows_sums_body<16>(prev, s_w, tq_mb_rows_upr(has_prev));
+      else tq_reduce_sums_fenced_body(prev, (Bp + TQ_UNIT_BLOCK - 1) / TQ_UNIT_BLOCK, Bp, s_w);
       // (the bodies end with gsum stored, a workgroup-scope fence and a barrier)
       if (lane == 0) {
         const int nsp = tq_num_gsites(prev);
@@ -467,7 +468,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
       // The step is lost.  Its row of partial sums carries a NaN ELBO, so the tail of this step (run by the next launch or
       // by tq_cosmos_tail) reports a NaN loss whichever workgroup was late, and Model.run rolls back to its last
       // checkpoint (model.py:220-232); CosmosEngine.reset_adam_clock zeroes the sync words on that path.
-      a.blk_part[wblk * (TQ_ROWS_GCOL + tq_num_gsum(a)) + TQ_ROWS_GCOL + TQ_GS_ELBO] = __builtin_nanf("");
+      tq_row_sum(a, tq_row_floats(tq_num_gsum(a)), wblk, TQ_GS_ELBO) = __builtin_nanf("");
       a.elbo_out[0] = __builtin_nan("");
       __hip_atomic_fetch_add(&a.sync[TQ_SYNC_LOST], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (never reset: a soak run reads it)
       count_out();  // still counted: the ticket counter is re-armed for the launches that follow
@@ -495,51 +496,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
   }
   TQ_MB_STAMP(TQ_ST_PIXEL);
   // ---- phase 3: per-unit terms + Adam, one lane per unit; row of partial sums ----
-  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
-  float part[TQ_MAX_NGSUM], aoi[TQ_ROWS_GCOL];
+  float part[TQ_MAX_NGSUM];
+  TqRowAoi aoi;
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) part[j] = 0.0f;
-#pragma unroll
-  for (int j = 0; j < TQ_ROWS_GCOL; ++j) aoi[j] = 0.0f;
+  tq_row_clear(aoi);
   // (units 16..19 of U = 20: the second lane of the first four 16-lane groups)
   const int64_t i = u0 + (tid >> 4) + 16 * (tid & 15);
   if ((tid & 15) < (U + 15) / 16 && i < u_end) {
     float aoi2[2];
     tq_body_unit<K, false, false, true>(a, i, part, aoi2);
     const uint32_t FC = (uint32_t)(a.fb * a.C);
-    const int c = (int)((uint32_t)i % (uint32_t)a.C);
-    const int slot = (uint32_t)i / FC == (uint32_t)u0 / FC ? 0 : 1;
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-#pragma unroll
-      for (int q = 0; q < TQ_MAXQ; ++q) {
-        const bool mine = sl == slot && q == c;
-        aoi[sl * TQ_ROWS_AOICOL + 2 * q] = mine ? aoi2[0] : 0.0f;
-        aoi[sl * TQ_ROWS_AOICOL + 2 * q + 1] = mine ? aoi2[1] : 0.0f;
-      }
-    }
+    tq_row_fill(aoi, tq_row_slot(tq_row_first_aoi((uint32_t)u0, FC), (uint32_t)i / FC), (int)((uint32_t)i % (uint32_t)a.C), aoi2);
   }
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int j = 0; j < TQ_ROWS_GCOL; ++j) {
-    if ((j % TQ_ROWS_AOICOL) < 2 * a.C) {
-      const float sum = tq_wave_sum_rows4(aoi[j]);
-      if (lane == 0) s_part[wave][j] = sum;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
-    if (j < nq) {
-      const float sum = tq_wave_sum_rows4(part[j]);
-      if (lane == 0) s_part[wave][TQ_ROWS_GCOL + j] = sum;
-    }
-  }
-  __syncthreads();
-  if (tid < ncol) {
-    const bool used = tid >= TQ_ROWS_GCOL || (tid % TQ_ROWS_AOICOL) < 2 * a.C;
-    const float sum = used ? (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]) : 0.0f;
-    a.blk_part[wblk * ncol + tid] = sum;
-  }
+  tq_row_store_wg(a, s_part, wblk, aoi, part);
   TQ_MB_STAMP(TQ_ST_UNIT);
   // the last workgroup to get here re-arms the ticket counter for the next launch (the flag holds the step number)
   if (tid == 0) count_out();

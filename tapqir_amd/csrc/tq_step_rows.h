@@ -1,31 +1,6 @@
 // tq_step_rows.h -- part of the translation unit tq_cosmos.hip, included from there only (it defines __global__ kernels):
-// the rows layout of full-batch steps and everything that writes or reads it -- the two per-unit kernels that leave
+// the full-batch steps that leave rows of partial sums (the format: tq_rows.h) -- the two per-unit kernels that write
 // rows, the group rows, the single-workgroup tail bodies, and the sampling launch that carries a pending tail.
-// =============================================================================================================
-// Per-unit kernel of full-batch steps (tq_cosmos_step_overlapped / tq_cosmos_step) with the per-AOI frame sums folded in.
-//
-// The units (f, c) of an AOI are contiguous, so a workgroup of 256 consecutive units touches at most TWO AOIs (when
-// F * C >= 256): its row of partial sums carries, next to the cross-unit sums, the sums of
-// d/d(background_mean_loc, background_std_loc) over its units of the first AOI (slot 0) and of the second (slot 1).  The
-// single-workgroup tail adds the few rows that overlap an AOI itself, so there is no per-AOI kernel (5 us + a launch
-// boundary at 400 000 units) and no aoi_part round trip (16 B per unit).  Workgroups stay 1 KiB-aligned in every
-// parameter row (AOI-aligned workgroups start at n * F * C and straddle cache lines: 9 % slower, measured).
-// Row layout: [2 slots][2 * TQ_MAXQ per-channel AOI partials][nq cross-unit sums]; fixed offsets keep every
-// register-array index a compile-time constant.
-//
-// Group rows: the tail's sums, spread over the otherwise idle workgroups of the sampling launch.
-// At c2 the fused launch leaves 6250 rows (one per wave).  The single-workgroup tail that adds them is a guest of the next
-// step's sampling launch, and under that launch's memory traffic each of its ~17 dependent round trips (per-AOI frame
-// sums: 16 rows per AOI, two AOIs per thread; cross-unit sums: 25 rows per thread) takes ~2.5 us: the sums alone kept it
-// busy for 50 of its 84 us, which made it the last workgroup of the launch.  The grid row of that launch that holds the
-// tail workgroup has B / 256 workgroups of which only the first did anything: now workgroup 1 + g of that row adds the rows
-// of GROUP g (4096 units: 64 rows of 64 units or 16 of 256) -- one lane per row, one round trip -- and leaves a group row:
-// the cross-unit sums in double and the per-AOI frame sums of the (at most 17) AOIs the group touches, published with
-// write-through (`sc1`) stores, a drained store queue and an agent-scope counter (MI355X_MICROARCH.md, inter-workgroup
-// visibility).  The tail workgroup polls the counter, then reads U / 4096 group rows with `sc1` loads: one round trip for
-// the cross-unit sums, one for the per-AOI sums (stamps build: sums complete 9 us after its start instead of 50).  The
-// reducers never wait, so the polling workgroup cannot deadlock.
-// =============================================================================================================
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,72 +8,30 @@
 #include "tq_bodies.h"
 #include "tq_ksmogn_dev.h"
 #include "tq_ksmogn_il2.h"
+#include "tq_rows.h"
 #include "tq_stamps.h"
 #include "tq_step_staged.h"
 
-#define TQ_ROWS_AOICOL (2 * TQ_MAXQ)
-#define TQ_ROWS_GCOL (2 * TQ_ROWS_AOICOL)
-#define TQ_ROWS_MAXCOL (TQ_ROWS_GCOL + TQ_MAX_NGSUM)
-
+// Per-unit kernel of full-batch steps (tq_cosmos_step_overlapped / tq_cosmos_step): a workgroup of 256 consecutive units
+// leaves one row, the per-AOI frame sums folded in.
 template <int K>
 __global__ __launch_bounds__(TQ_UNIT_BLOCK) void tq_unit_rows_kernel(const tq_cosmos_args a, const int64_t B) {
   __shared__ float s_part[TQ_UNIT_BLOCK / 64][TQ_ROWS_MAXCOL];
   const int64_t i = (int64_t)blockIdx.x * TQ_UNIT_BLOCK + threadIdx.x;
-  const bool live = i < B;
   const uint32_t FC = (uint32_t)(a.F * a.C);
-  const uint32_t n0 = ((uint32_t)blockIdx.x * TQ_UNIT_BLOCK) / FC;  // AOI of the workgroup's first unit
-  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
-  float part[TQ_MAX_NGSUM], aoi[TQ_ROWS_GCOL];
+  const uint32_t n0 = tq_row_first_aoi((uint32_t)blockIdx.x * TQ_UNIT_BLOCK, FC);
+  float part[TQ_MAX_NGSUM];
+  TqRowAoi aoi;
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) part[j] = 0.0f;
-#pragma unroll
-  for (int j = 0; j < TQ_ROWS_GCOL; ++j) aoi[j] = 0.0f;
-  if (live) {
+  tq_row_clear(aoi);
+  if (i < B) {
     float aoi2[2];
     tq_body_unit<K>(a, i, part, aoi2);
-    const uint32_t n = (uint32_t)i / FC;
-    const int c = (int)((uint32_t)i % (uint32_t)a.C);
-    const int slot = n == n0 ? 0 : 1;
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-#pragma unroll
-      for (int q = 0; q < TQ_MAXQ; ++q) {
-        const bool mine = sl == slot && q == c;
-        aoi[sl * TQ_ROWS_AOICOL + 2 * q] = mine ? aoi2[0] : 0.0f;
-        aoi[sl * TQ_ROWS_AOICOL + 2 * q + 1] = mine ? aoi2[1] : 0.0f;
-      }
-    }
+    tq_row_fill(aoi, tq_row_slot(n0, (uint32_t)i / FC), (int)((uint32_t)i % (uint32_t)a.C), aoi2);
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < TQ_ROWS_GCOL; ++j) {
-    if ((j % TQ_ROWS_AOICOL) < 2 * a.C) {
-      const float sum = tq_wave_sum_rows4(aoi[j]);
-      if (lane == 0) s_part[wave][j] = sum;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
-    if (j < nq) {
-      const float sum = tq_wave_sum_rows4(part[j]);
-      if (lane == 0) s_part[wave][TQ_ROWS_GCOL + j] = sum;
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < ncol) {
-    const bool used = (int)threadIdx.x >= TQ_ROWS_GCOL || ((int)threadIdx.x % TQ_ROWS_AOICOL) < 2 * a.C;
-    const float sum = used ? (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]) : 0.0f;
-    a.blk_part[(int64_t)blockIdx.x * ncol + threadIdx.x] = sum;
-  }
+  tq_row_store_wg(a, s_part, blockIdx.x, aoi, part);
 }
-
-// ---- group rows: the rows added per group of 4096 units for the tail workgroup (see the top of this file) ---------------
-#define TQ_GRP_UNITS 4096
-#define TQ_GRP_AOIS (TQ_GRP_UNITS / TQ_UNIT_BLOCK + 1)   /* AOIs a group can touch (F * C >= TQ_UNIT_BLOCK) */
-#define TQ_GGROW (2 * 16 + TQ_GRP_AOIS * 2 * TQ_MAXQ)    /* floats of a group row: 16 doubles, then 2 * TQ_MAXQ floats per AOI */
-__host__ __device__ __forceinline__ int64_t tq_grp_count(int64_t B) { return (B + TQ_GRP_UNITS - 1) / TQ_GRP_UNITS; }
-// group rows follow the rows in blk_part (16-byte aligned)
-__host__ __device__ __forceinline__ int64_t tq_grp_base(int64_t nrows, int ncol) { return ((nrows * ncol + 3) / 4) * 4; }
 
 // The pending tail: what a launch that carries the tail of the PREVIOUS step (`prev`, the kernels' `has_prev`) finds in
 // prev's workspace and has to do before prev's global sites, total ELBO and Adam of the per-AOI / global parameters.  The
@@ -123,38 +56,38 @@ __device__ __forceinline__ int tq_mb_rows_upr(int has_prev) { return has_prev ==
 // one wave: rows of group g of step `a` -> group row g (published); returns (lane 0) how many groups had been published before
 __device__ __forceinline__ int tq_group_reduce_rows(const tq_cosmos_args& a, const int g) {
   const int lane = threadIdx.x & 63;
-  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
+  const int nq = tq_num_gsum(a), ncol = tq_row_floats(nq);
   const int64_t B = tq_batch_units(a);
-  const uint32_t UPR = (uint32_t)tq_rows_upr(a), RPG = TQ_GRP_UNITS / UPR;
+  const uint32_t UPR = (uint32_t)tq_rows_upr(a), RPG = tq_grp_rows(UPR);
   const int64_t nrows = (B + UPR - 1) / UPR;
   const int64_t r0 = (int64_t)g * RPG;
   const int nw = (int)((nrows - r0) < (int64_t)RPG ? (nrows - r0) : (int64_t)RPG);
   const bool have = lane < nw;
-  const float* my = a.blk_part + (r0 + (have ? lane : 0)) * ncol;
+  const int64_t my = r0 + (have ? lane : 0);
+  const float *my0 = tq_row_slot_pairs(tq_row(a, ncol, my), 0), *my1 = tq_row_slot_pairs(tq_row(a, ncol, my), 1);
   float s0[2 * TQ_MAXQ], s1[2 * TQ_MAXQ], col[TQ_MAX_NGSUM];
 #pragma unroll
   for (int j = 0; j < 2 * TQ_MAXQ; ++j) {
     const bool used = j < 2 * a.C;
-    s0[j] = (have && used) ? my[j] : 0.0f;
-    s1[j] = (have && used) ? my[TQ_ROWS_AOICOL + j] : 0.0f;
+    s0[j] = (have && used) ? my0[j] : 0.0f;
+    s1[j] = (have && used) ? my1[j] : 0.0f;
   }
 #pragma unroll
-  for (int j = 0; j < TQ_MAX_NGSUM; ++j) col[j] = (have && j < nq) ? my[TQ_ROWS_GCOL + j] : 0.0f;
-  float* grow = a.blk_part + tq_grp_base(nrows, ncol) + (int64_t)g * TQ_GGROW;
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) col[j] = (have && j < nq) ? tq_row_sum(a, ncol, my, j) : 0.0f;
+  float* grow = tq_grp_row(a, nrows, ncol, g);
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
       const double sum = tq_wave_sum_d_lane0((double)col[j]);
-      if (lane == 0) __hip_atomic_store(&((double*)grow)[j], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (lane == 0) __hip_atomic_store(&tq_grp_sums(grow)[j], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
   const uint32_t FC = (uint32_t)(a.fb * a.C);
-  const uint32_t u_first = (uint32_t)g * TQ_GRP_UNITS;
-  const uint32_t u_last = (uint32_t)(((int64_t)u_first + TQ_GRP_UNITS - 1 < B - 1) ? u_first + TQ_GRP_UNITS - 1 : B - 1);
-  const uint32_t n_lo = u_first / FC, n_hi = u_last / FC;
-  const uint32_t n0 = (u_first + UPR * (uint32_t)lane) / FC;  // AOI of this row's first unit (slot 0; slot 1 is the next AOI)
+  const uint32_t u_first = tq_grp_first_unit((uint32_t)g), u_last = tq_grp_last_unit((uint32_t)g, B);
+  const uint32_t n_lo = tq_row_first_aoi(u_first, FC), n_hi = u_last / FC;  // (the group row's AOI 0 is n_lo)
+  const uint32_t n0 = tq_row_first_aoi(u_first + UPR * (uint32_t)lane, FC);  // this row's slot 0; slot 1 is the next AOI
   for (uint32_t n = n_lo; n <= n_hi; ++n) {
-    float* out = grow + 32 + (n - n_lo) * (2 * TQ_MAXQ);
+    float* out = tq_grp_aoi_pair(grow, n - n_lo, 0);
 #pragma unroll
     for (int j = 0; j < 2 * TQ_MAXQ; ++j) {
       if (j < 2 * a.C) {
@@ -275,43 +208,18 @@ __global__ __launch_bounds__(64, 2) void tq_pixel_unit_kernel(const tq_ksmogn_ar
   }
   const int64_t i = tile * 64 + threadIdx.x;
   const uint32_t FC = (uint32_t)(a.F * a.C);
-  const uint32_t n0 = ((uint32_t)tile * 64u) / FC;  // AOI of the wave's first unit
-  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
-  float part[TQ_MAX_NGSUM], aoi[TQ_ROWS_GCOL];
+  const uint32_t n0 = tq_row_first_aoi((uint32_t)tile * 64u, FC);
+  float part[TQ_MAX_NGSUM];
+  TqRowAoi aoi;
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) part[j] = 0.0f;
-#pragma unroll
-  for (int j = 0; j < TQ_ROWS_GCOL; ++j) aoi[j] = 0.0f;
+  tq_row_clear(aoi);
   if (i < B) {
     float aoi2[2];
     tq_body_unit<K, false, true>(a, i, part, aoi2, pixv);
-    const uint32_t n = (uint32_t)i / FC;
-    const int c = (int)((uint32_t)i % (uint32_t)a.C);
-    const int slot = n == n0 ? 0 : 1;
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-#pragma unroll
-      for (int q = 0; q < TQ_MAXQ; ++q) {
-        const bool mine = sl == slot && q == c;
-        aoi[sl * TQ_ROWS_AOICOL + 2 * q] = mine ? aoi2[0] : 0.0f;
-        aoi[sl * TQ_ROWS_AOICOL + 2 * q + 1] = mine ? aoi2[1] : 0.0f;
-      }
-    }
+    tq_row_fill(aoi, tq_row_slot(n0, (uint32_t)i / FC), (int)((uint32_t)i % (uint32_t)a.C), aoi2);
   }
-  float* row = a.blk_part + tile * ncol;
-#pragma unroll
-  for (int j = 0; j < TQ_ROWS_GCOL; ++j) {
-    const bool used = (j % TQ_ROWS_AOICOL) < 2 * a.C;
-    const float sum = used ? tq_wave_sum_rows4(aoi[j]) : 0.0f;
-    if (threadIdx.x == 0) row[j] = sum;
-  }
-#pragma unroll
-  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
-    if (j < nq) {
-      const float sum = tq_wave_sum_rows4(part[j]);
-      if (threadIdx.x == 0) row[TQ_ROWS_GCOL + j] = sum;
-    }
-  }
+  tq_row_store_wave(a, tile, aoi, part);
 }
 
 // acc[j] += sum over this thread's rows (r = threadIdx.x, + 256, ...) of column j of the cross-unit sums.  Four rows are
@@ -325,7 +233,7 @@ __device__ __forceinline__ void tq_rows_column_sums(const tq_cosmos_args& a, int
     for (int u = 0; u < 4; ++u) {
       const int64_t r = r0 + 256 * u;
 #pragma unroll
-      for (int j = 0; j < TQ_MAX_NGSUM; ++j) v[u][j] = (r < nrows && j < nq) ? a.blk_part[r * ncol + TQ_ROWS_GCOL + j] : 0.0f;
+      for (int j = 0; j < TQ_MAX_NGSUM; ++j) v[u][j] = (r < nrows && j < nq) ? tq_row_sum(a, ncol, r, j) : 0.0f;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -336,19 +244,18 @@ __device__ __forceinline__ void tq_rows_column_sums(const tq_cosmos_args& a, int
   }
 }
 
-// Tail of a step whose per-unit kernel wrote such rows (ONE workgroup of 256 threads): per-AOI sites from the rows that
-// overlap the AOI, cross-unit sums in fp64, global sites and the total ELBO.
+// Sums of a step whose per-unit kernel wrote such rows (ONE workgroup of 256 threads): per-AOI sites from the rows that
+// overlap the AOI, cross-unit sums in fp64 -> gsum.  Ends with gsum stored, a workgroup-scope fence and a barrier: the
+// workgroup goes on to the global sites (tq_globals_from_gsum_body) or to its own chain of them (tq_minibatch_kernel).
 // UPR = units per row: TQ_UNIT_BLOCK (tq_unit_rows_kernel) or 16 (the single-launch minibatch step, whose rows hold `mb_upr`
 // = 16 or 20 units: the host's tq_mb_upr)
 template <int UPR_T>
-__device__ __forceinline__ void tq_rows_reduce_globals_body(const tq_cosmos_args& a, double (*s_w)[TQ_MAX_NGSUM], double* s_e,
-                                                            const int mb_upr = 16, const bool with_globals = true) {
-  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
+__device__ __forceinline__ void tq_rows_sums_body(const tq_cosmos_args& a, double (*s_w)[TQ_MAX_NGSUM], const int mb_upr = 16) {
+  const int nq = tq_num_gsum(a), ncol = tq_row_floats(nq);
   const int64_t B = tq_batch_units(a);
   const uint32_t UPR = UPR_T == 16 ? (uint32_t)mb_upr : (uint32_t)tq_rows_upr(a);  // (one instance serves rows of 64 and of 256)
   const int64_t nrows = (B + UPR - 1) / UPR;
   const uint32_t FC = (uint32_t)(a.fb * a.C);  // units of one AOI of the batch
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double acc[TQ_MAX_NGSUM];
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) acc[j] = 0.0;
@@ -368,8 +275,7 @@ __device__ __forceinline__ void tq_rows_reduce_globals_body(const tq_cosmos_args
       if (on) {
         const uint32_t r_lo = (ai * FC) / UPR, r_hi = ((ai + 1) * FC - 1) / UPR;
         for (uint32_t r = r_lo + gl; r <= r_hi; r += 16) {
-          const int slot = (r * UPR) / FC == ai ? 0 : 1;
-          const float* row = a.blk_part + (int64_t)r * ncol + slot * TQ_ROWS_AOICOL + 2 * c;
+          const float* row = tq_row_aoi_pair(a, ncol, r, ai, c, UPR, FC);
           s1 += row[0];
           s2 += row[1];
         }
@@ -397,8 +303,7 @@ __device__ __forceinline__ void tq_rows_reduce_globals_body(const tq_cosmos_args
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const uint32_t r = rb + u;
-          const int slot = (r * UPR) / FC == ai ? 0 : 1;
-          const float* row = a.blk_part + (int64_t)r * ncol + slot * TQ_ROWS_AOICOL + 2 * c;
+          const float* row = tq_row_aoi_pair(a, ncol, r, ai, c, UPR, FC);
           p1[u] = r <= r_hi ? row[0] : 0.0f;
           p2[u] = r <= r_hi ? row[1] : 0.0f;
         }
@@ -417,24 +322,15 @@ __device__ __forceinline__ void tq_rows_reduce_globals_body(const tq_cosmos_args
     for (int64_t r = threadIdx.x; r < nrows; r += 256) {
 #pragma unroll
       for (int j = 0; j < TQ_MAX_NGSUM; ++j)
-        if (j < nq) acc[j] += (double)a.blk_part[r * ncol + TQ_ROWS_GCOL + j];
+        if (j < nq) acc[j] += (double)tq_row_sum(a, ncol, r, j);
     }
   } else {
     tq_rows_column_sums(a, nrows, nq, ncol, acc);
   }
-#pragma unroll
-  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
-    if (j < nq) {
-      const double s = tq_wave_sum_d_lane0(acc[j]);
-      if (lane == 0) s_w[wave][j] = s;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < nq) a.gsum[threadIdx.x] = s_w[0][threadIdx.x] + s_w[1][threadIdx.x] + s_w[2][threadIdx.x] + s_w[3][threadIdx.x];
+  tq_sums_finish(a, acc, s_w);
   __threadfence_block();
   __syncthreads();
   TQ_STAMP_AT(a, TQ_ST_GSUM);
-  if (with_globals) tq_globals_from_gsum_body(a, s_e);
 }
 
 // Sums of a step from the group rows that other workgroups publish (ONE workgroup of 256 threads): WAIT: polls the counter of
@@ -443,14 +339,12 @@ __device__ __forceinline__ void tq_rows_reduce_globals_body(const tq_cosmos_args
 // tq_group_sums_kernel).  Then per-AOI sites from the one or two groups that overlap the AOI and the cross-unit sums -> gsum.
 template <bool WAIT>
 __device__ __forceinline__ bool tq_groups_sums_body(const tq_cosmos_args& a, double (*s_w)[TQ_MAX_NGSUM]) {
-  const int nq = tq_num_gsum(a), ncol = TQ_ROWS_GCOL + nq;
+  const int nq = tq_num_gsum(a), ncol = tq_row_floats(nq);
   const int64_t B = tq_batch_units(a);
   const uint32_t UPR = (uint32_t)tq_rows_upr(a);
   const int64_t nrows = (B + UPR - 1) / UPR;
   const int ngroups = (int)tq_grp_count(B);
-  const float* grows = a.blk_part + tq_grp_base(nrows, ncol);
   const uint32_t FC = (uint32_t)(a.fb * a.C);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __shared__ int s_ok;
   if (threadIdx.x == 0) {
     int ok = 1;
@@ -478,11 +372,10 @@ __device__ __forceinline__ bool tq_groups_sums_body(const tq_cosmos_args& a, dou
   for (int ac = threadIdx.x; ac < nac; ac += 256) {
     const uint32_t ai = (uint32_t)ac / (uint32_t)a.C;
     const int c = ac - (int)ai * a.C;
-    const uint32_t g_lo = (ai * FC) / TQ_GRP_UNITS, g_hi = ((ai + 1) * FC - 1) / TQ_GRP_UNITS;
+    const uint32_t g_lo = tq_grp_of_unit(ai * FC), g_hi = tq_grp_of_unit((ai + 1) * FC - 1);
     float s1 = 0.0f, s2 = 0.0f;
     for (uint32_t g = g_lo; g <= g_hi; ++g) {
-      const uint32_t m = ai - (g * TQ_GRP_UNITS) / FC;
-      const float* p = grows + (int64_t)g * TQ_GGROW + 32 + m * (2 * TQ_MAXQ) + 2 * c;
+      const float* p = tq_grp_aoi_pair(tq_grp_row(a, nrows, ncol, g), tq_grp_aoi_index(g, ai, FC), c);
       s1 += ld(p);
       s2 += ld(p + 1);
     }
@@ -491,30 +384,22 @@ __device__ __forceinline__ bool tq_groups_sums_body(const tq_cosmos_args& a, dou
     acc[TQ_GS_ELBO] += (double)e;
   }
   for (int g = threadIdx.x; g < ngroups; g += 256) {
-    const double* p = (const double*)(grows + (int64_t)g * TQ_GGROW);
+    const double* p = tq_grp_sums(tq_grp_row(a, nrows, ncol, g));
 #pragma unroll
     for (int j = 0; j < TQ_MAX_NGSUM; ++j)
       if (j < nq) acc[j] += ldd(p + j);
   }
   TQ_STAMP_AT(a, TQ_ST_TAIL_SUMS);
-#pragma unroll
-  for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
-    if (j < nq) {
-      const double s = tq_wave_sum_d_lane0(acc[j]);
-      if (lane == 0) s_w[wave][j] = s;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < nq) a.gsum[threadIdx.x] = s_w[0][threadIdx.x] + s_w[1][threadIdx.x] + s_w[2][threadIdx.x] + s_w[3][threadIdx.x];
+  tq_sums_finish(a, acc, s_w);
   return true;
 }
-// ... and the global sites + total ELBO (the tail workgroup of a sampling launch)
-__device__ __forceinline__ bool tq_groups_reduce_globals_body(const tq_cosmos_args& a, double (*s_w)[TQ_MAX_NGSUM], double* s_e) {
+// ... for the tail workgroup of a sampling launch, which waits for them and goes on to the global sites: ends as
+// tq_rows_sums_body does
+__device__ __forceinline__ bool tq_groups_sums_fenced_body(const tq_cosmos_args& a, double (*s_w)[TQ_MAX_NGSUM]) {
   if (!tq_groups_sums_body<true>(a, s_w)) return false;
   __threadfence_block();
   __syncthreads();
   TQ_STAMP_AT(a, TQ_ST_GSUM);
-  tq_globals_from_gsum_body(a, s_e);
   return true;
 }
 
@@ -537,8 +422,9 @@ __global__ __launch_bounds__(256) void tq_group_sums_kernel(const tq_cosmos_args
 __global__ __launch_bounds__(256) void tq_rows_reduce_globals_kernel(const tq_cosmos_args a, const int upr) {
   __shared__ double s_w[4][TQ_MAX_NGSUM];
   __shared__ double s_e[TQ_NGSITES(TQ_MAXQ)];
-  if (upr <= 20) tq_rows_reduce_globals_body<16>(a, s_w, s_e, upr);
-  else tq_rows_reduce_globals_body<TQ_UNIT_BLOCK>(a, s_w, s_e);
+  if (upr <= 20) tq_rows_sums_body<16>(a, s_w, upr);
+  else tq_rows_sums_body<TQ_UNIT_BLOCK>(a, s_w);
+  tq_globals_from_gsum_body(a, s_e);
 }
 
 // Full-batch pipeline (tq_cosmos_step_overlapped): the local guide sampling of step t, with ONE extra workgroup (block (0, 0),
@@ -565,11 +451,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void t
     TQ_STAMP_AT(a, TQ_ST_TAIL_START);
     if (has_prev) {
       const int64_t Bp = tq_batch_units(prev);
-      if (has_prev == TQ_PREV_ROWS) tq_rows_reduce_globals_body<TQ_UNIT_BLOCK>(prev, s_w, s_e);
-      else if (has_prev == TQ_PREV_GROUPS) {
-        if (!tq_groups_reduce_globals_body(prev, s_w, s_e) && threadIdx.x == 0) prev.elbo_out[0] = __builtin_nan("");
-      } else if (has_prev == TQ_PREV_FLAT) tq_reduce_globals_body(prev, (Bp + TQ_UNIT_BLOCK - 1) / TQ_UNIT_BLOCK, Bp, s_w, s_e);
-      else tq_globals_from_gsum_body(prev, s_e);
+      bool have_gsum = true;  // (TQ_PREV_REDUCED: from the start)
+      if (has_prev == TQ_PREV_ROWS) tq_rows_sums_body<TQ_UNIT_BLOCK>(prev, s_w);
+      else if (has_prev == TQ_PREV_GROUPS) have_gsum = tq_groups_sums_fenced_body(prev, s_w);
+      else if (has_prev == TQ_PREV_FLAT) tq_reduce_sums_fenced_body(prev, (Bp + TQ_UNIT_BLOCK - 1) / TQ_UNIT_BLOCK, Bp, s_w);
+      if (have_gsum) tq_globals_from_gsum_body(prev, s_e);
+      else if (threadIdx.x == 0) prev.elbo_out[0] = __builtin_nan("");
       __syncthreads();
       TQ_STAMP_AT(a, TQ_ST_FB_GLOBALS);
       const int64_t total = tq_num_params(prev);

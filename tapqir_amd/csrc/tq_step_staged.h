@@ -153,23 +153,11 @@ __device__ __forceinline__ void tq_globals_from_gsum_body(const tq_cosmos_args& 
   }
 }
 
-// cross-unit sums in fp64 by ONE workgroup of 256 threads (s_w: its shared scratch): per-workgroup rows of the unit
-// kernel + per-AOI ELBO parts -> gsum
-__device__ __forceinline__ void tq_reduce_sums_body(const tq_cosmos_args& a, const int64_t nblk, const int64_t B,
-                                                    double (*s_w)[TQ_MAX_NGSUM]) {
+// the finish of every tail's sums: the per-thread fp64 partial sums `acc` of ONE workgroup of 256 threads (s_w: its shared
+// scratch) -> gsum.  Wave sums, then the four waves' in the order ((w0 + w1) + w2) + w3.
+__device__ __forceinline__ void tq_sums_finish(const tq_cosmos_args& a, const double* acc, double (*s_w)[TQ_MAX_NGSUM]) {
   const int nq = tq_num_gsum(a);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // every thread walks the rows once, carrying all columns (nq <= 15); then shuffle + 4-way LDS sum
-  double acc[TQ_MAX_NGSUM];
-#pragma unroll
-  for (int j = 0; j < TQ_MAX_NGSUM; ++j) acc[j] = 0.0;
-  for (int64_t r = threadIdx.x; r < nblk; r += 256) {
-#pragma unroll
-    for (int j = 0; j < TQ_MAX_NGSUM; ++j)
-      if (j < nq) acc[j] += (double)a.blk_part[r * nq + j];
-  }
-  const int nac = a.nb * a.C;
-  for (int r = threadIdx.x; r < nac; r += 256) acc[TQ_GS_ELBO] += (double)a.aoi_part[2 * B + r];
 #pragma unroll
   for (int j = 0; j < TQ_MAX_NGSUM; ++j) {
     if (j < nq) {
@@ -181,13 +169,32 @@ __device__ __forceinline__ void tq_reduce_sums_body(const tq_cosmos_args& a, con
   if (threadIdx.x < nq) a.gsum[threadIdx.x] = s_w[0][threadIdx.x] + s_w[1][threadIdx.x] + s_w[2][threadIdx.x] + s_w[3][threadIdx.x];
 }
 
-// sums, then the global sites and the total ELBO (single-GPU steps: no all-reduce in between)
-__device__ __forceinline__ void tq_reduce_globals_body(const tq_cosmos_args& a, const int64_t nblk, const int64_t B,
-                                                       double (*s_w)[TQ_MAX_NGSUM], double* s_e, const bool with_globals = true) {
+// cross-unit sums in fp64 by ONE workgroup of 256 threads (s_w: its shared scratch): per-workgroup rows of the unit
+// kernel + per-AOI ELBO parts -> gsum
+__device__ __forceinline__ void tq_reduce_sums_body(const tq_cosmos_args& a, const int64_t nblk, const int64_t B,
+                                                    double (*s_w)[TQ_MAX_NGSUM]) {
+  const int nq = tq_num_gsum(a);
+  // every thread walks the rows once, carrying all columns (nq <= 15); then shuffle + 4-way LDS sum
+  double acc[TQ_MAX_NGSUM];
+#pragma unroll
+  for (int j = 0; j < TQ_MAX_NGSUM; ++j) acc[j] = 0.0;
+  for (int64_t r = threadIdx.x; r < nblk; r += 256) {
+#pragma unroll
+    for (int j = 0; j < TQ_MAX_NGSUM; ++j)
+      if (j < nq) acc[j] += (double)a.blk_part[r * nq + j];
+  }
+  const int nac = a.nb * a.C;
+  for (int r = threadIdx.x; r < nac; r += 256) acc[TQ_GS_ELBO] += (double)a.aoi_part[2 * B + r];
+  tq_sums_finish(a, acc, s_w);
+}
+
+// ... for a workgroup that goes on to read gsum itself (single-GPU steps: no all-reduce between the sums and the global
+// sites): ends with gsum stored, a workgroup-scope fence and a barrier
+__device__ __forceinline__ void tq_reduce_sums_fenced_body(const tq_cosmos_args& a, const int64_t nblk, const int64_t B,
+                                                           double (*s_w)[TQ_MAX_NGSUM]) {
   tq_reduce_sums_body(a, nblk, B, s_w);
   __threadfence_block();
   __syncthreads();
-  if (with_globals) tq_globals_from_gsum_body(a, s_e);
 }
 
 // ---- finish the cross-unit sums in fp64 (single workgroup; sharded runs all-reduce gsum after it) ------------------
@@ -199,7 +206,8 @@ __global__ __launch_bounds__(256) void tq_reduce_kernel(const tq_cosmos_args a, 
 __global__ __launch_bounds__(256) void tq_reduce_globals_kernel(const tq_cosmos_args a, const int64_t nblk, const int64_t B) {
   __shared__ double s_w[4][TQ_MAX_NGSUM];
   __shared__ double s_e[TQ_NGSITES(TQ_MAXQ)];
-  tq_reduce_globals_body(a, nblk, B, s_w, s_e);
+  tq_reduce_sums_fenced_body(a, nblk, B, s_w);
+  tq_globals_from_gsum_body(a, s_e);
 }
 
 // AOI-sharded runs: everything of a step that follows the all-reduce of gsum, in one single-workgroup launch -- global

@@ -15,7 +15,8 @@ gradient it took -- recovered from exp_avg before and after -- for every paramet
 1e-4 |g64| + 16 E32 + R (helpers.assert_gradients_match; E32 = the error of the oracle's own plain-float32 evaluation),
 with exp_avg_sq and the update itself (helpers.check_step).  Measured worst excess over the relative term in units of E32
 (MI355X; budget 16): fused full batch 8.9 (m_probs, K = 1, P = 20), sharded sequence 2.5, single launch 1.9 (16 units per
-workgroup) / 1.5 (20), c1 1.6 on every route, overlapped narrow minibatch 1.1, staged dense Adam 0.7.
+workgroup) / 1.5 (20), c1 1.6 on every route, overlapped narrow minibatch 1.1, staged dense Adam 0.7; with two channels in
+the rows of a full batch (TWO_CHANNELS) fused 2.0, sharded sequence 3.2 (m_probs).
 Reference semantics: tapqir/models/cosmos.py:82-462, tapqir/models/model.py:169-183, 212.
 """
 
@@ -61,13 +62,23 @@ def setup(K, dkw, perturb=0.0, seed=11, **ekw):
     return d, o, eng
 
 
+# The rows layout with two channels: F C = 300 >= 256 units per AOI, 900 units as the 3 x 300 cases, AOI boundaries inside
+# rows, and the two channels of an AOI in different columns of a row's slot.
+TWO_CHANNELS = dict(N=3, F=150, C=2)
+
+
 # ---- (a) the fused pixel + per-unit kernel of full-batch steps ---------------------------------------------------------
 @pytest.mark.parametrize("perturb", [0.0, 0.3], ids=["init", "perturbed"])
-@pytest.mark.parametrize("K,P", [(2, 14), (1, 14), (2, 20), (1, 20)])
-def test_fused_pixel_unit_kernel_against_oracle(K, P, perturb):
-    """3 AOIs x 300 frames = 900 units: 15 tiles of 64, the last with 4 live lanes, AOI boundaries inside tiles."""
-    N, F = 3, 300
-    d, o, eng = setup(K, dict(N=N, F=F, P=P), perturb=perturb)
+@pytest.mark.parametrize("K,P,dkw", [
+    pytest.param(2, 14, dict(N=3, F=300), id="2-14"), pytest.param(1, 14, dict(N=3, F=300), id="1-14"),
+    pytest.param(2, 20, dict(N=3, F=300), id="2-20"), pytest.param(1, 20, dict(N=3, F=300), id="1-20"),
+    pytest.param(2, 14, TWO_CHANNELS, id="2-14-two_channels")])
+def test_fused_pixel_unit_kernel_against_oracle(K, P, dkw, perturb):
+    """3 AOIs x 300 frames = 900 units: 15 tiles of 64, the last with 4 live lanes, AOI boundaries inside tiles.
+    two_channels: 3 AOIs x 150 frames x 2 channels, the same 900 units with the channels alternating lane by lane (the
+    channel column of a row's AOI slots)."""
+    N, F = dkw["N"], dkw["F"]
+    d, o, eng = setup(K, dict(dkw, P=P), perturb=perturb)
     eng.il_min_units = 1
     eng.fuse_unit = True
     assert eng._fusable()
@@ -261,13 +272,15 @@ class _Done:
 
 
 @pytest.mark.parametrize("handle", [False, True], ids=["blocking", "in_flight"])
-@pytest.mark.parametrize("fuse", [False, True], ids=["two_launches", "fused"])
-def test_sharded_launch_sequence_against_oracle(handle, fuse):
+@pytest.mark.parametrize("fuse,dkw", [
+    pytest.param(False, dict(N=3, F=300), id="two_launches"), pytest.param(True, dict(N=3, F=300), id="fused"),
+    pytest.param(False, TWO_CHANNELS, id="two_launches_two_channels"), pytest.param(True, TWO_CHANNELS, id="fused_two_channels")])
+def test_sharded_launch_sequence_against_oracle(handle, fuse, dkw):
     """tq_cosmos_elbo_grads with the rows layout (pixel_mode 2 = fused pixel + per-unit launch, or pixel + tq_unit_rows_kernel)
     -> tq_group_sums_kernel -> all-reduce (one rank: identity) -> tq_cosmos_tail_reduced, inside the split sampling of the
     next step when the collective is left in flight."""
-    N, F = 3, 300
-    d, o, eng = setup(2, dict(N=N, F=F), perturb=0.3)
+    N, F = dkw["N"], dkw["F"]
+    d, o, eng = setup(2, dkw, perturb=0.3)
     eng.il_min_units = 1
     eng.fuse_unit = fuse
     replay(eng, o, N, F, steps=4, allreduce=(lambda g: _Done()) if handle else (lambda g: None))

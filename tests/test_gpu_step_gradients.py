@@ -13,7 +13,7 @@ of one geometry: the full-batch step changes family (fused, two launches with ro
 batches, the flat layout) at a fixed geometry below, and the minibatches carry the tails of minibatches.  Each sequence
 asserts which of its launches found a pending tail.
 Measured worst excess over the relative term in units of E32 (MI355X; budget 16): sharded in flight 2.5 (m_probs), full-batch
-families 1.9 (m_probs), full / minibatch in turn 1.4 (b_beta), 20 units per workgroup 1.1 (K = 1) / 0.8 (K = 3 hist), flat
+families 1.9 (m_probs; 3.1 with two channels), full / minibatch in turn 1.4 (b_beta), 20 units per workgroup 1.1 (K = 1) / 0.8 (K = 3 hist), flat
 layout 0.7 (b_loc).
 Reference semantics: tapqir/models/cosmos.py:82-462, tapqir/models/model.py:169-183.
 """
@@ -22,7 +22,7 @@ import pytest
 import torch
 
 from helpers import gradient_report, lr0_sequence
-from test_gpu_production_kernels import _Done, setup
+from test_gpu_production_kernels import TWO_CHANNELS, _Done, setup
 
 from tapqir_amd import _lib
 
@@ -84,13 +84,15 @@ def test_full_batch_and_minibatch_steps_in_turn():
     assert pend == [True] * 6 and found == [False, False, True, False, False, False]
 
 
-def test_full_batch_families_carry_each_other_s_tails():
-    """N = 3, F = 300, whole-batch steps of one geometry, so that every launch carries the tail of the step before, each time
-    of another family: fused -> two launches with rows of 256 (the fused step's rows tail inside
-    tq_sample_locals_tail_kernel) -> the single launch of small batches (rows or groups inside tq_minibatch_kernel) -> two
-    launches (tq_cosmos_tail of the rows-of-16 tail before the overlapped step) -> single launch -> fused."""
-    N, F = 3, 300
-    d, o, eng = setup(2, dict(N=N, F=F), perturb=0.3)
+@pytest.mark.parametrize("dkw", [dict(N=3, F=300), TWO_CHANNELS], ids=["3x300", "3x150x2"])
+def test_full_batch_families_carry_each_other_s_tails(dkw):
+    """N = 3, F = 300 (and N = 3, F = 150, C = 2: the channel columns of the rows), whole-batch steps of one geometry, so
+    that every launch carries the tail of the step before, each time of another family: fused -> two launches with rows of
+    256 (the fused step's rows tail inside tq_sample_locals_tail_kernel) -> the single launch of small batches (rows or
+    groups inside tq_minibatch_kernel) -> two launches (tq_cosmos_tail of the rows-of-16 tail before the overlapped step) ->
+    single launch -> fused."""
+    N, F = dkw["N"], dkw["F"]
+    d, o, eng = setup(2, dkw, perturb=0.3)
 
     def fused(e):
         e.il_min_units, e.fuse_unit = 1, True
@@ -114,7 +116,7 @@ def test_full_batch_families_carry_each_other_s_tails():
             dict(pre=one_launch, post=route("one_launch")), dict(pre=two_launches, post=route("overlapped")),
             dict(pre=one_launch, post=route("one_launch")), dict(pre=fused, post=route("overlapped"))]
     found = _carried(eng, plan)
-    pend = lr0_sequence(eng, o, plan, "full-batch families")
+    pend = lr0_sequence(eng, o, plan, "full-batch families" + (" C = 2" if dkw.get("C") else ""))
     assert pend == [True] * 6 and found == [False] + [True] * 5
 
 
