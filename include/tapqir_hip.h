@@ -590,6 +590,47 @@ typedef struct {
 int tq_dwell_fit(const tq_dwell_fit_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Two-state rate estimates (`tapqir_amd rates`; tapqir/utils/imscroll.py:199-246, 278-317).
+ *
+ * tq_rates_count replaces the sums of association_rate / dissociation_rate over Bernoulli(p).sample() rasters
+ * (imscroll.py:199-246 inside posterior_estimate / sample_and_bootstrap, 278-317) without storing the S x N x F raster.
+ * Row (s, n) is the row of tq_dwell_sample: frame f is z = (u < p[n, f]) with u the f-th uniform of Philox stream
+ * (seed, s, site 0xA01, n), so one seed gives both entry points the same rasters.  Over its F - 1 frame pairs
+ *   counts[s, n, 0] = n01 = sum (1 - z_f) z_{f+1}      counts[s, n, 1] = n0 = sum (1 - z_f)
+ *   counts[s, n, 2] = n10 = sum z_f (1 - z_{f+1})      counts[s, n, 3] = n1 = sum z_f = F - 1 - n0
+ * (F = 1: four zeros).  A row is 16 bytes, 16-byte aligned, written by one store.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const float* p;              /* (N, F) p(z = 1) of each AOI-frame, in [0, 1] */
+  int32_t* counts;             /* (S, N, TQ_RATES_COLS) out; 16-byte aligned */
+  int32_t N, F, S;
+  uint64_t seed;
+} tq_rates_count_args;
+#define TQ_RATES_COLS 4
+
+int tq_rates_count(const tq_rates_count_args* a, void* stream);
+
+/* tq_rates_estimate sums the rows of every sample and divides:
+ *   totals[s, j] = sum_{i < N} counts[s, a(s, i), j]   (int64)
+ *   estimand[s, 0] = kon = totals[s, 0] / totals[s, 1],  estimand[s, 1] = koff = totals[s, 2] / totals[s, 3]
+ * as IEEE double division: a zero denominator gives NaN or inf, as the reference's division does.
+ *   resample = 0: a(s, i) = i, every AOI once -- posterior_estimate(Bernoulli(p), association_rate) (imscroll.py:278-293).
+ *   resample = 1: a(s, i) = (uint32_t)(((uint64_t)w * N) >> 32), w the first 32-bit word of Philox stream
+ *     (seed, s, site 0xA02, i): N rows with replacement, a fresh draw per sample -- the 2-D analogue of
+ *     sample_and_bootstrap (imscroll.py:296-317).  An index is off the uniform law by at most N / 2^32.
+ * One wave per sample. */
+typedef struct {
+  const int32_t* counts;       /* (S, N, TQ_RATES_COLS) of tq_rates_count; 16-byte aligned */
+  int64_t* totals;             /* (S, TQ_RATES_COLS) out */
+  double* estimand;            /* (S, 2) out: kon, koff */
+  int32_t N, S;
+  int32_t resample;            /* 0: pooled; 1: bootstrap over AOIs */
+  uint64_t seed;               /* resample = 1 only */
+} tq_rates_estimate_args;
+
+int tq_rates_estimate(const tq_rates_estimate_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame
  * decode of GlimpseDataset.__getitem__ (168-186: big-endian int16 + 2^15) and the offset-region value counts

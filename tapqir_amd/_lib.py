@@ -214,6 +214,7 @@ EXPORTS = [
     "tq_cosmos_pu_slots", "tq_cosmos_pu_split_auto", "tq_cosmos_pu_scratch_bytes",
     "tq_cosmos_probs", "tq_glimpse_extract", "tq_ksmogn_rsample", "tq_snr_chi2", "tq_ttfb_sample", "tq_ttfb_fit",
     "tq_dwell_sample", "tq_dwell_fit", "tq_credible_intervals",
+    "tq_rates_count", "tq_rates_estimate",  # argument structs and prototypes: tapqir_amd/_lib_rates.py
 ]
 
 _lib = None

@@ -1,13 +1,23 @@
-// tq_dpp.h -- device-only helpers: cross-lane sums over the 16 lanes of a DPP row, float2 values for the packed
-// v_pk_{fma,mul,add}_f32 instructions.
+// tq_dpp.h -- device-only helpers: cross-lane sums over the 16 lanes of a DPP row (float, or an integer of 4 or 8 bytes),
+// float2 values for the packed v_pk_{fma,mul,add}_f32 instructions.
 #pragma once
 #include <hip/hip_runtime.h>
 
-template <int CTRL>
-__device__ __forceinline__ float tq_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+// lane permutation CTRL of a 4-byte value, or of both halves of an 8-byte one
+template <int CTRL, class T>
+__device__ __forceinline__ T tq_dpp(T v) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "tq_dpp moves 4- or 8-byte values");
+  if constexpr (sizeof(T) == 4) {
+    return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+  } else {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xF, 0xF, true);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, true);
+    return __builtin_bit_cast(T, ((unsigned long long)hi << 32) | lo);
+  }
 }
-__device__ __forceinline__ float tq_group_sum16(float v) {
+template <class T>
+__device__ __forceinline__ T tq_group_sum16(T v) {
   // sum over the 16 lanes of a unit = one DPP row: data-parallel-primitive adds, no LDS crossbar.
   v += tq_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
   v += tq_dpp<0x4E>(v);   // quad_perm [2,3,0,1]   -> quad sums
@@ -17,8 +27,8 @@ __device__ __forceinline__ float tq_group_sum16(float v) {
 }
 
 // sum over the LANES (16 or 64) lanes of a unit, in every lane: the DPP row sum, then -- a unit per wave -- the four rows
-template <int LANES>
-__device__ __forceinline__ float tq_group_sum(float v) {
+template <int LANES, class T>
+__device__ __forceinline__ T tq_group_sum(T v) {
   v = tq_group_sum16(v);
   if (LANES == 64) {
     v += __shfl_xor(v, 16, 64);

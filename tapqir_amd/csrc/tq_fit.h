@@ -49,4 +49,6 @@ __device__ __forceinline__ float tq_fit_wave_sum(float v) {
   v = tq_group_sum<64>(v);
   return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
+// the same butterfly on 64-bit integers (exact in any order): the sum in every lane
+__device__ __forceinline__ int64_t tq_fit_wave_sum(int64_t v) { return tq_group_sum<64>(v); }
 #endif

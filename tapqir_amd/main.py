@@ -297,8 +297,8 @@ def stats(
 
 
 def _kinetics_inputs(command, model, cuda, progress_bar):
-    """The checks `ttfb` and `dwelltime` share, in the order the exit-status tests rely on (``--cpu`` fails before any file
-    is read).  Returns the loaded model, the mask of the on-target AOIs and the progress bar."""
+    """The checks `ttfb`, `dwelltime` and `rates` share, in the order the exit-status tests rely on (``--cpu`` fails before
+    any file is read).  Returns the loaded model, the mask of the on-target AOIs and the progress bar."""
     import torch
 
     from tapqir_amd.exceptions import TapqirFileNotFoundError
@@ -570,6 +570,72 @@ def dwelltime(
                 _dwell_plot(cd, m.name, c, kind, map_dt, A_mean, k_mean, t_max, logger)
     except HipExtensionError:
         logger.exception("dwelltime failed: it needs an AMD GPU (--cuda) and the built HIP library")
+        raise typer.Exit(1)
+
+
+@app.command()
+def rates(
+    model: avail_models = typer.Option("cosmos", help="Tapqir model"),
+    cuda: bool = typer.Option(_default("cuda"), "--cuda/--cpu", help="Run computations on GPU or CPU", show_default=False),
+    num_samples: int = typer.Option(1000, "--num-samples", "-n", min=1, help="Number of posterior samples"),
+    ci: float = typer.Option(0.95, "--ci", help="Probability mass of the interval, in (0, 1)"),
+    bootstrap: bool = typer.Option(True, "--bootstrap/--no-bootstrap", help="Resample the AOIs of every posterior sample"),
+    seed: Optional[int] = typer.Option(None, "--seed", help="Seed of the posterior samples (default: the channel index)"),
+    no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
+    progress_bar=None,
+):
+    """
+    Two-state rate estimates (tapqir/utils/imscroll.py:199-317): kon = P(0 -> 1) and koff = P(1 -> 0) per frame, pooled
+    over the on-target AOIs of every posterior sample of the z raster (resampled with replacement unless
+    ``--no-bootstrap``), with mean and percentile interval over the samples and the rates of the MAP raster.
+    Needs ``data.tpqr`` and ``<model>_params.tpqr`` of a cosmos fit.
+
+    A sample whose rate has a zero denominator is left out of that rate's mean and interval (the count is logged), and a
+    rate that no sample determines is skipped with a warning.
+    """
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.exceptions import HipExtensionError
+    from tapqir_amd.utils.mle_analysis import rates_estimate, rates_sample, rates_summary
+
+    cd = DEFAULTS["cd"]
+    logger = logging.getLogger("tapqir")
+    # like -K of dwelltime: checked after the model and before --cpu
+    if model.value == "cosmos" and not 0.0 < ci < 1.0:
+        logger.error(f"rates: --ci must be between 0 and 1, got {ci}")
+        raise typer.Exit(1)
+    m, mask, progress_bar = _kinetics_inputs("rates", model, cuda, progress_bar)
+    data = m.data
+    z_map = m.params["z_map"][: data.N] if "z_map" in m.params else None
+    pct = f"{ci * 100:g}%"
+    try:
+        dev = torch.device("cuda")
+        for c in range(data.C):
+            logger.info(f"Channel #{c} ({data.channels[c]})")
+            p_bound = m.params["z_probs"][: data.N, :, c, 1][mask].float().to(dev)
+            chan_seed = c if seed is None else seed
+            estimate = rates_estimate(rates_sample(p_bound, num_samples, seed=chan_seed), bootstrap=bootstrap,
+                                      seed=chan_seed)
+            summary = rates_summary(estimate, ci)
+            map_rate = {"kon": float("nan"), "koff": float("nan")}
+            if z_map is not None:  # the MAP raster through the same count kernel: p = 0 never binds, p = 1 always does
+                map_p = z_map[:, :, c][mask].float().to(dev)
+                map_est = rates_estimate(rates_sample(map_p, 1, seed=chan_seed))
+                map_rate = {rate: map_est[rate][0].item() for rate in map_rate}
+            results = pd.DataFrame(columns=["Mean", f"{pct} LL", f"{pct} UL", "MAP"], dtype=float)
+            for rate in ("kon", "koff"):
+                row = summary[rate]
+                if row["left_out"] == num_samples:
+                    logger.warning(f"rates: no posterior sample determines {rate} (zero denominators): it is skipped")
+                elif row["left_out"]:
+                    logger.info(f"{row['left_out']} of {num_samples} posterior samples have a zero {rate} denominator "
+                                f"and are left out of its mean and interval")
+                results.loc[rate] = [row["mean"], row["ll"], row["ul"], map_rate[rate]]
+            results.to_csv(cd / f"{m.name}_rates-channel{c}.csv")
+            logger.info(f"Saved rate estimates in {m.name}_rates-channel{c}.csv file")
+    except HipExtensionError:
+        logger.exception("rates failed: it needs an AMD GPU (--cuda) and the built HIP library")
         raise typer.Exit(1)
 
 

@@ -7,6 +7,13 @@ For binary labels ``z`` (..., F) the result is the index of the first frame with
     ttfb = sum_{f=1}^{F-1} f z_f prod_{f' < f} (1 - z_f') + F prod_{f'} (1 - z_f')
 
 For probabilities ``q(z_f = 1)`` the same expression is the expectation of that index under independent frames.
+
+Two-state rates of binary rasters and their resampling intervals (imscroll.py:199-317): ``association_rate`` and
+``dissociation_rate`` are the per-frame transition frequencies kon = #(0 -> 1) / #(z_f = 0) and koff = #(1 -> 0) /
+#(z_f = 1) over the frame pairs of the last axis, pooled over the axis before it; ``bootstrap``, ``posterior_estimate``
+and ``sample_and_bootstrap`` are host loops over an arbitrary estimator that return the percentile interval of its
+values.  For the two rate estimators on posterior rasters the device computes the same estimands without the rasters
+(``tapqir_amd.utils.mle_analysis.rates_sample`` / ``rates_estimate``, the ``rates`` command).
 """
 
 from functools import singledispatch
@@ -115,3 +122,120 @@ def bound_dwell_times(intervals):
 def unbound_dwell_times(intervals):
     """Interior unbound dwell times (``low_or_high == 0``) per posterior sample, zero-padded."""
     return _dwell_times(intervals, 0)
+
+
+# ---- two-state rates and resampling intervals (tapqir/utils/imscroll.py:199-317) --------------------------------------
+def _pairs(labels):
+    """(z_f, z_{f+1}) over the frame pairs of the last axis."""
+    return labels[..., :-1], labels[..., 1:]
+
+
+@singledispatch
+def association_rate(labels):
+    r"""On-rate of binary labels (..., N, F) under a two-state model: the share of unbound frames followed by a bound one,
+    pooled over the last two axes."""
+    raise NotImplementedError
+
+
+@association_rate.register(np.ndarray)
+def _(labels):
+    now, nxt = _pairs(labels)
+    return ((1 - now) * nxt).sum((-2, -1)) / (1 - now).sum((-2, -1))
+
+
+@association_rate.register(torch.Tensor)
+def _(labels):
+    now, nxt = _pairs(labels.float())
+    return ((1 - now) * nxt).sum((-2, -1)) / (1 - now).sum((-2, -1))
+
+
+@singledispatch
+def dissociation_rate(labels):
+    r"""Off-rate of binary labels (..., N, F) under a two-state model: the share of bound frames followed by an unbound
+    one, pooled over the last two axes."""
+    raise NotImplementedError
+
+
+@dissociation_rate.register(np.ndarray)
+def _(labels):
+    now, nxt = _pairs(labels)
+    return (now * (1 - nxt)).sum((-2, -1)) / now.sum((-2, -1))
+
+
+@dissociation_rate.register(torch.Tensor)
+def _(labels):
+    now, nxt = _pairs(labels.float())
+    return (now * (1 - nxt)).sum((-2, -1)) / now.sum((-2, -1))
+
+
+def _percentile_interval(estimand, probs):
+    """pyro.ops.stats.pi: the linear-interpolation quantiles at (1 - probs) / 2 and (1 + probs) / 2."""
+    from tapqir_amd.utils.stats import quantile
+
+    estimand = torch.as_tensor(estimand)
+    return quantile(estimand, (1 - probs) / 2), quantile(estimand, (1 + probs) / 2)
+
+
+@singledispatch
+def bootstrap(samples, estimator, repetitions=1000, probs=0.68):
+    r"""Percentile interval of ``estimator`` over ``repetitions`` resamples of ``samples`` (along its first axis, with
+    replacement, each as long as ``samples``)."""
+    raise NotImplementedError
+
+
+@bootstrap.register(np.ndarray)
+def _(samples, estimator, repetitions=1000, probs=0.68):
+    estimand = np.zeros((repetitions,))
+    for i in range(repetitions):
+        estimand[i] = estimator(samples[np.random.randint(0, len(samples), size=len(samples))])
+    ll, ul = _percentile_interval(estimand, probs)
+    return ll.item(), ul.item()
+
+
+@bootstrap.register(torch.Tensor)
+def _(samples, estimator, repetitions=1000, probs=0.68):
+    estimand = torch.zeros(repetitions)
+    for i in range(repetitions):
+        estimand[i] = estimator(samples[torch.randint(0, len(samples), (len(samples),), device=samples.device)])
+    return _percentile_interval(estimand, probs)
+
+
+@singledispatch
+def posterior_estimate(dist, estimator, repetitions=1000, probs=0.68):
+    r"""Percentile interval of ``estimator`` over ``repetitions`` draws of ``dist``, each used whole.
+
+    With ``dist = Bernoulli(p_bound)`` and ``association_rate`` / ``dissociation_rate`` the device computes the same
+    estimands without the rasters: ``rates_estimate(rates_sample(p_bound, repetitions))`` of
+    ``tapqir_amd.utils.mle_analysis``."""
+    raise NotImplementedError
+
+
+@posterior_estimate.register(torch.distributions.Distribution)
+def _(dist, estimator, repetitions=1000, probs=0.68):
+    samples = dist.sample((repetitions,))
+    estimand = torch.zeros(repetitions)
+    for i in range(repetitions):
+        estimand[i] = estimator(samples[i])
+    return _percentile_interval(estimand, probs)
+
+
+@singledispatch
+def sample_and_bootstrap(dist, estimator, preprocess=None, repetitions=1000, probs=0.68):
+    r"""Percentile interval of ``estimator`` over ``repetitions`` rounds of: draw ``dist`` once, ``preprocess`` the draw
+    if given, resample it along its first axis with replacement.
+
+    With ``dist = Bernoulli(p_bound)`` and the two rate estimators, the device form is
+    ``rates_estimate(rates_sample(p_bound, repetitions), bootstrap=True)`` of ``tapqir_amd.utils.mle_analysis``: the rows
+    (AOIs) of every raster are resampled."""
+    raise NotImplementedError
+
+
+@sample_and_bootstrap.register(torch.distributions.Distribution)
+def _(dist, estimator, preprocess=None, repetitions=1000, probs=0.68):
+    estimand = torch.zeros(repetitions)
+    for i in range(repetitions):
+        samples = dist.sample()
+        if preprocess is not None:
+            samples = preprocess(samples)
+        estimand[i] = estimator(samples[np.random.randint(0, len(samples), size=len(samples))])
+    return _percentile_interval(estimand, probs)

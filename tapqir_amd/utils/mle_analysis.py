@@ -1,6 +1,6 @@
 """
-Kinetics analysis on the HIP device (tapqir/utils/mle_analysis.py and the ``ttfb`` / ``dwelltime`` commands,
-tapqir/main.py:926-1384):
+Kinetics analysis on the HIP device (tapqir/utils/mle_analysis.py, the ``ttfb`` / ``dwelltime`` commands,
+tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199-317):
 
 * ``ttfb_sample``: posterior samples of the first-binding frame of each AOI (``tq_ttfb_sample``);
 * ``ttfb_fit``: one maximum-likelihood fit of the censored two-exponential model (Friedman & Gelles 2015) per sample,
@@ -9,7 +9,12 @@ tapqir/main.py:926-1384):
 * ``dwell_sample`` / ``dwell_intervals``: interior dwell-time histograms and the interval table of posterior rasters
   drawn and walked on the device (``count_intervals(z_sample)`` of the ``dwelltime`` command, ``tq_dwell_sample``);
 * ``dwell_fit``: one maximum-likelihood fit of the K-exponential mixture per sample, ``train(exp_model, exp_guide, lr,
-  n_steps, data, K)`` of the reference (``tq_dwell_fit``).
+  n_steps, data, K)`` of the reference (``tq_dwell_fit``);
+* ``rates_sample`` / ``rates_estimate`` / ``rates_summary``: the transition counts of posterior rasters (the rasters of
+  ``dwell_sample`` at the same seed), their pooled or AOI-resampled totals with kon = P(0 -> 1) and koff = P(1 -> 0) per
+  frame, and mean and percentile interval of those -- ``posterior_estimate`` / ``sample_and_bootstrap`` of
+  tapqir/utils/imscroll.py:278-317 with ``association_rate`` / ``dissociation_rate`` (``tq_rates_count``,
+  ``tq_rates_estimate``).
 
 There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
 """
@@ -18,7 +23,7 @@ import ctypes as C
 
 import torch
 
-from tapqir_amd import _lib
+from tapqir_amd import _lib, _lib_rates
 from tapqir_amd.exceptions import HipExtensionError
 
 ADAM_BETAS = (0.9, 0.999)
@@ -274,3 +279,62 @@ def dwell_fit(data, K=3, lr=5e-3, n_steps=10000, chunk=1000, progress_bar=None, 
     _run_chunks(lambda step0, n: dwell_fit_steps(state, csr, K, lr, step0, n, loss, stage_lds), n_steps, chunk,
                 progress_bar)
     return {"k": state[:, :K].exp(), "A": torch.softmax(state[:, K:2 * K], dim=1), "loss": loss}
+
+
+# ---- two-state rates (`rates`, tapqir/utils/imscroll.py:199-317) -------------------------------------------------------
+def rates_sample(p_bound, num_samples, seed=0):
+    """Transition counts of ``num_samples`` posterior rasters of each AOI, drawn and counted on the device.
+
+    ``p_bound`` (N, F): q(z = 1) of each AOI-frame.  Returns ``counts`` (num_samples, N, 4) int32 on the device: over
+    the F - 1 frame pairs of row (s, n), the number of 0 -> 1 steps, of z_f = 0, of 1 -> 0 steps and of z_f = 1.  The
+    rows are those of ``dwell_sample(p_bound, num_samples, seed)``; nothing of size S x N x F is stored."""
+    p, N, F, seed = _sampler_inputs("rates_sample", p_bound, num_samples, seed)
+    S = int(num_samples)
+    counts = torch.empty(S, N, _lib_rates.RATES_COLS, dtype=torch.int32, device=p.device)
+    a = _lib_rates.RatesCountArgs(p=_lib.ptr(p), counts=_lib.ptr(counts), N=N, F=F, S=S, seed=seed)
+    _lib.check(_lib_rates.lib().tq_rates_count(C.byref(a), _stream(p.device)), "tq_rates_count")
+    return counts
+
+
+def rates_estimate(counts, bootstrap=False, seed=0):
+    """kon and koff of every posterior sample from the row counts of ``rates_sample``.
+
+    ``bootstrap=False`` pools every AOI once (``posterior_estimate(Bernoulli(p), association_rate)`` of the reference);
+    ``bootstrap=True`` sums N rows drawn with replacement, a fresh draw per sample from ``seed`` (the 2-D analogue of
+    ``sample_and_bootstrap``).  Returns ``{"kon", "koff"}``, (S,) float64, and ``"totals"`` (S, 4) int64, on the device.
+    A zero denominator gives NaN or inf, which stay in the arrays (``rates_summary`` leaves them out)."""
+    if not isinstance(counts, torch.Tensor) or counts.device.type != "cuda":
+        raise HipExtensionError("rates_estimate runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    if counts.ndim != 3 or counts.shape[2] != _lib_rates.RATES_COLS or counts.dtype != torch.int32 or 0 in counts.shape:
+        raise ValueError(f"rates_estimate: counts must be int32 (S, N, {_lib_rates.RATES_COLS}) with S, N >= 1, got "
+                         f"{counts.dtype} {tuple(counts.shape)}")
+    counts = counts.contiguous()
+    S, N = counts.shape[:2]
+    totals = torch.empty(S, _lib_rates.RATES_COLS, dtype=torch.int64, device=counts.device)
+    est = torch.empty(S, 2, dtype=torch.float64, device=counts.device)
+    a = _lib_rates.RatesEstimateArgs(counts=_lib.ptr(counts), totals=_lib.ptr(totals), estimand=_lib.ptr(est), N=N, S=S,
+                                     resample=1 if bootstrap else 0, seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib_rates.lib().tq_rates_estimate(C.byref(a), _stream(counts.device)), "tq_rates_estimate")
+    return {"kon": est[:, 0], "koff": est[:, 1], "totals": totals}
+
+
+def rates_summary(estimate, probs=0.68):
+    """Mean and percentile interval (pyro's ``pi(estimand, probs)``: the linear-interpolation quantiles at
+    (1 - probs) / 2 and (1 + probs) / 2) of each rate over its finite estimands.
+
+    Returns ``{"kon": {...}, "koff": {...}}`` with the floats ``"mean"``, ``"ll"``, ``"ul"`` and the int ``"left_out"``:
+    the number of non-finite estimands (zero denominators) that the three leave out.  A rate without a finite estimand
+    has NaN for all three."""
+    from tapqir_amd.utils.stats import quantile
+
+    out = {}
+    for rate in ("kon", "koff"):
+        x = estimate[rate].double()
+        x = x[torch.isfinite(x)]
+        left_out = estimate[rate].numel() - x.numel()
+        if x.numel() == 0:
+            out[rate] = {"mean": float("nan"), "ll": float("nan"), "ul": float("nan"), "left_out": left_out}
+            continue
+        out[rate] = {"mean": x.mean().item(), "ll": quantile(x, (1 - probs) / 2).item(),
+                     "ul": quantile(x, (1 + probs) / 2).item(), "left_out": left_out}
+    return out
