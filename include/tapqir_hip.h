@@ -631,6 +631,80 @@ typedef struct {
 int tq_rates_estimate(const tq_rates_estimate_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Two-state hidden Markov smoothing of a fit's z posterior (`tapqir_amd smooth`; the post-hoc counterpart of z_probs /
+ * z_sample of tapqir/models/hmm.py:628-633, 658-667).  One row is one on-target AOI of one channel: p[f] = the fit's
+ * p(z = 1) of frame f, clamped into [TQ_SMOOTH_PMIN, 1 - TQ_SMOOTH_PMIN], and `prior` = the fit's prior pi in (0, 1).
+ *   evidence  l_f = ((1 - p_f) / (1 - pi), p_f / pi)
+ *   chain     A = [[1 - kon, kon], [koff, 1 - koff]],  rho = (1 - pi0, pi0),  theta = (kon, koff, pi0): 3 doubles in
+ *             device memory, each read clamped into [TQ_SMOOTH_RMIN, 1 - TQ_SMOOTH_RMIN]
+ * Every entry point returns TQ_ERR_ARG, before anything touches the device, for a NULL required pointer, N, F or S < 1,
+ * F > TQ_SMOOTH_MAX_F, S > 65535 * 64, prior outside (0, 1) or counts not 16-byte aligned.
+ *
+ * tq_smooth_estep: scaled forward-backward of every row at theta.
+ *   filt[n, f]  = a_f(1),  a_0 ~ rho o l_0,  a_f ~ (a_{f-1} A) o l_f  with normalisers c_f
+ *   gamma[n, f] = p(z_f = 1 | all frames)  (gamma is also the kernel's scratch for a_f(0) between its two sweeps)
+ *   rows[n]     = E n01, E n0, E n10, E n1 (the sums of the pair marginals xi_f(i, j), f < F - 1, in the column order of
+ *                 tq_rates_count; F = 1: four zeros), loglik = sum_f log c_f, gamma_0(1)
+ * ------------------------------------------------------------------------------------- */
+#define TQ_SMOOTH_COLS 6
+#define TQ_SMOOTH_PMIN 1e-6
+#define TQ_SMOOTH_RMIN 1e-9
+#define TQ_SMOOTH_MAX_F 65536
+typedef struct {
+  const float* p;              /* (N, F) p(z = 1) of the fit */
+  const double* theta;         /* (3) kon, koff, pi0; device memory */
+  double* filt;                /* (N, F) out */
+  double* gamma;               /* (N, F) out */
+  double* rows;                /* (N, TQ_SMOOTH_COLS) out */
+  int32_t N, F;
+  double prior;
+} tq_smooth_estep_args;
+
+int tq_smooth_estep(const tq_smooth_estep_args* a, void* stream);
+
+/* tq_smooth_mstep: sums the N rows of an E-step in a fixed order (bit-reproducible), stores the total loglik into
+ * trace[it] and overwrites theta:  kon = sum E n01 / sum E n0,  koff = sum E n10 / sum E n1,  pi0 = mean gamma_0(1),
+ * each clamped into [TQ_SMOOTH_RMIN, 1 - TQ_SMOOTH_RMIN]; a 0 / 0 quotient keeps the previous value.  One workgroup.
+ * An EM run of I iterations is I pairs of launches on one stream; nothing in it needs the host. */
+typedef struct {
+  const double* rows;          /* (N, TQ_SMOOTH_COLS) of tq_smooth_estep */
+  double* theta;               /* (3) in / out; device memory */
+  double* trace;               /* trace[it] out: the total loglik at the theta the rows were computed with */
+  int32_t N, it;
+} tq_smooth_mstep_args;
+
+int tq_smooth_mstep(const tq_smooth_mstep_args* a, void* stream);
+
+/* tq_smooth_viterbi: the MAP path of every row under the same l, A and rho, in the log domain; a tie takes state 0.
+ * back: scratch of 2 bits per frame, ((F + 15) / 16) * N 32-bit words. */
+typedef struct {
+  const float* p;              /* (N, F) */
+  const double* theta;         /* (3); device memory */
+  uint32_t* back;              /* scratch, ((F + 15) / 16) * N words */
+  uint8_t* path;               /* (N, F) out: 0 / 1 */
+  int32_t N, F;
+  double prior;
+} tq_smooth_viterbi_args;
+
+int tq_smooth_viterbi(const tq_smooth_viterbi_args* a, void* stream);
+
+/* tq_smooth_count: S posterior rasters of every row by forward filtering, backward sampling, and their transition counts.
+ * With u_j the j-th uniform of Philox stream (seed, step = s, site 0xA03, elem = n), compared as a double:
+ *   z_{F-1} = (u_0 < filt[F-1]),   z_f = (u_{F-1-f} < q_f(z_{f+1})),
+ *   q_f(j) = a_f(1) A[1][j] / (a_f(1) A[1][j] + a_f(0) A[0][j]),  a_f = (1 - filt[f], filt[f]).
+ * counts has the layout of tq_rates_count, so tq_rates_estimate consumes it unchanged. */
+typedef struct {
+  const double* filt;          /* (N, F) of tq_smooth_estep */
+  const double* theta;         /* (3); device memory */
+  int32_t* counts;             /* (S, N, TQ_RATES_COLS) out; 16-byte aligned */
+  uint8_t* raster;             /* (S, N, F) out: 0 / 1; or NULL */
+  int32_t N, F, S;
+  uint64_t seed;
+} tq_smooth_count_args;
+
+int tq_smooth_count(const tq_smooth_count_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame
  * decode of GlimpseDataset.__getitem__ (168-186: big-endian int16 + 2^15) and the offset-region value counts

@@ -215,6 +215,7 @@ EXPORTS = [
     "tq_cosmos_probs", "tq_glimpse_extract", "tq_ksmogn_rsample", "tq_snr_chi2", "tq_ttfb_sample", "tq_ttfb_fit",
     "tq_dwell_sample", "tq_dwell_fit", "tq_credible_intervals",
     "tq_rates_count", "tq_rates_estimate",  # argument structs and prototypes: tapqir_amd/_lib_rates.py
+    "tq_smooth_estep", "tq_smooth_mstep", "tq_smooth_viterbi", "tq_smooth_count",  # ... tapqir_amd/_lib_smooth.py
 ]
 
 _lib = None

@@ -297,8 +297,8 @@ def stats(
 
 
 def _kinetics_inputs(command, model, cuda, progress_bar):
-    """The checks `ttfb`, `dwelltime` and `rates` share, in the order the exit-status tests rely on (``--cpu`` fails before
-    any file is read).  Returns the loaded model, the mask of the on-target AOIs and the progress bar."""
+    """The checks `ttfb`, `dwelltime`, `rates` and `smooth` share, in the order the exit-status tests rely on (``--cpu``
+    fails before any file is read).  Returns the loaded model, the mask of the on-target AOIs and the progress bar."""
     import torch
 
     from tapqir_amd.exceptions import TapqirFileNotFoundError
@@ -636,6 +636,87 @@ def rates(
             logger.info(f"Saved rate estimates in {m.name}_rates-channel{c}.csv file")
     except HipExtensionError:
         logger.exception("rates failed: it needs an AMD GPU (--cuda) and the built HIP library")
+        raise typer.Exit(1)
+
+
+@app.command()
+def smooth(
+    model: avail_models = typer.Option("cosmos", help="Tapqir model"),
+    cuda: bool = typer.Option(_default("cuda"), "--cuda/--cpu", help="Run computations on GPU or CPU", show_default=False),
+    num_iter: int = typer.Option(200, "--num-iter", min=1, help="Largest number of EM iterations"),
+    tol: float = typer.Option(1e-9, "--tol", help="Stop once an iteration gains at most tol * |log evidence|"),
+    num_samples: int = typer.Option(1000, "--num-samples", "-n", min=1, help="Number of posterior rasters"),
+    ci: float = typer.Option(0.95, "--ci", help="Probability mass of the interval, in (0, 1)"),
+    bootstrap: bool = typer.Option(True, "--bootstrap/--no-bootstrap", help="Resample the AOIs of every posterior raster"),
+    seed: Optional[int] = typer.Option(None, "--seed", help="Seed of the posterior rasters (default: the channel index)"),
+    no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
+    progress_bar=None,
+):
+    """
+    Two-state hidden Markov smoothing of the fitted z posterior (the post-hoc counterpart of the reference's experimental
+    cosmos+hmm model): the fit's ``z_probs`` are the evidence of a chain over the frames whose kon,
+    koff and initial probability are fitted by EM over the on-target AOIs.  Writes the smoothed p(z = 1) and the Viterbi
+    path to ``<model>_smooth.tpqr`` and, per channel, the rates to ``<model>_smooth-channel<c>.csv``: the EM value, mean and
+    percentile interval over posterior rasters of the chain (resampled over AOIs unless ``--no-bootstrap``) and the rates
+    of the Viterbi raster.  Needs ``data.tpqr`` and ``<model>_params.tpqr`` of a cosmos fit.
+    """
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.exceptions import HipExtensionError
+    from tapqir_amd.utils.mle_analysis import (rates_estimate, rates_sample, rates_summary, smooth_fit, smooth_sample,
+                                               smooth_viterbi)
+
+    cd = DEFAULTS["cd"]
+    logger = logging.getLogger("tapqir")
+    if model.value == "cosmos" and not 0.0 < ci < 1.0:  # as in rates: after the model, before --cpu
+        logger.error(f"smooth: --ci must be between 0 and 1, got {ci}")
+        raise typer.Exit(1)
+    m, mask, progress_bar = _kinetics_inputs("smooth", model, cuda, progress_bar)
+    data = m.data
+    pct = f"{ci * 100:g}%"
+    z_raw = m.params["z_probs"][: data.N, :, :, 1].float()  # (N, F, C)
+    out = {"z_probs": z_raw.clone(), "z_map": z_raw > 0.5,
+           "log_evidence": torch.full((data.N, data.C), float("nan"), dtype=torch.float64),
+           "theta": torch.zeros(data.C, 3, dtype=torch.float64), "prior": torch.zeros(data.C, dtype=torch.float64),
+           "loglik_trace": [], "mask": mask}
+    try:
+        dev = torch.device("cuda")
+        for c in range(data.C):
+            logger.info(f"Channel #{c} ({data.channels[c]})")
+            prior = float(torch.as_tensor(m.params["pi"]["Mean"]).reshape(-1, 2)[c, 1])
+            p = z_raw[:, :, c][mask].to(dev)
+            chan_seed = c if seed is None else seed
+            fit = smooth_fit(p, prior, num_iter=num_iter, tol=tol, progress_bar=progress_bar)
+            theta = fit["theta"]
+            kon, koff, pi0 = theta.tolist()
+            logger.info(f"EM: kon = {kon:.6g}, koff = {koff:.6g}, pi0 = {pi0:.6g}, log evidence = "
+                        f"{fit['rows'][:, 4].sum().item():.6f} after {fit['iterations']} iterations")
+            if not fit["converged"]:
+                logger.warning(f"smooth: the EM did not converge to --tol {tol:g} within {fit['iterations']} iterations")
+            path = smooth_viterbi(p, theta, prior)
+            summary = rates_summary(rates_estimate(smooth_sample(fit["filt"], theta, num_samples, seed=chan_seed),
+                                                   bootstrap=bootstrap, seed=chan_seed), ci)
+            map_est = rates_estimate(rates_sample(path.float(), 1, seed=chan_seed))  # p in {0, 1} is drawn as itself
+            results = pd.DataFrame(columns=["EM", "Mean", f"{pct} LL", f"{pct} UL", "MAP"], dtype=float)
+            for rate, em in (("kon", kon), ("koff", koff)):
+                row = summary[rate]
+                if row["left_out"]:
+                    logger.info(f"{row['left_out']} of {num_samples} posterior rasters have a zero {rate} denominator "
+                                f"and are left out of its mean and interval")
+                results.loc[rate] = [em, row["mean"], row["ll"], row["ul"], map_est[rate][0].item()]
+            results.to_csv(cd / f"{m.name}_smooth-channel{c}.csv")
+            logger.info(f"Saved smoothed rate estimates in {m.name}_smooth-channel{c}.csv file")
+            out["z_probs"][:, :, c][mask] = fit["gamma"].float().cpu()
+            out["z_map"][:, :, c][mask] = path.bool().cpu()
+            out["log_evidence"][:, c][mask] = fit["rows"][:, 4].cpu()
+            out["theta"][c] = theta.cpu()
+            out["prior"][c] = prior
+            out["loglik_trace"].append(fit["trace"].cpu())
+        torch.save(out, cd / f"{m.name}_smooth.tpqr")
+        logger.info(f"Saved the smoothed posterior in {m.name}_smooth.tpqr file")
+    except HipExtensionError:
+        logger.exception("smooth failed: it needs an AMD GPU (--cuda) and the built HIP library")
         raise typer.Exit(1)
 
 

@@ -14,7 +14,11 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
   ``dwell_sample`` at the same seed), their pooled or AOI-resampled totals with kon = P(0 -> 1) and koff = P(1 -> 0) per
   frame, and mean and percentile interval of those -- ``posterior_estimate`` / ``sample_and_bootstrap`` of
   tapqir/utils/imscroll.py:278-317 with ``association_rate`` / ``dissociation_rate`` (``tq_rates_count``,
-  ``tq_rates_estimate``).
+  ``tq_rates_estimate``);
+* ``smooth_estep`` / ``smooth_fit`` / ``smooth_viterbi`` / ``smooth_sample``: a two-state hidden Markov chain over the
+  frames with the fit's ``z_probs`` as evidence -- forward-backward marginals and expected transition counts, the EM fit
+  of kon, koff and the initial probability, the MAP path, and posterior rasters by backward sampling, counted like those
+  of ``rates_sample`` (``tq_smooth_estep``, ``tq_smooth_mstep``, ``tq_smooth_viterbi``, ``tq_smooth_count``).
 
 There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
 """
@@ -23,7 +27,7 @@ import ctypes as C
 
 import torch
 
-from tapqir_amd import _lib, _lib_rates
+from tapqir_amd import _lib, _lib_rates, _lib_smooth
 from tapqir_amd.exceptions import HipExtensionError
 
 ADAM_BETAS = (0.9, 0.999)
@@ -338,3 +342,133 @@ def rates_summary(estimate, probs=0.68):
         out[rate] = {"mean": x.mean().item(), "ll": quantile(x, (1 - probs) / 2).item(),
                      "ul": quantile(x, (1 + probs) / 2).item(), "left_out": left_out}
     return out
+
+
+# ---- two-state hidden Markov smoothing (`smooth`) --------------------------------------------------
+def _smooth_inputs(who, p, theta, prior):
+    """``p`` through ``_sampler_inputs``, ``theta`` as 3 doubles on p's device, the prior as a float in (0, 1)."""
+    p, N, F, _ = _sampler_inputs(who, p, 1, 0)
+    if F > _lib_smooth.SMOOTH_MAX_F:
+        raise ValueError(f"{who}: at most {_lib_smooth.SMOOTH_MAX_F} frames, got {F}")
+    if not isinstance(theta, torch.Tensor) or theta.device != p.device or theta.dtype != torch.float64 or theta.numel() != 3:
+        raise ValueError(f"{who}: theta must be 3 float64 values (kon, koff, pi0) on the device of p")
+    prior = float(prior)
+    if not 0.0 < prior < 1.0:
+        raise ValueError(f"{who}: prior must lie in (0, 1), got {prior}")
+    return p, N, F, theta.contiguous(), prior
+
+
+def _smooth_estep(p, N, F, theta, prior, out):
+    a = _lib_smooth.SmoothEstepArgs(p=_lib.ptr(p), theta=_lib.ptr(theta), filt=_lib.ptr(out["filt"]),
+                                    gamma=_lib.ptr(out["gamma"]), rows=_lib.ptr(out["rows"]), N=N, F=F, prior=prior)
+    _lib.check(_lib_smooth.lib().tq_smooth_estep(C.byref(a), _stream(p.device)), "tq_smooth_estep")
+    return out
+
+
+def _smooth_buffers(N, F, device):
+    return {"filt": torch.empty(N, F, dtype=torch.float64, device=device),
+            "gamma": torch.empty(N, F, dtype=torch.float64, device=device),
+            "rows": torch.empty(N, _lib_smooth.SMOOTH_COLS, dtype=torch.float64, device=device)}
+
+
+def smooth_estep(p, theta, prior):
+    """Forward-backward of every row of ``p`` (N, F), the fit's p(z = 1), under the chain ``theta`` = (kon, koff, pi0)
+    (3 float64 on the device) with the fit's ``prior`` divided out of ``p``.
+
+    Returns ``{"filt", "gamma"}``, (N, F) float64: the filtered and the smoothed p(z = 1), and ``"rows"`` (N, 6): the
+    expected counts E n01, E n0, E n10, E n1 of the row's frame pairs (the columns of ``rates_sample``), its
+    log-evidence and gamma_0(1)."""
+    p, N, F, theta, prior = _smooth_inputs("smooth_estep", p, theta, prior)
+    return _smooth_estep(p, N, F, theta, prior, _smooth_buffers(N, F, p.device))
+
+
+def smooth_mstep(rows, theta, trace, it=0):
+    """One launch of ``tq_smooth_mstep``: ``theta`` (3 float64, in place) from the summed ``rows`` of an E-step, and the
+    total log-evidence of those rows into ``trace[it]``.  Returns ``theta``."""
+    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
+        raise HipExtensionError("smooth_mstep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    if (rows.ndim != 2 or rows.shape[1] != _lib_smooth.SMOOTH_COLS or rows.shape[0] < 1 or rows.dtype != torch.float64
+            or not rows.is_contiguous()):
+        raise ValueError(f"smooth_mstep: rows must be contiguous float64 (N, {_lib_smooth.SMOOTH_COLS}), N >= 1")
+    for name, x, n in (("theta", theta, 3), ("trace", trace, int(it) + 1)):
+        if (not isinstance(x, torch.Tensor) or x.device != rows.device or x.dtype != torch.float64 or x.ndim != 1
+                or x.numel() < n or not x.is_contiguous() or it < 0):
+            raise ValueError(f"smooth_mstep: {name} must be a float64 vector of at least {n} values on the device of rows")
+    a = _lib_smooth.SmoothMstepArgs(rows=_lib.ptr(rows), theta=_lib.ptr(theta), trace=_lib.ptr(trace), N=rows.shape[0],
+                                    it=int(it))
+    _lib.check(_lib_smooth.lib().tq_smooth_mstep(C.byref(a), _stream(rows.device)), "tq_smooth_mstep")
+    return theta
+
+
+def smooth_fit(p, prior, kon=0.5, koff=0.5, init=0.5, num_iter=200, tol=1e-9, chunk=50, progress_bar=None):
+    """EM fit of the chain (kon, koff, pi0 from ``kon``, ``koff``, ``init``) to the rows of ``p`` (N, F).
+
+    The iterations are launched in chunks of ``chunk`` pairs of E-step and M-step, with no host synchronisation inside
+    a chunk; after each chunk the trace of the log-evidence is read, and the run stops once an iteration has gained
+    at most ``tol * |loglik|`` over the one before.  One more E-step at the final theta gives the outputs.
+
+    Returns ``theta`` (3,), ``gamma``, ``filt`` (N, F), ``rows`` (N, 6), ``trace`` (iterations,) -- trace[i] is the
+    log-evidence at the theta after i iterations -- all float64 on the device, and the Python values ``iterations``
+    (the number run: whole chunks) and ``converged``."""
+    num_iter = int(num_iter)
+    theta = torch.tensor([kon, koff, init], dtype=torch.float64)
+    if num_iter < 1 or not bool(((theta > 0) & (theta < 1)).all()):
+        raise ValueError("smooth_fit: num_iter must be positive and kon, koff, init lie in (0, 1)")
+    if not isinstance(p, torch.Tensor) or p.device.type != "cuda":
+        raise HipExtensionError("smooth_fit runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    theta = theta.to(p.device)
+    p, N, F, theta, prior = _smooth_inputs("smooth_fit", p, theta, prior)
+    out = _smooth_buffers(N, F, p.device)
+    trace = torch.full((num_iter,), float("nan"), dtype=torch.float64, device=p.device)
+    state = {"iterations": 0, "converged": False}
+
+    def em_steps(step0, n):
+        if state["converged"]:
+            return
+        for it in range(step0, step0 + n):
+            _smooth_estep(p, N, F, theta, prior, out)
+            smooth_mstep(out["rows"], theta, trace, it)
+        state["iterations"] = step0 + n
+        ll = trace[: step0 + n].cpu()
+        gain = ll[1:] - ll[:-1]
+        state["converged"] = bool((gain <= tol * ll[1:].abs()).any())
+
+    _run_chunks(em_steps, num_iter, chunk, progress_bar)
+    _smooth_estep(p, N, F, theta, prior, out)
+    return {"theta": theta, **out, "trace": trace[: state["iterations"]], **state}
+
+
+def smooth_viterbi(p, theta, prior):
+    """MAP path of every row of ``p`` (N, F) under the chain ``theta`` and the evidence of ``smooth_estep``: (N, F) uint8
+    on the device.  A tie takes state 0."""
+    p, N, F, theta, prior = _smooth_inputs("smooth_viterbi", p, theta, prior)
+    back = torch.empty(((F + 15) // 16) * N, dtype=torch.int32, device=p.device)
+    path = torch.empty(N, F, dtype=torch.uint8, device=p.device)
+    a = _lib_smooth.SmoothViterbiArgs(p=_lib.ptr(p), theta=_lib.ptr(theta), back=_lib.ptr(back), path=_lib.ptr(path), N=N,
+                                      F=F, prior=prior)
+    _lib.check(_lib_smooth.lib().tq_smooth_viterbi(C.byref(a), _stream(p.device)), "tq_smooth_viterbi")
+    return path
+
+
+def smooth_sample(filt, theta, num_samples, seed=0, raster=False):
+    """Transition counts of ``num_samples`` posterior rasters of the chain, drawn by backward sampling from ``filt``
+    (N, F) of ``smooth_estep`` at ``theta``.
+
+    Returns ``counts`` (num_samples, N, 4) int32 in the layout of ``rates_sample`` (``rates_estimate`` takes them as they
+    are); with ``raster=True`` returns ``(counts, z)`` with the rasters ``z`` (num_samples, N, F) uint8."""
+    if not isinstance(filt, torch.Tensor) or filt.device.type != "cuda":
+        raise HipExtensionError("smooth_sample runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    S = int(num_samples)
+    if filt.ndim != 2 or 0 in filt.shape or filt.dtype != torch.float64 or S < 1 or filt.shape[1] > _lib_smooth.SMOOTH_MAX_F:
+        raise ValueError(f"smooth_sample: filt must be float64 (N, F) with N >= 1, 1 <= F <= {_lib_smooth.SMOOTH_MAX_F}, "
+                         f"and num_samples >= 1, got {filt.dtype} {tuple(filt.shape)}")
+    if not isinstance(theta, torch.Tensor) or theta.device != filt.device or theta.dtype != torch.float64 or theta.numel() != 3:
+        raise ValueError("smooth_sample: theta must be 3 float64 values (kon, koff, pi0) on the device of filt")
+    filt, theta = filt.contiguous(), theta.contiguous()
+    N, F = filt.shape
+    counts = torch.empty(S, N, _lib_rates.RATES_COLS, dtype=torch.int32, device=filt.device)
+    z = torch.empty(S, N, F, dtype=torch.uint8, device=filt.device) if raster else None
+    a = _lib_smooth.SmoothCountArgs(filt=_lib.ptr(filt), theta=_lib.ptr(theta), counts=_lib.ptr(counts), raster=_lib.ptr(z),
+                                    N=N, F=F, S=S, seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib_smooth.lib().tq_smooth_count(C.byref(a), _stream(filt.device)), "tq_smooth_count")
+    return (counts, z) if raster else counts
