@@ -704,6 +704,39 @@ typedef struct {
 
 int tq_smooth_count(const tq_smooth_count_args* a, void* stream);
 
+/* tq_smooth_dwell: the rasters of tq_smooth_count walked into dwell-time intervals and first-binding frames as they are
+ * drawn (`dwelltime --smooth`, `ttfb --smooth`); no raster is stored.
+ * Row (s, n) is, bit for bit, the row tq_smooth_count draws for the same filt, theta and seed: the same Philox stream
+ * (seed, step = s, site 0xA03, elem = n), the same order of draws (u_0 for frame F - 1, then downwards), the same
+ * thresholds q_f, clamps of theta and double compare -- so one seed gives `smooth`, `dwelltime --smooth` and
+ * `ttfb --smooth` the same rasters.  The outputs are those of tq_dwell_sample for such a raster:
+ *   mode TQ_DWELL_COUNT: counts[s, n] = number of intervals of the row; every interior interval (low_or_high 0 / 1) of
+ *     dwell time d adds 1 to hist_unbound[s, d] / hist_bound[s, d] (the caller zeroes both histograms); and, when tau is
+ *     not NULL, tau[s, n] = the smallest f with z_f = 1, or F if there is none (time_to_first_binding,
+ *     tapqir/utils/imscroll.py:187-196; what tq_ttfb_sample writes).
+ *   mode TQ_DWELL_EMIT: the same draws again; the table `intervals` of tq_dwell_sample's EMIT, (sample, AOI) row-major and
+ *     ascending in start_frame within a row.  The row is walked from its last frame, so the k-th run it closes is written
+ *     at offsets[s, n] + counts[s, n] - 1 - k; a position outside [offsets[s, n], min(offsets[s, n] + counts[s, n], total))
+ *     is dropped, never written.  total = 0 launches nothing.
+ * TQ_ERR_ARG, before anything touches the device, for a NULL required pointer of the mode, N, F or S < 1,
+ * F > TQ_SMOOTH_MAX_F, S > 65535 * 64, total < 0 or an unknown mode. */
+typedef struct {
+  const double* filt;          /* (N, F) of tq_smooth_estep */
+  const double* theta;         /* (3); device memory */
+  int32_t* counts;             /* (S, N) out (COUNT), in (EMIT) */
+  int32_t* hist_bound;         /* (S, F) in/out (COUNT): interior bound runs by dwell time */
+  int32_t* hist_unbound;       /* (S, F) in/out (COUNT): interior unbound runs by dwell time */
+  float* tau;                  /* (S, N) out (COUNT): integer-valued first-binding frames in [0, F]; or NULL */
+  const int64_t* offsets;      /* (S, N) in (EMIT): exclusive scan of counts */
+  int32_t* intervals;          /* (TQ_DWELL_COLS, total) out (EMIT) */
+  int64_t total;               /* EMIT: number of intervals (the column stride) */
+  int32_t N, F, S;
+  int32_t mode;                /* TQ_DWELL_COUNT or TQ_DWELL_EMIT */
+  uint64_t seed;
+} tq_smooth_dwell_args;
+
+int tq_smooth_dwell(const tq_smooth_dwell_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame

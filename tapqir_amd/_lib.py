@@ -216,6 +216,7 @@ EXPORTS = [
     "tq_dwell_sample", "tq_dwell_fit", "tq_credible_intervals",
     "tq_rates_count", "tq_rates_estimate",  # argument structs and prototypes: tapqir_amd/_lib_rates.py
     "tq_smooth_estep", "tq_smooth_mstep", "tq_smooth_viterbi", "tq_smooth_count",  # ... tapqir_amd/_lib_smooth.py
+    "tq_smooth_dwell",
 ]
 
 _lib = None

@@ -1,8 +1,8 @@
 """
 ctypes mirrors of the hidden-Markov smoothing entry points of ``libtapqir_hip.so`` (``tq_smooth_estep`` /
-``tq_smooth_mstep`` / ``tq_smooth_viterbi`` / ``tq_smooth_count``, include/tapqir_hip.h).  Import this module as a module
-(``from tapqir_amd import _lib_smooth``); ``lib()`` returns the library of ``tapqir_amd._lib.load()`` with the four
-prototypes bound.
+``tq_smooth_mstep`` / ``tq_smooth_viterbi`` / ``tq_smooth_count`` / ``tq_smooth_dwell``, include/tapqir_hip.h).  Import
+this module as a module (``from tapqir_amd import _lib_smooth``); ``lib()`` returns the library of
+``tapqir_amd._lib.load()`` with the five prototypes bound.
 """
 
 import ctypes as C
@@ -46,10 +46,22 @@ class SmoothCountArgs(C.Structure):
     ]
 
 
+class SmoothDwellArgs(C.Structure):
+    """``tq_smooth_dwell_args`` (include/tapqir_hip.h); ``mode`` is ``_lib.DWELL_COUNT`` or ``_lib.DWELL_EMIT``."""
+
+    _fields_ = [
+        ("filt", C.c_void_p), ("theta", C.c_void_p), ("counts", C.c_void_p), ("hist_bound", C.c_void_p),
+        ("hist_unbound", C.c_void_p), ("tau", C.c_void_p), ("offsets", C.c_void_p), ("intervals", C.c_void_p),
+        ("total", C.c_int64), ("N", C.c_int32), ("F", C.c_int32), ("S", C.c_int32), ("mode", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
 def bind(lib):
-    """Set the prototypes of the four entry points on a loaded library; returns it."""
+    """Set the prototypes of the five entry points on a loaded library; returns it."""
     for name, args in (("tq_smooth_estep", SmoothEstepArgs), ("tq_smooth_mstep", SmoothMstepArgs),
-                       ("tq_smooth_viterbi", SmoothViterbiArgs), ("tq_smooth_count", SmoothCountArgs)):
+                       ("tq_smooth_viterbi", SmoothViterbiArgs), ("tq_smooth_count", SmoothCountArgs),
+                       ("tq_smooth_dwell", SmoothDwellArgs)):
         fn = getattr(lib, name)
         fn.argtypes = [C.POINTER(args), C.c_void_p]
         fn.restype = C.c_int

@@ -3,7 +3,8 @@
 //   * the chain and the evidence of a frame, products of 2x2 matrices kept in range by powers of two;
 //   * what one lane of the E-step does with its chunk of frames: the chunk product, the forward sweep from the chunk's
 //     exclusive prefix, the backward sweep from its exclusive suffix with the pair marginals;
-//   * the M-step of the summed rows, the Viterbi path of a row, and the backward sampler's thresholds and row counter.
+//   * the M-step of the summed rows, the Viterbi path of a row, and the backward sampler's thresholds and row counter;
+//   * the interval walker of a row drawn backwards, with the table position and the table row of a run it closes.
 // Nothing here subtracts nearly equal quantities: 1 - p, 1 - kon, 1 - koff, 1 - pi and 1 - pi0 are formed once, from
 // their clamped arguments, and a_f(0) is kept beside a_f(1) instead of being recovered from it.
 // The __global__ wrappers are in tq_smooth.hip; the test suite runs the same bodies from a g++ build.
@@ -11,6 +12,7 @@
 #include <math.h>
 
 #include "../../include/tapqir_hip.h"
+#include "tq_dwell.h"
 #include "tq_rates.h"
 
 #define TQ_SMOOTH_SITE 0xA03u        // Philox site id of the backward sampler: stream (seed, step = s, site, elem = n)
@@ -238,4 +240,61 @@ TQ_HD void tq_smooth_back_step(TqRatesRow& r, int z) {
   r.n01 += (1 - z) & r.prev;
   r.n10 += z & (1 - r.prev);
   r.prev = z;
+}
+
+// ---- backward interval walker -----------------------------------------------------------------------------------------
+// The mirror of TqDwellWalk (tq_dwell.h) for a row that is visited from frame F - 1 down to 0: the open run is known by
+// its last frame.  The run open at F - 1 is the last run of the record, the one still open after frame 0 the first;
+// low_or_high is tq_dwell_code's.  Runs close in descending order of start_frame.
+struct TqSmoothWalk {
+  int cur, stop, last;
+};
+
+TQ_HD void tq_smooth_walk_begin(TqSmoothWalk& w, int F, int z) {  // z of frame F - 1
+  w.cur = z;
+  w.stop = F - 1;
+  w.last = 1;
+}
+
+// frame f <= F - 2 with label z: returns 1 and fills `out` when it closes the run that began at f + 1
+TQ_HD int tq_smooth_walk_step(TqSmoothWalk& w, int f, int z, TqDwellInterval& out) {
+  if (z == w.cur) return 0;
+  out.start = f + 1;
+  out.stop = w.stop;
+  out.z = w.cur;
+  out.low_or_high = tq_dwell_code(w.cur, 0, w.last);
+  w.cur = z;
+  w.stop = f;
+  w.last = 0;
+  return 1;
+}
+
+// the run still open after frame 0 (F = 1: the only run, first and last)
+TQ_HD void tq_smooth_walk_finish(const TqSmoothWalk& w, TqDwellInterval& out) {
+  out.start = 0;
+  out.stop = w.stop;
+  out.z = w.cur;
+  out.low_or_high = tq_dwell_code(w.cur, 1, w.last);
+}
+
+// Position in the interval table of the k-th run that row (s, n) closes (k = 0 is its last run): the table is ascending in
+// start_frame within a row, so the run goes to o + count - 1 - k, o the row's offset.  -1 for a position outside
+// [o, min(o + count, total)): a caller whose offsets or counts disagree with the draws gets a short table, never a stray
+// write.
+TQ_HD int64_t tq_smooth_emit_slot(int64_t o, int count, int k, int64_t total) {
+  const int64_t pos = o + count - 1 - k;
+  const int64_t end = o + count < total ? o + count : total;
+  return o >= 0 && pos >= o && pos < end ? pos : -1;
+}
+
+// one row of the table (TQ_DWELL_COLS, total): the columns of tq_dwell_sample's EMIT
+TQ_HD void tq_smooth_emit_row(int32_t* intervals, int64_t total, int64_t pos, int s, int n, const TqDwellInterval& v) {
+  int32_t* col = intervals + pos;
+  col[0] = s;
+  col[total] = n;
+  col[2 * total] = v.start;
+  col[3 * total] = v.stop;
+  col[4 * total] = v.stop + 1 - v.start;
+  col[5 * total] = v.low_or_high;
+  col[6 * total] = v.z;
 }

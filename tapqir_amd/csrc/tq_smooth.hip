@@ -1,6 +1,7 @@
 // tq_smooth.hip -- two-state hidden Markov smoothing on the device (bodies in tq_smooth.h): the E-step as a chunked
 // forward-backward with a wave scan of 2x2 products, the M-step of the summed rows, the Viterbi path and the backward
-// sampler with its transition counts.
+// sampler with its transition counts, and the same sampler walked into dwell-time intervals and
+// first-binding frames.
 #include <hip/hip_runtime.h>
 
 #include "tq_dpp.h"
@@ -201,4 +202,100 @@ extern "C" int tq_smooth_count(const tq_smooth_count_args* a, void* stream) {
   }
   hipLaunchKernelGGL(tq_smooth_count_kernel, grid, dim3(64), 0, (hipStream_t)stream, *a);
   return tq_launch_status("tq_smooth_count_kernel");
+}
+
+// ---- backward sampler walked into intervals: the geometry, the staging and the draws of tq_smooth_count_kernel ----------
+// Row (s, n) is the raster that kernel draws; here it is walked, as it is drawn, into runs of equal labels
+// (TqSmoothWalk), and no raster is stored.  EMIT = false: per-row interval counts, the interior-run histograms (integer
+// atomics: order-free, so deterministic) and the first-binding frame; EMIT = true: the same draws again, the k-th run a
+// row closes written at tq_smooth_emit_slot, so that the table is the one tq_dwell_sample's EMIT writes for that raster.
+template <bool EMIT>
+__global__ __launch_bounds__(64) void tq_smooth_dwell_kernel(const tq_smooth_dwell_args a) {
+  __shared__ double qbuf[2][64];
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const int s = blockIdx.y * 64 + lane;
+  const bool active = s < a.S;
+  const int F = a.F;
+  const double* fr = a.filt + (int64_t)n * F;
+  const int64_t row = (int64_t)s * a.N + n;
+  const TqSmoothModel m = tq_smooth_model(a.theta, 0.5);  // the prior is already in filt
+  int32_t* hb = EMIT ? nullptr : a.hist_bound + (int64_t)s * F;
+  int32_t* hu = EMIT ? nullptr : a.hist_unbound + (int64_t)s * F;
+  const int64_t total = a.total;
+  int64_t o = 0;
+  int count = 0;
+  if (EMIT && active) {
+    o = a.offsets[row];
+    count = a.counts[row];
+  }
+
+  TqPhilox ph;
+  tq_smooth_stream(&ph, a.seed, s, n);
+  TqSmoothWalk w = {0, 0, 0};
+  TqDwellInterval iv;
+  int closed = 0;  // runs closed so far
+  int tau = F;     // the last frame seen bound: the first bound frame of the row
+
+  auto emit = [&](const TqDwellInterval& v) {
+    if (EMIT) {
+      const int64_t pos = tq_smooth_emit_slot(o, count, closed, total);
+      if (pos >= 0) tq_smooth_emit_row(a.intervals, total, pos, s, n, v);
+    } else if (v.low_or_high == 0 || v.low_or_high == 1) {
+      atomicAdd((v.z ? hb : hu) + (v.stop + 1 - v.start), 1);
+    }
+    ++closed;
+  };
+
+  for (int f0 = (F - 1) & ~63; f0 >= 0; f0 -= 64) {
+    const int cnt = min(64, F - f0);
+    if (lane < cnt) tq_smooth_thresholds(m, fr[f0 + lane], f0 + lane == F - 1, qbuf[0][lane], qbuf[1][lane]);
+    __syncthreads();
+    if (active) {
+      for (int j = cnt - 1; j >= 0; --j) {
+        const int f = f0 + j;
+        const bool last = f == F - 1;
+        const int z = tq_smooth_label(&ph, qbuf[last ? 0 : w.cur][j]);
+        if (last) tq_smooth_walk_begin(w, F, z);
+        else if (tq_smooth_walk_step(w, f, z, iv)) emit(iv);
+        if (!EMIT && z) tau = f;
+      }
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  tq_smooth_walk_finish(w, iv);
+  emit(iv);
+  if (!EMIT) {
+    a.counts[row] = closed;
+    if (a.tau) a.tau[row] = (float)tau;
+  }
+}
+
+extern "C" int tq_smooth_dwell(const tq_smooth_dwell_args* a, void* stream) {
+  if (!a || !a->filt || !a->theta || !a->counts) {
+    tq_set_error("tq_smooth_dwell: NULL required pointer");
+    return TQ_ERR_ARG;
+  }
+  if (a->mode == TQ_DWELL_COUNT ? (!a->hist_bound || !a->hist_unbound)
+                                : (a->mode != TQ_DWELL_EMIT || !a->offsets || (a->total > 0 && !a->intervals))) {
+    tq_set_error(a->mode == TQ_DWELL_COUNT || a->mode == TQ_DWELL_EMIT ? "tq_smooth_dwell: NULL required pointer"
+                                                                       : "tq_smooth_dwell: unknown mode");
+    return TQ_ERR_ARG;
+  }
+  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F || a->total < 0) {
+    tq_set_error("tq_smooth_dwell: N, F and S must be positive, F at most 65536 and total non-negative");
+    return TQ_ERR_ARG;
+  }
+  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
+  if (grid.y > 65535u) {
+    tq_set_error("tq_smooth_dwell: S too large");
+    return TQ_ERR_ARG;
+  }
+  if (a->mode == TQ_DWELL_COUNT) {
+    hipLaunchKernelGGL(tq_smooth_dwell_kernel<false>, grid, dim3(64), 0, (hipStream_t)stream, *a);
+  } else {
+    if (a->total == 0) return TQ_OK;
+    hipLaunchKernelGGL(tq_smooth_dwell_kernel<true>, grid, dim3(64), 0, (hipStream_t)stream, *a);
+  }
+  return tq_launch_status("tq_smooth_dwell_kernel");
 }

@@ -337,6 +337,37 @@ def _kinetics_inputs(command, model, cuda, progress_bar):
     return m, mask, progress_bar
 
 
+def _smoothed_posterior(command, cd, name, mask, logger):
+    """``<name>_smooth.tpqr`` for the ``--smooth`` switch of `ttfb` and `dwelltime`: the chain of every channel (``theta``,
+    ``prior``), the smoothed ``z_probs`` and the Viterbi path ``z_map``.  Exits with status 1 when the file is missing or
+    was written for another selection of AOIs."""
+    import torch
+
+    from tapqir_amd.utils.safe_load import load_tpqr
+
+    path = cd / f"{name}_smooth.tpqr"
+    if not path.is_file():
+        logger.error(f"{command} --smooth needs {path.name}: run `smooth` first")
+        raise typer.Exit(1)
+    sm = load_tpqr(path)
+    if sm["mask"].shape != mask.shape or not torch.equal(sm["mask"].bool(), mask):
+        logger.error(f"{command} --smooth: {path.name} was written for another mask of on-target AOIs than the data "
+                     f"has now: run `smooth` again")
+        raise typer.Exit(1)
+    return sm
+
+
+def _smoothed_filter(sm, c, p_bound):
+    """The filtered marginals of channel ``c`` under the chain of ``smooth``: one E-step on the fit's ``p_bound`` at the
+    stored theta and prior.  Returns (filt, theta) on the device of ``p_bound``: the inputs of the backward sampler."""
+    import torch
+
+    from tapqir_amd.utils.mle_analysis import smooth_estep
+
+    theta = sm["theta"][c].to(device=p_bound.device, dtype=torch.float64)
+    return smooth_estep(p_bound, theta, float(sm["prior"][c]))["filt"], theta
+
+
 def _summary_table(rows):
     """Mean and 95% highest-density interval of each ``(label, values)`` pair, one row per label."""
     import pandas as pd
@@ -364,8 +395,9 @@ def _pyplot():
     return mpl, plt
 
 
-def _ttfb_plots(cd, name, c, z_masked, sdx, r_type, Tmax, fb_mean, fb_ll, fb_ul, best_fit, logger):
-    """Rastergram and cumulative-fraction plot of one channel (main.py:988-1005, 1108-1147)."""
+def _ttfb_plots(cd, stem, c, z_masked, sdx, r_type, Tmax, fb_mean, fb_ll, fb_ul, best_fit, logger):
+    """Rastergram and cumulative-fraction plot of one channel (main.py:988-1005, 1108-1147); ``stem`` is the start of the
+    file names, ``<model>_ttfb`` or ``<model>_ttfb-smooth``."""
     mpl, plt = _pyplot()
     if plt is None:
         logger.warning("matplotlib is not available: the ttfb plots are not drawn")
@@ -375,9 +407,9 @@ def _ttfb_plots(cd, name, c, z_masked, sdx, r_type, Tmax, fb_mean, fb_ll, fb_ul,
     ax.set_xlabel("Time (frame)")
     ax.set_ylabel("AOI")
     ax.set_title(f"Channel {c}")
-    plt.savefig(cd / f"{name}_ttfb-rastergram-channel{c}.png", dpi=600)
+    plt.savefig(cd / f"{stem}-rastergram-channel{c}.png", dpi=600)
     plt.close(fig)
-    logger.info(f"Saved a {r_type} rastergram in {name}_ttfb-rastergram-channel{c}.png file")
+    logger.info(f"Saved a {r_type} rastergram in {stem}-rastergram-channel{c}.png file")
 
     t = range(Tmax)
     fig, ax = plt.subplots()
@@ -393,9 +425,9 @@ def _ttfb_plots(cd, name, c, z_masked, sdx, r_type, Tmax, fb_mean, fb_ll, fb_ul,
     ax.set_ylabel("Cumulative fraction")
     ax.set_title(f"Channel {c}")
     ax.set_ylim(-0.05, 1.05)
-    plt.savefig(cd / f"{name}_ttfb-plot-channel{c}.png", dpi=600)
+    plt.savefig(cd / f"{stem}-plot-channel{c}.png", dpi=600)
     plt.close(fig)
-    logger.info(f"Saved data plots in {name}_ttfb-plot-channel{c}.png file")
+    logger.info(f"Saved data plots in {stem}-plot-channel{c}.png file")
 
 
 @app.command()
@@ -405,6 +437,7 @@ def ttfb(
     cuda: bool = typer.Option(_default("cuda"), "--cuda/--cpu", help="Run computations on GPU or CPU", show_default=False),
     num_samples: int = typer.Option(2000, "--num-samples", "-n", min=1, help="Number of posterior samples"),
     num_iter: int = typer.Option(15000, "--num-iter", "-it", min=1, help="Number of iterations"),
+    smooth: bool = typer.Option(False, "--smooth", help="Sample the rasters of the chain fitted by `smooth`"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -412,20 +445,30 @@ def ttfb(
     Time-to-first-binding analysis (tapqir/main.py:926-1147): posterior samples of the first-binding frame of every
     on-target AOI, one censored two-exponential fit (ka, kns, Af) per sample, and the cumulative fraction bound.
     Needs ``data.tpqr`` and ``<model>_params.tpqr`` of a cosmos fit.
+
+    With ``--smooth`` the first-binding frames are those of posterior rasters of the two-state chain that `smooth` fitted
+    (``<model>_smooth.tpqr``; the rasters behind its rate table) instead of independent draws of every frame, the
+    rastergram shows the smoothed posterior, and the files are named ``<model>_ttfb-smooth-...``.
     """
     import pandas as pd
     import torch
 
     from tapqir_amd.exceptions import HipExtensionError
     from tapqir_amd.utils.imscroll import time_to_first_binding
-    from tapqir_amd.utils.mle_analysis import fraction_bound, fraction_bound_fit, hpdi_columns, ttfb_fit, ttfb_sample
+    from tapqir_amd.utils.mle_analysis import (fraction_bound, fraction_bound_fit, hpdi_columns, smooth_dwell_sample,
+                                               ttfb_fit, ttfb_sample)
 
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
     m, mask, progress_bar = _kinetics_inputs("ttfb", model, cuda, progress_bar)
     data = m.data
-    p_specific = m.params["p_specific"][: data.N].float()
-    z = (p_specific > 0.5).float() if binary else p_specific
+    sm = _smoothed_posterior("ttfb", cd, m.name, mask, logger) if smooth else None
+    stem = f"{m.name}_ttfb-smooth" if smooth else f"{m.name}_ttfb"
+    if smooth:
+        z = sm["z_map"].float() if binary else sm["z_probs"].float()
+    else:
+        p_specific = m.params["p_specific"][: data.N].float()
+        z = (p_specific > 0.5).float() if binary else p_specific
     r_type = "binary" if binary else "probabilistic"
     Tmax = data.F
     try:
@@ -436,15 +479,18 @@ def ttfb(
             sdx = torch.argsort(time_to_first_binding(z_masked), descending=True)
 
             p_bound = m.params["z_probs"][: data.N, :, c, 1][mask].float().to(dev)
-            tau = ttfb_sample(p_bound, num_samples, seed=c)
+            if smooth:  # seed c: the default of `smooth`, so these are the rasters of its rate table
+                tau = smooth_dwell_sample(*_smoothed_filter(sm, c, p_bound), num_samples, seed=c)["tau"]
+            else:
+                tau = ttfb_sample(p_bound, num_samples, seed=c)
             tau_host = tau.cpu()
-            pd.DataFrame(data=tau_host.numpy()).to_csv(cd / f"{m.name}_ttfb-data-points-channel{c}.csv")
-            logger.info(f"Saved time-to-first-binding values in {m.name}_ttfb-data-points-channel{c}.csv file")
+            pd.DataFrame(data=tau_host.numpy()).to_csv(cd / f"{stem}-data-points-channel{c}.csv")
+            logger.info(f"Saved time-to-first-binding values in {stem}-data-points-channel{c}.csv file")
 
             fit = ttfb_fit(tau, Tmax, lr=5e-3, n_steps=num_iter, progress_bar=progress_bar)
             results = _summary_table((name, fit[name].squeeze(-1).cpu()) for name in ("ka", "kns", "Af"))
-            results.to_csv(cd / f"{m.name}_ttfb-params-channel{c}.csv")
-            logger.info(f"Saved fit parameters in {m.name}_ttfb-params-channel{c}.csv file")
+            results.to_csv(cd / f"{stem}-params-channel{c}.csv")
+            logger.info(f"Saved fit parameters in {stem}-params-channel{c}.csv file")
 
             fb = fraction_bound(tau_host, Tmax)
             fb_ll, fb_ul = hpdi_columns(fb, 0.95)
@@ -454,17 +500,18 @@ def ttfb(
             pd.DataFrame(data={"time": torch.arange(Tmax).numpy(), "best fit": best_fit.numpy(),
                                "fraction bound mean": fb_mean.numpy(), "fraction bound 95% ll": fb_ll.numpy(),
                                "fraction bound 95% ul": fb_ul.numpy()}).to_csv(
-                cd / f"{m.name}_ttfb-fraction-bound-channel{c}.csv")
-            logger.info(f"Saved fit data in {m.name}_ttfb-fraction-bound-channel{c}.csv file")
-            _ttfb_plots(cd, m.name, c, z_masked.cpu(), sdx.cpu(), r_type, Tmax, fb_mean.numpy(), fb_ll.numpy(),
+                cd / f"{stem}-fraction-bound-channel{c}.csv")
+            logger.info(f"Saved fit data in {stem}-fraction-bound-channel{c}.csv file")
+            _ttfb_plots(cd, stem, c, z_masked.cpu(), sdx.cpu(), r_type, Tmax, fb_mean.numpy(), fb_ll.numpy(),
                         fb_ul.numpy(), best_fit.numpy(), logger)
     except HipExtensionError:
         logger.exception("ttfb failed: it needs an AMD GPU (--cuda) and the built HIP library")
         raise typer.Exit(1)
 
 
-def _dwell_plot(cd, name, c, kind, map_dt, A, k, t_max, logger):
-    """Dwell-time histogram of the MAP raster with the fitted mixture (main.py:1266-1296, 1350-1381)."""
+def _dwell_plot(cd, stem, c, kind, map_dt, A, k, t_max, logger):
+    """Dwell-time histogram of the MAP raster with the fitted mixture (main.py:1266-1296, 1350-1381); ``stem`` is the
+    start of the file name, ``<model>_dwelltime`` or ``<model>_dwelltime-smooth``."""
     mpl, plt = _pyplot()
     if plt is None:
         logger.warning("matplotlib is not available: the dwelltime plots are not drawn")
@@ -484,9 +531,9 @@ def _dwell_plot(cd, name, c, kind, map_dt, A, k, t_max, logger):
     ax.set_xlabel("Time interval (frame)")
     ax.set_ylabel("Density")
     ax.set_title(f"{kind.capitalize()} dwell times channel {c}")
-    plt.savefig(cd / f"{name}_dwelltime-{kind}-histogram-channel{c}.png", dpi=600)
+    plt.savefig(cd / f"{stem}-{kind}-histogram-channel{c}.png", dpi=600)
     plt.close(fig)
-    logger.info(f"Saved {kind} dwell-time histograms in {name}_dwelltime-{kind}-histogram-channel{c}.png file")
+    logger.info(f"Saved {kind} dwell-time histograms in {stem}-{kind}-histogram-channel{c}.png file")
 
 
 @app.command()
@@ -496,6 +543,7 @@ def dwelltime(
     cuda: bool = typer.Option(_default("cuda"), "--cuda/--cpu", help="Run computations on GPU or CPU", show_default=False),
     num_samples: int = typer.Option(500, "--num-samples", "-n", min=1, help="Number of posterior samples"),
     num_iter: int = typer.Option(10000, "--num-iter", "-it", min=1, help="Number of iterations"),
+    smooth: bool = typer.Option(False, "--smooth", help="Sample the rasters of the chain fitted by `smooth`"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -506,13 +554,18 @@ def dwelltime(
 
     Unlike the reference, a sample without an interior interval of a kind is left out of that kind's fit and statistics
     (the count is logged), and a kind that no sample has is skipped with a warning.
+
+    With ``--smooth`` the rasters are posterior rasters of the two-state chain that `smooth` fitted
+    (``<model>_smooth.tpqr``; the rasters behind its rate table) instead of independent draws of every frame, the plotted
+    histogram is that of its Viterbi path, and the files are named ``<model>_dwelltime-smooth-...``.
     """
     import torch
 
     from tapqir_amd import _lib
     from tapqir_amd.exceptions import HipExtensionError
     from tapqir_amd.utils.imscroll import bound_dwell_times, count_intervals, unbound_dwell_times
-    from tapqir_amd.utils.mle_analysis import dwell_csr_from_hist, dwell_fit, dwell_intervals, dwell_sample
+    from tapqir_amd.utils.mle_analysis import (dwell_csr_from_hist, dwell_fit, dwell_intervals, dwell_sample,
+                                               smooth_dwell_intervals, smooth_dwell_sample)
 
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
@@ -527,20 +580,30 @@ def dwelltime(
         savemat = None
 
     data = m.data
-    z_map = m.params["z_map"][: data.N] if "z_map" in m.params else None
+    sm = _smoothed_posterior("dwelltime", cd, m.name, mask, logger) if smooth else None
+    stem = f"{m.name}_dwelltime-smooth" if smooth else f"{m.name}_dwelltime"
+    if smooth:
+        z_map = sm["z_map"]
+    else:
+        z_map = m.params["z_map"][: data.N] if "z_map" in m.params else None
     kinds = (("bound", "koff", "Off-rate", bound_dwell_times), ("unbound", "kon", "On-rate", unbound_dwell_times))
     try:
         dev = torch.device("cuda")
         for c in range(data.C):
             logger.info(f"Channel #{c} ({data.channels[c]})")
             p_bound = m.params["z_probs"][: data.N, :, c, 1][mask].float().to(dev)
-            sample = dwell_sample(p_bound, num_samples, seed=c)
-            intervals = dwell_intervals(p_bound, num_samples, seed=c, sample=sample)
-            intervals.to_pickle(cd / f"{m.name}_dwelltime-intervals-channel{c}.pkl")
-            logger.info(f"Saved time intervals in {m.name}_dwelltime-intervals-channel{c}.pkl file")
+            if smooth:  # seed c: the default of `smooth`, so these are the rasters of its rate table
+                filt, theta = _smoothed_filter(sm, c, p_bound)
+                sample = smooth_dwell_sample(filt, theta, num_samples, seed=c)
+                intervals = smooth_dwell_intervals(filt, theta, num_samples, seed=c, sample=sample)
+            else:
+                sample = dwell_sample(p_bound, num_samples, seed=c)
+                intervals = dwell_intervals(p_bound, num_samples, seed=c, sample=sample)
+            intervals.to_pickle(cd / f"{stem}-intervals-channel{c}.pkl")
+            logger.info(f"Saved time intervals in {stem}-intervals-channel{c}.pkl file")
             if savemat is not None:
-                savemat(cd / f"{m.name}_dwelltime-intervals-channel{c}.mat", intervals.to_dict("list"))
-                logger.info(f"Saved time intervals in {m.name}_dwelltime-intervals-channel{c}.mat file")
+                savemat(cd / f"{stem}-intervals-channel{c}.mat", intervals.to_dict("list"))
+                logger.info(f"Saved time intervals in {stem}-intervals-channel{c}.mat file")
             else:
                 logger.info("scipy is not available: the .mat file of the intervals is not written")
 
@@ -561,13 +624,13 @@ def dwelltime(
                     (f"A{i}", fit["A"][:, i].cpu()), (f"{rate}{i}", fit["k"][:, i].cpu())))
                 A_mean = [results.loc[f"A{i}", "Mean"] for i in range(K)]
                 k_mean = [results.loc[f"{rate}{i}", "Mean"] for i in range(K)]
-                results.to_csv(cd / f"{m.name}_dwelltime-{rate}-channel{c}.csv")
-                logger.info(f"Saved {title.lower()} parameters in {m.name}_dwelltime-{rate}-channel{c}.csv file")
+                results.to_csv(cd / f"{stem}-{rate}-channel{c}.csv")
+                logger.info(f"Saved {title.lower()} parameters in {stem}-{rate}-channel{c}.csv file")
 
                 t_max = int(torch.nonzero(hist.sum(0)).max().item())  # the largest sampled dwell time
                 map_dt = (host_dwell_times(count_intervals(z_map[None, mask, :, c].cpu().numpy()))
                           if z_map is not None else torch.zeros(0).numpy())
-                _dwell_plot(cd, m.name, c, kind, map_dt, A_mean, k_mean, t_max, logger)
+                _dwell_plot(cd, stem, c, kind, map_dt, A_mean, k_mean, t_max, logger)
     except HipExtensionError:
         logger.exception("dwelltime failed: it needs an AMD GPU (--cuda) and the built HIP library")
         raise typer.Exit(1)

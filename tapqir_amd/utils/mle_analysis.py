@@ -18,7 +18,10 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
 * ``smooth_estep`` / ``smooth_fit`` / ``smooth_viterbi`` / ``smooth_sample``: a two-state hidden Markov chain over the
   frames with the fit's ``z_probs`` as evidence -- forward-backward marginals and expected transition counts, the EM fit
   of kon, koff and the initial probability, the MAP path, and posterior rasters by backward sampling, counted like those
-  of ``rates_sample`` (``tq_smooth_estep``, ``tq_smooth_mstep``, ``tq_smooth_viterbi``, ``tq_smooth_count``).
+  of ``rates_sample`` (``tq_smooth_estep``, ``tq_smooth_mstep``, ``tq_smooth_viterbi``, ``tq_smooth_count``);
+* ``smooth_dwell_sample`` / ``smooth_dwell_intervals``: the outputs of ``dwell_sample`` / ``dwell_intervals`` and the
+  first-binding frames of ``ttfb_sample`` for the rasters of ``smooth_sample``, walked as they are drawn
+  (``tq_smooth_dwell``).
 
 There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
 """
@@ -450,25 +453,80 @@ def smooth_viterbi(p, theta, prior):
     return path
 
 
+def _smooth_sample_inputs(who, filt, theta, num_samples):
+    """What the backward samplers share: ``filt`` as contiguous float64 (N, F) on the device, ``theta`` as 3 doubles on
+    the same device, S, N and F."""
+    if not isinstance(filt, torch.Tensor) or filt.device.type != "cuda":
+        raise HipExtensionError(f"{who} runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    S = int(num_samples)
+    if filt.ndim != 2 or 0 in filt.shape or filt.dtype != torch.float64 or S < 1 or filt.shape[1] > _lib_smooth.SMOOTH_MAX_F:
+        raise ValueError(f"{who}: filt must be float64 (N, F) with N >= 1, 1 <= F <= {_lib_smooth.SMOOTH_MAX_F}, "
+                         f"and num_samples >= 1, got {filt.dtype} {tuple(filt.shape)}")
+    if not isinstance(theta, torch.Tensor) or theta.device != filt.device or theta.dtype != torch.float64 or theta.numel() != 3:
+        raise ValueError(f"{who}: theta must be 3 float64 values (kon, koff, pi0) on the device of filt")
+    return filt.contiguous(), theta.contiguous(), S, filt.shape[0], filt.shape[1]
+
+
 def smooth_sample(filt, theta, num_samples, seed=0, raster=False):
     """Transition counts of ``num_samples`` posterior rasters of the chain, drawn by backward sampling from ``filt``
     (N, F) of ``smooth_estep`` at ``theta``.
 
     Returns ``counts`` (num_samples, N, 4) int32 in the layout of ``rates_sample`` (``rates_estimate`` takes them as they
     are); with ``raster=True`` returns ``(counts, z)`` with the rasters ``z`` (num_samples, N, F) uint8."""
-    if not isinstance(filt, torch.Tensor) or filt.device.type != "cuda":
-        raise HipExtensionError("smooth_sample runs on the HIP device only (no CPU fallback): pass a cuda tensor")
-    S = int(num_samples)
-    if filt.ndim != 2 or 0 in filt.shape or filt.dtype != torch.float64 or S < 1 or filt.shape[1] > _lib_smooth.SMOOTH_MAX_F:
-        raise ValueError(f"smooth_sample: filt must be float64 (N, F) with N >= 1, 1 <= F <= {_lib_smooth.SMOOTH_MAX_F}, "
-                         f"and num_samples >= 1, got {filt.dtype} {tuple(filt.shape)}")
-    if not isinstance(theta, torch.Tensor) or theta.device != filt.device or theta.dtype != torch.float64 or theta.numel() != 3:
-        raise ValueError("smooth_sample: theta must be 3 float64 values (kon, koff, pi0) on the device of filt")
-    filt, theta = filt.contiguous(), theta.contiguous()
-    N, F = filt.shape
+    filt, theta, S, N, F = _smooth_sample_inputs("smooth_sample", filt, theta, num_samples)
     counts = torch.empty(S, N, _lib_rates.RATES_COLS, dtype=torch.int32, device=filt.device)
     z = torch.empty(S, N, F, dtype=torch.uint8, device=filt.device) if raster else None
     a = _lib_smooth.SmoothCountArgs(filt=_lib.ptr(filt), theta=_lib.ptr(theta), counts=_lib.ptr(counts), raster=_lib.ptr(z),
                                     N=N, F=F, S=S, seed=int(seed) & (2**64 - 1))
     _lib.check(_lib_smooth.lib().tq_smooth_count(C.byref(a), _stream(filt.device)), "tq_smooth_count")
     return (counts, z) if raster else counts
+
+
+# ---- dwell times and first binding of the smoothed chain (`dwelltime --smooth`, `ttfb --smooth`, DESIGN.md section 21) ----
+def smooth_dwell_sample(filt, theta, num_samples, seed=0):
+    """Launch A of the interval sampler on the rasters of ``smooth_sample(filt, theta, num_samples, seed)``: every row is
+    walked into runs of equal labels as it is drawn backwards, and no raster is stored.
+
+    Returns ``{"hist_bound", "hist_unbound", "counts"}`` with the shapes and meaning of ``dwell_sample``, and ``"tau"``
+    (num_samples, N) float32 on the device: the first frame with z = 1 of each row, or F if there is none, as
+    ``ttfb_sample`` returns it.  The histograms go to ``dwell_csr_from_hist`` / ``dwell_fit``, ``tau`` to ``ttfb_fit``."""
+    filt, theta, S, N, F = _smooth_sample_inputs("smooth_dwell_sample", filt, theta, num_samples)
+    dev = filt.device
+    counts = torch.empty(S, N, dtype=torch.int32, device=dev)
+    hb = torch.zeros(S, F, dtype=torch.int32, device=dev)
+    hu = torch.zeros(S, F, dtype=torch.int32, device=dev)
+    tau = torch.empty(S, N, dtype=torch.float32, device=dev)
+    a = _lib_smooth.SmoothDwellArgs(filt=_lib.ptr(filt), theta=_lib.ptr(theta), counts=_lib.ptr(counts),
+                                    hist_bound=_lib.ptr(hb), hist_unbound=_lib.ptr(hu), tau=_lib.ptr(tau), N=N, F=F, S=S,
+                                    mode=_lib.DWELL_COUNT, seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib_smooth.lib().tq_smooth_dwell(C.byref(a), _stream(dev)), "tq_smooth_dwell")
+    return {"hist_bound": hb, "hist_unbound": hu, "counts": counts, "tau": tau}
+
+
+def smooth_dwell_intervals(filt, theta, num_samples, seed=0, sample=None):
+    """The interval table of the rasters of ``smooth_sample(filt, theta, num_samples, seed)``: launch A (or its result
+    ``sample`` from ``smooth_dwell_sample`` with the same arguments), an exclusive scan of the row counts, and launch B,
+    which draws the same bits again and writes every row's intervals, last run first, back from the end of the row's
+    slice.  Returns the DataFrame of ``dwell_intervals``: the columns of ``tapqir_amd.utils.imscroll.INTERVAL_COLUMNS``,
+    int64, in (sample, AOI, frame) order."""
+    import pandas as pd
+
+    from tapqir_amd.utils.imscroll import INTERVAL_COLUMNS
+
+    given = num_samples if sample is None else sample["counts"].shape[0]
+    filt, theta, S, N, F = _smooth_sample_inputs("smooth_dwell_intervals", filt, theta, given)
+    if sample is None:
+        sample = smooth_dwell_sample(filt, theta, S, seed)
+    counts = sample["counts"].contiguous()
+    if counts.shape != (S, N) or counts.dtype != torch.int32 or counts.device != filt.device:
+        raise ValueError(f"smooth_dwell_intervals: sample['counts'] must be int32 ({S}, {N}) on the device of filt")
+    csum = torch.cumsum(counts.reshape(-1).to(torch.int64), 0)
+    offsets = (csum - counts.reshape(-1)).contiguous()
+    total = int(csum[-1].item())
+    cols = torch.empty(_lib.DWELL_COLS, max(total, 1), dtype=torch.int32, device=filt.device)
+    a = _lib_smooth.SmoothDwellArgs(filt=_lib.ptr(filt), theta=_lib.ptr(theta), counts=_lib.ptr(counts),
+                                    offsets=_lib.ptr(offsets), intervals=_lib.ptr(cols), total=total, N=N, F=F, S=S,
+                                    mode=_lib.DWELL_EMIT, seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib_smooth.lib().tq_smooth_dwell(C.byref(a), _stream(filt.device)), "tq_smooth_dwell")
+    host = cols[:, :total].to(torch.int64).cpu().numpy()
+    return pd.DataFrame({name: host[i] for i, name in enumerate(INTERVAL_COLUMNS)})
