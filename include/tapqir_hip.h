@@ -738,6 +738,101 @@ typedef struct {
 int tq_smooth_dwell(const tq_smooth_dwell_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Hidden Markov smoothing with several hidden states per observable class (`tapqir_amd smooth --unbound-states U
+ * --bound-states B`): an aggregated chain of M = U + B <= TQ_HMM_MAX_STATES states.  States
+ * 0 .. U - 1 are unbound (class 0), states U .. M - 1 bound (class 1); state i emits l_f(class(i)) with p, `prior`, the
+ * clamp and l_f of the two-state section above.
+ *   theta = (A row-major (M, M), rho (M)): M * M + M doubles in device memory.  Every kernel reads it floored at
+ *           TQ_SMOOTH_RMIN entry by entry and renormalised row by row (A) and as a whole (rho).
+ * Every entry point returns TQ_ERR_ARG, before anything touches the device, for a NULL required pointer, N, F or S < 1,
+ * F > TQ_SMOOTH_MAX_F, S > 65535 * 64, U or B < 1, U + B > TQ_HMM_MAX_STATES, prior outside (0, 1) or counts not 16-byte
+ * aligned.
+ *
+ * tq_hmm_estep: scaled forward-backward of every row at theta.
+ *   filt[n, f, i]  = a_f(i),  a_0 ~ rho o l_0,  a_f ~ (a_{f-1} A) o l_f  with normalisers c_f
+ *   gamma[n, f, i] = p(state_f = i | all frames)
+ *   rows[n]        = E n_ij of the M * M ordered pairs, summed over f < F - 1, row-major (F = 1: zeros); gamma_0(i) of the
+ *                    M states; loglik = sum_f log c_f
+ * ------------------------------------------------------------------------------------- */
+#define TQ_HMM_MAX_STATES 4
+#define TQ_HMM_COLS(M) ((M) * (M) + (M) + 1)
+typedef struct {
+  const float* p;              /* (N, F) p(z = 1) of the fit */
+  const double* theta;         /* (M * M + M) A, rho; device memory */
+  double* filt;                /* (N, F, M) out */
+  double* gamma;               /* (N, F, M) out */
+  double* rows;                /* (N, TQ_HMM_COLS(M)) out */
+  int32_t N, F;
+  int32_t U, B;                /* unbound and bound states, M = U + B */
+  double prior;
+} tq_hmm_estep_args;
+
+int tq_hmm_estep(const tq_hmm_estep_args* a, void* stream);
+
+/* tq_hmm_mstep: sums the N rows of an E-step in a fixed order (bit-reproducible), stores the total loglik into trace[it]
+ * and overwrites theta:  A_ij = sum E n_ij / sum_j sum E n_ij (a state without expected occupancy keeps its row),
+ * rho_i = mean gamma_0(i); both floored and renormalised as above.  One workgroup. */
+typedef struct {
+  const double* rows;          /* (N, TQ_HMM_COLS(M)) of tq_hmm_estep */
+  double* theta;               /* (M * M + M) in / out; device memory */
+  double* trace;               /* trace[it] out: the total loglik at the theta the rows were computed with */
+  int32_t N, it;
+  int32_t U, B;
+} tq_hmm_mstep_args;
+
+int tq_hmm_mstep(const tq_hmm_mstep_args* a, void* stream);
+
+/* tq_hmm_viterbi: the MAP path in hidden states, in the log domain, scores relative to state 0's; a tie takes the
+ * lowest state.  back: scratch of 2 bits per state and frame, four frames to a word, ((F + 3) / 4) * N 32-bit words. */
+typedef struct {
+  const float* p;              /* (N, F) */
+  const double* theta;         /* (M * M + M); device memory */
+  uint32_t* back;              /* scratch, ((F + 3) / 4) * N words */
+  uint8_t* path;               /* (N, F) out: hidden states 0 .. M - 1 */
+  int32_t N, F;
+  int32_t U, B;
+  double prior;
+} tq_hmm_viterbi_args;
+
+int tq_hmm_viterbi(const tq_hmm_viterbi_args* a, void* stream);
+
+/* tq_hmm_count: S posterior rasters of every row by forward filtering, backward sampling, with their counts.
+ * u_k is the k-th uniform of Philox stream (seed, step = s, site 0xA04, elem = n), compared as a double; u_0 is for
+ * frame F - 1, then downwards.  The draw is the largest i with u < t(i) (state 0 if there is none), t(i) the mass of the
+ * states >= i under filt[F - 1] for the last frame and under P(state_f = . | state_{f+1} = j) ~ a_f(.) A[.][j] otherwise.
+ *   counts[s, n]: the class-level counts of the row in the layout of tq_rates_count (tq_rates_estimate takes them)
+ *   trans[s, n, i * M + j]: the number of frame pairs (f, f + 1) with states (i, j)
+ *   raster[s, n, f]: the hidden state */
+typedef struct {
+  const double* filt;          /* (N, F, M) of tq_hmm_estep */
+  const double* theta;         /* (M * M + M); device memory */
+  int32_t* counts;             /* (S, N, TQ_RATES_COLS) out; 16-byte aligned */
+  int32_t* trans;              /* (S, N, M * M) out; or NULL */
+  uint8_t* raster;             /* (S, N, F) out; or NULL */
+  int32_t N, F, S;
+  int32_t U, B;
+  uint64_t seed;
+} tq_hmm_count_args;
+
+int tq_hmm_count(const tq_hmm_count_args* a, void* stream);
+
+/* tq_hmm_estimate: totals[s, i, j] = sum_{k < N} trans[s, a(s, k), i, j] (int64) and
+ * estimand[s, i, j] = totals[s, i, j] / sum_j totals[s, i, j] as IEEE double division (a zero denominator gives NaN).
+ * a(s, k) is that of tq_rates_estimate for the same `resample` and `seed` -- the same Philox site 0xA02 and formula -- so
+ * one seed resamples the same AOIs for the class-level rates and for A.  One wave per sample. */
+typedef struct {
+  const int32_t* trans;        /* (S, N, M * M) of tq_hmm_count */
+  int64_t* totals;             /* (S, M * M) out */
+  double* estimand;            /* (S, M * M) out */
+  int32_t N, S;
+  int32_t U, B;
+  int32_t resample;            /* 0: pooled; 1: bootstrap over AOIs */
+  uint64_t seed;               /* resample = 1 only */
+} tq_hmm_estimate_args;
+
+int tq_hmm_estimate(const tq_hmm_estimate_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame
  * decode of GlimpseDataset.__getitem__ (168-186: big-endian int16 + 2^15) and the offset-region value counts

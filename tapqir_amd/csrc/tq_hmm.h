@@ -1,0 +1,367 @@
+// tq_hmm.h -- hidden Markov smoothing with several hidden states per observable class (`smooth --bound-states`,
+// DESIGN.md section 22), host+device inline bodies, templated on the number of states M = U + B in {2, 3, 4}:
+//   * the chain read from theta = (A, rho), floored and renormalised, and the emission of a state: the evidence of its
+//     class, tq_smooth_evidence;
+//   * products of MxM matrices kept in range by powers of two, and what one lane of the E-step does with its chunk of
+//     frames (tq_smooth_lane_range): the chunk product, the forward sweep from the chunk's exclusive prefix, the backward
+//     sweep from its exclusive suffix with the pair marginals;
+//   * the M-step of the summed rows, the Viterbi path of a row in hidden states, and the backward sampler's thresholds.
+// The two-state bodies of tq_smooth.h are not touched; this is their generalisation next to them.  Nothing here
+// subtracts nearly equal quantities: a_f is stored whole, and the sampler's thresholds are sums of tails.
+// The __global__ wrappers are in tq_hmm.hip; the test suite runs the same bodies from a g++ build.
+#pragma once
+#include <math.h>
+
+#include "../../include/tapqir_hip.h"
+#include "tq_smooth.h"
+
+#define TQ_HMM_SITE 0xA04u  // Philox site id of the backward sampler: stream (seed, step = s, site, elem = n)
+
+// ---- chain and emission -----------------------------------------------------------------------------------------------
+template <int M>
+struct TqHmmModel {
+  double A[M][M];
+  double rho[M];
+  TqSmoothModel ev;  // inv0, inv1 only: the fit's prior, divided out of p by tq_smooth_evidence
+  int U;             // states 0 .. U - 1 are class 0
+};
+
+// out = max(in, TQ_SMOOTH_RMIN) / its sum: no zero entry and a sum of 1
+template <int M>
+TQ_HD void tq_hmm_floor(const double* in, double* out) {
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    out[i] = fmax(in[i], TQ_SMOOTH_RMIN);
+    s += out[i];
+  }
+#pragma unroll
+  for (int i = 0; i < M; ++i) out[i] /= s;
+}
+
+template <int M>
+TQ_HD TqHmmModel<M> tq_hmm_model(const double* theta, int U, double prior) {
+  TqHmmModel<M> m;
+#pragma unroll
+  for (int i = 0; i < M; ++i) tq_hmm_floor<M>(theta + i * M, m.A[i]);
+  tq_hmm_floor<M>(theta + M * M, m.rho);
+  m.ev = TqSmoothModel{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0 / (1.0 - prior), 1.0 / prior};
+  m.U = U;
+  return m;
+}
+
+// l[i] = l_f(class(i))
+template <int M>
+TQ_HD void tq_hmm_emission(const TqHmmModel<M>& m, float pf, double* l) {
+  double l0, l1;
+  tq_smooth_evidence(m.ev, pf, l0, l1);
+#pragma unroll
+  for (int i = 0; i < M; ++i) l[i] = i < m.U ? l0 : l1;
+}
+
+// ---- MxM products -----------------------------------------------------------------------------------------------------
+template <int M>
+struct TqHmmMat {
+  double m[M][M];
+};
+
+template <int M>
+TQ_HD TqHmmMat<M> tq_hmm_identity() {
+  TqHmmMat<M> x;
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) x.m[i][j] = i == j ? 1.0 : 0.0;
+  return x;
+}
+
+// the power of two that brings the sum of the entries into [1/2, 1): exact (tq_smooth_rescale)
+template <int M>
+TQ_HD void tq_hmm_rescale(TqHmmMat<M>& x) {
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) s += x.m[i][j];
+  int e;
+  (void)frexp(s, &e);
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) x.m[i][j] = ldexp(x.m[i][j], -e);
+}
+
+// x y, rescaled (x is the earlier frames)
+template <int M>
+TQ_HD TqHmmMat<M> tq_hmm_mul(const TqHmmMat<M>& x, const TqHmmMat<M>& y) {
+  TqHmmMat<M> r;
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      double s = x.m[i][0] * y.m[0][j];
+#pragma unroll
+      for (int k = 1; k < M; ++k) s += x.m[i][k] * y.m[k][j];
+      r.m[i][j] = s;
+    }
+  tq_hmm_rescale(r);
+  return r;
+}
+
+// product of M_f = A diag(l_f) over the lane's frames; M_0 has every row equal to rho o l_0, so that every prefix that
+// holds frame 0 has rows proportional to a_f.  No frames: the identity.
+template <int M>
+TQ_HD TqHmmMat<M> tq_hmm_chunk(const TqHmmModel<M>& m, const float* pr, int lo, int hi) {
+  TqHmmMat<M> c = tq_hmm_identity<M>();
+  for (int f = lo; f < hi; ++f) {
+    double l[M];
+    tq_hmm_emission(m, pr[f], l);
+    TqHmmMat<M> t;
+#pragma unroll
+    for (int i = 0; i < M; ++i)
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        double s = c.m[i][0] * m.A[0][j];
+#pragma unroll
+        for (int k = 1; k < M; ++k) s += c.m[i][k] * m.A[k][j];
+        t.m[i][j] = (f == 0 ? m.rho[j] : s) * l[j];
+      }
+    tq_hmm_rescale(t);
+    c = t;
+  }
+  return c;
+}
+
+// ---- the two sweeps of a lane -----------------------------------------------------------------------------------------
+// a_{lo-1} from the lane's exclusive prefix (every row proportional to it; lane 0 has none and does not use it)
+template <int M>
+TQ_HD void tq_hmm_prefix_vector(const TqHmmMat<M>& e, double* v) {
+  double s = 0.0;
+#pragma unroll
+  for (int j = 0; j < M; ++j) s += e.m[0][j];
+  const double r = 1.0 / s;
+#pragma unroll
+  for (int j = 0; j < M; ++j) v[j] = e.m[0][j] * r;
+}
+
+// beta_{hi-1} from the lane's exclusive suffix: its row sums (the last lane with frames has the identity: ones)
+template <int M>
+TQ_HD void tq_hmm_suffix_vector(const TqHmmMat<M>& e, double* b) {
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < M; ++j) s += e.m[i][j];
+    b[i] = s;
+  }
+}
+
+// Forward sweep over [lo, hi) from a_{lo-1} = v0: writes a_f into filt[f * M ..].  Returns the lane's sum of log c_f: the
+// normalisers are multiplied up as mantissa and binary exponent, and one logarithm is taken at the end.
+template <int M>
+TQ_HD double tq_hmm_forward(const TqHmmModel<M>& m, const float* pr, int lo, int hi, const double* v0, double* filt) {
+  double v[M], mant = 1.0;
+  int expo = 0;
+#pragma unroll
+  for (int i = 0; i < M; ++i) v[i] = v0[i];
+  for (int f = lo; f < hi; ++f) {
+    double l[M], u[M], c = 0.0;
+    tq_hmm_emission(m, pr[f], l);
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      double s = v[0] * m.A[0][j];
+#pragma unroll
+      for (int k = 1; k < M; ++k) s += v[k] * m.A[k][j];
+      u[j] = (f == 0 ? m.rho[j] : s) * l[j];
+      c += u[j];
+    }
+    const double r = 1.0 / c;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      v[j] = u[j] * r;
+      filt[(int64_t)f * M + j] = v[j];
+    }
+    int e;
+    mant = frexp(mant * c, &e);
+    expo += e;
+  }
+  return log(mant) + (double)expo * 0.69314718055994530942;
+}
+
+// Backward sweep over [lo, hi), g = hi - 1 .. lo, from beta_{hi-1} = b0.  Frame g gives gamma_g, and with a_{g-1} -- the
+// lane's own, or v = a_{lo-1} of its prefix -- the pair marginals xi_{g-1}(i, j) ~ a_{g-1}(i) A[i][j] l_g(j) beta_g(j):
+// the pair (g - 1, g) belongs to the lane that owns g.  acc[i * M + j] += E n_ij; acc[M * M + i] = gamma_0(i) in the lane
+// that owns frame 0.
+template <int M>
+TQ_HD void tq_hmm_backward(const TqHmmModel<M>& m, const float* pr, int lo, int hi, const double* b0, const double* v,
+                           const double* filt, double* gam, double* acc) {
+  double b[M];
+#pragma unroll
+  for (int i = 0; i < M; ++i) b[i] = b0[i];
+  for (int g = hi - 1; g >= lo; --g) {
+    double r[M], s = 0.0;
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      r[i] = filt[(int64_t)g * M + i] * b[i];
+      s += r[i];
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      r[i] /= s;
+      gam[(int64_t)g * M + i] = r[i];
+    }
+    if (g == 0) {
+#pragma unroll
+      for (int i = 0; i < M; ++i) acc[M * M + i] = r[i];
+      break;
+    }
+    double l[M], w[M], x[M][M], tot = 0.0;
+    tq_hmm_emission(m, pr[g], l);
+#pragma unroll
+    for (int j = 0; j < M; ++j) w[j] = l[j] * b[j];
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      const double pi = g > lo ? filt[(int64_t)(g - 1) * M + i] : v[i];  // a_{g-1}(i)
+      double rs = 0.0;
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        x[i][j] = pi * m.A[i][j] * w[j];
+        rs += x[i][j];
+      }
+      tot += rs;
+    }
+    const double rt = 1.0 / tot;
+#pragma unroll
+    for (int i = 0; i < M; ++i)
+#pragma unroll
+      for (int j = 0; j < M; ++j) acc[i * M + j] += x[i][j] * rt;
+    // beta_{g-1} = A (l_g o beta_g), scaled by a power of two
+    double bs = 0.0;
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      double t = m.A[i][0] * w[0];
+#pragma unroll
+      for (int j = 1; j < M; ++j) t += m.A[i][j] * w[j];
+      b[i] = t;
+      bs += t;
+    }
+    int e;
+    (void)frexp(bs, &e);
+#pragma unroll
+    for (int i = 0; i < M; ++i) b[i] = ldexp(b[i], -e);
+  }
+}
+
+// ---- M-step -----------------------------------------------------------------------------------------------------------
+// sums[0 .. TQ_HMM_COLS(M)) over the N rows -> theta, floored and renormalised; a state without expected occupancy keeps
+// its old row
+template <int M>
+TQ_HD void tq_hmm_mstep_theta(const double* sums, int N, double* theta) {
+  double q[M];
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    double rs = 0.0;
+#pragma unroll
+    for (int j = 0; j < M; ++j) rs += sums[i * M + j];
+    if (rs > 0.0) {
+#pragma unroll
+      for (int j = 0; j < M; ++j) q[j] = sums[i * M + j] / rs;
+      tq_hmm_floor<M>(q, theta + i * M);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < M; ++i) q[i] = sums[M * M + i] / (double)N;
+  tq_hmm_floor<M>(q, theta + M * M);
+}
+
+// ---- Viterbi ----------------------------------------------------------------------------------------------------------
+// One row, sequential in f.  The scores are kept relative to state 0's (d[i] = delta(i) - delta(0), d[0] = 0), so their
+// size does not grow with F.  Back-pointers: the two bits at 8 (f & 3) + 2 j of word back[(f >> 2) * stride] are the best
+// predecessor of state j at frame f >= 1; a tie takes the lowest state.
+template <int M>
+TQ_HD void tq_hmm_viterbi_row(const TqHmmModel<M>& m, const float* pr, int F, uint32_t* back, int64_t stride,
+                              uint8_t* path) {
+  double la[M][M], d[M], l[M];
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) la[i][j] = log(m.A[i][j]);
+  tq_hmm_emission(m, pr[0], l);
+  const double s00 = log(m.rho[0]) + log(l[0]);
+  d[0] = 0.0;
+#pragma unroll
+  for (int i = 1; i < M; ++i) d[i] = (log(m.rho[i]) + log(l[i])) - s00;
+  uint32_t word = 0;
+  for (int f = 1; f < F; ++f) {
+    tq_hmm_emission(m, pr[f], l);
+    const double ll0 = log(l[0]), ll1 = log(l[M - 1]);  // the two classes: state 0 is unbound, state M - 1 bound
+    double s[M];
+    uint32_t bits = 0;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      double best = la[0][j];
+      uint32_t bp = 0;
+#pragma unroll
+      for (int i = 1; i < M; ++i) {
+        const double cand = d[i] + la[i][j];
+        if (cand > best) {
+          best = cand;
+          bp = (uint32_t)i;
+        }
+      }
+      s[j] = best + (j < m.U ? ll0 : ll1);
+      bits |= bp << (2 * j);
+    }
+#pragma unroll
+    for (int j = 1; j < M; ++j) d[j] = s[j] - s[0];
+    word |= bits << (8 * (f & 3));
+    if ((f & 3) == 3 || f == F - 1) {
+      back[(int64_t)(f >> 2) * stride] = word;
+      word = 0;
+    }
+  }
+  uint32_t z = 0;
+  double best = 0.0;
+#pragma unroll
+  for (int i = 1; i < M; ++i)
+    if (d[i] > best) {
+      best = d[i];
+      z = (uint32_t)i;
+    }
+  path[F - 1] = (uint8_t)z;
+  for (int f = F - 1; f >= 1; --f) {
+    if ((f & 3) == 3 || f == F - 1) word = back[(int64_t)(f >> 2) * stride];
+    z = (word >> (8 * (f & 3) + 2 * z)) & 3u;
+    path[f - 1] = (uint8_t)z;
+  }
+}
+
+// ---- backward sampler -------------------------------------------------------------------------------------------------
+// t[j * (M - 1) + i - 1] = t(i) given state_{f+1} = j, i = 1 .. M - 1: the mass of the states >= i under
+// w(.) ~ a_f(.) A[.][j], as a sum of tails over the whole sum.  The last frame has no successor: w = a_{F-1} for every j.
+template <int M>
+TQ_HD void tq_hmm_thresholds(const TqHmmModel<M>& m, const double* af, bool last, double* t) {
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    double tail[M];
+    tail[M - 1] = last ? af[M - 1] : af[M - 1] * m.A[M - 1][j];
+#pragma unroll
+    for (int i = M - 2; i >= 0; --i) tail[i] = (last ? af[i] : af[i] * m.A[i][j]) + tail[i + 1];
+#pragma unroll
+    for (int i = 1; i < M; ++i) t[j * (M - 1) + i - 1] = tail[i] / tail[0];
+  }
+}
+
+TQ_HD void tq_hmm_stream(TqPhilox* ph, uint64_t seed, int s, int n) {
+  tq_philox_init(ph, seed, (uint32_t)s, TQ_HMM_SITE, (uint64_t)n);
+}
+
+// the largest i with u < t(i), or 0: u a uniform of the stream as a double, t the M - 1 thresholds of the successor's
+// state, non-increasing in i
+template <int M>
+TQ_HD int tq_hmm_label(double u, const double* t) {
+  int z = 0;
+#pragma unroll
+  for (int i = 1; i < M; ++i) z = u < t[i - 1] ? i : z;
+  return z;
+}

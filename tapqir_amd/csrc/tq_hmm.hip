@@ -1,0 +1,363 @@
+// tq_hmm.hip -- hidden Markov smoothing with M = U + B <= 4 hidden states on the device (bodies in tq_hmm.h): the E-step
+// as a chunked forward-backward with two wave scans of MxM products, the M-step of the summed rows, the Viterbi path in
+// hidden states, the backward sampler with its class-level and state-level counts, and the pooled or AOI-resampled
+// estimate of A.  The kernels are templates over M; the two-state kernels of tq_smooth.hip stay.
+#include <hip/hip_runtime.h>
+
+#include "tq_dpp.h"
+#include "tq_hmm.h"
+#include "tq_host.h"
+
+// runs `...` with the compile-time constant MM = M, which tq_hmm_states has checked to be 2, 3 or 4
+#define TQ_HMM_SWITCH_M(M, ...)  \
+  switch (M) {                   \
+    case 2: {                    \
+      constexpr int MM = 2;      \
+      __VA_ARGS__;               \
+    } break;                     \
+    case 3: {                    \
+      constexpr int MM = 3;      \
+      __VA_ARGS__;               \
+    } break;                     \
+    default: {                   \
+      constexpr int MM = 4;      \
+      __VA_ARGS__;               \
+    } break;                     \
+  }
+
+static bool tq_hmm_states(const char* who, int U, int B) {
+  if (U >= 1 && B >= 1 && U + B <= TQ_HMM_MAX_STATES) return true;
+  char buf[120];
+  snprintf(buf, sizeof(buf), "%s: U and B must be at least 1 and U + B at most %d", who, TQ_HMM_MAX_STATES);
+  tq_set_error(buf);
+  return false;
+}
+
+// ---- E-step: one wave (= one workgroup) per row, L = ceil(F / 64) consecutive frames per lane --------------------------
+template <int M>
+__device__ __forceinline__ TqHmmMat<M> tq_hmm_shfl_up(const TqHmmMat<M>& x, int d) {
+  TqHmmMat<M> r;
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) r.m[i][j] = __shfl_up(x.m[i][j], d, 64);
+  return r;
+}
+template <int M>
+__device__ __forceinline__ TqHmmMat<M> tq_hmm_shfl_down(const TqHmmMat<M>& x, int d) {
+  TqHmmMat<M> r;
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) r.m[i][j] = __shfl_down(x.m[i][j], d, 64);
+  return r;
+}
+
+// The scans of tq_smooth_estep_kernel, one after the other so that only one running product is live at a time: the
+// prefix scan multiplies the lower lanes' product from the left and leaves a_{lo-1}, the suffix scan the higher lanes'
+// from the right and leaves beta_{hi-1} (Hillis-Steele, six steps each, one more shuffle makes them exclusive).  Every
+// lane takes part in every shuffle.
+template <int M>
+__global__ __launch_bounds__(64) void tq_hmm_estep_kernel(const tq_hmm_estep_args a) {
+  constexpr int COLS = TQ_HMM_COLS(M);
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const int F = a.F;
+  const float* pr = a.p + (int64_t)n * F;
+  double* filt = a.filt + (int64_t)n * F * M;
+  double* gam = a.gamma + (int64_t)n * F * M;
+  const TqHmmModel<M> m = tq_hmm_model<M>(a.theta, a.U, a.prior);
+  int lo, hi;
+  tq_smooth_lane_range(lane, F, lo, hi);
+
+  const TqHmmMat<M> c = tq_hmm_chunk(m, pr, lo, hi);
+  double v[M], b[M];
+  {
+    TqHmmMat<M> pre = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const TqHmmMat<M> left = tq_hmm_shfl_up(pre, d);
+      if (lane >= d) pre = tq_hmm_mul(left, pre);
+    }
+    pre = tq_hmm_shfl_up(pre, 1);
+    if (lane == 0) pre = tq_hmm_identity<M>();
+    tq_hmm_prefix_vector(pre, v);
+  }
+  {
+    TqHmmMat<M> suf = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const TqHmmMat<M> right = tq_hmm_shfl_down(suf, d);
+      if (lane + d < 64) suf = tq_hmm_mul(suf, right);
+    }
+    suf = tq_hmm_shfl_down(suf, 1);
+    if (lane == 63) suf = tq_hmm_identity<M>();
+    tq_hmm_suffix_vector(suf, b);
+  }
+
+  double acc[COLS];
+#pragma unroll
+  for (int j = 0; j < COLS; ++j) acc[j] = 0.0;
+  acc[COLS - 1] = tq_hmm_forward(m, pr, lo, hi, v, filt);
+  tq_hmm_backward(m, pr, lo, hi, b, v, filt, gam, acc);
+#pragma unroll
+  for (int j = 0; j < COLS; ++j) acc[j] = tq_group_sum<64>(acc[j]);  // every lane is back here
+  if (lane == 0) {
+    double* out = a.rows + (int64_t)n * COLS;
+#pragma unroll
+    for (int j = 0; j < COLS; ++j) out[j] = acc[j];
+  }
+}
+
+extern "C" int tq_hmm_estep(const tq_hmm_estep_args* a, void* stream) {
+  if (!a || !a->p || !a->theta || !a->filt || !a->gamma || !a->rows) {
+    tq_set_error("tq_hmm_estep: NULL required pointer");
+    return TQ_ERR_ARG;
+  }
+  if (a->N < 1 || a->F < 1 || a->F > TQ_SMOOTH_MAX_F) {
+    tq_set_error("tq_hmm_estep: N and F must be positive and F at most 65536");
+    return TQ_ERR_ARG;
+  }
+  if (!tq_hmm_states("tq_hmm_estep", a->U, a->B)) return TQ_ERR_ARG;
+  if (!(a->prior > 0.0 && a->prior < 1.0)) {
+    tq_set_error("tq_hmm_estep: prior must lie in (0, 1)");
+    return TQ_ERR_ARG;
+  }
+  TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_hmm_estep_kernel<MM>), dim3((unsigned)a->N), dim3(64), 0,
+                                                  (hipStream_t)stream, *a));
+  return tq_launch_status("tq_hmm_estep_kernel");
+}
+
+// ---- M-step: one workgroup; thread t sums rows t, t + 256, ..., then a fixed tree in LDS -------------------------------
+template <int M>
+__global__ __launch_bounds__(TQ_SMOOTH_MSTEP_THREADS) void tq_hmm_mstep_kernel(const tq_hmm_mstep_args a) {
+  constexpr int COLS = TQ_HMM_COLS(M);
+  __shared__ double part[COLS][TQ_SMOOTH_MSTEP_THREADS];
+  const int t = threadIdx.x;
+  double s[COLS];
+#pragma unroll
+  for (int j = 0; j < COLS; ++j) s[j] = 0.0;
+  for (int n = t; n < a.N; n += TQ_SMOOTH_MSTEP_THREADS) {
+    const double* row = a.rows + (int64_t)n * COLS;
+#pragma unroll
+    for (int j = 0; j < COLS; ++j) s[j] += row[j];
+  }
+#pragma unroll
+  for (int j = 0; j < COLS; ++j) part[j][t] = s[j];
+  __syncthreads();
+  for (int h = TQ_SMOOTH_MSTEP_THREADS / 2; h > 0; h >>= 1) {
+    if (t < h) {
+#pragma unroll
+      for (int j = 0; j < COLS; ++j) part[j][t] += part[j][t + h];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    double sums[COLS], theta[M * M + M];
+#pragma unroll
+    for (int j = 0; j < COLS; ++j) sums[j] = part[j][0];
+#pragma unroll
+    for (int j = 0; j < M * M + M; ++j) theta[j] = a.theta[j];
+    tq_hmm_mstep_theta<M>(sums, a.N, theta);
+#pragma unroll
+    for (int j = 0; j < M * M + M; ++j) a.theta[j] = theta[j];
+    a.trace[a.it] = sums[COLS - 1];
+  }
+}
+
+extern "C" int tq_hmm_mstep(const tq_hmm_mstep_args* a, void* stream) {
+  if (!a || !a->rows || !a->theta || !a->trace) {
+    tq_set_error("tq_hmm_mstep: NULL required pointer");
+    return TQ_ERR_ARG;
+  }
+  if (a->N < 1 || a->it < 0) {
+    tq_set_error("tq_hmm_mstep: N must be positive and it non-negative");
+    return TQ_ERR_ARG;
+  }
+  if (!tq_hmm_states("tq_hmm_mstep", a->U, a->B)) return TQ_ERR_ARG;
+  TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_hmm_mstep_kernel<MM>), dim3(1), dim3(TQ_SMOOTH_MSTEP_THREADS), 0,
+                                                  (hipStream_t)stream, *a));
+  return tq_launch_status("tq_hmm_mstep_kernel");
+}
+
+// ---- Viterbi: one lane per row, sequential in f; the back-pointer words of a wave's rows are adjacent -------------------
+template <int M>
+__global__ __launch_bounds__(64) void tq_hmm_viterbi_kernel(const tq_hmm_viterbi_args a) {
+  const int64_t n = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (n >= a.N) return;
+  const TqHmmModel<M> m = tq_hmm_model<M>(a.theta, a.U, a.prior);
+  tq_hmm_viterbi_row(m, a.p + n * a.F, a.F, a.back + n, a.N, a.path + n * a.F);
+}
+
+extern "C" int tq_hmm_viterbi(const tq_hmm_viterbi_args* a, void* stream) {
+  if (!a || !a->p || !a->theta || !a->back || !a->path) {
+    tq_set_error("tq_hmm_viterbi: NULL required pointer");
+    return TQ_ERR_ARG;
+  }
+  if (a->N < 1 || a->F < 1 || a->F > TQ_SMOOTH_MAX_F) {
+    tq_set_error("tq_hmm_viterbi: N and F must be positive and F at most 65536");
+    return TQ_ERR_ARG;
+  }
+  if (!tq_hmm_states("tq_hmm_viterbi", a->U, a->B)) return TQ_ERR_ARG;
+  if (!(a->prior > 0.0 && a->prior < 1.0)) {
+    tq_set_error("tq_hmm_viterbi: prior must lie in (0, 1)");
+    return TQ_ERR_ARG;
+  }
+  TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_hmm_viterbi_kernel<MM>), dim3((unsigned)((a->N + 63) / 64)),
+                                                  dim3(64), 0, (hipStream_t)stream, *a));
+  return tq_launch_status("tq_hmm_viterbi_kernel");
+}
+
+// ---- backward sampler: one wave per (row n, block of 64 samples), one lane per sample ----------------------------------
+// The geometry of tq_smooth_count_kernel: lane j of the wave stages the M (M - 1) thresholds of frame f0 + j in LDS, then
+// every lane draws its own row through the 64 frames, highest first, and only compares.  The class of a state goes
+// through the row counter of the two-state sampler; the state pairs are counted by M * M compare-and-adds, so that the
+// counters stay in registers.  Inactive lanes reach every barrier and touch no memory but the staging.
+template <int M>
+__global__ __launch_bounds__(64) void tq_hmm_count_kernel(const tq_hmm_count_args a) {
+  constexpr int T = M * (M - 1);
+  __shared__ double qbuf[64][T];
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const int s = blockIdx.y * 64 + lane;
+  const bool active = s < a.S;
+  const int F = a.F, U = a.U;
+  const double* fr = a.filt + (int64_t)n * F * M;
+  const int64_t row = (int64_t)s * a.N + n;
+  uint8_t* zr = a.raster ? a.raster + row * F : nullptr;
+  const bool pairs = a.trans != nullptr;
+  const TqHmmModel<M> m = tq_hmm_model<M>(a.theta, U, 0.5);  // the prior is already in filt
+
+  TqPhilox ph;
+  tq_hmm_stream(&ph, a.seed, s, n);
+  TqRatesRow r = {0, 0, 0, 0};
+  int next = 0;  // the state of the frame after the current one
+  double u4[4] = {0.0, 0.0, 0.0, 0.0};
+  int32_t tr[M * M];
+#pragma unroll
+  for (int k = 0; k < M * M; ++k) tr[k] = 0;
+
+  for (int f0 = (F - 1) & ~63; f0 >= 0; f0 -= 64) {
+    const int cnt = min(64, F - f0);
+    if (lane < cnt) {
+      double af[M], t[T];
+#pragma unroll
+      for (int i = 0; i < M; ++i) af[i] = fr[(int64_t)(f0 + lane) * M + i];
+      tq_hmm_thresholds(m, af, f0 + lane == F - 1, t);
+#pragma unroll
+      for (int k = 0; k < T; ++k) qbuf[lane][k] = t[k];
+    }
+    __syncthreads();
+    if (active) {
+      for (int j = cnt - 1; j >= 0; --j) {
+        const int k = F - 1 - (f0 + j);  // the frame takes the k-th uniform of the stream
+        if ((k & 3) == 0) {              // one Philox block is four of them: drawn together, so its words stay in registers
+#pragma unroll
+          for (int q = 0; q < 4; ++q) u4[q] = (double)tq_uniform(&ph);
+        }
+        const double u = (k & 3) == 0 ? u4[0] : (k & 3) == 1 ? u4[1] : (k & 3) == 2 ? u4[2] : u4[3];
+        const bool last = k == 0;
+        const int z = tq_hmm_label<M>(u, &qbuf[j][(last ? 0 : next) * (M - 1)]);
+        const int zc = z >= U ? 1 : 0;
+        if (last) {
+          tq_smooth_back_begin(r, zc);
+        } else {
+          tq_smooth_back_step(r, zc);
+          if (pairs) {
+            const int idx = z * M + next;
+#pragma unroll
+            for (int k = 0; k < M * M; ++k) tr[k] += idx == k ? 1 : 0;
+          }
+        }
+        next = z;
+        if (zr) zr[f0 + j] = (uint8_t)z;
+      }
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  int32_t c[TQ_RATES_COLS];
+  tq_rates_finish(r, F, c);
+  reinterpret_cast<int4*>(a.counts)[row] = make_int4(c[0], c[1], c[2], c[3]);
+  if (pairs) {
+    int32_t* out = a.trans + row * (M * M);
+#pragma unroll
+    for (int k = 0; k < M * M; ++k) out[k] = tr[k];
+  }
+}
+
+extern "C" int tq_hmm_count(const tq_hmm_count_args* a, void* stream) {
+  if (!a || !a->filt || !a->theta || !a->counts) {
+    tq_set_error("tq_hmm_count: NULL required pointer");
+    return TQ_ERR_ARG;
+  }
+  if (((uintptr_t)a->counts & 15u) != 0) {
+    tq_set_error("tq_hmm_count: counts must be 16-byte aligned");
+    return TQ_ERR_ARG;
+  }
+  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F) {
+    tq_set_error("tq_hmm_count: N, F and S must be positive and F at most 65536");
+    return TQ_ERR_ARG;
+  }
+  if (!tq_hmm_states("tq_hmm_count", a->U, a->B)) return TQ_ERR_ARG;
+  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
+  if (grid.y > 65535u) {
+    tq_set_error("tq_hmm_count: S too large");
+    return TQ_ERR_ARG;
+  }
+  TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_hmm_count_kernel<MM>), grid, dim3(64), 0, (hipStream_t)stream, *a));
+  return tq_launch_status("tq_hmm_count_kernel");
+}
+
+// ---- estimate: one wave (= one workgroup) per posterior sample ----------------------------------------------------------
+// The geometry of tq_rates_estimate_kernel and its index draw: lanes stride over k < N, M * M int64 partial sums per lane,
+// one wave reduction each (exact in any order), and lane 0 writes the totals and the row quotients.
+template <int M>
+__global__ __launch_bounds__(64) void tq_hmm_estimate_kernel(const tq_hmm_estimate_args a) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const uint32_t N = (uint32_t)a.N;
+  const int32_t* rows = a.trans + (int64_t)s * a.N * (M * M);
+  int64_t t[M * M];
+#pragma unroll
+  for (int j = 0; j < M * M; ++j) t[j] = 0;
+  for (uint32_t i = lane; i < N; i += 64) {
+    const uint32_t k = a.resample ? tq_rates_index(a.seed, s, i, N) : i;  // k < N
+    const int32_t* c = rows + (int64_t)k * (M * M);
+#pragma unroll
+    for (int j = 0; j < M * M; ++j) t[j] += c[j];
+  }
+#pragma unroll
+  for (int j = 0; j < M * M; ++j) t[j] = tq_group_sum<64>(t[j]);  // every lane is back here: the wave is whole
+  if (lane == 0) {
+    int64_t* tot = a.totals + (int64_t)s * (M * M);
+    double* est = a.estimand + (int64_t)s * (M * M);
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      int64_t rs = 0;
+#pragma unroll
+      for (int j = 0; j < M; ++j) rs += t[i * M + j];
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        tot[i * M + j] = t[i * M + j];
+        est[i * M + j] = (double)t[i * M + j] / (double)rs;
+      }
+    }
+  }
+}
+
+extern "C" int tq_hmm_estimate(const tq_hmm_estimate_args* a, void* stream) {
+  if (!a || !a->trans || !a->totals || !a->estimand) {
+    tq_set_error("tq_hmm_estimate: NULL required pointer");
+    return TQ_ERR_ARG;
+  }
+  if (a->N < 1 || a->S < 1 || (a->resample != 0 && a->resample != 1)) {
+    tq_set_error("tq_hmm_estimate: N and S must be positive and resample 0 or 1");
+    return TQ_ERR_ARG;
+  }
+  if (a->S > 65535 * 64) {
+    tq_set_error("tq_hmm_estimate: S too large");
+    return TQ_ERR_ARG;
+  }
+  if (!tq_hmm_states("tq_hmm_estimate", a->U, a->B)) return TQ_ERR_ARG;
+  TQ_HMM_SWITCH_M(a->U + a->B,
+                  hipLaunchKernelGGL((tq_hmm_estimate_kernel<MM>), dim3((unsigned)a->S), dim3(64), 0, (hipStream_t)stream, *a));
+  return tq_launch_status("tq_hmm_estimate_kernel");
+}

@@ -702,6 +702,84 @@ def rates(
         raise typer.Exit(1)
 
 
+def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci, bootstrap, seed, progress_bar):
+    """`smooth` with U + B > 2 hidden states: ``<model>_smooth-u<U>b<B>.tpqr`` and, per channel,
+    ``<model>_smooth-u<U>b<B>-channel<c>.csv``.  AOIs outside the mask keep the fit's z_probs and have NaN state
+    probabilities and state 255."""
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.exceptions import HipExtensionError
+    from tapqir_amd.utils.mle_analysis import (estimand_summary, hmm_estimate, hmm_fit, hmm_sample, hmm_summary, hmm_viterbi,
+                                               rates_estimate, rates_sample, rates_summary)
+
+    data, M = m.data, U + B
+    stem = f"{m.name}_smooth-u{U}b{B}"
+    pct = f"{ci * 100:g}%"
+    columns = ["EM", "Mean", f"{pct} LL", f"{pct} UL", "MAP"]
+    z_raw = m.params["z_probs"][: data.N, :, :, 1].float()  # (N, F, C)
+    out = {"z_probs": z_raw.clone(), "state_probs": torch.full((*z_raw.shape, M), float("nan")), "z_map": z_raw > 0.5,
+           "state_map": torch.full(z_raw.shape, 255, dtype=torch.uint8),
+           "log_evidence": torch.full((data.N, data.C), float("nan"), dtype=torch.float64),
+           "theta": torch.zeros(data.C, M * M + M, dtype=torch.float64), "prior": torch.zeros(data.C, dtype=torch.float64),
+           "bic": torch.zeros(data.C, dtype=torch.float64), "n_params": M * (M - 1) + (M - 1), "loglik_trace": [],
+           "mask": mask, "unbound": U, "bound": B}
+    try:
+        dev = torch.device("cuda")
+        for c in range(data.C):
+            logger.info(f"Channel #{c} ({data.channels[c]})")
+            prior = float(torch.as_tensor(m.params["pi"]["Mean"]).reshape(-1, 2)[c, 1])
+            p = z_raw[:, :, c][mask].to(dev)
+            chan_seed = c if seed is None else seed
+            fit = hmm_fit(p, prior, U, B, num_iter=num_iter, tol=tol, progress_bar=progress_bar)
+            theta = fit["theta"]
+            A = theta[: M * M].reshape(M, M).cpu()
+            logger.info(f"EM with {U} unbound and {B} bound states: log evidence = {fit['loglik']:.6f}, BIC = "
+                        f"{fit['bic']:.6f} ({fit['n_params']} parameters; the lower, the better) after "
+                        f"{fit['iterations']} iterations")
+            if not fit["converged"]:
+                logger.warning(f"smooth: the EM did not converge to --tol {tol:g} within {fit['iterations']} iterations")
+            path = hmm_viterbi(p, theta, prior, U, B)
+            sample = hmm_sample(fit["filt"], theta, U, B, num_samples, seed=chan_seed, trans=True)
+            est = hmm_estimate(sample["trans"], bootstrap=bootstrap, seed=chan_seed)
+            summary = hmm_summary(est, ci)
+            pairs = torch.bincount((path[:, :-1].long() * M + path[:, 1:].long()).reshape(-1), minlength=M * M)
+            A_map = (pairs.double().reshape(M, M) / pairs.double().reshape(M, M).sum(1, keepdim=True)).cpu()
+            results = pd.DataFrame(columns=columns, dtype=float)
+            for i in range(M):
+                for j in range(M):
+                    row = summary[f"A{i}{j}"]
+                    results.loc[f"A{i}{j}"] = [A[i, j].item(), row["mean"], row["ll"], row["ul"], A_map[i, j].item()]
+            for i in range(M):  # mean dwell of state i in frames, 1 / (1 - A_ii)
+                row = estimand_summary(1.0 / (1.0 - est["A"][:, i, i]), ci)
+                results.loc[f"dwell{i}"] = [1.0 / (1.0 - A[i, i].item()), row["mean"], row["ll"], row["ul"],
+                                            (1.0 / (1.0 - A_map[i, i])).item()]
+            pair_sums = fit["rows"][:, : M * M].sum(0).reshape(M, M).cpu()  # expected pairs by state, summed over AOIs
+            em = {"kon": (pair_sums[:U, U:].sum() / pair_sums[:U].sum()).item(),
+                  "koff": (pair_sums[U:, :U].sum() / pair_sums[U:].sum()).item()}
+            rates = rates_summary(rates_estimate(sample["counts"], bootstrap=bootstrap, seed=chan_seed), ci)
+            map_est = rates_estimate(rates_sample((path >= U).float(), 1, seed=chan_seed))  # p in {0, 1} is drawn as itself
+            for rate in ("kon", "koff"):
+                row = rates[rate]
+                results.loc[rate] = [em[rate], row["mean"], row["ll"], row["ul"], map_est[rate][0].item()]
+            results.to_csv(cd / f"{stem}-channel{c}.csv")
+            logger.info(f"Saved the transition matrix, dwells and rates in {stem}-channel{c}.csv file")
+            out["z_probs"][:, :, c][mask] = fit["gamma"][..., U:].sum(-1).float().cpu()
+            out["state_probs"][:, :, c][mask] = fit["gamma"].float().cpu()
+            out["z_map"][:, :, c][mask] = (path >= U).cpu()
+            out["state_map"][:, :, c][mask] = path.cpu()
+            out["log_evidence"][:, c][mask] = fit["rows"][:, -1].cpu()
+            out["theta"][c] = theta.cpu()
+            out["prior"][c] = prior
+            out["bic"][c] = fit["bic"]
+            out["loglik_trace"].append(fit["trace"].cpu())
+        torch.save(out, cd / f"{stem}.tpqr")
+        logger.info(f"Saved the smoothed posterior in {stem}.tpqr file")
+    except HipExtensionError:
+        logger.exception("smooth failed: it needs an AMD GPU (--cuda) and the built HIP library")
+        raise typer.Exit(1)
+
+
 @app.command()
 def smooth(
     model: avail_models = typer.Option("cosmos", help="Tapqir model"),
@@ -712,6 +790,8 @@ def smooth(
     ci: float = typer.Option(0.95, "--ci", help="Probability mass of the interval, in (0, 1)"),
     bootstrap: bool = typer.Option(True, "--bootstrap/--no-bootstrap", help="Resample the AOIs of every posterior raster"),
     seed: Optional[int] = typer.Option(None, "--seed", help="Seed of the posterior rasters (default: the channel index)"),
+    unbound_states: int = typer.Option(1, "--unbound-states", min=1, help="Hidden states that look unbound (z = 0)"),
+    bound_states: int = typer.Option(1, "--bound-states", min=1, help="Hidden states that look bound (z = 1); at most 4 in all"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -722,6 +802,12 @@ def smooth(
     path to ``<model>_smooth.tpqr`` and, per channel, the rates to ``<model>_smooth-channel<c>.csv``: the EM value, mean and
     percentile interval over posterior rasters of the chain (resampled over AOIs unless ``--no-bootstrap``) and the rates
     of the Viterbi raster.  Needs ``data.tpqr`` and ``<model>_params.tpqr`` of a cosmos fit.
+
+    With ``--unbound-states U --bound-states B`` other than 1 and 1 the chain has U + B <= 4 hidden states, U of them
+    emitting the evidence of z = 0 and B that of z = 1: short-lived and long-lived complexes side by
+    side.  The files are then ``<model>_smooth-u<U>b<B>.tpqr`` (with the state marginals, the Viterbi path in hidden
+    states and the BIC: the lower, the better) and ``<model>_smooth-u<U>b<B>-channel<c>.csv`` (every entry of the
+    transition matrix, the mean dwell of every state and the class-level kon and koff); the two-state files stay.
     """
     import pandas as pd
     import torch
@@ -735,7 +821,14 @@ def smooth(
     if model.value == "cosmos" and not 0.0 < ci < 1.0:  # as in rates: after the model, before --cpu
         logger.error(f"smooth: --ci must be between 0 and 1, got {ci}")
         raise typer.Exit(1)
+    if model.value == "cosmos" and unbound_states + bound_states > 4:
+        logger.error(f"smooth: --unbound-states + --bound-states must be at most 4, got {unbound_states} + {bound_states}")
+        raise typer.Exit(1)
     m, mask, progress_bar = _kinetics_inputs("smooth", model, cuda, progress_bar)
+    if (unbound_states, bound_states) != (1, 1):
+        _smooth_multistate(m, mask, cd, logger, unbound_states, bound_states, num_iter, tol, num_samples, ci, bootstrap,
+                           seed, progress_bar)
+        return
     data = m.data
     pct = f"{ci * 100:g}%"
     z_raw = m.params["z_probs"][: data.N, :, :, 1].float()  # (N, F, C)

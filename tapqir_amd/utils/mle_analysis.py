@@ -21,7 +21,12 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
   of ``rates_sample`` (``tq_smooth_estep``, ``tq_smooth_mstep``, ``tq_smooth_viterbi``, ``tq_smooth_count``);
 * ``smooth_dwell_sample`` / ``smooth_dwell_intervals``: the outputs of ``dwell_sample`` / ``dwell_intervals`` and the
   first-binding frames of ``ttfb_sample`` for the rasters of ``smooth_sample``, walked as they are drawn
-  (``tq_smooth_dwell``).
+  (``tq_smooth_dwell``);
+* ``hmm_estep`` / ``hmm_mstep`` / ``hmm_fit`` / ``hmm_viterbi`` / ``hmm_sample`` / ``hmm_estimate`` / ``hmm_summary``: the
+  same chain with up to four hidden states, several of them sharing the evidence of z = 0 or of z = 1 -- state marginals,
+  the EM fit of the whole transition matrix with its BIC, the MAP path in hidden states, posterior rasters with their
+  class-level and state-level counts, and the transition matrix of every raster, pooled or resampled over AOIs
+  (``tq_hmm_estep``, ``tq_hmm_mstep``, ``tq_hmm_viterbi``, ``tq_hmm_count``, ``tq_hmm_estimate``).
 
 There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
 """
@@ -30,7 +35,7 @@ import ctypes as C
 
 import torch
 
-from tapqir_amd import _lib, _lib_rates, _lib_smooth
+from tapqir_amd import _lib, _lib_hmm, _lib_rates, _lib_smooth
 from tapqir_amd.exceptions import HipExtensionError
 
 ADAM_BETAS = (0.9, 0.999)
@@ -332,19 +337,20 @@ def rates_summary(estimate, probs=0.68):
     Returns ``{"kon": {...}, "koff": {...}}`` with the floats ``"mean"``, ``"ll"``, ``"ul"`` and the int ``"left_out"``:
     the number of non-finite estimands (zero denominators) that the three leave out.  A rate without a finite estimand
     has NaN for all three."""
+    return {rate: estimand_summary(estimate[rate], probs) for rate in ("kon", "koff")}
+
+
+def estimand_summary(estimand, probs):
+    """``{"mean", "ll", "ul", "left_out"}`` of one estimand over the samples: what ``rates_summary`` returns per rate."""
     from tapqir_amd.utils.stats import quantile
 
-    out = {}
-    for rate in ("kon", "koff"):
-        x = estimate[rate].double()
-        x = x[torch.isfinite(x)]
-        left_out = estimate[rate].numel() - x.numel()
-        if x.numel() == 0:
-            out[rate] = {"mean": float("nan"), "ll": float("nan"), "ul": float("nan"), "left_out": left_out}
-            continue
-        out[rate] = {"mean": x.mean().item(), "ll": quantile(x, (1 - probs) / 2).item(),
-                     "ul": quantile(x, (1 + probs) / 2).item(), "left_out": left_out}
-    return out
+    x = estimand.double()
+    x = x[torch.isfinite(x)]
+    left_out = estimand.numel() - x.numel()
+    if x.numel() == 0:
+        return {"mean": float("nan"), "ll": float("nan"), "ul": float("nan"), "left_out": left_out}
+    return {"mean": x.mean().item(), "ll": quantile(x, (1 - probs) / 2).item(), "ul": quantile(x, (1 + probs) / 2).item(),
+            "left_out": left_out}
 
 
 # ---- two-state hidden Markov smoothing (`smooth`, DESIGN.md section 20) --------------------------------------------------
@@ -530,3 +536,238 @@ def smooth_dwell_intervals(filt, theta, num_samples, seed=0, sample=None):
     _lib.check(_lib_smooth.lib().tq_smooth_dwell(C.byref(a), _stream(filt.device)), "tq_smooth_dwell")
     host = cols[:, :total].to(torch.int64).cpu().numpy()
     return pd.DataFrame({name: host[i] for i, name in enumerate(INTERVAL_COLUMNS)})
+
+
+# ---- hidden Markov smoothing with several states per class (`smooth --bound-states`) ---------------
+def _hmm_states(who, unbound, bound):
+    U, B = int(unbound), int(bound)
+    if U < 1 or B < 1 or U + B > _lib_hmm.HMM_MAX_STATES:
+        raise ValueError(f"{who}: unbound and bound must be at least 1 and sum to at most {_lib_hmm.HMM_MAX_STATES}, got "
+                         f"{unbound} and {bound}")
+    return U, B, U + B
+
+
+def _hmm_theta(who, theta, M, device):
+    if (not isinstance(theta, torch.Tensor) or theta.device != device or theta.dtype != torch.float64
+            or theta.numel() != M * M + M):
+        raise ValueError(f"{who}: theta must be {M * M + M} float64 values (A row-major, rho) on the device of the data")
+    return theta.contiguous().reshape(-1)
+
+
+def _hmm_inputs(who, p, theta, prior, unbound, bound):
+    """``p`` through ``_sampler_inputs``, U, B, M, ``theta`` as M * M + M doubles on p's device, the prior in (0, 1)."""
+    U, B, M = _hmm_states(who, unbound, bound)
+    p, N, F, _ = _sampler_inputs(who, p, 1, 0)
+    if F > _lib_smooth.SMOOTH_MAX_F:
+        raise ValueError(f"{who}: at most {_lib_smooth.SMOOTH_MAX_F} frames, got {F}")
+    prior = float(prior)
+    if not 0.0 < prior < 1.0:
+        raise ValueError(f"{who}: prior must lie in (0, 1), got {prior}")
+    return p, N, F, _hmm_theta(who, theta, M, p.device), prior, U, B, M
+
+
+def _hmm_buffers(N, F, M, device):
+    return {"filt": torch.empty(N, F, M, dtype=torch.float64, device=device),
+            "gamma": torch.empty(N, F, M, dtype=torch.float64, device=device),
+            "rows": torch.empty(N, _lib_hmm.hmm_cols(M), dtype=torch.float64, device=device)}
+
+
+def _hmm_estep(p, N, F, theta, prior, U, B, out):
+    a = _lib_hmm.HmmEstepArgs(p=_lib.ptr(p), theta=_lib.ptr(theta), filt=_lib.ptr(out["filt"]), gamma=_lib.ptr(out["gamma"]),
+                              rows=_lib.ptr(out["rows"]), N=N, F=F, U=U, B=B, prior=prior)
+    _lib.check(_lib_hmm.lib().tq_hmm_estep(C.byref(a), _stream(p.device)), "tq_hmm_estep")
+    return out
+
+
+def hmm_estep(p, theta, prior, unbound=1, bound=1):
+    """Forward-backward of every row of ``p`` (N, F), the fit's p(z = 1), under a chain of M = ``unbound`` + ``bound``
+    hidden states: ``theta`` = (A row-major, rho), M * M + M float64 on the device; states 0 .. unbound - 1 emit the
+    evidence of z = 0, the others that of z = 1, with the fit's ``prior`` divided out of ``p``.
+
+    Returns ``{"filt", "gamma"}``, (N, F, M) float64: the filtered and the smoothed state probabilities, and ``"rows"``
+    (N, M * M + M + 1): the expected number of frame pairs in states (i, j), row-major, gamma_0 and the log-evidence."""
+    p, N, F, theta, prior, U, B, M = _hmm_inputs("hmm_estep", p, theta, prior, unbound, bound)
+    return _hmm_estep(p, N, F, theta, prior, U, B, _hmm_buffers(N, F, M, p.device))
+
+
+def hmm_mstep(rows, theta, trace, it=0, unbound=1, bound=1):
+    """One launch of ``tq_hmm_mstep``: ``theta`` (M * M + M float64, in place) from the summed ``rows`` of an E-step, and
+    the total log-evidence of those rows into ``trace[it]``.  Returns ``theta``."""
+    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
+        raise HipExtensionError("hmm_mstep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states("hmm_mstep", unbound, bound)
+    cols = _lib_hmm.hmm_cols(M)
+    if rows.ndim != 2 or rows.shape[1] != cols or rows.shape[0] < 1 or rows.dtype != torch.float64 or not rows.is_contiguous():
+        raise ValueError(f"hmm_mstep: rows must be contiguous float64 (N, {cols}), N >= 1")
+    for name, x, n in (("theta", theta, M * M + M), ("trace", trace, int(it) + 1)):
+        if (not isinstance(x, torch.Tensor) or x.device != rows.device or x.dtype != torch.float64 or x.ndim != 1
+                or x.numel() < n or not x.is_contiguous() or it < 0):
+            raise ValueError(f"hmm_mstep: {name} must be a float64 vector of at least {n} values on the device of rows")
+    a = _lib_hmm.HmmMstepArgs(rows=_lib.ptr(rows), theta=_lib.ptr(theta), trace=_lib.ptr(trace), N=rows.shape[0], it=int(it),
+                              U=U, B=B)
+    _lib.check(_lib_hmm.lib().tq_hmm_mstep(C.byref(a), _stream(rows.device)), "tq_hmm_mstep")
+    return theta
+
+
+def hmm_default_start(unbound, bound):
+    """The deterministic default start of ``hmm_fit`` as (A (M, M), rho (M,)) float64: the r-th state of a class leaves
+    with probability 0.3 / 4^r, spread evenly over the other M - 1 states, so no two states of a class start alike; rho is
+    uniform."""
+    U, B, M = _hmm_states("hmm_default_start", unbound, bound)
+    A = torch.zeros(M, M, dtype=torch.float64)
+    for i in range(M):
+        leave = 0.3 / 4.0 ** (i if i < U else i - U)
+        A[i] = leave / (M - 1)
+        A[i, i] = 1.0 - leave
+    return A, torch.full((M,), 1.0 / M, dtype=torch.float64)
+
+
+def hmm_canonical_order(theta, unbound, bound):
+    """The permutation (a list: new state k is old state order[k]) that puts the states of each class in descending
+    A_ii; equal values keep their order."""
+    U, B, M = _hmm_states("hmm_canonical_order", unbound, bound)
+    stay = theta.detach().cpu().reshape(-1)[: M * M].reshape(M, M).diagonal().tolist()
+    return sorted(range(U), key=lambda i: -stay[i]) + sorted(range(U, M), key=lambda i: -stay[i])
+
+
+def hmm_permute(order, M, theta=None, filt=None, gamma=None, rows=None):
+    """The given outputs of ``hmm_estep`` / ``hmm_fit`` with their states relabelled by ``order``, as a dict."""
+    idx = torch.as_tensor(order, dtype=torch.int64)
+    out = {}
+    if theta is not None:
+        t = theta.reshape(-1)
+        ix = idx.to(t.device)
+        out["theta"] = torch.cat([t[: M * M].reshape(M, M)[ix][:, ix].reshape(-1), t[M * M:][ix]])
+    for name, x in (("filt", filt), ("gamma", gamma)):
+        if x is not None:
+            out[name] = x[..., idx.to(x.device)].contiguous()
+    if rows is not None:
+        ix = idx.to(rows.device)
+        n = rows.shape[0]
+        out["rows"] = torch.cat([rows[:, : M * M].reshape(n, M, M)[:, ix][:, :, ix].reshape(n, M * M),
+                                 rows[:, M * M: M * M + M][:, ix], rows[:, M * M + M:]], 1)
+    return out
+
+
+def hmm_fit(p, prior, unbound=1, bound=1, A0=None, rho0=None, num_iter=200, tol=1e-9, chunk=50, progress_bar=None):
+    """EM fit of a chain of ``unbound`` + ``bound`` hidden states to the rows of ``p`` (N, F), from (``A0``, ``rho0``) or
+    from ``hmm_default_start``; the chunks, the stopping rule and the final E-step are those of ``smooth_fit``.
+
+    After the fit the states of each class are put in descending A_ii (``hmm_canonical_order``), in ``theta`` and in
+    every output alike.  Returns what ``smooth_fit`` returns -- ``theta`` (M * M + M,), ``gamma``, ``filt`` (N, F, M),
+    ``rows`` (N, M * M + M + 1), ``trace``, ``iterations``, ``converged`` -- and ``loglik`` (the log-evidence at the final
+    theta), ``n_params`` = M (M - 1) + (M - 1) and ``bic`` = -2 loglik + n_params log(N F): the lower, the better."""
+    import math
+
+    num_iter = int(num_iter)
+    U, B, M = _hmm_states("hmm_fit", unbound, bound)
+    A, rho = hmm_default_start(U, B)
+    if A0 is not None:
+        A = torch.as_tensor(A0, dtype=torch.float64).cpu()
+    if rho0 is not None:
+        rho = torch.as_tensor(rho0, dtype=torch.float64).cpu()
+    if (num_iter < 1 or A.shape != (M, M) or rho.shape != (M,) or not bool((A >= 0).all()) or not bool((rho >= 0).all())
+            or not bool((A.sum(1) > 0).all()) or not float(rho.sum()) > 0):
+        raise ValueError(f"hmm_fit: num_iter must be positive, A0 ({M}, {M}) and rho0 ({M},) non-negative with positive sums")
+    if not isinstance(p, torch.Tensor) or p.device.type != "cuda":
+        raise HipExtensionError("hmm_fit runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    theta = torch.cat([(A / A.sum(1, keepdim=True)).reshape(-1), rho / rho.sum()]).to(p.device)
+    p, N, F, theta, prior, U, B, M = _hmm_inputs("hmm_fit", p, theta, prior, U, B)
+    out = _hmm_buffers(N, F, M, p.device)
+    trace = torch.full((num_iter,), float("nan"), dtype=torch.float64, device=p.device)
+    state = {"iterations": 0, "converged": False}
+
+    def em_steps(step0, n):
+        if state["converged"]:
+            return
+        for it in range(step0, step0 + n):
+            _hmm_estep(p, N, F, theta, prior, U, B, out)
+            hmm_mstep(out["rows"], theta, trace, it, U, B)
+        state["iterations"] = step0 + n
+        ll = trace[: step0 + n].cpu()
+        gain = ll[1:] - ll[:-1]
+        state["converged"] = bool((gain <= tol * ll[1:].abs()).any())
+
+    _run_chunks(em_steps, num_iter, chunk, progress_bar)
+    _hmm_estep(p, N, F, theta, prior, U, B, out)
+    order = hmm_canonical_order(theta, U, B)
+    out = hmm_permute(order, M, theta=theta, **out)
+    loglik = out["rows"][:, -1].sum().item()
+    n_params = M * (M - 1) + (M - 1)
+    return {**out, "trace": trace[: state["iterations"]], **state, "loglik": loglik, "n_params": n_params,
+            "bic": -2.0 * loglik + n_params * math.log(N * F), "order": order}
+
+
+def hmm_viterbi(p, theta, prior, unbound=1, bound=1):
+    """MAP path in hidden states of every row of ``p`` (N, F) under the chain ``theta`` and the evidence of ``hmm_estep``:
+    (N, F) uint8 on the device; ``path >= unbound`` is its class.  A tie takes the lowest state."""
+    p, N, F, theta, prior, U, B, M = _hmm_inputs("hmm_viterbi", p, theta, prior, unbound, bound)
+    back = torch.empty(((F + 3) // 4) * N, dtype=torch.int32, device=p.device)
+    path = torch.empty(N, F, dtype=torch.uint8, device=p.device)
+    a = _lib_hmm.HmmViterbiArgs(p=_lib.ptr(p), theta=_lib.ptr(theta), back=_lib.ptr(back), path=_lib.ptr(path), N=N, F=F,
+                                U=U, B=B, prior=prior)
+    _lib.check(_lib_hmm.lib().tq_hmm_viterbi(C.byref(a), _stream(p.device)), "tq_hmm_viterbi")
+    return path
+
+
+def hmm_sample(filt, theta, unbound, bound, num_samples, seed=0, trans=False, raster=False):
+    """``num_samples`` posterior rasters of the chain in hidden states, drawn by backward sampling from ``filt`` (N, F, M)
+    of ``hmm_estep`` at ``theta``, and their counts.
+
+    Returns a dict with ``"counts"`` (num_samples, N, 4) int32, the class-level counts in the layout of ``rates_sample``
+    (``rates_estimate`` takes them as they are); with ``trans=True`` also ``"trans"`` (num_samples, N, M * M) int32, the
+    number of frame pairs in states (i, j), for ``hmm_estimate``; with ``raster=True`` also ``"raster"`` (num_samples, N, F)
+    uint8, the hidden states."""
+    if not isinstance(filt, torch.Tensor) or filt.device.type != "cuda":
+        raise HipExtensionError("hmm_sample runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states("hmm_sample", unbound, bound)
+    S = int(num_samples)
+    if (filt.ndim != 3 or 0 in filt.shape or filt.shape[2] != M or filt.dtype != torch.float64 or S < 1
+            or filt.shape[1] > _lib_smooth.SMOOTH_MAX_F):
+        raise ValueError(f"hmm_sample: filt must be float64 (N, F, {M}) with N >= 1, 1 <= F <= {_lib_smooth.SMOOTH_MAX_F}, "
+                         f"and num_samples >= 1, got {filt.dtype} {tuple(filt.shape)}")
+    theta = _hmm_theta("hmm_sample", theta, M, filt.device)
+    filt = filt.contiguous()
+    N, F = filt.shape[:2]
+    out = {"counts": torch.empty(S, N, _lib_rates.RATES_COLS, dtype=torch.int32, device=filt.device)}
+    if trans:
+        out["trans"] = torch.empty(S, N, M * M, dtype=torch.int32, device=filt.device)
+    if raster:
+        out["raster"] = torch.empty(S, N, F, dtype=torch.uint8, device=filt.device)
+    a = _lib_hmm.HmmCountArgs(filt=_lib.ptr(filt), theta=_lib.ptr(theta), counts=_lib.ptr(out["counts"]),
+                              trans=_lib.ptr(out.get("trans")), raster=_lib.ptr(out.get("raster")), N=N, F=F, S=S, U=U, B=B,
+                              seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib_hmm.lib().tq_hmm_count(C.byref(a), _stream(filt.device)), "tq_hmm_count")
+    return out
+
+
+def hmm_estimate(trans, bootstrap=False, seed=0):
+    """The transition matrix of every posterior sample from the state-pair counts ``trans`` (S, N, M * M) of
+    ``hmm_sample``: pooled over the AOIs, or with ``bootstrap=True`` over N AOIs drawn with replacement -- the AOIs that
+    ``rates_estimate`` draws for the same ``seed``.  Returns ``"A"`` (S, M, M) float64, rows of counts divided by their
+    sums (NaN for a state never visited), and ``"totals"`` (S, M, M) int64, on the device."""
+    import math
+
+    if not isinstance(trans, torch.Tensor) or trans.device.type != "cuda":
+        raise HipExtensionError("hmm_estimate runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    M = math.isqrt(trans.shape[2]) if trans.ndim == 3 else 0
+    if (trans.ndim != 3 or M * M != trans.shape[2] or not 2 <= M <= _lib_hmm.HMM_MAX_STATES or trans.dtype != torch.int32
+            or 0 in trans.shape):
+        raise ValueError(f"hmm_estimate: trans must be int32 (S, N, M * M) with S, N >= 1 and M in 2 .. "
+                         f"{_lib_hmm.HMM_MAX_STATES}, got {trans.dtype} {tuple(trans.shape)}")
+    trans = trans.contiguous()
+    S, N = trans.shape[:2]
+    totals = torch.empty(S, M, M, dtype=torch.int64, device=trans.device)
+    est = torch.empty(S, M, M, dtype=torch.float64, device=trans.device)
+    a = _lib_hmm.HmmEstimateArgs(trans=_lib.ptr(trans), totals=_lib.ptr(totals), estimand=_lib.ptr(est), N=N, S=S, U=1,
+                                 B=M - 1, resample=1 if bootstrap else 0, seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib_hmm.lib().tq_hmm_estimate(C.byref(a), _stream(trans.device)), "tq_hmm_estimate")
+    return {"A": est, "totals": totals}
+
+
+def hmm_summary(estimate, probs=0.68):
+    """``rates_summary`` per entry of A: ``{"A<i><j>": {"mean", "ll", "ul", "left_out"}}`` over the finite estimands of
+    ``hmm_estimate``."""
+    A = estimate["A"]
+    M = A.shape[1]
+    return {f"A{i}{j}": estimand_summary(A[:, i, j], probs) for i in range(M) for j in range(M)}
