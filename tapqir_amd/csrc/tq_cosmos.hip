@@ -513,7 +513,7 @@ extern "C" int tq_cosmos_minibatch_step(const tq_cosmos_args* a, const tq_cosmos
   const int upr = tq_mb_upr(*a);
   const dim3 grid((unsigned)((B + upr - 1) / upr) + 1), block(256);
   const int tail_last = tq_env_int("TAPQIR_AMD_MB_TAIL_LAST", 1) != 0 && grid.x > 1 && (grid.x - 1) % 256 == 0 && grid.x <= 513;  // (<= 2 workgroups per CU: all resident)
-  size_t lds = sizeof(float) * tq_tile16_lds_floats(a->P, a->K, a->O);
+  size_t lds = sizeof(float) * tq_tile16_lds_floats(a->P, a->K, a->O, TQ_UNITS_PER_BLOCK, !one);
   if (a->next_ndx || a->next_fdx) {
     if ((a->next_ndx && a->Nt > TQ_SUBSAMPLE_MAX) || (a->next_fdx && a->F > TQ_SUBSAMPLE_MAX)) {
       tq_set_error("tq_cosmos_minibatch_step: next_ndx / next_fdx need Nt, F <= TQ_SUBSAMPLE_MAX");

@@ -459,13 +459,13 @@ static int launch_kb(const tq_ksmogn_args& a, int64_t B, hipStream_t st) {
     // gathered batch is small: at 16 lanes per unit a 10 x 512 minibatch fills 1.25 waves per SIMD)
     constexpr int UNITS = TQ_BLOCK / 64;
     const dim3 gridw((unsigned)((B + UNITS - 1) / UNITS)), blockw(TQ_BLOCK);
-    const size_t ldsw = sizeof(float) * tq_tile16_lds_floats(a.P, K, a.O, UNITS);
+    const size_t ldsw = sizeof(float) * tq_tile16_lds_floats(a.P, K, a.O, UNITS, true);
     if (bwd) hipLaunchKernelGGL((tq_ksmogn_kernel<K, false, true, 64>), gridw, blockw, ldsw, st, a, B);
     else hipLaunchKernelGGL((tq_ksmogn_kernel<K, false, false, 64>), gridw, blockw, ldsw, st, a, B);
     return tq_launch_status("tq_ksmogn_kernel (64 lanes per unit)");
   }
   const dim3 grid((unsigned)((B + TQ_UNITS_PER_BLOCK - 1) / TQ_UNITS_PER_BLOCK)), block(TQ_BLOCK);
-  const size_t lds = sizeof(float) * tq_tile16_lds_floats(a.P, K, a.O);
+  const size_t lds = sizeof(float) * tq_tile16_lds_floats(a.P, K, a.O, TQ_UNITS_PER_BLOCK, !ONE);
   if (bwd) hipLaunchKernelGGL((tq_ksmogn_kernel<K, ONE, true>), grid, block, lds, st, a, B);
   else hipLaunchKernelGGL((tq_ksmogn_kernel<K, ONE, false>), grid, block, lds, st, a, B);
   return tq_launch_status("tq_ksmogn_kernel");

@@ -299,9 +299,17 @@ __device__ __forceinline__ void tq_pixel_loop(TqPixAcc<K>& A, const tq_ksmogn_ar
 // The 16 units [blk * 16, blk * 16 + 16) of the batch by one workgroup of 256 threads; `smem` holds
 // tq_tile16_lds_floats(P, K) floats.  Called by tq_ksmogn_kernel (tq_ksmogn.hip) and by the single-launch minibatch step
 // (tq_step_minibatch.h), which runs it between its sampling and per-unit phases.
+// The dynamic LDS of a launch, in floats.  No launch checks the request against the device: the most any admitted shape asks
+// for is 115728 B (K = TQ_MAX_K, P = TQ_MAX_P, O = TQ_OFFTAB_MAX, 16 slots), 124992 B with the 9264 B of static LDS of
+// tq_minibatch_kernel, against the 163840 B per workgroup the HIP runtime reports for gfx950 (MI355X,
+// hipDeviceAttributeMaxSharedMemoryPerBlock; no opt-in needed above 64 KB).  tests/helpers.py restates the formula
+// (lds_request_bytes) and the GPU tests check it against the reported limit before every launch; DESIGN.md section 23,
+// "Offset histograms at every length".  A larger TQ_MAX_P, TQ_OFFTAB_MAX or slot count has to keep that bound.
 #define TQ_OFFTAB_MAX 2048  /* offsets whose table the workgroup keeps in LDS (16 B each: 32 KB); longer histograms read global memory */
-__host__ __device__ inline size_t tq_tile16_lds_floats(int P, int K, int O = 1, int units = TQ_UNITS_PER_BLOCK) {
-  return (size_t)units * (tq_tile_stride(P * P) + 2 * K * TQ_MAX_P) + ((O > 1 && O <= TQ_OFFTAB_MAX) ? 4 + 4 * (size_t)O : 0);
+// `histogram_form`: the launch is of the ONE_OFFSET = false form, which builds its table at O = 1 as well (a caller that passes
+// one offset without pixel statistics); the single-offset form has none.
+__host__ __device__ inline size_t tq_tile16_lds_floats(int P, int K, int O = 1, int units = TQ_UNITS_PER_BLOCK, bool histogram_form = false) {
+  return (size_t)units * (tq_tile_stride(P * P) + 2 * K * TQ_MAX_P) + (((O > 1 || histogram_form) && O <= TQ_OFFTAB_MAX) ? 4 + 4 * (size_t)O : 0);
 }
 // LANES lanes per unit (16: sixteen units per workgroup of 256 threads; 64: four units, a wave each -- the offset-histogram
 // form of gathered batches, whose offset loop is long enough to want every wave slot of the chip: a 10 x 512 minibatch is

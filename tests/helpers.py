@@ -157,9 +157,59 @@ def make_dataset(N=4, F=6, C=1, P=14, K=2, seed=0, offsets="sim", mask=None):
         w = torch.exp(-0.5 * ((s - 90.0) / 4.0) ** 2)
         d = CosmosDataset(d.images, d.xy, d.is_ontarget, labels=d.labels, offset_samples=s,
                           offset_weights=(w / w.sum()).float())
+    if isinstance(offsets, tuple):  # ("grid", O, lo, hi, sigma): a histogram of any length, see offset_grid
+        s, w = offset_grid(*offsets[1:])
+        d = CosmosDataset(d.images, d.xy, d.is_ontarget, labels=d.labels, offset_samples=s, offset_weights=w)
     if mask is not None:
         d.mask = mask
     return d
+
+
+def offset_grid(O, lo=70.0, hi=110.0, sigma=6.0):
+    """An offset histogram of exactly ``O`` DISTINCT samples torch.linspace(lo, hi, O) (fractional spacing, like a bin size
+    below 1; merge_offsets keeps every one) with Gaussian weights of width ``sigma`` about 90, normalised, float64.
+    The simulated pixels are >= 141 at the suite's shapes, so [70, 110] keeps every offset below every pixel (the unmasked branch of the packed
+    kernel) at any length; hi = 330 reaches above the dimmest pixels (the masked branch, as "wide"); sigma = 2 spreads the
+    weights over more than 2^40 (merge_offsets clamps them at 2^-52: the non-factored form of the packed kernel, as "peaked")."""
+    s = torch.linspace(lo, hi, O, dtype=torch.float32)
+    assert O == 1 or bool((s[1:] > s[:-1]).all()), "offset samples must stay distinct in float32"
+    w = torch.exp(-0.5 * ((s.double() - 90.0) / sigma) ** 2)
+    return s, w / w.sum()
+
+
+def grid(O, lo=70.0, hi=110.0, sigma=6.0):
+    """``offsets=`` of make_dataset for offset_grid(O, lo, hi, sigma)."""
+    return ("grid", O, lo, hi, sigma)
+
+
+# ---- the LDS a launch of the 16-lane tile routine asks for ------------------------------------------------------------------
+# The request of tq_tile16_lds_floats (tapqir_amd/csrc/tq_ksmogn_dev.h), restated once: per unit slot the staged tile (npix
+# floats rounded up to 16 mod 32) and the separable factors (2 K rows of TQ_MAX_P), then, for 1 < O <= TQ_OFFTAB_MAX (and at O = 1 in the histogram form), the
+# offset table (4 extrema + 4 floats per offset).  16 slots for the 16-lane kernel and the single-launch minibatch step, 4 for
+# the wave-per-unit kernel of gathered histogram batches.  The minibatch kernel adds its static LDS (9264 B in the code
+# object: s_bias 8 KB, s_part, flags) and asks for at least TQ_SUBSAMPLE_LDS where it also draws the next subsample.
+LDS_MAX_P, LDS_OFFTAB_MAX, LDS_SLOTS, LDS_SLOTS_WAVE = 32, 2048, 16, 4
+MB_STATIC_LDS, SUBSAMPLE_LDS = 9264, 4 * (2048 + 8)
+
+
+def tile_stride(npix):
+    return ((npix + 15) // 32) * 32 + 16
+
+
+def lds_request_bytes(P, K, O=1, slots=LDS_SLOTS, minibatch=False, draws=False, no_pixstats=False):
+    """Bytes of LDS per workgroup of a launch: the dynamic request, plus (``minibatch``) the static LDS of
+    tq_minibatch_kernel; ``draws``: the launch also draws the next step's subsample; ``no_pixstats``: a caller that passes
+    O = 1 without pixel statistics gets the histogram form, which builds its (one-entry) table at O = 1 too."""
+    table = 4 + 4 * O if (1 < O or no_pixstats) and O <= LDS_OFFTAB_MAX else 0
+    dyn = 4 * (slots * (tile_stride(P * P) + 2 * K * LDS_MAX_P) + table)
+    if not minibatch:
+        return dyn
+    return max(dyn, SUBSAMPLE_LDS if draws else 0) + MB_STATIC_LDS
+
+
+def device_lds_limit(device=0):
+    """LDS a workgroup may ask for on this device, as the runtime reports it (hipDeviceAttributeMaxSharedMemoryPerBlock)."""
+    return int(torch.cuda.get_device_properties(device).shared_memory_per_block)
 
 
 def make_oracle(d, K, perturb=0.3, seed=1, eps=EPS32, crosstalk=False):
