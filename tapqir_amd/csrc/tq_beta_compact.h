@@ -23,6 +23,7 @@
 // (1-x)-small series down}, R3 = {saddle point of one direction}.  One 16-byte record per task.
 struct TqBetaCompactLds {
   float4 r1[2 * TQ_BC_NT], r2[2 * TQ_BC_NT], r3[TQ_BC_NT];  // {draw, its alpha, size, bits((lane << 2) | direction code)}
+                                                            // ((1-x)-small series: 1 - draw, which is what it takes)
   float c0[TQ_BC_NT];                                       // class 3: the other direction's alpha (rounding fallback)
   float res[2 * TQ_BC_NT];
   int cnt[8];                                               // tasks per class
@@ -49,13 +50,14 @@ __device__ __forceinline__ void tq_site_beta_compact(const tq_cosmos_args& a, co
   if (tid < 8) L.cnt[tid] = 0;
   __syncthreads();  // (at the top of the kernel: every wave arrives at once)
   TqSiteDraw d;
-  float t = 0.0f, c1 = 0.0f, c0 = 0.0f, size = 0.0f;
+  float t = 0.0f, omt = 1.0f, c1 = 0.0f, c0 = 0.0f, size = 0.0f;
   int r0 = -1, r1 = -1;
   bool pair = false, clamped = true;
   if (live) {
     d = tq_site_draw(a, site, i);
     const float sc = d.hi - d.lo, rsc = TQ_FRCP(sc);  // (the expressions of tq_affine_beta_site_terms)
     t = (d.val - d.lo) * rsc;
+    omt = tq_affine_one_minus_t(d.val, d.hi, rsc, t);
     size = d.p1;
     c1 = size * (d.p0 - d.lo) * rsc;
     c0 = size * (d.hi - d.p0) * rsc;
@@ -65,7 +67,7 @@ __device__ __forceinline__ void tq_site_beta_compact(const tq_cosmos_args& a, co
       if (!pair) {
         const double total = size;
         r0 = tq_dirichlet_grad_regime((double)t, (double)c1, total - (double)c1, total);
-        r1 = tq_dirichlet_grad_regime((double)(1.0f - t), (double)c0, total - (double)c0, total);
+        r1 = tq_dirichlet_grad_regime((double)omt, (double)c0, total - (double)c0, total);
       }
     }
   }
@@ -106,13 +108,13 @@ __device__ __forceinline__ void tq_site_beta_compact(const tq_cosmos_args& a, co
       L.c0[tid] = c0;
     }
     {
-      const float xf[2] = {t, 1.0f - t}, af[2] = {c1, c0};
+      const float xf[2] = {t, omt}, af[2] = {c1, c0};
       const int rr[2] = {r0, r1};
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int r = rr[j];
         if (r == 0) put(1, pos[1]++, xf[j], af[j], j);
-        if (r == 1) put(2, pos[2]++, xf[j], af[j], j);
+        if (r == 1) put(2, pos[2]++, xf[1 - j], af[j], j);  // (the series takes 1 - x: the record holds that)
         if (r == 3) put(4, pos[4]++, xf[j], af[j], j);
       }
     }
@@ -145,7 +147,7 @@ __device__ __forceinline__ void tq_site_beta_compact(const tq_cosmos_args& a, co
         } else if (c == 1) {
           L.res[2 * dst + code] = (float)tq_beta_grad_alpha_small((double)x, (double)al, total - (double)al);
         } else if (c == 2) {
-          L.res[2 * dst + code] = -tq_beta_grad_beta_small_f(1.0f - x, sz - al, al);
+          L.res[2 * dst + code] = -tq_beta_grad_beta_small_f(x, sz - al, al);
         } else if (c == 3) {
           double ga = 0.0, gb = 0.0;
           if (!tq_beta_grad_pair_mid<true>((double)x, (double)al, total - (double)al, &ga, &gb)) {

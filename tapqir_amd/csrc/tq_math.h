@@ -710,8 +710,10 @@ TQ_HD_NOINLINE float tq_dirichlet_grad(float x_, float alpha_, float total_) {
 // 1 - x >= 1/2 for the other), the (1-x)-small series or -- outside the pair routine -- the saddle point, so each of
 // series runs ONCE with per-lane arguments from whichever direction needs it; only the (float) rational regime can be
 // needed by both.
-TQ_HD_NOINLINE void tq_beta_grad_pair_rest(float t, float c1, float c0, float size, float* dd) {
-  const float xf[2] = {t, 1.0f - t};
+// omt = 1 - t as the caller knows it (an AffineBeta draw next to a bound: the complement of the small one of t, 1 - t must
+// not be formed from the rounded large one -- at 1 - t = 3e-7 that was 6 % of d t / d c0).
+TQ_HD_NOINLINE void tq_beta_grad_pair_rest(float t, float omt, float c1, float c0, float size, float* dd) {
+  const float xf[2] = {t, omt};
   const float af[2] = {c1, c0};
   const double total = size;
   int regime[2];
@@ -742,9 +744,10 @@ TQ_HD_NOINLINE void tq_beta_grad_pair_rest(float t, float c1, float c0, float si
       if (act) {
         const bool first = pass == 0 && n0;
         const float xs = first ? xf[0] : xf[1], as = first ? af[0] : af[1];
+        const float xc = first ? xf[1] : xf[0];  // 1 - xs
         float g;
         if (r == 0) g = (float)tq_beta_grad_alpha_small((double)xs, (double)as, total - (double)as);
-        else g = -tq_beta_grad_beta_small_f(1.0f - xs, size - as, as);
+        else g = -tq_beta_grad_beta_small_f(xc, size - as, as);
         if (first) dd[0] = g;
         else dd[1] = g;
       }
@@ -753,4 +756,8 @@ TQ_HD_NOINLINE void tq_beta_grad_pair_rest(float t, float c1, float c0, float si
 #pragma nounroll
   for (int j = 0; j < 2; ++j)
     if (regime[j] == 3) dd[j] = tq_beta_grad_rational(xf[j], af[j], size);
+}
+// (the draw alone: 1 - t formed here, for callers that have nothing better)
+TQ_HD void tq_beta_grad_pair_rest(float t, float c1, float c0, float size, float* dd) {
+  tq_beta_grad_pair_rest(t, 1.0f - t, c1, c0, size, dd);
 }

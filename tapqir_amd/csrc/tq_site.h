@@ -58,15 +58,84 @@ struct TqSiteConsts {
   float bg_mean_std, bg_std_std;  // only used by the AOI kernel
 };
 
-// ln(1 + u) with the rounding of 1 + u compensated (|u| < 1/2): one hardware log, one reciprocal
+// ln(1 + u) for -1/2 <= u <= 1 without a logarithm: 2 atanh(s), s = u / (2 + u), |s| <= 1/3.  Four terms up to |u| = 1/4
+// (the next one is below 3e-11 of the result), seven beyond.  The result is RELATIVELY accurate however small u is.  (It
+// was one hardware logarithm of 1 + u with the rounding of the sum compensated: the device's log2 is good to an ulp of its
+// argument near 1, not of its result, and the densities below multiply ln(1 + u) by concentrations of hundreds -- 1e-5 of
+// log q at c1 = 90.  The short form costs what that one did.)
 TQ_HD float tq_log1p_small(float u) {
+  const float s = u * TQ_FRCP(2.0f + u);
+  const float s2 = s * s;
+  float p = 1.0f / 3.0f + s2 * (1.0f / 5.0f + s2 * (1.0f / 7.0f + s2 * (1.0f / 9.0f)));
+  if (s2 > 0.0125f)
+    p = 1.0f / 3.0f + s2 * (1.0f / 5.0f + s2 * (1.0f / 7.0f + s2 * (1.0f / 9.0f + s2 * (1.0f / 11.0f + s2 * (1.0f / 13.0f + s2 * (1.0f / 15.0f))))));
+  const float s_2 = s + s;
+  return s_2 + s_2 * (s2 * p);
+}
+// ln(1 + u), |u| < 1/2, from one hardware logarithm of 1 + u with the rounding of the sum compensated: what the Binet branch
+// of tq_beta_logpdf uses for a draw within half its concentration of the mean (every draw at the initial parameters), where
+// its two terms (c1 - 1) u1 + (c0 - 1) u0 take their errors with opposite signs
+TQ_HD float tq_log1p_hw(float u) {
   const float w = 1.0f + u;
   return TQ_FLOG(w) - ((w - 1.0f) - u) * TQ_FRCP(w);
+}
+// ln x of a float, good to 4e-8 absolutely whatever its size: the exponent times ln 2 in double, the mantissa, brought to
+// [3/4, 3/2), through the seven-term form of tq_log1p_small
+TQ_HD double tq_log_split(float x) {
+  int e;
+  float m = frexpf(x, &e);  // [1/2, 1)
+  if (m < 0.75f) {
+    m += m;
+    e -= 1;
+  }
+  const float u = m - 1.0f, s = u * TQ_FRCP(2.0f + u), s2 = s * s;
+  const float p = 1.0f / 3.0f + s2 * (1.0f / 5.0f + s2 * (1.0f / 7.0f + s2 * (1.0f / 9.0f + s2 * (1.0f / 11.0f + s2 * (1.0f / 13.0f + s2 * (1.0f / 15.0f))))));
+  const float s_2 = s + s;
+  return fma((double)e, 0.69314718055994530942, (double)(s_2 + s_2 * (s2 * p)));
+}
+// ... of a double inside the float range: the rounding of z to float put back to first order
+TQ_HD double tq_log_split(double z) {
+  const float zf = (float)z;
+  return tq_log_split(zf) + (z - (double)zf) * (double)TQ_FRCP(zf);
+}
+// lgamma(a), 0 < a < 16, to about 5e-7 absolutely: shifted up by 8 with the sums in double and the
+// logarithms from tq_log_split.  (The fp32 form of tq_lgamma_digamma builds its result from terms of ~40 and is good to
+// 4e-6; the general double routine tq_lgamma_digamma_d costs five times this one.)
+// (fp32: sixteen roundings of 6e-8 each, 1e-6 of the logarithm at worst and 3e-7 typically; in double the three products
+// of the normaliser were a fifth of the sampling launch of a converged fit)
+TQ_HD float tq_shift8_product(float a) {
+  float prod = a;
+#pragma unroll
+  for (int i = 1; i < 8; ++i) prod *= a + (float)i;
+  return prod;
+}
+TQ_HD double tq_lgamma_shift8(float a) {
+  const double ad = a, b = ad + 8.0;
+  float S, dS;
+  tq_binet_series<float>((float)b, TQ_FRCP((float)b), &S, &dS);
+  return (b - 0.5) * tq_log_split(b) - b + 0.91893853320467274178 + (double)S - tq_log_split(tq_shift8_product(a));
+}
+// lgamma(c1 + c0) - lgamma(c1) - lgamma(c0) for c1, c0 < 8, the same way with the three products under one logarithm
+TQ_HD float tq_neg_lbeta_shift8(float c1, float c0) {
+  const double a1 = c1, a0 = c0, aT = a1 + a0;
+  const double b1 = a1 + 8.0, b0 = a0 + 8.0, bT = aT + 8.0;
+  float S1, S0, ST, dS;
+  tq_binet_series<float>((float)b1, TQ_FRCP((float)b1), &S1, &dS);
+  tq_binet_series<float>((float)b0, TQ_FRCP((float)b0), &S0, &dS);
+  tq_binet_series<float>((float)bT, TQ_FRCP((float)bT), &ST, &dS);
+  const float ratio = tq_shift8_product(c1) * tq_shift8_product(c0) * TQ_FRCP(tq_shift8_product(c1 + c0));
+  const double logs = (bT - 0.5) * tq_log_split(bT) - (b1 - 0.5) * tq_log_split(b1) - (b0 - 0.5) * tq_log_split(b0);
+  return (float)(logs + (8.0 - 0.91893853320467274178) + tq_log_split(ratio)) + (ST - S1 - S0);
 }
 
 // ---- log-densities with derivatives ---------------------------------------------------------------
 // Gamma(v; alpha = loc*beta, rate = beta) in the cancellation-free form (see tq_pixel.h):
 //   = -ln v + alpha phi(v/loc) + (1/2) ln alpha - ln sqrt(2pi) - S(alpha)
+// SITE: the form of the guide sites (tq_gamma_site_terms), where phi = ln rho + 1 - rho = O((rho - 1)^2) near the mean comes
+// from u = (v - loc) / loc and a relatively accurate log1p: 1 - rho carries the rounding of rho, 6e-8, and the hardware
+// logarithm as much, which alpha = 1500 of a converged height site turned into 1e-4 of log q.  The per-unit phase evaluates
+// the background prior with the short form (its machine code is the dominant kernel's; not changed here).
+template <bool SITE = false>
 TQ_HD void tq_gamma_logpdf(float v, float loc, float beta, float* lp, float* d_v, float* d_alpha, float* d_beta) {
   const float alpha = loc * beta;
   const float rloc = TQ_FRCP(loc);
@@ -74,20 +143,31 @@ TQ_HD void tq_gamma_logpdf(float v, float loc, float beta, float* lp, float* d_v
   const float lnv = TQ_FLOG(v);
   // ln(v / loc): log1p near the mean (no cancellation in phi), difference of logs far from it (a draw many orders of
   // magnitude below loc, as Gamma draws with concentration < 1 are, must not round (v - loc) / loc to -1)
-  const float lrho = (fabsf(v - loc) < 0.5f * loc) ? tq_log1p_small((v - loc) * rloc) : lnv - TQ_FLOG(loc);
+  const bool near = fabsf(v - loc) < 0.5f * loc;
+  const float u = (v - loc) * rloc;  // rho - 1 (v - loc is exact near the mean)
+  float lrho, phi;
+  if (SITE) {
+    lrho = near ? tq_log1p_small(u) : lnv - TQ_FLOG(loc);
+    phi = near ? lrho - u : lrho + 1.0f - rho;
+  } else {
+    lrho = near ? tq_log1p_hw(u) : lnv - TQ_FLOG(loc);
+    phi = lrho + 1.0f - rho;
+  }
   const float lna = TQ_FLOG(alpha), ra = TQ_FRCP(alpha);
   float S, dS;
   tq_binet(alpha, lna, ra, &S, &dS);
-  *lp = -lnv + alpha * (lrho + 1.0f - rho) + 0.5f * lna - TQ_LN_SQRT_2PI - S;
+  *lp = -lnv + alpha * phi + 0.5f * lna - TQ_LN_SQRT_2PI - S;
   *d_v = (alpha - 1.0f) * TQ_FRCP(v) - beta;
   *d_alpha = lrho + 0.5f * ra - dS;  // = ln beta + ln v - digamma(alpha)
   *d_beta = loc - v;                 // = alpha / beta - v
 }
 
-// Beta(t; c1, c0)
-TQ_HD void tq_beta_logpdf(float t, float c1, float c0, float* lp, float* d_t, float* d_c1, float* d_c0) {
+// Beta(t; c1, c0).  omt = 1 - t as the caller knows it: formed from a rounded t it has lost half its digits by t = 1 - 2 eps
+// (an AffineBeta draw on its upper clamp: log q off by 0.6, d lq/d c0 by 0.76 at c0 = 0.18, 8 % of that unit's gradient of
+// x_mean), formed as (high - y) / scale it is as good as t is near 0.
+TQ_HD void tq_beta_logpdf(float t, float omt, float c1, float c0, float* lp, float* d_t, float* d_c1, float* d_c0) {
   const float T = c1 + c0;
-  *d_t = (c1 - 1.0f) * TQ_FRCP(t) - (c0 - 1.0f) * TQ_FRCP(1.0f - t);
+  *d_t = (c1 - 1.0f) * TQ_FRCP(t) - (c0 - 1.0f) * TQ_FRCP(omt);
   if (c1 >= 8.0f && c0 >= 8.0f) {
     // Binet form throughout: lgamma(a) = (a - 1/2) ln a - a + ln sqrt(2 pi) + S(a), psi(a) = ln a - 1/(2a) + S'(a).
     // d lp / d c1 = ln t - psi(c1) + psi(T) is O(|t - mean| / mean + 1/c) while its three terms are O(ln c): the
@@ -98,20 +178,57 @@ TQ_HD void tq_beta_logpdf(float t, float c1, float c0, float* lp, float* d_t, fl
     tq_binet_series<float>(c0, r0, &S0, &dS0);
     tq_binet_series<float>(T, rT, &ST, &dST);
     const float num = t * T - c1;
-    const float u1 = tq_log1p_small(num * r1), u0 = tq_log1p_small(-num * r0);  // ln(t T / c1), ln((1-t) T / c0)
+    // ln(t T / c1), ln((1-t) T / c0).  A draw far out in a tail (in practice: a given draw, or one on the clamp) has
+    // |u| >= 1/2, outside tq_log1p_small (the former form gave 0.29 of error in d lq/d c1 at t = eps): the quotient is
+    // formed by multiplication there.
+    const float x1 = num * r1, x0 = -num * r0;
+    float u1, u0;
+    if (__builtin_expect(fabsf(num) < 0.5f * fminf(c1, c0), 1)) {
+      u1 = tq_log1p_hw(x1);
+      u0 = tq_log1p_hw(x0);
+    } else {
+      u1 = fabsf(x1) < 0.5f ? tq_log1p_small(x1) : TQ_FLOG(t * (T * r1));
+      u0 = fabsf(x0) < 0.5f ? tq_log1p_small(x0) : TQ_FLOG(omt * (T * r0));
+    }
     // (c1-1) ln t + (c0-1) ln(1-t) + lgamma(T) - lgamma(c1) - lgamma(c0) with ln t = u1 + ln(c1/T) etc.: the O(c ln c)
     // terms cancel analytically, leaving (c1-1) u1 + (c0-1) u0 + (3/2) ln T - (1/2)(ln c1 + ln c0) - ln sqrt(2 pi) + S terms
     *lp = ((c1 - 1.0f) * u1 + (c0 - 1.0f) * u0) + (1.5f * TQ_FLOG(T) - 0.5f * (TQ_FLOG(c1) + TQ_FLOG(c0))) - TQ_LN_SQRT_2PI +
           (ST - S1 - S0);
     *d_c1 = u1 + 0.5f * (r1 - rT) + (dST - dS1);
     *d_c0 = u0 + 0.5f * (r0 - rT) + (dST - dS0);
+  } else if (fmaxf(c1, c0) >= 8.0f) {
+    // One concentration below 8 (a converged fit: a mean near one end of the support), the other one and T in the Binet
+    // range.  lgamma(T) and lgamma(big) are O(T ln T) each (500 at T = 135) and differ by O(small ln T): formed apart in
+    // fp32 they left 1e-4 of absolute error in log q.  With ln T - ln big = log1p(small / big):
+    //   lgamma(T) - lgamma(big) = (big - 1/2) ln(T / big) + small (ln T - 1) + S(T) - S(big)
+    //   psi(T) - psi(big)       = ln(T / big) + (1/big - 1/T) / 2 + S'(T) - S'(big)
+    // and small ln T goes with (small - 1) ln x: (small - 1) ln(x T) + ln T, ln(x T) = O(ln small).
+    const bool big1 = c1 > c0;
+    const float cs = big1 ? c0 : c1, cb = big1 ? c1 : c0;
+    const float xs = big1 ? omt : t, xb = big1 ? t : omt;  // the variable each concentration is the exponent of
+    const float lsT = TQ_FLOG(xs * T), lb = xs < 0.5f ? tq_log1p_small(-xs) : TQ_FLOG(xb);  // (xb = 1 - xs)
+    const float rb = TQ_FRCP(cb), rT = TQ_FRCP(T), lnT = TQ_FLOG(T);
+    float Sb, dSb, ST, dST;
+    float lgs_f, dgs;  // (digamma from the fp32 routine; its lgamma, built from terms of ~40, is good to 4e-6 only)
+    tq_lgamma_digamma(cs, &lgs_f, &dgs);
+    const float lgs = (float)tq_lgamma_shift8(cs);
+    tq_binet_series<float>(cb, rb, &Sb, &dSb);
+    tq_binet_series<float>(T, rT, &ST, &dST);
+    const float lTb = tq_log1p_small(cs * rb);  // ln(T / big), small / big < 1
+    *lp = ((cs - 1.0f) * lsT + ((cb - 1.0f) * lb + (cb - 0.5f) * lTb)) + ((lnT - cs) - lgs) + (ST - Sb);
+    const float d_s = (lsT - dgs) - 0.5f * rT + dST;
+    const float d_b = (lb + lTb) + 0.5f * (rb - rT) + (dST - dSb);
+    *d_c1 = big1 ? d_b : d_s;
+    *d_c0 = big1 ? d_s : d_b;
   } else {
-    const float lt = TQ_FLOG(t), l1t = TQ_FLOG(1.0f - t);
+    // Both concentrations below 8 (absent spots of a converged fit: size 5 .. 18).  Three shifted fp32 lgammas, each formed
+    // from terms of ~40, left 8e-6 in a log q of O(1): the normaliser from tq_neg_lbeta_shift8 (the digammas stay in fp32).
+    const float lt = TQ_FLOG(t), l1t = TQ_FLOG(omt);
     float lg1, dg1, lg0, dg0, lgt, dgt;
     tq_lgamma_digamma(c1, &lg1, &dg1);
     tq_lgamma_digamma(c0, &lg0, &dg0);
     tq_lgamma_digamma(T, &lgt, &dgt);
-    *lp = (c1 - 1.0f) * lt + (c0 - 1.0f) * l1t + lgt - lg1 - lg0;
+    *lp = ((c1 - 1.0f) * lt + (c0 - 1.0f) * l1t) + tq_neg_lbeta_shift8(c1, c0);
     *d_c1 = lt - dg1 + dgt;
     *d_c0 = l1t - dg0 + dgt;
   }
@@ -131,6 +248,9 @@ TQ_HD void tq_beta_logpdf(float t, float c1, float c0, float* lp, float* d_t, fl
 // phase holds anyway, and are rebuilt there (48 B per unit less written by one launch and read by the next at K = 2).
 //   stored rows: 0 = s[0], 1 = s[2], 2 = s[4], and for AffineBeta sites 3 = s[3], 4 = s[5]
 #define TQ_NSITE_STORED 5
+// 1 - t of an AffineBeta draw y, t = (y - low) / scale: from t in the lower half of the support (t carries its relative
+// rounding, 1 - t half an ulp of 1), from the draw itself in the upper half, where high - y is exact (see tq_beta_logpdf)
+TQ_HD float tq_affine_one_minus_t(float y, float high, float rsc, float t) { return t < 0.5f ? 1.0f - t : (high - y) * rsc; }
 TQ_HD void tq_gamma_terms_expand(const float* c, float v, float loc, float beta, float* s) {
   s[0] = c[0];
   s[1] = (loc * beta - 1.0f) * TQ_FRCP(v) - beta;  // d lq / d v   (tq_gamma_logpdf)
@@ -141,11 +261,11 @@ TQ_HD void tq_gamma_terms_expand(const float* c, float v, float loc, float beta,
 }
 TQ_HD void tq_affine_beta_terms_expand(const float* c, float y, float mean, float size, float low, float high, float* s) {
   const float rsc = TQ_FRCP(high - low);
-  const float t = (y - low) * rsc;
+  const float t = (y - low) * rsc, omt = (high - y) * rsc;  // (1 - t from the draw: a reciprocal needs its relative rounding only)
   const float c1 = size * (mean - low) * rsc;
   const float c0 = size * (high - mean) * rsc;
   s[0] = c[0];
-  s[1] = ((c1 - 1.0f) * TQ_FRCP(t) - (c0 - 1.0f) * TQ_FRCP(1.0f - t)) * rsc;  // d lq / d y   (tq_beta_logpdf, tq_affine_beta_site_terms)
+  s[1] = ((c1 - 1.0f) * TQ_FRCP(t) - (c0 - 1.0f) * TQ_FRCP(omt)) * rsc;  // d lq / d y   (tq_beta_logpdf, tq_affine_beta_site_terms)
   s[2] = c[1];
   s[3] = c[3];
   s[4] = c[2];
@@ -154,7 +274,7 @@ TQ_HD void tq_affine_beta_terms_expand(const float* c, float y, float mean, floa
 
 TQ_HD void tq_gamma_site_terms(float v, float loc, float beta, float* s) {
   float lq, d_v, d_alpha, d_beta;
-  tq_gamma_logpdf(v, loc, beta, &lq, &d_v, &d_alpha, &d_beta);
+  tq_gamma_logpdf<true>(v, loc, beta, &lq, &d_v, &d_alpha, &d_beta);
   s[0] = lq;
   s[1] = d_v;
   s[2] = d_alpha;
@@ -173,7 +293,8 @@ TQ_HD void tq_affine_beta_site_terms(float y, float mean, float size, float low,
   const float c1 = size * (mean - low) * rsc;
   const float c0 = size * (high - mean) * rsc;
   float lq, d_t, d_c1, d_c0;
-  tq_beta_logpdf(t, c1, c0, &lq, &d_t, &d_c1, &d_c0);
+  const float omt = tq_affine_one_minus_t(y, high, rsc, t);
+  tq_beta_logpdf(t, omt, c1, c0, &lq, &d_t, &d_c1, &d_c0);
   s[0] = lq - TQ_FLOG(sc);
   s[1] = d_t * rsc;
   s[2] = d_c1;
@@ -190,10 +311,10 @@ TQ_HD void tq_affine_beta_site_terms(float y, float mean, float size, float low,
       dd[0] = (float)ga;  // common case: both directions in the saddle-point regime, evaluated together
       dd[1] = (float)gb;
     } else {
-      tq_beta_grad_pair_rest(t, c1, c0, size, dd);  // the other regimes, each run once for both directions
+      tq_beta_grad_pair_rest(t, omt, c1, c0, size, dd);  // the other regimes, each run once for both directions
     }
   }
-  s[4] = sc * dd[0] * (1.0f - t);
+  s[4] = sc * dd[0] * omt;
   s[5] = -sc * dd[1] * t;
 }
 

@@ -267,10 +267,14 @@ def put_latents(eng, lat32, base):
     eng.gbase.copy_(gb)
 
 
-def oracle_grads(o, ndx, fdx, base):
+def oracle_grads(o, ndx, fdx, base, detach=None):
+    """``detach``: {latent name: mask} of draws that carry no pathwise gradient (the kernels' float32 clamp of an AffineBeta
+    draw, which the float64 oracle does not reach at the same value: torch's clamp passes no gradient for a clamped draw)."""
     for u in o.params.values():
         u.grad = None
     lat = o.latents_from_base(o.params, ndx, fdx, base)
+    for n, mask in (detach or {}).items():
+        lat[n] = torch.where(mask.reshape(lat[n].shape), lat[n].detach(), lat[n])
     elbo = o.elbo(o.params, ndx, fdx, lat)
     elbo.backward()
     return float(elbo.detach()), {n: (u.grad.clone() if u.grad is not None else torch.zeros_like(u)) for n, u in o.params.items()}
@@ -319,7 +323,7 @@ FP32_FACTOR = 16   # allowance over the plain-fp32 oracle's own error: 2 (hardwa
 #                    sums of 196-400 pixel terms against torch's pairwise sums) x 2 (fp32 series of the implicit gradients)
 
 
-def oracle_grads32(o, nd, fd, base):
+def oracle_grads32(o, nd, fd, base, detach=None):
     """The gradients of ``oracle_grads`` from the reference's plain float32 evaluation: a second oracle built inside
     ``oracle.cosmos.working_dtype(torch.float32)`` on the same data with the same parameter values, the base draws cast to
     float32.  Returns float64 tensors.  |oracle_grads32 - oracle_grads| is the error fp32 torch makes on the same formula."""
@@ -330,7 +334,7 @@ def oracle_grads32(o, nd, fd, base):
         od = OracleData(d.images, d.xy, d.is_ontarget, d.offset_samples, d.offset_weights, mask=d.mask)
         t = type(o)(od, K=o.K, priors=o.priors, eps=o.eps)
         t.params = {n: u.detach().float().requires_grad_(True) for n, u in o.params.items()}
-        _, g = oracle_grads(t, nd, fd, {k: v.float() for k, v in base.items()})
+        _, g = oracle_grads(t, nd, fd, {k: v.float() for k, v in base.items()}, detach=detach)
     return {n: v.double() for n, v in g.items()}
 
 
@@ -457,11 +461,13 @@ def gradient_report(capsys, request):
 ELBO_RTOL, PARAM_ATOL = 2e-5, 1e-4
 
 
-def replay_steps(eng, o, step, steps=3, where="replay", norm_only=()):
+def replay_steps(eng, o, step, steps=3, where="replay", norm_only=(), clamped=None):
     """``step(eng, it)`` runs step ``it`` on the engine and returns the AOI and frame indices it ran on (host int64 tensors).
     The oracle replays each step from the device's draws: -ELBO to ELBO_RTOL, every parameter after the update to
     PARAM_ATOL; and -- what the parameters cannot show -- the gradient of every parameter recovered from the moments,
-    the second moments and the update itself (check_step).  Then the oracle's parameters go back into the engine."""
+    the second moments and the update itself (check_step).  Then the oracle's parameters go back into the engine.
+    ``clamped(o, lat32)``: a hook that returns, per step, {latent name: mask} of the read-back draws the kernel treated as
+    clamped; the oracle detaches those before the ELBO (oracle_grads).  Without it nothing changes."""
     cuda = eng.device.type == "cuda"
     for it in range(steps):
         before = engine_state(eng)  # (joins: every unit current)
@@ -473,8 +479,9 @@ def replay_steps(eng, o, step, steps=3, where="replay", norm_only=()):
         lat32 = read_engine_latents(eng, len(nd), len(fd))
         with torch.no_grad():
             base = o.base_draws(lat32, o._guide_dists(o.constrained(o.params), nd, fd))
-        elbo_o, g64 = oracle_grads(o, nd, fd, base)  # at the pre-step parameters: the gradients the oracle's own step takes
-        g32 = oracle_grads32(o, nd, fd, base)
+        det = None if clamped is None else clamped(o, lat32)
+        elbo_o, g64 = oracle_grads(o, nd, fd, base, detach=det)  # at the pre-step parameters: the gradients the oracle's own step takes
+        g32 = oracle_grads32(o, nd, fd, base, detach=det)
         for n, u in o.params.items():  # CosmosOracle.step on those gradients (the loss is -ELBO)
             u.grad = -g64[n]
             o.optim[n].step()

@@ -292,6 +292,26 @@ void hc_cosmos_sample_locals(const tq_cosmos_args* a) {
   for (int site = 0; site < 1 + 4 * a->K; ++site)
     for (int64_t i = 0; i < B; ++i) tq_body_site(*a, site, i);
 }
+// The float32 values the site terms are evaluated at, out[3][(1 + 4K) B]: Gamma sites v, alpha = loc beta, beta; AffineBeta
+// sites t, c1, c0 (the expressions of tq_gamma_logpdf and tq_affine_beta_site_terms).  The tests separate the rounding of
+// these inputs from the arithmetic after them.
+void hc_cosmos_site_inputs(const tq_cosmos_args* a, float* out) {
+  const int64_t B = tq_batch_units(*a), NS = (int64_t)(1 + 4 * a->K) * B;
+  for (int site = 0; site < 1 + 4 * a->K; ++site)
+    for (int64_t i = 0; i < B; ++i) {
+      const TqSiteDraw d = tq_site_draw(*a, site, i);
+      if (site <= a->K) {
+        out[d.t] = d.val;
+        out[NS + d.t] = d.p0 * d.p1;
+        out[2 * NS + d.t] = d.p1;
+      } else {
+        const float rsc = TQ_FRCP(d.hi - d.lo);
+        out[d.t] = (d.val - d.lo) * rsc;
+        out[NS + d.t] = d.p1 * (d.p0 - d.lo) * rsc;
+        out[2 * NS + d.t] = d.p1 * (d.hi - d.p0) * rsc;
+      }
+    }
+}
 
 }  // extern "C"
 
