@@ -832,6 +832,41 @@ typedef struct {
 
 int tq_hmm_estimate(const tq_hmm_estimate_args* a, void* stream);
 
+/* tq_chain_dwell: the rasters of tq_hmm_count walked into dwell-time intervals and first-binding frames as they are drawn
+ * (`dwelltime --smooth` / `ttfb --smooth` with `--unbound-states U --bound-states B`); neither a
+ * raster nor the state pairs are stored.
+ * Row (s, n) is, state for state, the row tq_hmm_count draws for the same filt, theta, U, B and seed: the same Philox
+ * stream (seed, step = s, site 0xA04, elem = n), the same order of draws (u_0 for frame F - 1, then downwards, four
+ * uniforms to a Philox block), the same floor of theta, thresholds t(i) and double compare -- so one seed gives
+ * `smooth --bound-states B` and the two kinetics commands rasters of the same chain.  The class z = (state >= U) of every
+ * frame goes through the walker of tq_smooth_dwell, and the outputs are tq_smooth_dwell's for that class raster:
+ *   mode TQ_DWELL_COUNT: counts[s, n] = number of intervals of the row; every interior interval (low_or_high 0 / 1) of
+ *     dwell time d adds 1 to hist_unbound[s, d] / hist_bound[s, d] (the caller zeroes both histograms); and, when tau is
+ *     not NULL, tau[s, n] = the smallest f with a bound state, or F if there is none.
+ *   mode TQ_DWELL_EMIT: the same draws again; the table `intervals` of tq_dwell_sample's EMIT, (sample, AOI) row-major and
+ *     ascending in start_frame within a row.  The k-th run a row closes is written at offsets[s, n] + counts[s, n] - 1 - k; a
+ *     position outside [offsets[s, n], min(offsets[s, n] + counts[s, n], total)) is dropped, never written.  total = 0
+ *     launches nothing.
+ * TQ_ERR_ARG, before anything touches the device, for a NULL required pointer of the mode, N, F or S < 1,
+ * F > TQ_SMOOTH_MAX_F, S > 65535 * 64, total < 0, an unknown mode, U or B < 1 or U + B > TQ_HMM_MAX_STATES. */
+typedef struct {
+  const double* filt;          /* (N, F, M) of tq_hmm_estep */
+  const double* theta;         /* (M * M + M); device memory */
+  int32_t* counts;             /* (S, N) out (COUNT), in (EMIT) */
+  int32_t* hist_bound;         /* (S, F) in/out (COUNT): interior bound runs by dwell time */
+  int32_t* hist_unbound;       /* (S, F) in/out (COUNT): interior unbound runs by dwell time */
+  float* tau;                  /* (S, N) out (COUNT): integer-valued first-binding frames in [0, F]; or NULL */
+  const int64_t* offsets;      /* (S, N) in (EMIT): exclusive scan of counts */
+  int32_t* intervals;          /* (TQ_DWELL_COLS, total) out (EMIT) */
+  int64_t total;               /* EMIT: number of intervals (the column stride) */
+  int32_t N, F, S;
+  int32_t U, B;                /* unbound and bound states, M = U + B */
+  int32_t mode;                /* TQ_DWELL_COUNT or TQ_DWELL_EMIT */
+  uint64_t seed;
+} tq_chain_dwell_args;
+
+int tq_chain_dwell(const tq_chain_dwell_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame

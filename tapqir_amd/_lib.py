@@ -218,6 +218,7 @@ EXPORTS = [
     "tq_smooth_estep", "tq_smooth_mstep", "tq_smooth_viterbi", "tq_smooth_count",  # ... tapqir_amd/_lib_smooth.py
     "tq_smooth_dwell",
     "tq_hmm_estep", "tq_hmm_mstep", "tq_hmm_viterbi", "tq_hmm_count", "tq_hmm_estimate",  # ... tapqir_amd/_lib_hmm.py
+    "tq_chain_dwell",
 ]
 
 _lib = None

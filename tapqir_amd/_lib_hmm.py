@@ -1,8 +1,8 @@
 """
 ctypes mirrors of the multi-state hidden-Markov smoothing entry points of ``libtapqir_hip.so`` (``tq_hmm_estep`` /
-``tq_hmm_mstep`` / ``tq_hmm_viterbi`` / ``tq_hmm_count`` / ``tq_hmm_estimate``, include/tapqir_hip.h).  Import this
-module as a module (``from tapqir_amd import _lib_hmm``); ``lib()`` returns the library of ``tapqir_amd._lib.load()``
-with the five prototypes bound.
+``tq_hmm_mstep`` / ``tq_hmm_viterbi`` / ``tq_hmm_count`` / ``tq_hmm_estimate`` / ``tq_chain_dwell``,
+include/tapqir_hip.h).  Import this module as a module (``from tapqir_amd import _lib_hmm``); ``lib()`` returns the
+library of ``tapqir_amd._lib.load()`` with the six prototypes bound.
 """
 
 import ctypes as C
@@ -61,10 +61,22 @@ class HmmEstimateArgs(C.Structure):
     ]
 
 
+class ChainDwellArgs(C.Structure):
+    """``tq_chain_dwell_args`` (include/tapqir_hip.h); ``mode`` is ``_lib.DWELL_COUNT`` or ``_lib.DWELL_EMIT``."""
+
+    _fields_ = [
+        ("filt", C.c_void_p), ("theta", C.c_void_p), ("counts", C.c_void_p), ("hist_bound", C.c_void_p),
+        ("hist_unbound", C.c_void_p), ("tau", C.c_void_p), ("offsets", C.c_void_p), ("intervals", C.c_void_p),
+        ("total", C.c_int64), ("N", C.c_int32), ("F", C.c_int32), ("S", C.c_int32), ("U", C.c_int32), ("B", C.c_int32),
+        ("mode", C.c_int32), ("seed", C.c_uint64),
+    ]
+
+
 def bind(lib):
-    """Set the prototypes of the five entry points on a loaded library; returns it."""
+    """Set the prototypes of the six entry points on a loaded library; returns it."""
     for name, args in (("tq_hmm_estep", HmmEstepArgs), ("tq_hmm_mstep", HmmMstepArgs), ("tq_hmm_viterbi", HmmViterbiArgs),
-                       ("tq_hmm_count", HmmCountArgs), ("tq_hmm_estimate", HmmEstimateArgs)):
+                       ("tq_hmm_count", HmmCountArgs), ("tq_hmm_estimate", HmmEstimateArgs),
+                       ("tq_chain_dwell", ChainDwellArgs)):
         fn = getattr(lib, name)
         fn.argtypes = [C.POINTER(args), C.c_void_p]
         fn.restype = C.c_int

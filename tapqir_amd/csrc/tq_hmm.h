@@ -5,7 +5,9 @@
 //   * products of MxM matrices kept in range by powers of two, and what one lane of the E-step does with its chunk of
 //     frames (tq_smooth_lane_range): the chunk product, the forward sweep from the chunk's exclusive prefix, the backward
 //     sweep from its exclusive suffix with the pair marginals;
-//   * the M-step of the summed rows, the Viterbi path of a row in hidden states, and the backward sampler's thresholds.
+//   * the M-step of the summed rows, the Viterbi path of a row in hidden states, and the backward sampler's thresholds;
+//   * the sampler's uniforms in its order of draws, and a row drawn backwards and walked, as it is drawn, into runs of
+//     equal class (tq_chain_dwell).
 // The two-state bodies of tq_smooth.h are not touched; this is their generalisation next to them.  Nothing here
 // subtracts nearly equal quantities: a_f is stored whole, and the sampler's thresholds are sums of tails.
 // The __global__ wrappers are in tq_hmm.hip; the test suite runs the same bodies from a g++ build.
@@ -365,3 +367,61 @@ TQ_HD int tq_hmm_label(double u, const double* t) {
   for (int i = 1; i < M; ++i) z = u < t[i - 1] ? i : z;
   return z;
 }
+
+// ---- backward sampler walked into intervals (tq_chain_dwell) --------------------------------------
+// The uniforms of row (s, n) in the order the sampler takes them: u_k belongs to frame F - 1 - k.  One Philox block is four
+// of them, drawn together when k & 3 == 0 so that its words stay in registers; the values are those of one tq_uniform
+// per frame.
+struct TqHmmDraws {
+  TqPhilox ph;
+  double u0, u1, u2, u3;
+};
+
+TQ_HD void tq_hmm_draws_begin(TqHmmDraws& d, uint64_t seed, int s, int n) {
+  tq_hmm_stream(&d.ph, seed, s, n);
+  d.u0 = d.u1 = d.u2 = d.u3 = 0.0;
+}
+
+TQ_HD double tq_hmm_draws_next(TqHmmDraws& d, int k) {
+  if ((k & 3) == 0) {
+    d.u0 = (double)tq_uniform(&d.ph);
+    d.u1 = (double)tq_uniform(&d.ph);
+    d.u2 = (double)tq_uniform(&d.ph);
+    d.u3 = (double)tq_uniform(&d.ph);
+  }
+  return (k & 3) == 0 ? d.u0 : (k & 3) == 1 ? d.u1 : (k & 3) == 2 ? d.u2 : d.u3;
+}
+
+// What a row keeps while it is drawn from frame F - 1 down to 0 and walked, as it is drawn, into runs of equal class: the
+// hidden state of the frame after the current one, the walker of tq_smooth.h on the class z = (state >= U), and the
+// lowest frame seen bound so far -- after frame 0 the first bound frame of the row, or F.
+struct TqChainDwellRow {
+  TqSmoothWalk w;
+  int next;
+  int tau;
+};
+
+TQ_HD void tq_chain_dwell_begin(TqChainDwellRow& r, int F) {
+  r.w = TqSmoothWalk{0, 0, 0};
+  r.next = 0;
+  r.tau = F;
+}
+
+// Frame f with its uniform u and the M (M - 1) thresholds t of tq_hmm_thresholds for that frame: draws the state as the
+// sampler of tq_hmm_count does, and returns 1 and fills `out` when the frame closes the run that began at f + 1.
+template <int M>
+TQ_HD int tq_chain_dwell_frame(TqChainDwellRow& r, double u, const double* t, int f, int F, int U, TqDwellInterval& out) {
+  const bool last = f == F - 1;
+  const int state = tq_hmm_label<M>(u, t + (last ? 0 : r.next) * (M - 1));
+  const int z = state >= U ? 1 : 0;
+  r.next = state;
+  if (z) r.tau = f;
+  if (last) {
+    tq_smooth_walk_begin(r.w, F, z);
+    return 0;
+  }
+  return tq_smooth_walk_step(r.w, f, z, out);
+}
+
+// the run still open after frame 0
+TQ_HD void tq_chain_dwell_finish(const TqChainDwellRow& r, TqDwellInterval& out) { tq_smooth_walk_finish(r.w, out); }

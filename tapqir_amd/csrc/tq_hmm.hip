@@ -1,7 +1,8 @@
 // tq_hmm.hip -- hidden Markov smoothing with M = U + B <= 4 hidden states on the device (bodies in tq_hmm.h): the E-step
 // as a chunked forward-backward with two wave scans of MxM products, the M-step of the summed rows, the Viterbi path in
-// hidden states, the backward sampler with its class-level and state-level counts, and the pooled or AOI-resampled
-// estimate of A.  The kernels are templates over M; the two-state kernels of tq_smooth.hip stay.
+// hidden states, the backward sampler with its class-level and state-level counts, the same sampler walked into dwell-time
+// intervals and first-binding frames, and the pooled or AOI-resampled estimate of A (DESIGN.md
+// section 22).  The kernels are templates over M; the two-state kernels of tq_smooth.hip stay.
 #include <hip/hip_runtime.h>
 
 #include "tq_dpp.h"
@@ -305,6 +306,119 @@ extern "C" int tq_hmm_count(const tq_hmm_count_args* a, void* stream) {
   }
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_hmm_count_kernel<MM>), grid, dim3(64), 0, (hipStream_t)stream, *a));
   return tq_launch_status("tq_hmm_count_kernel");
+}
+
+// ---- backward sampler walked into intervals: the geometry, the staging and the draws of tq_hmm_count_kernel -------------
+// Row (s, n) is the raster that kernel draws, state for state; here its class z = (state >= U) is walked, as it is drawn,
+// into runs of equal labels (tq_chain_dwell_frame), and neither a raster nor the state pairs are stored.  EMIT = false:
+// per-row interval counts, the interior-run histograms (integer atomics: order-free, so deterministic) and the
+// first-binding frame; EMIT = true: the same draws again, the k-th run a row closes written at tq_smooth_emit_slot, so
+// that the table is the one tq_smooth_dwell writes for that class raster.  Inactive lanes reach every barrier and touch
+// no memory but the staging; every loop is bounded by F.
+template <int M, bool EMIT>
+__global__ __launch_bounds__(64) void tq_chain_dwell_kernel(const tq_chain_dwell_args a) {
+  constexpr int T = M * (M - 1);
+  __shared__ double qbuf[64][T];
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const int s = blockIdx.y * 64 + lane;
+  const bool active = s < a.S;
+  const int F = a.F, U = a.U;
+  const double* fr = a.filt + (int64_t)n * F * M;
+  const TqHmmModel<M> m = tq_hmm_model<M>(a.theta, U, 0.5);  // the prior is already in filt
+  int32_t* hb = EMIT || !active ? nullptr : a.hist_bound + (int64_t)s * F;
+  int32_t* hu = EMIT || !active ? nullptr : a.hist_unbound + (int64_t)s * F;
+  const int64_t total = a.total;
+  int64_t o = 0;
+  int count = 0;
+  if (EMIT && active) {
+    o = a.offsets[(int64_t)s * a.N + n];
+    count = a.counts[(int64_t)s * a.N + n];
+  }
+
+  TqHmmDraws draws;
+  tq_hmm_draws_begin(draws, a.seed, s, n);
+  TqChainDwellRow r;
+  tq_chain_dwell_begin(r, F);
+  TqDwellInterval iv;
+  int closed = 0;  // runs closed so far
+
+  auto emit = [&](const TqDwellInterval& v) {
+    if (EMIT) {
+      const int64_t pos = tq_smooth_emit_slot(o, count, closed, total);
+      if (pos >= 0) tq_smooth_emit_row(a.intervals, total, pos, s, n, v);
+    } else if (v.low_or_high == 0 || v.low_or_high == 1) {
+      atomicAdd((v.z ? hb : hu) + (v.stop + 1 - v.start), 1);
+    }
+    ++closed;
+  };
+
+  for (int f0 = (F - 1) & ~63; f0 >= 0; f0 -= 64) {
+    const int cnt = min(64, F - f0);
+    if (lane < cnt) {
+      double af[M];
+#pragma unroll
+      for (int i = 0; i < M; ++i) af[i] = fr[(int64_t)(f0 + lane) * M + i];
+      // M = 4 writes its twelve quotients to LDS as they come, so that they do not wait in registers (96 VGPRs in place
+      // of 126); at M = 3 the same costs 30 registers, so the smaller chains go through a local array
+      if constexpr (M == 4) {
+        tq_hmm_thresholds(m, af, f0 + lane == F - 1, qbuf[lane]);
+      } else {
+        double t[T];
+        tq_hmm_thresholds(m, af, f0 + lane == F - 1, t);
+#pragma unroll
+        for (int k = 0; k < T; ++k) qbuf[lane][k] = t[k];
+      }
+    }
+    __syncthreads();
+    if (active) {
+      for (int j = cnt - 1; j >= 0; --j) {
+        const int f = f0 + j;
+        const double u = tq_hmm_draws_next(draws, F - 1 - f);
+        if (tq_chain_dwell_frame<M>(r, u, qbuf[j], f, F, U, iv)) emit(iv);
+      }
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  tq_chain_dwell_finish(r, iv);
+  emit(iv);
+  if (!EMIT) {
+    const int64_t row = (int64_t)s * a.N + n;
+    a.counts[row] = closed;
+    if (a.tau) a.tau[row] = (float)r.tau;
+  }
+}
+
+extern "C" int tq_chain_dwell(const tq_chain_dwell_args* a, void* stream) {
+  if (!a || !a->filt || !a->theta || !a->counts) {
+    tq_set_error("tq_chain_dwell: NULL required pointer");
+    return TQ_ERR_ARG;
+  }
+  if (a->mode == TQ_DWELL_COUNT ? (!a->hist_bound || !a->hist_unbound)
+                                : (a->mode != TQ_DWELL_EMIT || !a->offsets || (a->total > 0 && !a->intervals))) {
+    tq_set_error(a->mode == TQ_DWELL_COUNT || a->mode == TQ_DWELL_EMIT ? "tq_chain_dwell: NULL required pointer"
+                                                                       : "tq_chain_dwell: unknown mode");
+    return TQ_ERR_ARG;
+  }
+  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F || a->total < 0) {
+    tq_set_error("tq_chain_dwell: N, F and S must be positive, F at most 65536 and total non-negative");
+    return TQ_ERR_ARG;
+  }
+  if (!tq_hmm_states("tq_chain_dwell", a->U, a->B)) return TQ_ERR_ARG;
+  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
+  if (grid.y > 65535u) {
+    tq_set_error("tq_chain_dwell: S too large");
+    return TQ_ERR_ARG;
+  }
+  if (a->mode == TQ_DWELL_COUNT) {
+    TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_chain_dwell_kernel<MM, false>), grid, dim3(64), 0,
+                                                    (hipStream_t)stream, *a));
+  } else {
+    if (a->total == 0) return TQ_OK;
+    TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_chain_dwell_kernel<MM, true>), grid, dim3(64), 0,
+                                                    (hipStream_t)stream, *a));
+  }
+  return tq_launch_status("tq_chain_dwell_kernel");
 }
 
 // ---- estimate: one wave (= one workgroup) per posterior sample ----------------------------------------------------------

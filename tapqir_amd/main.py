@@ -337,35 +337,58 @@ def _kinetics_inputs(command, model, cuda, progress_bar):
     return m, mask, progress_bar
 
 
-def _smoothed_posterior(command, cd, name, mask, logger):
-    """``<name>_smooth.tpqr`` for the ``--smooth`` switch of `ttfb` and `dwelltime`: the chain of every channel (``theta``,
-    ``prior``), the smoothed ``z_probs`` and the Viterbi path ``z_map``.  Exits with status 1 when the file is missing or
-    was written for another selection of AOIs."""
+def _chain_states(command, model, cuda, smooth, U, B, logger):
+    """The checks of ``--unbound-states`` / ``--bound-states`` of `ttfb` and `dwelltime`: the bound on their sum where
+    `smooth` checks it (after the model, before ``--cpu``), and, once the model and ``--cpu`` have passed, that a chain
+    other than (1, 1) comes with ``--smooth``."""
+    if model.value != "cosmos":
+        return
+    if U + B > 4:
+        logger.error(f"{command}: --unbound-states + --bound-states must be at most 4, got {U} + {B}")
+        raise typer.Exit(1)
+    if cuda and not smooth and (U, B) != (1, 1):
+        logger.error(f"{command}: --unbound-states and --bound-states need --smooth: they choose the chain of `smooth` "
+                     f"whose rasters are sampled")
+        raise typer.Exit(1)
+
+
+def _smooth_suffix(U, B):
+    """What follows ``smooth`` in the file names of a chain: nothing for the two-state chain, ``-u<U>b<B>`` otherwise."""
+    return "" if (U, B) == (1, 1) else f"-u{U}b{B}"
+
+
+def _smoothed_posterior(command, cd, name, mask, logger, U=1, B=1):
+    """``<name>_smooth.tpqr`` (``<name>_smooth-u<U>b<B>.tpqr`` for a chain other than (1, 1)) for the ``--smooth`` switch
+    of `ttfb` and `dwelltime`: the chain of every channel (``theta``, ``prior``), the smoothed ``z_probs`` and the Viterbi
+    path ``z_map``.  Exits with status 1 when the file is missing or was written for another selection of AOIs."""
     import torch
 
     from tapqir_amd.utils.safe_load import load_tpqr
 
-    path = cd / f"{name}_smooth.tpqr"
+    path = cd / f"{name}_smooth{_smooth_suffix(U, B)}.tpqr"
+    again = "smooth" if (U, B) == (1, 1) else f"smooth --unbound-states {U} --bound-states {B}"
     if not path.is_file():
-        logger.error(f"{command} --smooth needs {path.name}: run `smooth` first")
+        logger.error(f"{command} --smooth needs {path.name}: run `{again}` first")
         raise typer.Exit(1)
     sm = load_tpqr(path)
     if sm["mask"].shape != mask.shape or not torch.equal(sm["mask"].bool(), mask):
         logger.error(f"{command} --smooth: {path.name} was written for another mask of on-target AOIs than the data "
-                     f"has now: run `smooth` again")
+                     f"has now: run `{again}` again")
         raise typer.Exit(1)
     return sm
 
 
-def _smoothed_filter(sm, c, p_bound):
+def _smoothed_filter(sm, c, p_bound, U=1, B=1):
     """The filtered marginals of channel ``c`` under the chain of ``smooth``: one E-step on the fit's ``p_bound`` at the
     stored theta and prior.  Returns (filt, theta) on the device of ``p_bound``: the inputs of the backward sampler."""
     import torch
 
-    from tapqir_amd.utils.mle_analysis import smooth_estep
+    from tapqir_amd.utils.mle_analysis import hmm_estep, smooth_estep
 
     theta = sm["theta"][c].to(device=p_bound.device, dtype=torch.float64)
-    return smooth_estep(p_bound, theta, float(sm["prior"][c]))["filt"], theta
+    if (U, B) == (1, 1):
+        return smooth_estep(p_bound, theta, float(sm["prior"][c]))["filt"], theta
+    return hmm_estep(p_bound, theta, float(sm["prior"][c]), U, B)["filt"], theta
 
 
 def _summary_table(rows):
@@ -438,6 +461,8 @@ def ttfb(
     num_samples: int = typer.Option(2000, "--num-samples", "-n", min=1, help="Number of posterior samples"),
     num_iter: int = typer.Option(15000, "--num-iter", "-it", min=1, help="Number of iterations"),
     smooth: bool = typer.Option(False, "--smooth", help="Sample the rasters of the chain fitted by `smooth`"),
+    unbound_states: int = typer.Option(1, "--unbound-states", min=1, help="Hidden states that look unbound (z = 0)"),
+    bound_states: int = typer.Option(1, "--bound-states", min=1, help="Hidden states that look bound (z = 1); at most 4 in all"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -449,21 +474,30 @@ def ttfb(
     With ``--smooth`` the first-binding frames are those of posterior rasters of the two-state chain that `smooth` fitted
     (``<model>_smooth.tpqr``; the rasters behind its rate table) instead of independent draws of every frame, the
     rastergram shows the smoothed posterior, and the files are named ``<model>_ttfb-smooth-...``.
+
+    With ``--smooth --unbound-states U --bound-states B`` other than 1 and 1 the rasters are those of the chain of U + B <= 4
+    hidden states that `smooth` fitted with the same two options (``<model>_smooth-u<U>b<B>.tpqr``), walked at the level
+    of the classes z = 0 / z = 1, and the files are named ``<model>_ttfb-smooth-u<U>b<B>-...``.  They
+    are rasters of the same chain at the same seed as those behind ``<model>_smooth-u<U>b<B>-channel<c>.csv``, but not bit
+    for bit: the filtered marginals are computed again at the stored chain, and a draw whose uniform lies within rounding
+    of a threshold can fall on the other side.
     """
     import pandas as pd
     import torch
 
     from tapqir_amd.exceptions import HipExtensionError
     from tapqir_amd.utils.imscroll import time_to_first_binding
-    from tapqir_amd.utils.mle_analysis import (fraction_bound, fraction_bound_fit, hpdi_columns, smooth_dwell_sample,
-                                               ttfb_fit, ttfb_sample)
+    from tapqir_amd.utils.mle_analysis import (fraction_bound, fraction_bound_fit, hmm_dwell_sample, hpdi_columns,
+                                               smooth_dwell_sample, ttfb_fit, ttfb_sample)
 
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
+    U, B = unbound_states, bound_states
+    _chain_states("ttfb", model, cuda, smooth, U, B, logger)
     m, mask, progress_bar = _kinetics_inputs("ttfb", model, cuda, progress_bar)
     data = m.data
-    sm = _smoothed_posterior("ttfb", cd, m.name, mask, logger) if smooth else None
-    stem = f"{m.name}_ttfb-smooth" if smooth else f"{m.name}_ttfb"
+    sm = _smoothed_posterior("ttfb", cd, m.name, mask, logger, U, B) if smooth else None
+    stem = f"{m.name}_ttfb-smooth{_smooth_suffix(U, B)}" if smooth else f"{m.name}_ttfb"
     if smooth:
         z = sm["z_map"].float() if binary else sm["z_probs"].float()
     else:
@@ -479,7 +513,9 @@ def ttfb(
             sdx = torch.argsort(time_to_first_binding(z_masked), descending=True)
 
             p_bound = m.params["z_probs"][: data.N, :, c, 1][mask].float().to(dev)
-            if smooth:  # seed c: the default of `smooth`, so these are the rasters of its rate table
+            if smooth and (U, B) != (1, 1):  # seed c: the default of `smooth`
+                tau = hmm_dwell_sample(*_smoothed_filter(sm, c, p_bound, U, B), U, B, num_samples, seed=c)["tau"]
+            elif smooth:  # seed c: the default of `smooth`, so these are the rasters of its rate table
                 tau = smooth_dwell_sample(*_smoothed_filter(sm, c, p_bound), num_samples, seed=c)["tau"]
             else:
                 tau = ttfb_sample(p_bound, num_samples, seed=c)
@@ -544,6 +580,8 @@ def dwelltime(
     num_samples: int = typer.Option(500, "--num-samples", "-n", min=1, help="Number of posterior samples"),
     num_iter: int = typer.Option(10000, "--num-iter", "-it", min=1, help="Number of iterations"),
     smooth: bool = typer.Option(False, "--smooth", help="Sample the rasters of the chain fitted by `smooth`"),
+    unbound_states: int = typer.Option(1, "--unbound-states", min=1, help="Hidden states that look unbound (z = 0)"),
+    bound_states: int = typer.Option(1, "--bound-states", min=1, help="Hidden states that look bound (z = 1); at most 4 in all"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -558,6 +596,13 @@ def dwelltime(
     With ``--smooth`` the rasters are posterior rasters of the two-state chain that `smooth` fitted
     (``<model>_smooth.tpqr``; the rasters behind its rate table) instead of independent draws of every frame, the plotted
     histogram is that of its Viterbi path, and the files are named ``<model>_dwelltime-smooth-...``.
+
+    With ``--smooth --unbound-states U --bound-states B`` other than 1 and 1 the rasters are those of the chain of U + B <= 4
+    hidden states that `smooth` fitted with the same two options (``<model>_smooth-u<U>b<B>.tpqr``), walked at the level
+    of the classes z = 0 / z = 1, and the files are named ``<model>_dwelltime-smooth-u<U>b<B>-...``.
+    They are rasters of the same chain at the same seed as those behind ``<model>_smooth-u<U>b<B>-channel<c>.csv``, but not
+    bit for bit: the filtered marginals are computed again at the stored chain, and a draw whose uniform lies within
+    rounding of a threshold can fall on the other side.
     """
     import torch
 
@@ -565,7 +610,8 @@ def dwelltime(
     from tapqir_amd.exceptions import HipExtensionError
     from tapqir_amd.utils.imscroll import bound_dwell_times, count_intervals, unbound_dwell_times
     from tapqir_amd.utils.mle_analysis import (dwell_csr_from_hist, dwell_fit, dwell_intervals, dwell_sample,
-                                               smooth_dwell_intervals, smooth_dwell_sample)
+                                               hmm_dwell_intervals, hmm_dwell_sample, smooth_dwell_intervals,
+                                               smooth_dwell_sample)
 
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
@@ -573,6 +619,8 @@ def dwelltime(
     if model.value == "cosmos" and not 1 <= K <= _lib.DWELL_KMAX:
         logger.error(f"dwelltime: -K must be between 1 and {_lib.DWELL_KMAX}, got {K}")
         raise typer.Exit(1)
+    U, B = unbound_states, bound_states
+    _chain_states("dwelltime", model, cuda, smooth, U, B, logger)
     m, mask, progress_bar = _kinetics_inputs("dwelltime", model, cuda, progress_bar)
     try:
         from scipy.io import savemat
@@ -580,8 +628,8 @@ def dwelltime(
         savemat = None
 
     data = m.data
-    sm = _smoothed_posterior("dwelltime", cd, m.name, mask, logger) if smooth else None
-    stem = f"{m.name}_dwelltime-smooth" if smooth else f"{m.name}_dwelltime"
+    sm = _smoothed_posterior("dwelltime", cd, m.name, mask, logger, U, B) if smooth else None
+    stem = f"{m.name}_dwelltime-smooth{_smooth_suffix(U, B)}" if smooth else f"{m.name}_dwelltime"
     if smooth:
         z_map = sm["z_map"]
     else:
@@ -592,7 +640,11 @@ def dwelltime(
         for c in range(data.C):
             logger.info(f"Channel #{c} ({data.channels[c]})")
             p_bound = m.params["z_probs"][: data.N, :, c, 1][mask].float().to(dev)
-            if smooth:  # seed c: the default of `smooth`, so these are the rasters of its rate table
+            if smooth and (U, B) != (1, 1):  # seed c: the default of `smooth`
+                filt, theta = _smoothed_filter(sm, c, p_bound, U, B)
+                sample = hmm_dwell_sample(filt, theta, U, B, num_samples, seed=c)
+                intervals = hmm_dwell_intervals(filt, theta, U, B, num_samples, seed=c, sample=sample)
+            elif smooth:  # seed c: the default of `smooth`, so these are the rasters of its rate table
                 filt, theta = _smoothed_filter(sm, c, p_bound)
                 sample = smooth_dwell_sample(filt, theta, num_samples, seed=c)
                 intervals = smooth_dwell_intervals(filt, theta, num_samples, seed=c, sample=sample)

@@ -26,7 +26,9 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
   same chain with up to four hidden states, several of them sharing the evidence of z = 0 or of z = 1 -- state marginals,
   the EM fit of the whole transition matrix with its BIC, the MAP path in hidden states, posterior rasters with their
   class-level and state-level counts, and the transition matrix of every raster, pooled or resampled over AOIs
-  (``tq_hmm_estep``, ``tq_hmm_mstep``, ``tq_hmm_viterbi``, ``tq_hmm_count``, ``tq_hmm_estimate``).
+  (``tq_hmm_estep``, ``tq_hmm_mstep``, ``tq_hmm_viterbi``, ``tq_hmm_count``, ``tq_hmm_estimate``);
+* ``hmm_dwell_sample`` / ``hmm_dwell_intervals``: the outputs of ``smooth_dwell_sample`` / ``smooth_dwell_intervals`` for
+  the class rasters of ``hmm_sample``, walked as they are drawn (``tq_chain_dwell``).
 
 There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
 """
@@ -489,6 +491,46 @@ def smooth_sample(filt, theta, num_samples, seed=0, raster=False):
 
 
 # ---- dwell times and first binding of the smoothed chain (`dwelltime --smooth`, `ttfb --smooth`) ----
+def _walk_count(launch, S, N, F, dev):
+    """Launch A of a sampler that walks its rasters as it draws them (``tq_smooth_dwell``, ``tq_chain_dwell``):
+    ``launch(**fields)`` fills the argument block's remaining fields and calls the entry point."""
+    counts = torch.empty(S, N, dtype=torch.int32, device=dev)
+    hb = torch.zeros(S, F, dtype=torch.int32, device=dev)
+    hu = torch.zeros(S, F, dtype=torch.int32, device=dev)
+    tau = torch.empty(S, N, dtype=torch.float32, device=dev)
+    launch(counts=_lib.ptr(counts), hist_bound=_lib.ptr(hb), hist_unbound=_lib.ptr(hu), tau=_lib.ptr(tau),
+           mode=_lib.DWELL_COUNT)
+    return {"hist_bound": hb, "hist_unbound": hu, "counts": counts, "tau": tau}
+
+
+def _walk_emit(who, launch, sample, S, N, dev):
+    """The exclusive scan of the row counts of launch A and launch B of the same sampler; the DataFrame of
+    ``dwell_intervals``."""
+    import pandas as pd
+
+    from tapqir_amd.utils.imscroll import INTERVAL_COLUMNS
+
+    counts = sample["counts"].contiguous()
+    if counts.shape != (S, N) or counts.dtype != torch.int32 or counts.device != dev:
+        raise ValueError(f"{who}: sample['counts'] must be int32 ({S}, {N}) on the device of filt")
+    csum = torch.cumsum(counts.reshape(-1).to(torch.int64), 0)
+    offsets = (csum - counts.reshape(-1)).contiguous()
+    total = int(csum[-1].item())
+    cols = torch.empty(_lib.DWELL_COLS, max(total, 1), dtype=torch.int32, device=dev)
+    launch(counts=_lib.ptr(counts), offsets=_lib.ptr(offsets), intervals=_lib.ptr(cols), total=total, mode=_lib.DWELL_EMIT)
+    host = cols[:, :total].to(torch.int64).cpu().numpy()
+    return pd.DataFrame({name: host[i] for i, name in enumerate(INTERVAL_COLUMNS)})
+
+
+def _smooth_dwell_launch(filt, theta, S, N, F, seed):
+    def launch(**fields):
+        a = _lib_smooth.SmoothDwellArgs(filt=_lib.ptr(filt), theta=_lib.ptr(theta), N=N, F=F, S=S,
+                                        seed=int(seed) & (2**64 - 1), **fields)
+        _lib.check(_lib_smooth.lib().tq_smooth_dwell(C.byref(a), _stream(filt.device)), "tq_smooth_dwell")
+
+    return launch
+
+
 def smooth_dwell_sample(filt, theta, num_samples, seed=0):
     """Launch A of the interval sampler on the rasters of ``smooth_sample(filt, theta, num_samples, seed)``: every row is
     walked into runs of equal labels as it is drawn backwards, and no raster is stored.
@@ -497,16 +539,7 @@ def smooth_dwell_sample(filt, theta, num_samples, seed=0):
     (num_samples, N) float32 on the device: the first frame with z = 1 of each row, or F if there is none, as
     ``ttfb_sample`` returns it.  The histograms go to ``dwell_csr_from_hist`` / ``dwell_fit``, ``tau`` to ``ttfb_fit``."""
     filt, theta, S, N, F = _smooth_sample_inputs("smooth_dwell_sample", filt, theta, num_samples)
-    dev = filt.device
-    counts = torch.empty(S, N, dtype=torch.int32, device=dev)
-    hb = torch.zeros(S, F, dtype=torch.int32, device=dev)
-    hu = torch.zeros(S, F, dtype=torch.int32, device=dev)
-    tau = torch.empty(S, N, dtype=torch.float32, device=dev)
-    a = _lib_smooth.SmoothDwellArgs(filt=_lib.ptr(filt), theta=_lib.ptr(theta), counts=_lib.ptr(counts),
-                                    hist_bound=_lib.ptr(hb), hist_unbound=_lib.ptr(hu), tau=_lib.ptr(tau), N=N, F=F, S=S,
-                                    mode=_lib.DWELL_COUNT, seed=int(seed) & (2**64 - 1))
-    _lib.check(_lib_smooth.lib().tq_smooth_dwell(C.byref(a), _stream(dev)), "tq_smooth_dwell")
-    return {"hist_bound": hb, "hist_unbound": hu, "counts": counts, "tau": tau}
+    return _walk_count(_smooth_dwell_launch(filt, theta, S, N, F, seed), S, N, F, filt.device)
 
 
 def smooth_dwell_intervals(filt, theta, num_samples, seed=0, sample=None):
@@ -515,27 +548,12 @@ def smooth_dwell_intervals(filt, theta, num_samples, seed=0, sample=None):
     which draws the same bits again and writes every row's intervals, last run first, back from the end of the row's
     slice.  Returns the DataFrame of ``dwell_intervals``: the columns of ``tapqir_amd.utils.imscroll.INTERVAL_COLUMNS``,
     int64, in (sample, AOI, frame) order."""
-    import pandas as pd
-
-    from tapqir_amd.utils.imscroll import INTERVAL_COLUMNS
-
     given = num_samples if sample is None else sample["counts"].shape[0]
     filt, theta, S, N, F = _smooth_sample_inputs("smooth_dwell_intervals", filt, theta, given)
+    launch = _smooth_dwell_launch(filt, theta, S, N, F, seed)
     if sample is None:
-        sample = smooth_dwell_sample(filt, theta, S, seed)
-    counts = sample["counts"].contiguous()
-    if counts.shape != (S, N) or counts.dtype != torch.int32 or counts.device != filt.device:
-        raise ValueError(f"smooth_dwell_intervals: sample['counts'] must be int32 ({S}, {N}) on the device of filt")
-    csum = torch.cumsum(counts.reshape(-1).to(torch.int64), 0)
-    offsets = (csum - counts.reshape(-1)).contiguous()
-    total = int(csum[-1].item())
-    cols = torch.empty(_lib.DWELL_COLS, max(total, 1), dtype=torch.int32, device=filt.device)
-    a = _lib_smooth.SmoothDwellArgs(filt=_lib.ptr(filt), theta=_lib.ptr(theta), counts=_lib.ptr(counts),
-                                    offsets=_lib.ptr(offsets), intervals=_lib.ptr(cols), total=total, N=N, F=F, S=S,
-                                    mode=_lib.DWELL_EMIT, seed=int(seed) & (2**64 - 1))
-    _lib.check(_lib_smooth.lib().tq_smooth_dwell(C.byref(a), _stream(filt.device)), "tq_smooth_dwell")
-    host = cols[:, :total].to(torch.int64).cpu().numpy()
-    return pd.DataFrame({name: host[i] for i, name in enumerate(INTERVAL_COLUMNS)})
+        sample = _walk_count(launch, S, N, F, filt.device)
+    return _walk_emit("smooth_dwell_intervals", launch, sample, S, N, filt.device)
 
 
 # ---- hidden Markov smoothing with several states per class (`smooth --bound-states`, DESIGN.md section 22) ---------------
@@ -710,6 +728,21 @@ def hmm_viterbi(p, theta, prior, unbound=1, bound=1):
     return path
 
 
+def _hmm_sample_inputs(who, filt, theta, unbound, bound, num_samples):
+    """What the multi-state backward samplers share: ``filt`` as contiguous float64 (N, F, M) on the device, ``theta`` as
+    M * M + M doubles on the same device, U, B, M, S, N and F."""
+    if not isinstance(filt, torch.Tensor) or filt.device.type != "cuda":
+        raise HipExtensionError(f"{who} runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states(who, unbound, bound)
+    S = int(num_samples)
+    if (filt.ndim != 3 or 0 in filt.shape or filt.shape[2] != M or filt.dtype != torch.float64 or S < 1
+            or filt.shape[1] > _lib_smooth.SMOOTH_MAX_F):
+        raise ValueError(f"{who}: filt must be float64 (N, F, {M}) with N >= 1, 1 <= F <= {_lib_smooth.SMOOTH_MAX_F}, "
+                         f"and num_samples >= 1, got {filt.dtype} {tuple(filt.shape)}")
+    theta = _hmm_theta(who, theta, M, filt.device)
+    return filt.contiguous(), theta, U, B, M, S, filt.shape[0], filt.shape[1]
+
+
 def hmm_sample(filt, theta, unbound, bound, num_samples, seed=0, trans=False, raster=False):
     """``num_samples`` posterior rasters of the chain in hidden states, drawn by backward sampling from ``filt`` (N, F, M)
     of ``hmm_estep`` at ``theta``, and their counts.
@@ -718,17 +751,7 @@ def hmm_sample(filt, theta, unbound, bound, num_samples, seed=0, trans=False, ra
     (``rates_estimate`` takes them as they are); with ``trans=True`` also ``"trans"`` (num_samples, N, M * M) int32, the
     number of frame pairs in states (i, j), for ``hmm_estimate``; with ``raster=True`` also ``"raster"`` (num_samples, N, F)
     uint8, the hidden states."""
-    if not isinstance(filt, torch.Tensor) or filt.device.type != "cuda":
-        raise HipExtensionError("hmm_sample runs on the HIP device only (no CPU fallback): pass a cuda tensor")
-    U, B, M = _hmm_states("hmm_sample", unbound, bound)
-    S = int(num_samples)
-    if (filt.ndim != 3 or 0 in filt.shape or filt.shape[2] != M or filt.dtype != torch.float64 or S < 1
-            or filt.shape[1] > _lib_smooth.SMOOTH_MAX_F):
-        raise ValueError(f"hmm_sample: filt must be float64 (N, F, {M}) with N >= 1, 1 <= F <= {_lib_smooth.SMOOTH_MAX_F}, "
-                         f"and num_samples >= 1, got {filt.dtype} {tuple(filt.shape)}")
-    theta = _hmm_theta("hmm_sample", theta, M, filt.device)
-    filt = filt.contiguous()
-    N, F = filt.shape[:2]
+    filt, theta, U, B, M, S, N, F = _hmm_sample_inputs("hmm_sample", filt, theta, unbound, bound, num_samples)
     out = {"counts": torch.empty(S, N, _lib_rates.RATES_COLS, dtype=torch.int32, device=filt.device)}
     if trans:
         out["trans"] = torch.empty(S, N, M * M, dtype=torch.int32, device=filt.device)
@@ -739,6 +762,39 @@ def hmm_sample(filt, theta, unbound, bound, num_samples, seed=0, trans=False, ra
                               seed=int(seed) & (2**64 - 1))
     _lib.check(_lib_hmm.lib().tq_hmm_count(C.byref(a), _stream(filt.device)), "tq_hmm_count")
     return out
+
+
+# ---- dwell times and first binding of the multi-state chain ---------------------------------------
+def _chain_dwell_launch(filt, theta, U, B, S, N, F, seed):
+    def launch(**fields):
+        a = _lib_hmm.ChainDwellArgs(filt=_lib.ptr(filt), theta=_lib.ptr(theta), N=N, F=F, S=S, U=U, B=B,
+                                    seed=int(seed) & (2**64 - 1), **fields)
+        _lib.check(_lib_hmm.lib().tq_chain_dwell(C.byref(a), _stream(filt.device)), "tq_chain_dwell")
+
+    return launch
+
+
+def hmm_dwell_sample(filt, theta, unbound, bound, num_samples, seed=0):
+    """``smooth_dwell_sample`` for the chain in hidden states: launch A of the interval sampler on the class rasters
+    ``hmm_sample(filt, theta, unbound, bound, num_samples, seed, raster=True)["raster"] >= unbound``, walked as they are
+    drawn; neither the rasters nor the state pairs are stored.
+
+    Returns ``{"hist_bound", "hist_unbound", "counts", "tau"}`` with the shapes and meaning of ``smooth_dwell_sample``:
+    the histograms go to ``dwell_csr_from_hist`` / ``dwell_fit``, ``tau`` to ``ttfb_fit``."""
+    filt, theta, U, B, M, S, N, F = _hmm_sample_inputs("hmm_dwell_sample", filt, theta, unbound, bound, num_samples)
+    return _walk_count(_chain_dwell_launch(filt, theta, U, B, S, N, F, seed), S, N, F, filt.device)
+
+
+def hmm_dwell_intervals(filt, theta, unbound, bound, num_samples, seed=0, sample=None):
+    """``smooth_dwell_intervals`` for the chain in hidden states: launch A (or its result ``sample`` from
+    ``hmm_dwell_sample`` with the same arguments), the exclusive scan of the row counts, and launch B.  Returns the
+    DataFrame of ``dwell_intervals``; ``z`` is the class of a run, not its hidden state."""
+    given = num_samples if sample is None else sample["counts"].shape[0]
+    filt, theta, U, B, M, S, N, F = _hmm_sample_inputs("hmm_dwell_intervals", filt, theta, unbound, bound, given)
+    launch = _chain_dwell_launch(filt, theta, U, B, S, N, F, seed)
+    if sample is None:
+        sample = _walk_count(launch, S, N, F, filt.device)
+    return _walk_emit("hmm_dwell_intervals", launch, sample, S, N, filt.device)
 
 
 def hmm_estimate(trans, bootstrap=False, seed=0):
