@@ -868,6 +868,51 @@ typedef struct {
 int tq_chain_dwell(const tq_chain_dwell_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * R EM fits of the chain above side by side (`tapqir_amd smooth --restarts R`, `--forbid i-j`).
+ * Replica r has its own theta[r] (M * M + M doubles), its own rows[r] and its own slice of the scratch; p is shared.  A
+ * replica computes, from the same theta, what tq_hmm_estep and tq_hmm_mstep compute: the same lane geometry, scans, sweeps,
+ * strided sums and tree.  `active` (R int32 in device memory, or NULL for all active) freezes replicas: the workgroups of
+ * a replica with active[r] == 0 return at once and write nothing, so its theta, rows and trace keep their values.
+ * Both entry points return TQ_ERR_ARG, before anything touches the device, for what the pair above refuses, for R < 1 or
+ * R > TQ_MULTISTART_MAX, and the M-step for T <= it, for an `allow` with a bit beyond M * M or a row without a free entry.
+ *
+ * tq_multistart_estep: grid (N, R), one wave per (row, replica).  Writes only rows[r, n] (the columns of tq_hmm_estep);
+ *   gamma is not stored, and the a_f that the backward sweep needs go to the caller's scratch `filt`.
+ * ------------------------------------------------------------------------------------- */
+#define TQ_MULTISTART_MAX 64
+typedef struct {
+  const float* p;              /* (N, F) p(z = 1) of the fit, shared by the replicas */
+  const double* theta;         /* (R, M * M + M); device memory */
+  double* filt;                /* (R, N, F, M) scratch */
+  double* rows;                /* (R, N, TQ_HMM_COLS(M)) out */
+  const int32_t* active;       /* (R); device memory; or NULL: every replica runs */
+  int32_t N, F, R;
+  int32_t U, B;                /* unbound and bound states, M = U + B */
+  double prior;
+} tq_multistart_estep_args;
+
+int tq_multistart_estep(const tq_multistart_estep_args* a, void* stream);
+
+/* tq_multistart_mstep: grid R, one workgroup per replica.  Sums the N rows of replica r in the fixed order of
+ * tq_hmm_mstep, stores the total loglik into trace[r * T + it] and overwrites theta[r].
+ *   allow: bit i * M + j set means A_ij is free.  The summed E n_ij of a cleared bit is set to 0 before the quotient, so
+ *   the entry leaves the floor at TQ_SMOOTH_RMIN over the row's sum: a forbidden transition is pinned at 1e-9 -- the value
+ *   every kernel reads a zero of theta as -- not at an exact zero.  All M * M bits set is the M-step of tq_hmm_mstep.
+ * An inactive replica keeps theta[r] and writes no trace entry. */
+typedef struct {
+  const double* rows;          /* (R, N, TQ_HMM_COLS(M)) of tq_multistart_estep */
+  double* theta;               /* (R, M * M + M) in / out; device memory */
+  double* trace;               /* (R, T): trace[r * T + it] out */
+  const int32_t* active;       /* (R); device memory; or NULL */
+  int32_t N, it;
+  int32_t T, R;                /* entries of a replica's trace, T > it; replicas */
+  int32_t U, B;
+  uint32_t allow;              /* topology mask, M * M bits */
+} tq_multistart_mstep_args;
+
+int tq_multistart_mstep(const tq_multistart_mstep_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame
  * decode of GlimpseDataset.__getitem__ (168-186: big-endian int16 + 2^15) and the offset-region value counts

@@ -193,8 +193,8 @@ TQ_HD double tq_hmm_forward(const TqHmmModel<M>& m, const float* pr, int lo, int
 // Backward sweep over [lo, hi), g = hi - 1 .. lo, from beta_{hi-1} = b0.  Frame g gives gamma_g, and with a_{g-1} -- the
 // lane's own, or v = a_{lo-1} of its prefix -- the pair marginals xi_{g-1}(i, j) ~ a_{g-1}(i) A[i][j] l_g(j) beta_g(j):
 // the pair (g - 1, g) belongs to the lane that owns g.  acc[i * M + j] += E n_ij; acc[M * M + i] = gamma_0(i) in the lane
-// that owns frame 0.
-template <int M>
+// that owns frame 0.  GAMMA = false stores no gamma_g and does not read `gam` (tq_multistart.h); the sums are the same.
+template <int M, bool GAMMA = true>
 TQ_HD void tq_hmm_backward(const TqHmmModel<M>& m, const float* pr, int lo, int hi, const double* b0, const double* v,
                            const double* filt, double* gam, double* acc) {
   double b[M];
@@ -210,7 +210,7 @@ TQ_HD void tq_hmm_backward(const TqHmmModel<M>& m, const float* pr, int lo, int 
 #pragma unroll
     for (int i = 0; i < M; ++i) {
       r[i] /= s;
-      gam[(int64_t)g * M + i] = r[i];
+      if constexpr (GAMMA) gam[(int64_t)g * M + i] = r[i];
     }
     if (g == 0) {
 #pragma unroll

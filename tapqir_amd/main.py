@@ -754,16 +754,43 @@ def rates(
         raise typer.Exit(1)
 
 
-def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci, bootstrap, seed, progress_bar):
+def _smooth_multistart_options(U, B, restarts, restart_seed, forbid, logger):
+    """The checks of ``--restarts``, ``--restart-seed`` and ``--forbid`` of `smooth`, made where ``--ci`` is checked (after
+    the model, before ``--cpu``).  Returns ``{"restarts", "seed", "allow"}``, allow an (M, M) list of booleans."""
+    import re
+
+    M = U + B
+    if (U, B) == (1, 1):
+        logger.error("smooth: --restarts, --restart-seed and --forbid need a chain of more than two states "
+                     "(--unbound-states, --bound-states): the two-state EM has one optimum and one topology")
+        raise typer.Exit(1)
+    allow = [[True] * M for _ in range(M)]
+    for item in forbid or []:
+        match = re.fullmatch(r"(\d+)-(\d+)", item.strip())
+        i, j = (int(match.group(1)), int(match.group(2))) if match else (-1, -1)
+        if not match or i == j or i >= M or j >= M:
+            logger.error(f"smooth: --forbid takes i-j with two different states below {M}, got {item!r}")
+            raise typer.Exit(1)
+        allow[i][j] = False
+    if not all(any(row) for row in allow):
+        logger.error("smooth: --forbid leaves a state without a free transition")
+        raise typer.Exit(1)
+    return {"restarts": restarts, "seed": restart_seed, "allow": allow}
+
+
+def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci, bootstrap, seed, progress_bar,
+                       multistart=None):
     """`smooth` with U + B > 2 hidden states: ``<model>_smooth-u<U>b<B>.tpqr`` and, per channel,
     ``<model>_smooth-u<U>b<B>-channel<c>.csv``.  AOIs outside the mask keep the fit's z_probs and have NaN state
-    probabilities and state 255."""
+    probabilities and state 255.  With ``multistart`` (``--restarts`` / ``--forbid``, section 26) every channel is fitted
+    by ``hmm_fit_restarts`` and the file gains ``restart_logliks``, ``restart_best`` and ``topology``."""
     import pandas as pd
     import torch
 
     from tapqir_amd.exceptions import HipExtensionError
-    from tapqir_amd.utils.mle_analysis import (estimand_summary, hmm_estimate, hmm_fit, hmm_sample, hmm_summary, hmm_viterbi,
-                                               rates_estimate, rates_sample, rates_summary)
+    from tapqir_amd.utils.mle_analysis import (estimand_summary, hmm_estimate, hmm_fit, hmm_fit_restarts, hmm_n_params,
+                                               hmm_sample, hmm_summary, hmm_viterbi, rates_estimate, rates_sample,
+                                               rates_summary)
 
     data, M = m.data, U + B
     stem = f"{m.name}_smooth-u{U}b{B}"
@@ -776,6 +803,12 @@ def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci
            "theta": torch.zeros(data.C, M * M + M, dtype=torch.float64), "prior": torch.zeros(data.C, dtype=torch.float64),
            "bic": torch.zeros(data.C, dtype=torch.float64), "n_params": M * (M - 1) + (M - 1), "loglik_trace": [],
            "mask": mask, "unbound": U, "bound": B}
+    if multistart is not None:
+        topology = torch.tensor(multistart["allow"], dtype=torch.bool)
+        out.update({"n_params": hmm_n_params(topology), "topology": topology,
+                    "restart_logliks": torch.zeros(data.C, multistart["restarts"] + 1, dtype=torch.float64),
+                    "restart_best": torch.zeros(data.C, dtype=torch.int64),
+                    "topology_by_channel": torch.ones(data.C, M, M, dtype=torch.bool)})
     try:
         dev = torch.device("cuda")
         for c in range(data.C):
@@ -783,7 +816,19 @@ def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci
             prior = float(torch.as_tensor(m.params["pi"]["Mean"]).reshape(-1, 2)[c, 1])
             p = z_raw[:, :, c][mask].to(dev)
             chan_seed = c if seed is None else seed
-            fit = hmm_fit(p, prior, U, B, num_iter=num_iter, tol=tol, progress_bar=progress_bar)
+            if multistart is None:
+                fit = hmm_fit(p, prior, U, B, num_iter=num_iter, tol=tol, progress_bar=progress_bar)
+            else:
+                fit = hmm_fit_restarts(p, prior, U, B, restarts=multistart["restarts"], seed=multistart["seed"],
+                                       allow=topology, num_iter=num_iter, tol=tol, progress_bar=progress_bar)
+                best = fit["best"]
+                logger.info(f"EM from {multistart['restarts'] + 1} starts: log evidence {fit['logliks'][0].item():.6f} from "
+                            f"the default start, {fit['logliks'][best].item():.6f} from the best one, start #{best}"
+                            + (" (the default start)" if best == 0 else f" (random start {best} of seed {multistart['seed']})"))
+                out["restart_logliks"][c] = fit["logliks"]
+                out["restart_best"][c] = best
+                out["topology_by_channel"][c] = fit["allow"]  # in the canonical order of the states, as theta is
+                fit = {**fit, "iterations": fit["iterations"][best], "converged": fit["converged"][best]}
             theta = fit["theta"]
             A = theta[: M * M].reshape(M, M).cpu()
             logger.info(f"EM with {U} unbound and {B} bound states: log evidence = {fit['loglik']:.6f}, BIC = "
@@ -844,6 +889,9 @@ def smooth(
     seed: Optional[int] = typer.Option(None, "--seed", help="Seed of the posterior rasters (default: the channel index)"),
     unbound_states: int = typer.Option(1, "--unbound-states", min=1, help="Hidden states that look unbound (z = 0)"),
     bound_states: int = typer.Option(1, "--bound-states", min=1, help="Hidden states that look bound (z = 1); at most 4 in all"),
+    restarts: int = typer.Option(0, "--restarts", min=0, max=63, help="Random starts of the EM fitted next to the default start; the best one is kept"),
+    restart_seed: int = typer.Option(0, "--restart-seed", help="Seed of the random starts"),
+    forbid: Optional[List[str]] = typer.Option(None, "--forbid", help="i-j: fix the transition from state i to state j at the floor, 1e-9 (repeatable)"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -860,6 +908,12 @@ def smooth(
     side.  The files are then ``<model>_smooth-u<U>b<B>.tpqr`` (with the state marginals, the Viterbi path in hidden
     states and the BIC: the lower, the better) and ``<model>_smooth-u<U>b<B>-channel<c>.csv`` (every entry of the
     transition matrix, the mean dwell of every state and the class-level kon and koff); the two-state files stay.
+
+    With ``--restarts R`` the EM of such a chain runs from the default start and from R random starts (``--restart-seed``)
+    side by side, and the start with the largest log evidence is kept; ``--forbid i-j`` (repeatable) removes the transition
+    from hidden state i to hidden state j from the chain.  The file names do not change; the
+    ``.tpqr`` gains ``restart_logliks``, ``restart_best`` and ``topology``, and the BIC counts the free entries only.
+    Neither option applies to the two-state chain.
     """
     import pandas as pd
     import torch
@@ -876,10 +930,13 @@ def smooth(
     if model.value == "cosmos" and unbound_states + bound_states > 4:
         logger.error(f"smooth: --unbound-states + --bound-states must be at most 4, got {unbound_states} + {bound_states}")
         raise typer.Exit(1)
+    multistart = None
+    if model.value == "cosmos" and (restarts or restart_seed or forbid):
+        multistart = _smooth_multistart_options(unbound_states, bound_states, restarts, restart_seed, forbid, logger)
     m, mask, progress_bar = _kinetics_inputs("smooth", model, cuda, progress_bar)
     if (unbound_states, bound_states) != (1, 1):
         _smooth_multistate(m, mask, cd, logger, unbound_states, bound_states, num_iter, tol, num_samples, ci, bootstrap,
-                           seed, progress_bar)
+                           seed, progress_bar, multistart)
         return
     data = m.data
     pct = f"{ci * 100:g}%"

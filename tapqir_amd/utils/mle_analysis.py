@@ -28,7 +28,9 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
   class-level and state-level counts, and the transition matrix of every raster, pooled or resampled over AOIs
   (``tq_hmm_estep``, ``tq_hmm_mstep``, ``tq_hmm_viterbi``, ``tq_hmm_count``, ``tq_hmm_estimate``);
 * ``hmm_dwell_sample`` / ``hmm_dwell_intervals``: the outputs of ``smooth_dwell_sample`` / ``smooth_dwell_intervals`` for
-  the class rasters of ``hmm_sample``, walked as they are drawn (``tq_chain_dwell``).
+  the class rasters of ``hmm_sample``, walked as they are drawn (``tq_chain_dwell``);
+* ``hmm_random_starts`` / ``hmm_fit_restarts``: the EM of ``hmm_fit`` from several starts fitted side by side, under an
+  optional topology of forbidden transitions, and the best of them (``tq_multistart_estep``, ``tq_multistart_mstep``).
 
 There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
 """
@@ -37,7 +39,7 @@ import ctypes as C
 
 import torch
 
-from tapqir_amd import _lib, _lib_hmm, _lib_rates, _lib_smooth
+from tapqir_amd import _lib, _lib_hmm, _lib_multistart, _lib_rates, _lib_smooth
 from tapqir_amd.exceptions import HipExtensionError
 
 ADAM_BETAS = (0.9, 0.999)
@@ -827,3 +829,234 @@ def hmm_summary(estimate, probs=0.68):
     A = estimate["A"]
     M = A.shape[1]
     return {f"A{i}{j}": estimand_summary(A[:, i, j], probs) for i in range(M) for j in range(M)}
+
+
+# ---- several EM starts side by side and constrained topologies (`smooth --restarts`) ---------------
+MULTISTART_SCRATCH_BYTES = 8 * 2**30  # the largest scratch of a_f that hmm_fit_restarts allocates
+
+
+def hmm_allow(allow, M, who="hmm_allow"):
+    """The topology ``allow`` as an (M, M) bool tensor on the host: True where A_ij is free.  ``None`` is the fully
+    connected chain.  Self-transitions are always free, so every row has a free entry."""
+    if allow is None:
+        return torch.ones(M, M, dtype=torch.bool)
+    a = torch.as_tensor(allow).detach().cpu()
+    if a.shape != (M, M) or not bool(((a == 0) | (a == 1)).all()):
+        raise ValueError(f"{who}: allow must be ({M}, {M}) booleans, got {tuple(a.shape)}")
+    a = a.bool()
+    if not bool(a.diagonal().all()):
+        raise ValueError(f"{who}: allow must leave every self-transition A_ii free")
+    return a
+
+
+def hmm_n_params(allow):
+    """Free parameters of a chain with the topology ``allow`` (M, M): (free entries of A - M) + (M - 1)."""
+    M = allow.shape[0]
+    return int(allow.sum()) - M + (M - 1)
+
+
+def hmm_random_starts(unbound, bound, restarts, seed=0, allow=None):
+    """``restarts`` + 1 starts of the EM as (restarts + 1, M * M + M) float64 on the host, theta = (A row-major, rho).
+
+    Row 0 is ``hmm_default_start``; with ``allow`` its forbidden entries are zeroed and its rows renormalised.  Rows 1 ...
+    come from ``numpy.random.default_rng(seed)``, the draws of a start taken in this order: for state i = 0 .. M - 1,
+    ``leave = 10 ** rng.uniform(-2.5, -0.3)`` and then ``w = rng.dirichlet(ones(k))`` over the k allowed off-diagonal
+    entries of row i in ascending j, giving A_ij = leave * w and A_ii = 1 - leave; after the M rows,
+    ``rho = rng.dirichlet(ones(M))``.  A row with k = 0 still takes its ``leave`` draw (so the draws of the other rows do
+    not depend on the topology of this one) but no Dirichlet draw, and has A_ii = 1.  Forbidden entries are exact zeros
+    here; the kernels read them at the floor of theta, 1e-9."""
+    import numpy as np
+
+    U, B, M = _hmm_states("hmm_random_starts", unbound, bound)
+    restarts = int(restarts)
+    if restarts < 0 or restarts + 1 > _lib_multistart.MULTISTART_MAX:
+        raise ValueError(f"hmm_random_starts: restarts must lie in 0 .. {_lib_multistart.MULTISTART_MAX - 1}, got {restarts}")
+    free = hmm_allow(allow, M, "hmm_random_starts").numpy()
+    A, rho = hmm_default_start(U, B)
+    A = A.numpy()
+    for i in range(M):
+        if not free[i].all():  # a row without forbidden entries keeps the bits of hmm_default_start
+            A[i] = A[i] * free[i] / (A[i] * free[i]).sum()
+    out = np.zeros((restarts + 1, M * M + M))
+    out[0] = np.concatenate([A.ravel(), rho.numpy()])
+    rng = np.random.default_rng(seed)
+    for r in range(1, restarts + 1):
+        A = np.zeros((M, M))
+        for i in range(M):
+            leave = 10.0 ** rng.uniform(-2.5, -0.3)
+            js = [j for j in range(M) if j != i and free[i, j]]
+            if js:
+                A[i, js] = leave * rng.dirichlet(np.ones(len(js)))
+                A[i, i] = 1.0 - leave
+            else:
+                A[i, i] = 1.0
+        out[r] = np.concatenate([A.ravel(), rng.dirichlet(np.ones(M))])
+    return torch.from_numpy(out)
+
+
+def _multistart_inputs(who, x, shape_tail, what):
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+        raise HipExtensionError(f"{who} runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    if (x.dtype != torch.float64 or not x.is_contiguous() or x.ndim != len(shape_tail) + 1
+            or tuple(x.shape[1:]) != shape_tail or not 1 <= x.shape[0] <= _lib_multistart.MULTISTART_MAX):
+        raise ValueError(f"{who}: {what} must be contiguous float64 (R, {', '.join(map(str, shape_tail))}) with 1 <= R <= "
+                         f"{_lib_multistart.MULTISTART_MAX}, got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def _multistart_active(who, active, R, device):
+    if active is None:
+        return None
+    if (not isinstance(active, torch.Tensor) or active.device != device or active.dtype != torch.int32
+            or active.shape != (R,) or not active.is_contiguous()):
+        raise ValueError(f"{who}: active must be int32 ({R},) on the device of the data")
+    return active
+
+
+def multistart_estep(p, thetas, prior, unbound=1, bound=1, active=None, rows=None, scratch=None):
+    """One launch of ``tq_multistart_estep``: the E-step of ``hmm_estep`` for the R chains ``thetas`` (R, M * M + M) on the
+    shared rows of ``p`` (N, F).  Returns ``rows`` (R, N, M * M + M + 1); gamma is not computed.  ``active`` (R,) int32 on
+    the device leaves the rows of a replica with a 0 as they are; ``rows`` and ``scratch`` (R, N, F, M) are reused when
+    given."""
+    if not isinstance(p, torch.Tensor) or p.device.type != "cuda":
+        raise HipExtensionError("multistart_estep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states("multistart_estep", unbound, bound)
+    thetas = _multistart_inputs("multistart_estep", thetas, (M * M + M,), "thetas")
+    R = thetas.shape[0]
+    p, N, F, _, prior, U, B, M = _hmm_inputs("multistart_estep", p, thetas[0], prior, U, B)
+    active = _multistart_active("multistart_estep", active, R, p.device)
+    if rows is None:
+        rows = torch.empty(R, N, _lib_hmm.hmm_cols(M), dtype=torch.float64, device=p.device)
+    if scratch is None:
+        scratch = torch.empty(R, N, F, M, dtype=torch.float64, device=p.device)
+    for name, x, shape in (("rows", rows, (R, N, _lib_hmm.hmm_cols(M))), ("scratch", scratch, (R, N, F, M))):
+        if x.shape != shape or x.dtype != torch.float64 or x.device != p.device or not x.is_contiguous():
+            raise ValueError(f"multistart_estep: {name} must be contiguous float64 {shape} on the device of p")
+    a = _lib_multistart.MultistartEstepArgs(p=_lib.ptr(p), theta=_lib.ptr(thetas), filt=_lib.ptr(scratch), rows=_lib.ptr(rows),
+                                            active=_lib.ptr(active), N=N, F=F, R=R, U=U, B=B, prior=prior)
+    _lib.check(_lib_multistart.lib().tq_multistart_estep(C.byref(a), _stream(p.device)), "tq_multistart_estep")
+    return rows
+
+
+def multistart_mstep(rows, thetas, trace, it=0, unbound=1, bound=1, allow=None, active=None):
+    """One launch of ``tq_multistart_mstep``: ``thetas`` (R, M * M + M, in place) from the summed ``rows`` (R, N, M * M + M
+    + 1) of ``multistart_estep`` under the topology ``allow`` (M, M), and every replica's total log-evidence into
+    ``trace[r, it]``, trace (R, T).  A forbidden A_ij is pinned at the floor of theta, 1e-9, not at an exact zero.  A
+    replica with ``active[r] == 0`` keeps its theta and its trace.  Returns ``thetas``."""
+    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
+        raise HipExtensionError("multistart_mstep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states("multistart_mstep", unbound, bound)
+    if rows.ndim != 3 or rows.shape[1] < 1:
+        raise ValueError(f"multistart_mstep: rows must be (R, N, {_lib_hmm.hmm_cols(M)}) with N >= 1")
+    rows = _multistart_inputs("multistart_mstep", rows, (rows.shape[1], _lib_hmm.hmm_cols(M)), "rows")
+    R, N = rows.shape[:2]
+    it = int(it)
+    for name, x, ok in (("thetas", thetas, lambda x: x.shape == (R, M * M + M)),
+                        ("trace", trace, lambda x: x.ndim == 2 and x.shape[0] == R and 0 <= it < x.shape[1])):
+        if (not isinstance(x, torch.Tensor) or x.device != rows.device or x.dtype != torch.float64 or not x.is_contiguous()
+                or not ok(x)):
+            raise ValueError(f"multistart_mstep: {name} must be contiguous float64 on the device of rows, thetas "
+                             f"({R}, {M * M + M}) and trace ({R}, T) with 0 <= it < T")
+    active = _multistart_active("multistart_mstep", active, R, rows.device)
+    bits = _lib_multistart.allow_bits(hmm_allow(allow, M, "multistart_mstep").tolist())
+    a = _lib_multistart.MultistartMstepArgs(rows=_lib.ptr(rows), theta=_lib.ptr(thetas), trace=_lib.ptr(trace),
+                                            active=_lib.ptr(active), N=N, it=it, T=trace.shape[1], R=R, U=U, B=B, allow=bits)
+    _lib.check(_lib_multistart.lib().tq_multistart_mstep(C.byref(a), _stream(rows.device)), "tq_multistart_mstep")
+    return thetas
+
+
+def multistart_em(estep, mstep, trace, active, num_iter, tol, chunk, progress_bar=None):
+    """The chunks and the stopping rule of ``hmm_fit``, applied per replica.  ``estep()`` and ``mstep(it)`` launch one
+    batched step on buffers the caller owns, among them ``trace`` (R, num_iter), NaN where nothing is written, and
+    ``active`` (R,) int32, all ones.  After each chunk the trace is read, a replica some iteration of which has gained at
+    most ``tol * |loglik|`` over the one before is marked inactive (one copy into ``active``), and the run stops when none
+    is active: a replica ends after the whole chunks, and at the theta, that ``hmm_fit`` from its start would end with.
+    Returns the lists ``iterations`` and ``converged`` (R,)."""
+    R = trace.shape[0]
+    iterations, converged = [0] * R, [False] * R
+
+    def em_steps(step0, n):
+        if all(converged):
+            return
+        for it in range(step0, step0 + n):
+            estep()
+            mstep(it)
+        ll = trace[:, : step0 + n].cpu()
+        for r in range(R):
+            if not converged[r]:
+                iterations[r] = step0 + n
+                gain = ll[r, 1:] - ll[r, :-1]
+                converged[r] = bool((gain <= tol * ll[r, 1:].abs()).any())
+        active.copy_(torch.tensor([0 if c else 1 for c in converged], dtype=torch.int32))
+
+    _run_chunks(em_steps, num_iter, chunk, progress_bar)
+    return iterations, converged
+
+
+def hmm_fit_restarts(p, prior, unbound, bound, restarts=8, seed=0, allow=None, starts=None, num_iter=200, tol=1e-9, chunk=50,
+                     progress_bar=None):
+    """``hmm_fit`` from R = ``restarts`` + 1 starts at once -- ``hmm_random_starts(unbound, bound, restarts, seed, allow)``,
+    or the rows of ``starts`` (R, M * M + M), normalised as ``hmm_fit`` normalises A0 and rho0 -- under the topology
+    ``allow`` (M, M; True where A_ij is free, None: fully connected), and the best of them.
+
+    Every EM iteration is one batched E-step and one batched M-step for all replicas (``multistart_em``), so R fits cost
+    the launches of one; a replica that meets the stopping rule of ``hmm_fit`` is frozen at the iteration count and the
+    theta ``hmm_fit`` from the same start would return.  One more batched E-step gives every replica's final log-evidence;
+    the best replica is the largest, a tie going to the lowest index.  For the best replica only, the closing E-step, the
+    canonical order and the relabelling of ``hmm_fit`` follow; ``allow`` is relabelled with the states.
+
+    Returns what ``hmm_fit`` returns for the winner -- ``theta``, ``gamma``, ``filt``, ``rows``, ``trace``, ``loglik``,
+    ``order`` -- with ``n_params`` = (free entries of A - M) + (M - 1) and ``bic`` from that, and for all replicas
+    ``best``, ``logliks`` (R,) float64 on the host, the lists ``iterations`` and ``converged`` (R,) (the winner's are
+    ``iterations[best]`` and ``converged[best]``), ``thetas`` (R, M * M + M) in the order of the states the EM ran in,
+    ``traces`` (R, T) with NaN after a replica's stop, ``starts`` (R, M * M + M) and ``allow`` (M, M) bool."""
+    import math
+
+    num_iter = int(num_iter)
+    U, B, M = _hmm_states("hmm_fit_restarts", unbound, bound)
+    free = hmm_allow(allow, M, "hmm_fit_restarts")
+    if starts is None:
+        starts = hmm_random_starts(U, B, restarts, seed, free)
+    starts = torch.as_tensor(starts, dtype=torch.float64).detach().cpu()
+    if (num_iter < 1 or starts.ndim != 2 or starts.shape[1] != M * M + M
+            or not 1 <= starts.shape[0] <= _lib_multistart.MULTISTART_MAX or not bool((starts >= 0).all())):
+        raise ValueError(f"hmm_fit_restarts: num_iter must be positive and starts (R, {M * M + M}) non-negative with 1 <= R "
+                         f"<= {_lib_multistart.MULTISTART_MAX}")
+    R = starts.shape[0]
+    A, rho = starts[:, : M * M].reshape(R, M, M), starts[:, M * M:]
+    if not bool((A.sum(2) > 0).all()) or not bool((rho.sum(1) > 0).all()):
+        raise ValueError("hmm_fit_restarts: every row of A and every rho of starts must have a positive sum")
+    if not isinstance(p, torch.Tensor) or p.device.type != "cuda":
+        raise HipExtensionError("hmm_fit_restarts runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    # row by row the expression of hmm_fit, so that a replica starts from the bits hmm_fit starts from
+    thetas = torch.stack([torch.cat([(A[r] / A[r].sum(1, keepdim=True)).reshape(-1), rho[r] / rho[r].sum()])
+                          for r in range(R)]).to(p.device)
+    p, N, F, _, prior, U, B, M = _hmm_inputs("hmm_fit_restarts", p, thetas[0], prior, U, B)
+    if R * N * F * M * 8 > MULTISTART_SCRATCH_BYTES:
+        raise ValueError(f"hmm_fit_restarts: the scratch of R = {R} replicas, N = {N} rows, F = {F} frames and M = {M} states "
+                         f"takes {R * N * F * M * 8} bytes, more than {MULTISTART_SCRATCH_BYTES}: use fewer restarts")
+    dev = p.device
+    rows = torch.empty(R, N, _lib_hmm.hmm_cols(M), dtype=torch.float64, device=dev)
+    scratch = torch.empty(R, N, F, M, dtype=torch.float64, device=dev)
+    trace = torch.full((R, num_iter), float("nan"), dtype=torch.float64, device=dev)
+    active = torch.ones(R, dtype=torch.int32, device=dev)
+    iterations, converged = multistart_em(
+        lambda: multistart_estep(p, thetas, prior, U, B, active, rows, scratch),
+        lambda it: multistart_mstep(rows, thetas, trace, it, U, B, free, active), trace, active, num_iter, tol, chunk,
+        progress_bar)
+    multistart_estep(p, thetas, prior, U, B, None, rows, scratch)
+    logliks = rows[:, :, -1].sum(1).cpu()
+    finite = torch.where(torch.isnan(logliks), torch.full_like(logliks, -math.inf), logliks)
+    best = min(r for r in range(R) if finite[r] == finite.max())
+    del scratch
+    theta = thetas[best].clone()
+    out = _hmm_estep(p, N, F, theta, prior, U, B, _hmm_buffers(N, F, M, dev))
+    order = hmm_canonical_order(theta, U, B)
+    out = hmm_permute(order, M, theta=theta, **out)
+    idx = torch.as_tensor(order, dtype=torch.int64)
+    loglik = out["rows"][:, -1].sum().item()
+    n_params = hmm_n_params(free)
+    return {**out, "trace": trace[best, : iterations[best]], "iterations": iterations, "converged": converged,
+            "loglik": loglik, "n_params": n_params, "bic": -2.0 * loglik + n_params * math.log(N * F), "order": order,
+            "best": best, "logliks": logliks, "thetas": thetas, "traces": trace[:, : max(iterations)], "starts": starts,
+            "allow": free[idx][:, idx]}
