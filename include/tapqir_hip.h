@@ -913,6 +913,79 @@ typedef struct {
 int tq_multistart_mstep(const tq_multistart_mstep_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Two colour channels as one chain (`tapqir_amd smooth --joint A,B`).  Channels a and b of one
+ * cosmos fit, hidden state s = z_a + 2 z_b: 0 neither bound, 1 only a, 2 only b, 3 both.
+ *   theta = (A row-major (4, 4), rho (4)): 20 doubles in device memory, read floored at TQ_SMOOTH_RMIN and renormalised as
+ *           the chain of four states above reads its theta.
+ *   l_f(s) = l^a_f(s & 1) l^b_f(s >> 1), l^c the evidence of the two-state section of channel c's p under channel c's
+ *           prior, with the same clamp at TQ_SMOOTH_PMIN.
+ * Replicas, `active` and the layout are those of the side-by-side section: replica r has theta[r], rows[r],
+ * filt[r] and gamma[r]; p_a and p_b are shared.  The workgroups of a replica with active[r] == 0 return at once and write
+ * nothing.  No atomics and a fixed order of additions: two runs give the same bits.
+ * Every entry point returns TQ_ERR_ARG, before anything touches the device, for a NULL required pointer, N, F or R < 1,
+ * F > TQ_SMOOTH_MAX_F, R > TQ_MULTISTART_MAX, a prior outside (0, 1), it < 0, T <= it, or a structure outside 0 .. 4 among
+ * the first R entries.
+ *
+ * tq_joint_estep: grid (N, R), one wave per (row, replica), the lane ranges, scans, sweeps and lane sums of tq_hmm_estep.
+ *   filt[r, n, f, s] = a_f(s), gamma[r, n, f, s] = p(state_f = s | all frames), rows[r, n] in the column order of
+ *   tq_hmm_estep: E n_ss' of the 16 ordered pairs, gamma_0 of the 4 states, loglik.  gamma == NULL stores no gamma; rows
+ *   have the same bits either way.
+ * ------------------------------------------------------------------------------------- */
+#define TQ_JOINT_INDEPENDENT 0 /* A = P_a(z_a' | z_a) P_b(z_b' | z_b): 4 free parameters of A */
+#define TQ_JOINT_A_DRIVES_B 1  /* A = P_a(z_a' | z_a) P_b(z_b' | z_a, z_b): 6 */
+#define TQ_JOINT_B_DRIVES_A 2  /* A = P_a(z_a' | z_a, z_b) P_b(z_b' | z_b): 6 */
+#define TQ_JOINT_COUPLED 3     /* A = P_a(z_a' | s) P_b(z_b' | s), no concerted events beyond chance: 8 */
+#define TQ_JOINT_FULL 4        /* A[s][s'] = n[s -> s'] / n[s -> .]: 12 */
+typedef struct {
+  const float* p_a;            /* (N, F) p(z = 1) of channel a, shared by the replicas */
+  const float* p_b;            /* (N, F) of channel b */
+  const double* theta;         /* (R, 20); device memory */
+  double* filt;                /* (R, N, F, 4) out */
+  double* gamma;               /* (R, N, F, 4) out; or NULL */
+  double* rows;                /* (R, N, TQ_HMM_COLS(4)) out */
+  const int32_t* active;       /* (R); device memory; or NULL: every replica runs */
+  int32_t N, F, R;
+  double prior_a, prior_b;     /* pi of each channel */
+} tq_joint_estep_args;
+
+int tq_joint_estep(const tq_joint_estep_args* a, void* stream);
+
+/* tq_joint_mstep: grid R, one workgroup per replica.  Sums the N rows of replica r in the fixed order of tq_hmm_mstep (the
+ * same bits for the same rows), stores the total loglik into trace[r * T + it] and overwrites theta[r] under structure[r].
+ * With n the summed E n_ss' and s = (z_a, z_b):
+ *   P_a(z_a' | s) = sum_{z_b'} n[s -> (z_a', z_b')] / n[s -> .]; where channel a does not see z_b (independent,
+ *   a-drives-b), numerator and denominator are both summed over z_b first.  P_b is the mirror image.
+ *   A[s][s'] = P_a P_b, then the floor of theta; TQ_JOINT_FULL is the M-step of tq_hmm_mstep.  A row whose denominator --
+ *   for a pooled factor, the pooled denominator -- is zero keeps its old values.  rho = mean gamma_0, floored.
+ * An inactive replica keeps theta[r] and writes no trace entry. */
+typedef struct {
+  const double* rows;          /* (R, N, TQ_HMM_COLS(4)) of tq_joint_estep */
+  double* theta;               /* (R, 20) in / out; device memory */
+  double* trace;               /* (R, T): trace[r * T + it] out */
+  const int32_t* active;       /* (R); device memory; or NULL */
+  int32_t N, it;
+  int32_t T, R;                /* entries of a replica's trace, T > it; replicas */
+  int32_t structure[TQ_MULTISTART_MAX]; /* TQ_JOINT_* of replica r; host memory, part of this struct */
+} tq_joint_mstep_args;
+
+int tq_joint_mstep(const tq_joint_mstep_args* a, void* stream);
+
+/* tq_joint_viterbi: the MAP path in joint states at one theta: tq_hmm_viterbi of four states with the emission logarithm
+ * of state s formed as log l^a(s & 1) + log l^b(s >> 1); the same back-pointer words and tie rule (lowest state).  One
+ * lane per row. */
+typedef struct {
+  const float* p_a;            /* (N, F) */
+  const float* p_b;            /* (N, F) */
+  const double* theta;         /* (20); device memory */
+  uint32_t* back;              /* scratch, ((F + 3) / 4) * N words */
+  uint8_t* path;               /* (N, F) out: joint states 0 .. 3 */
+  int32_t N, F;
+  double prior_a, prior_b;
+} tq_joint_viterbi_args;
+
+int tq_joint_viterbi(const tq_joint_viterbi_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame
  * decode of GlimpseDataset.__getitem__ (168-186: big-endian int16 + 2^15) and the offset-region value counts

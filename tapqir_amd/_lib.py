@@ -220,6 +220,7 @@ EXPORTS = [
     "tq_hmm_estep", "tq_hmm_mstep", "tq_hmm_viterbi", "tq_hmm_count", "tq_hmm_estimate",  # ... tapqir_amd/_lib_hmm.py
     "tq_chain_dwell",
     "tq_multistart_estep", "tq_multistart_mstep",  # ... tapqir_amd/_lib_multistart.py
+    "tq_joint_estep", "tq_joint_mstep", "tq_joint_viterbi",  # ... tapqir_amd/_lib_joint.py
 ]
 
 _lib = None

@@ -877,6 +877,135 @@ def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci
         raise typer.Exit(1)
 
 
+def _smooth_joint_options(joint, structure, U, B, restarts, restart_seed, forbid, logger):
+    """The checks of ``--joint`` and ``--structure`` of `smooth`, made where ``--ci`` is checked (after the model, before
+    ``--cpu``).  Returns ``{"a", "b", "structure"}``, structure a name or None for ``auto``."""
+    import re
+
+    from tapqir_amd._lib_joint import STRUCTURES
+
+    names = [name for name, _ in STRUCTURES]
+    if joint is None:
+        logger.error("smooth: --structure needs --joint A,B")
+        raise typer.Exit(1)
+    match = re.fullmatch(r"\s*(\d+)\s*,\s*(\d+)\s*", joint)
+    if not match or int(match.group(1)) == int(match.group(2)):
+        logger.error(f"smooth: --joint takes A,B with two different channel indices, got {joint!r}")
+        raise typer.Exit(1)
+    if (U, B) != (1, 1):
+        logger.error("smooth: --joint smooths two two-state channels together: it does not go with --unbound-states / "
+                     "--bound-states other than 1 and 1")
+        raise typer.Exit(1)
+    if restarts or restart_seed or forbid:
+        logger.error("smooth: --joint does not go with --restarts, --restart-seed or --forbid: its structures are fitted from "
+                     "the chain of the two separate fits")
+        raise typer.Exit(1)
+    if structure is not None and structure != "auto" and structure not in names:
+        logger.error(f"smooth: --structure takes auto, {', '.join(names)}; got {structure!r}")
+        raise typer.Exit(1)
+    return {"a": int(match.group(1)), "b": int(match.group(2)), "structure": None if structure in (None, "auto") else structure}
+
+
+def _smooth_joint(m, mask, cd, logger, pair, num_iter, tol, num_samples, ci, bootstrap, seed, progress_bar):
+    """`smooth --joint A,B`: the two channels as one chain of four states, s = z_A + 2 z_B, fitted
+    under the five structures side by side from the chain of the two separate two-state fits and ranked by BIC.  Writes
+    ``<model>_smooth-joint<A><B>.tpqr`` and ``<model>_smooth-joint<A><B>.csv``; no other file is touched.
+
+    The CSV has the sixteen entries of A, the eight conditional rates and their four ratios.  ``EM`` is the fitted value
+    under the chosen structure, ``MAP`` the quotient of the Viterbi path's pair counts, and ``Mean`` with its interval comes
+    from the pair counts of posterior rasters of the chain.  Those quotients are unconstrained: under a constrained
+    structure the intervals are those of free count quotients, not of the constrained estimator, so they need not be
+    centred on ``EM`` and do not vanish for a rate the structure ties to another."""
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.exceptions import HipExtensionError
+    from tapqir_amd.utils.joint_analysis import (RATE_NAMES, RATIO_NAMES, STRUCTURE_NAMES, joint_fit, joint_rates,
+                                                 joint_start_from, joint_viterbi)
+    from tapqir_amd.utils.mle_analysis import estimand_summary, hmm_estimate, hmm_sample, smooth_fit
+
+    data, a, b = m.data, pair["a"], pair["b"]
+    if a >= data.C or b >= data.C:
+        logger.error(f"smooth: --joint {a},{b} needs channels {a} and {b}, the data has {data.C} "
+                     f"channel{'s' if data.C != 1 else ''}")
+        raise typer.Exit(1)
+    stem = f"{m.name}_smooth-joint{a}{b}"
+    pct = f"{ci * 100:g}%"
+    z_raw = m.params["z_probs"][: data.N, :, :, 1].float()  # (N, F, C)
+    try:
+        dev = torch.device("cuda")
+        p, prior, two_state = {}, {}, {}
+        for c in (a, b):
+            prior[c] = float(torch.as_tensor(m.params["pi"]["Mean"]).reshape(-1, 2)[c, 1])
+            p[c] = z_raw[:, :, c][mask].to(dev)
+            two_state[c] = smooth_fit(p[c], prior[c], num_iter=num_iter, tol=tol, progress_bar=progress_bar)
+        ll_sep = sum(two_state[c]["rows"][:, 4].sum().item() for c in (a, b))
+        logger.info(f"Channels #{a} ({data.channels[a]}) and #{b} ({data.channels[b]}): log evidence of the two separate "
+                    f"two-state fits = {ll_sep:.6f}")
+        start = joint_start_from(two_state[a]["theta"], two_state[b]["theta"])
+        fit = joint_fit(p[a], p[b], prior[a], prior[b], start=start, num_iter=num_iter, tol=tol, choose=pair["structure"],
+                        progress_bar=progress_bar)
+        fits = fit["fits"]
+        for f in fits:
+            logger.info(f"structure {f['name']}: log evidence = {f['loglik']:.6f}, {f['n_params']} parameters, BIC = "
+                        f"{f['bic']:.6f} after {f['iterations']} iterations")
+            if not f["converged"]:
+                logger.warning(f"smooth: the EM of structure {f['name']} did not converge to --tol {tol:g} within "
+                               f"{f['iterations']} iterations")
+        # independent is nested in both driven structures, those in coupled, and every structure in full
+        nested = {1: (0,), 2: (0,), 3: (0, 1, 2), 4: (0, 1, 2, 3)}
+        for big, smalls in nested.items():
+            for small in smalls:
+                if fits[big]["loglik"] < fits[small]["loglik"] - 1e-6 * abs(fits[small]["loglik"]):
+                    logger.warning(f"smooth: structure {fits[big]['name']} ends below {fits[small]['name']}, which is nested in "
+                                   f"it ({fits[big]['loglik']:.6f} < {fits[small]['loglik']:.6f}): a local optimum")
+        chosen = fit["chosen"]
+        logger.info(f"chosen structure: {STRUCTURE_NAMES[chosen]} ("
+                    + ("forced by --structure" if pair["structure"] is not None else "the lowest BIC") + ")")
+        theta = fit["theta"]
+        A = theta[:16].reshape(4, 4).cpu()
+        path = joint_viterbi(p[a], p[b], theta, prior[a], prior[b])
+        chan_seed = a if seed is None else seed
+        sample = hmm_sample(fit["filt"], theta, 2, 2, num_samples, seed=chan_seed, trans=True)
+        est = hmm_estimate(sample["trans"], bootstrap=bootstrap, seed=chan_seed)
+        pairs = torch.bincount((path[:, :-1].long() * 4 + path[:, 1:].long()).reshape(-1), minlength=16).double().reshape(4, 4)
+        A_map = (pairs / pairs.sum(1, keepdim=True)).cpu()
+        em, drawn, mapped = joint_rates(A), joint_rates(est["A"]), joint_rates(A_map)
+        results = pd.DataFrame(columns=["EM", "Mean", f"{pct} LL", f"{pct} UL", "MAP"], dtype=float)
+        for i in range(4):
+            for j in range(4):
+                row = estimand_summary(est["A"][:, i, j], ci)
+                results.loc[f"A{i}{j}"] = [A[i, j].item(), row["mean"], row["ll"], row["ul"], A_map[i, j].item()]
+        for name in RATE_NAMES + RATIO_NAMES:
+            row = estimand_summary(drawn[name], ci)
+            results.loc[name] = [em[name].item(), row["mean"], row["ll"], row["ul"], mapped[name].item()]
+        results.to_csv(cd / f"{stem}.csv")
+        logger.info(f"Saved the joint transition matrix, conditional rates and ratios in {stem}.csv file")
+
+        gamma = fit["gamma"].float().cpu()  # (n, F, 4)
+        state_probs = torch.full((data.N, data.F, 4), float("nan"))
+        state_probs[mask] = gamma
+        z_probs = torch.stack([state_probs[..., 1] + state_probs[..., 3], state_probs[..., 2] + state_probs[..., 3]], -1)
+        state_map = torch.full((data.N, data.F), 255, dtype=torch.uint8)
+        state_map[mask] = path.cpu()
+        z_map = torch.stack([state_map & 1, state_map >> 1], -1)
+        z_map[~mask] = 255
+        log_evidence = torch.full((data.N,), float("nan"), dtype=torch.float64)
+        log_evidence[mask] = fit["rows"][:, -1].cpu()
+        out = {"state_probs": state_probs, "z_probs": z_probs, "state_map": state_map, "z_map": z_map,
+               "log_evidence": log_evidence, "theta": theta.cpu(),
+               "prior": torch.tensor([prior[a], prior[b]], dtype=torch.float64), "channels": (a, b),
+               "structures": [f["name"] for f in fits], "logliks": torch.tensor([f["loglik"] for f in fits], dtype=torch.float64),
+               "bics": torch.tensor([f["bic"] for f in fits], dtype=torch.float64),
+               "n_params": torch.tensor([f["n_params"] for f in fits], dtype=torch.int64), "chosen": STRUCTURE_NAMES[chosen],
+               "loglik_trace": [f["trace"] for f in fits], "mask": mask}
+        torch.save(out, cd / f"{stem}.tpqr")
+        logger.info(f"Saved the jointly smoothed posterior in {stem}.tpqr file")
+    except HipExtensionError:
+        logger.exception("smooth failed: it needs an AMD GPU (--cuda) and the built HIP library")
+        raise typer.Exit(1)
+
+
 @app.command()
 def smooth(
     model: avail_models = typer.Option("cosmos", help="Tapqir model"),
@@ -892,6 +1021,8 @@ def smooth(
     restarts: int = typer.Option(0, "--restarts", min=0, max=63, help="Random starts of the EM fitted next to the default start; the best one is kept"),
     restart_seed: int = typer.Option(0, "--restart-seed", help="Seed of the random starts"),
     forbid: Optional[List[str]] = typer.Option(None, "--forbid", help="i-j: fix the transition from state i to state j at the floor, 1e-9 (repeatable)"),
+    joint: Optional[str] = typer.Option(None, "--joint", help="A,B: smooth the colour channels A and B together as one chain of four states"),
+    structure: Optional[str] = typer.Option(None, "--structure", help="With --joint: auto (the lowest BIC, the default), independent, a-drives-b, b-drives-a, coupled or full"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -914,6 +1045,12 @@ def smooth(
     from hidden state i to hidden state j from the chain.  The file names do not change; the
     ``.tpqr`` gains ``restart_logliks``, ``restart_best`` and ``topology``, and the BIC counts the free entries only.
     Neither option applies to the two-state chain.
+
+    With ``--joint A,B`` the colour channels A and B are smoothed together as one chain of the four states neither / only A
+    / only B / both bound, fitted under five structures of its transition matrix -- ``independent``,
+    ``a-drives-b``, ``b-drives-a``, ``coupled``, ``full`` -- side by side; the BIC ranks them and ``--structure`` forces one.
+    Only ``<model>_smooth-joint<A><B>.tpqr`` and ``<model>_smooth-joint<A><B>.csv`` are written: the matrix, the on and off
+    rates of each channel given the partner's state, and their ratios.
     """
     import pandas as pd
     import torch
@@ -930,10 +1067,16 @@ def smooth(
     if model.value == "cosmos" and unbound_states + bound_states > 4:
         logger.error(f"smooth: --unbound-states + --bound-states must be at most 4, got {unbound_states} + {bound_states}")
         raise typer.Exit(1)
+    pair = None
+    if model.value == "cosmos" and (joint is not None or structure is not None):
+        pair = _smooth_joint_options(joint, structure, unbound_states, bound_states, restarts, restart_seed, forbid, logger)
     multistart = None
     if model.value == "cosmos" and (restarts or restart_seed or forbid):
         multistart = _smooth_multistart_options(unbound_states, bound_states, restarts, restart_seed, forbid, logger)
     m, mask, progress_bar = _kinetics_inputs("smooth", model, cuda, progress_bar)
+    if pair is not None:
+        _smooth_joint(m, mask, cd, logger, pair, num_iter, tol, num_samples, ci, bootstrap, seed, progress_bar)
+        return
     if (unbound_states, bound_states) != (1, 1):
         _smooth_multistate(m, mask, cd, logger, unbound_states, bound_states, num_iter, tol, num_samples, ci, bootstrap,
                            seed, progress_bar, multistart)

@@ -32,6 +32,8 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
 * ``hmm_random_starts`` / ``hmm_fit_restarts``: the EM of ``hmm_fit`` from several starts fitted side by side, under an
   optional topology of forbidden transitions, and the best of them (``tq_multistart_estep``, ``tq_multistart_mstep``).
 
+Two colour channels smoothed together as one chain (``smooth --joint``) are in ``tapqir_amd/utils/joint_analysis.py``.
+
 There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
 """
 
