@@ -4,12 +4,15 @@
 //     class, tq_smooth_evidence;
 //   * products of MxM matrices kept in range by powers of two, and what one lane of the E-step does with its chunk of
 //     frames (tq_smooth_lane_range): the chunk product, the forward sweep from the chunk's exclusive prefix, the backward
-//     sweep from its exclusive suffix with the pair marginals;
+//     sweep from its exclusive suffix with the pair marginals.  These tq_chain_* bodies and the Viterbi row see the chain
+//     as anything with A[M][M] and rho[M], and a frame's emission through a callable em(f, l): TqHmmEmit here, TqJointEmit
+//     in tq_joint.h.  Every chain with M x M products runs this one text;
 //   * the M-step of the summed rows, the Viterbi path of a row in hidden states, and the backward sampler's thresholds;
 //   * the sampler's uniforms in its order of draws, and a row drawn backwards and walked, as it is drawn, into runs of
 //     equal class (tq_chain_dwell).
-// The two-state bodies of tq_smooth.h are not touched; this is their generalisation next to them.  Nothing here
-// subtracts nearly equal quantities: a_f is stored whole, and the sampler's thresholds are sums of tails.
+// The two-state bodies of tq_smooth.h stay apart on purpose: their layout differs (filt holds a_f(1) alone, gamma's row
+// holds a_f(0), theta has three parameters), so folding them in would change what they store.  Nothing here subtracts
+// nearly equal quantities: a_f is stored whole, and the sampler's thresholds are sums of tails.
 // The __global__ wrappers are in tq_hmm.hip; the test suite runs the same bodies from a g++ build.
 #pragma once
 #include <math.h>
@@ -60,6 +63,28 @@ TQ_HD void tq_hmm_emission(const TqHmmModel<M>& m, float pf, double* l) {
 #pragma unroll
   for (int i = 0; i < M; ++i) l[i] = i < m.U ? l0 : l1;
 }
+
+// the emission of frame f of one row, as the tq_chain_* bodies take it
+template <int M>
+struct TqHmmEmit {
+  const TqHmmModel<M>& m;
+  const float* pr;
+  TQ_HD void operator()(int f, double* l) const { tq_hmm_emission(m, pr[f], l); }
+};
+
+// ll[i] = log l_f(class(i)): two logarithms per frame, state 0 is unbound and state M - 1 bound
+template <int M>
+struct TqHmmLogEmit {
+  const TqHmmModel<M>& m;
+  const float* pr;
+  TQ_HD void operator()(int f, double* ll) const {
+    double l[M];
+    tq_hmm_emission(m, pr[f], l);
+    const double ll0 = log(l[0]), ll1 = log(l[M - 1]);
+#pragma unroll
+    for (int i = 0; i < M; ++i) ll[i] = i < m.U ? ll0 : ll1;
+  }
+};
 
 // ---- MxM products -----------------------------------------------------------------------------------------------------
 template <int M>
@@ -112,12 +137,12 @@ TQ_HD TqHmmMat<M> tq_hmm_mul(const TqHmmMat<M>& x, const TqHmmMat<M>& y) {
 
 // product of M_f = A diag(l_f) over the lane's frames; M_0 has every row equal to rho o l_0, so that every prefix that
 // holds frame 0 has rows proportional to a_f.  No frames: the identity.
-template <int M>
-TQ_HD TqHmmMat<M> tq_hmm_chunk(const TqHmmModel<M>& m, const float* pr, int lo, int hi) {
+template <int M, class Chain, class Emit>
+TQ_HD TqHmmMat<M> tq_chain_chunk(const Chain& m, const Emit& em, int lo, int hi) {
   TqHmmMat<M> c = tq_hmm_identity<M>();
   for (int f = lo; f < hi; ++f) {
     double l[M];
-    tq_hmm_emission(m, pr[f], l);
+    em(f, l);
     TqHmmMat<M> t;
 #pragma unroll
     for (int i = 0; i < M; ++i)
@@ -160,15 +185,15 @@ TQ_HD void tq_hmm_suffix_vector(const TqHmmMat<M>& e, double* b) {
 
 // Forward sweep over [lo, hi) from a_{lo-1} = v0: writes a_f into filt[f * M ..].  Returns the lane's sum of log c_f: the
 // normalisers are multiplied up as mantissa and binary exponent, and one logarithm is taken at the end.
-template <int M>
-TQ_HD double tq_hmm_forward(const TqHmmModel<M>& m, const float* pr, int lo, int hi, const double* v0, double* filt) {
+template <int M, class Chain, class Emit>
+TQ_HD double tq_chain_forward(const Chain& m, const Emit& em, int lo, int hi, const double* v0, double* filt) {
   double v[M], mant = 1.0;
   int expo = 0;
 #pragma unroll
   for (int i = 0; i < M; ++i) v[i] = v0[i];
   for (int f = lo; f < hi; ++f) {
     double l[M], u[M], c = 0.0;
-    tq_hmm_emission(m, pr[f], l);
+    em(f, l);
 #pragma unroll
     for (int j = 0; j < M; ++j) {
       double s = v[0] * m.A[0][j];
@@ -193,10 +218,10 @@ TQ_HD double tq_hmm_forward(const TqHmmModel<M>& m, const float* pr, int lo, int
 // Backward sweep over [lo, hi), g = hi - 1 .. lo, from beta_{hi-1} = b0.  Frame g gives gamma_g, and with a_{g-1} -- the
 // lane's own, or v = a_{lo-1} of its prefix -- the pair marginals xi_{g-1}(i, j) ~ a_{g-1}(i) A[i][j] l_g(j) beta_g(j):
 // the pair (g - 1, g) belongs to the lane that owns g.  acc[i * M + j] += E n_ij; acc[M * M + i] = gamma_0(i) in the lane
-// that owns frame 0.  GAMMA = false stores no gamma_g and does not read `gam` (tq_multistart.h); the sums are the same.
-template <int M, bool GAMMA = true>
-TQ_HD void tq_hmm_backward(const TqHmmModel<M>& m, const float* pr, int lo, int hi, const double* b0, const double* v,
-                           const double* filt, double* gam, double* acc) {
+// that owns frame 0.  GAMMA = false stores no gamma_g and does not read `gam`; the sums are the same.
+template <int M, bool GAMMA, class Chain, class Emit>
+TQ_HD void tq_chain_backward(const Chain& m, const Emit& em, int lo, int hi, const double* b0, const double* v,
+                             const double* filt, double* gam, double* acc) {
   double b[M];
 #pragma unroll
   for (int i = 0; i < M; ++i) b[i] = b0[i];
@@ -218,7 +243,7 @@ TQ_HD void tq_hmm_backward(const TqHmmModel<M>& m, const float* pr, int lo, int 
       break;
     }
     double l[M], w[M], x[M][M], tot = 0.0;
-    tq_hmm_emission(m, pr[g], l);
+    em(g, l);
 #pragma unroll
     for (int j = 0; j < M; ++j) w[j] = l[j] * b[j];
 #pragma unroll
@@ -254,6 +279,33 @@ TQ_HD void tq_hmm_backward(const TqHmmModel<M>& m, const float* pr, int lo, int 
   }
 }
 
+// acc[0 .. TQ_HMM_COLS(M)) of the lane that owns [lo, hi): v = a_{lo-1} of its exclusive prefix, b = beta_{hi-1} of its
+// exclusive suffix, filt the row's scratch of a_f.  The last column is the lane's sum of log c_f.
+template <int M, bool GAMMA, class Chain, class Emit>
+TQ_HD void tq_chain_sweeps(const Chain& m, const Emit& em, int lo, int hi, const double* v, const double* b, double* filt,
+                           double* gam, double* acc) {
+  constexpr int COLS = TQ_HMM_COLS(M);
+#pragma unroll
+  for (int j = 0; j < COLS; ++j) acc[j] = 0.0;
+  acc[COLS - 1] = tq_chain_forward<M>(m, em, lo, hi, v, filt);
+  tq_chain_backward<M, GAMMA>(m, em, lo, hi, b, v, filt, gam, acc);
+}
+
+// the same bodies under their names for the class chain on one row's p: one line each, nothing of their own
+template <int M>
+TQ_HD TqHmmMat<M> tq_hmm_chunk(const TqHmmModel<M>& m, const float* pr, int lo, int hi) {
+  return tq_chain_chunk<M>(m, TqHmmEmit<M>{m, pr}, lo, hi);
+}
+template <int M>
+TQ_HD double tq_hmm_forward(const TqHmmModel<M>& m, const float* pr, int lo, int hi, const double* v0, double* filt) {
+  return tq_chain_forward<M>(m, TqHmmEmit<M>{m, pr}, lo, hi, v0, filt);
+}
+template <int M, bool GAMMA = true>
+TQ_HD void tq_hmm_backward(const TqHmmModel<M>& m, const float* pr, int lo, int hi, const double* b0, const double* v,
+                           const double* filt, double* gam, double* acc) {
+  tq_chain_backward<M, GAMMA>(m, TqHmmEmit<M>{m, pr}, lo, hi, b0, v, filt, gam, acc);
+}
+
 // ---- M-step -----------------------------------------------------------------------------------------------------------
 // sums[0 .. TQ_HMM_COLS(M)) over the N rows -> theta, floored and renormalised; a state without expected occupancy keeps
 // its old row
@@ -279,24 +331,23 @@ TQ_HD void tq_hmm_mstep_theta(const double* sums, int N, double* theta) {
 // ---- Viterbi ----------------------------------------------------------------------------------------------------------
 // One row, sequential in f.  The scores are kept relative to state 0's (d[i] = delta(i) - delta(0), d[0] = 0), so their
 // size does not grow with F.  Back-pointers: the two bits at 8 (f & 3) + 2 j of word back[(f >> 2) * stride] are the best
-// predecessor of state j at frame f >= 1; a tie takes the lowest state.
-template <int M>
-TQ_HD void tq_hmm_viterbi_row(const TqHmmModel<M>& m, const float* pr, int F, uint32_t* back, int64_t stride,
-                              uint8_t* path) {
-  double la[M][M], d[M], l[M];
+// predecessor of state j at frame f >= 1; a tie takes the lowest state.  lem(f, ll) fills the M emission logarithms of
+// frame f: TqHmmLogEmit, or TqJointLogEmit of tq_joint.h.
+template <int M, class Chain, class LogEmit>
+TQ_HD void tq_chain_viterbi_row(const Chain& m, const LogEmit& lem, int F, uint32_t* back, int64_t stride, uint8_t* path) {
+  double la[M][M], d[M], ll[M];
 #pragma unroll
   for (int i = 0; i < M; ++i)
 #pragma unroll
     for (int j = 0; j < M; ++j) la[i][j] = log(m.A[i][j]);
-  tq_hmm_emission(m, pr[0], l);
-  const double s00 = log(m.rho[0]) + log(l[0]);
+  lem(0, ll);
+  const double s00 = log(m.rho[0]) + ll[0];
   d[0] = 0.0;
 #pragma unroll
-  for (int i = 1; i < M; ++i) d[i] = (log(m.rho[i]) + log(l[i])) - s00;
+  for (int i = 1; i < M; ++i) d[i] = (log(m.rho[i]) + ll[i]) - s00;
   uint32_t word = 0;
   for (int f = 1; f < F; ++f) {
-    tq_hmm_emission(m, pr[f], l);
-    const double ll0 = log(l[0]), ll1 = log(l[M - 1]);  // the two classes: state 0 is unbound, state M - 1 bound
+    lem(f, ll);
     double s[M];
     uint32_t bits = 0;
 #pragma unroll
@@ -311,7 +362,7 @@ TQ_HD void tq_hmm_viterbi_row(const TqHmmModel<M>& m, const float* pr, int F, ui
           bp = (uint32_t)i;
         }
       }
-      s[j] = best + (j < m.U ? ll0 : ll1);
+      s[j] = best + ll[j];
       bits |= bp << (2 * j);
     }
 #pragma unroll
@@ -336,6 +387,12 @@ TQ_HD void tq_hmm_viterbi_row(const TqHmmModel<M>& m, const float* pr, int F, ui
     z = (word >> (8 * (f & 3) + 2 * z)) & 3u;
     path[f - 1] = (uint8_t)z;
   }
+}
+
+template <int M>
+TQ_HD void tq_hmm_viterbi_row(const TqHmmModel<M>& m, const float* pr, int F, uint32_t* back, int64_t stride,
+                              uint8_t* path) {
+  tq_chain_viterbi_row<M>(m, TqHmmLogEmit<M>{m, pr}, F, back, stride, path);
 }
 
 // ---- backward sampler -------------------------------------------------------------------------------------------------

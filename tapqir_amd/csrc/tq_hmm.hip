@@ -2,111 +2,23 @@
 // as a chunked forward-backward with two wave scans of MxM products, the M-step of the summed rows, the Viterbi path in
 // hidden states, the backward sampler with its class-level and state-level counts, the same sampler walked into dwell-time
 // intervals and first-binding frames, and the pooled or AOI-resampled estimate of A (DESIGN.md
-// section 22).  The kernels are templates over M; the two-state kernels of tq_smooth.hip stay.
+// section 22).  The kernels are templates over M; the two-state kernels of tq_smooth.hip stay.  The E-step's body and the
+// M-step's sum of rows are tq_chain_dev.h's, shared with tq_multistart.hip and tq_joint.hip.
 #include <hip/hip_runtime.h>
 
-#include "tq_dpp.h"
-#include "tq_hmm.h"
+#include "tq_chain_dev.h"
 #include "tq_host.h"
 
-// runs `...` with the compile-time constant MM = M, which tq_hmm_states has checked to be 2, 3 or 4
-#define TQ_HMM_SWITCH_M(M, ...)  \
-  switch (M) {                   \
-    case 2: {                    \
-      constexpr int MM = 2;      \
-      __VA_ARGS__;               \
-    } break;                     \
-    case 3: {                    \
-      constexpr int MM = 3;      \
-      __VA_ARGS__;               \
-    } break;                     \
-    default: {                   \
-      constexpr int MM = 4;      \
-      __VA_ARGS__;               \
-    } break;                     \
-  }
-
-static bool tq_hmm_states(const char* who, int U, int B) {
-  if (U >= 1 && B >= 1 && U + B <= TQ_HMM_MAX_STATES) return true;
-  char buf[120];
-  snprintf(buf, sizeof(buf), "%s: U and B must be at least 1 and U + B at most %d", who, TQ_HMM_MAX_STATES);
-  tq_set_error(buf);
-  return false;
-}
-
-// ---- E-step: one wave (= one workgroup) per row, L = ceil(F / 64) consecutive frames per lane --------------------------
-template <int M>
-__device__ __forceinline__ TqHmmMat<M> tq_hmm_shfl_up(const TqHmmMat<M>& x, int d) {
-  TqHmmMat<M> r;
-#pragma unroll
-  for (int i = 0; i < M; ++i)
-#pragma unroll
-    for (int j = 0; j < M; ++j) r.m[i][j] = __shfl_up(x.m[i][j], d, 64);
-  return r;
-}
-template <int M>
-__device__ __forceinline__ TqHmmMat<M> tq_hmm_shfl_down(const TqHmmMat<M>& x, int d) {
-  TqHmmMat<M> r;
-#pragma unroll
-  for (int i = 0; i < M; ++i)
-#pragma unroll
-    for (int j = 0; j < M; ++j) r.m[i][j] = __shfl_down(x.m[i][j], d, 64);
-  return r;
-}
-
-// The scans of tq_smooth_estep_kernel, one after the other so that only one running product is live at a time: the
-// prefix scan multiplies the lower lanes' product from the left and leaves a_{lo-1}, the suffix scan the higher lanes'
-// from the right and leaves beta_{hi-1} (Hillis-Steele, six steps each, one more shuffle makes them exclusive).  Every
-// lane takes part in every shuffle.
+// ---- E-step: one wave (= one workgroup) per row; the scans and the sweeps are tq_chain_estep_row ------------------------
 template <int M>
 __global__ __launch_bounds__(64) void tq_hmm_estep_kernel(const tq_hmm_estep_args a) {
-  constexpr int COLS = TQ_HMM_COLS(M);
   const int n = blockIdx.x, lane = threadIdx.x;
   const int F = a.F;
   const float* pr = a.p + (int64_t)n * F;
   double* filt = a.filt + (int64_t)n * F * M;
   double* gam = a.gamma + (int64_t)n * F * M;
   const TqHmmModel<M> m = tq_hmm_model<M>(a.theta, a.U, a.prior);
-  int lo, hi;
-  tq_smooth_lane_range(lane, F, lo, hi);
-
-  const TqHmmMat<M> c = tq_hmm_chunk(m, pr, lo, hi);
-  double v[M], b[M];
-  {
-    TqHmmMat<M> pre = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const TqHmmMat<M> left = tq_hmm_shfl_up(pre, d);
-      if (lane >= d) pre = tq_hmm_mul(left, pre);
-    }
-    pre = tq_hmm_shfl_up(pre, 1);
-    if (lane == 0) pre = tq_hmm_identity<M>();
-    tq_hmm_prefix_vector(pre, v);
-  }
-  {
-    TqHmmMat<M> suf = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const TqHmmMat<M> right = tq_hmm_shfl_down(suf, d);
-      if (lane + d < 64) suf = tq_hmm_mul(suf, right);
-    }
-    suf = tq_hmm_shfl_down(suf, 1);
-    if (lane == 63) suf = tq_hmm_identity<M>();
-    tq_hmm_suffix_vector(suf, b);
-  }
-
-  double acc[COLS];
-#pragma unroll
-  for (int j = 0; j < COLS; ++j) acc[j] = 0.0;
-  acc[COLS - 1] = tq_hmm_forward(m, pr, lo, hi, v, filt);
-  tq_hmm_backward(m, pr, lo, hi, b, v, filt, gam, acc);
-#pragma unroll
-  for (int j = 0; j < COLS; ++j) acc[j] = tq_group_sum<64>(acc[j]);  // every lane is back here
-  if (lane == 0) {
-    double* out = a.rows + (int64_t)n * COLS;
-#pragma unroll
-    for (int j = 0; j < COLS; ++j) out[j] = acc[j];
-  }
+  tq_chain_estep_row<M, true>(m, TqHmmEmit<M>{m, pr}, F, lane, filt, gam, a.rows + (int64_t)n * TQ_HMM_COLS(M));
 }
 
 extern "C" int tq_hmm_estep(const tq_hmm_estep_args* a, void* stream) {
@@ -114,15 +26,9 @@ extern "C" int tq_hmm_estep(const tq_hmm_estep_args* a, void* stream) {
     tq_set_error("tq_hmm_estep: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->N < 1 || a->F < 1 || a->F > TQ_SMOOTH_MAX_F) {
-    tq_set_error("tq_hmm_estep: N and F must be positive and F at most 65536");
+  if (!tq_chain_frames_ok("tq_hmm_estep", a->N, a->F) || !tq_chain_states_ok("tq_hmm_estep", a->U, a->B) ||
+      !tq_chain_prior_ok("tq_hmm_estep", a->prior))
     return TQ_ERR_ARG;
-  }
-  if (!tq_hmm_states("tq_hmm_estep", a->U, a->B)) return TQ_ERR_ARG;
-  if (!(a->prior > 0.0 && a->prior < 1.0)) {
-    tq_set_error("tq_hmm_estep: prior must lie in (0, 1)");
-    return TQ_ERR_ARG;
-  }
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_hmm_estep_kernel<MM>), dim3((unsigned)a->N), dim3(64), 0,
                                                   (hipStream_t)stream, *a));
   return tq_launch_status("tq_hmm_estep_kernel");
@@ -133,29 +39,9 @@ template <int M>
 __global__ __launch_bounds__(TQ_SMOOTH_MSTEP_THREADS) void tq_hmm_mstep_kernel(const tq_hmm_mstep_args a) {
   constexpr int COLS = TQ_HMM_COLS(M);
   __shared__ double part[COLS][TQ_SMOOTH_MSTEP_THREADS];
-  const int t = threadIdx.x;
-  double s[COLS];
-#pragma unroll
-  for (int j = 0; j < COLS; ++j) s[j] = 0.0;
-  for (int n = t; n < a.N; n += TQ_SMOOTH_MSTEP_THREADS) {
-    const double* row = a.rows + (int64_t)n * COLS;
-#pragma unroll
-    for (int j = 0; j < COLS; ++j) s[j] += row[j];
-  }
-#pragma unroll
-  for (int j = 0; j < COLS; ++j) part[j][t] = s[j];
-  __syncthreads();
-  for (int h = TQ_SMOOTH_MSTEP_THREADS / 2; h > 0; h >>= 1) {
-    if (t < h) {
-#pragma unroll
-      for (int j = 0; j < COLS; ++j) part[j][t] += part[j][t + h];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    double sums[COLS], theta[M * M + M];
-#pragma unroll
-    for (int j = 0; j < COLS; ++j) sums[j] = part[j][0];
+  double sums[COLS];
+  if (tq_chain_reduce_rows<COLS>(a.rows, a.N, part, sums)) {
+    double theta[M * M + M];
 #pragma unroll
     for (int j = 0; j < M * M + M; ++j) theta[j] = a.theta[j];
     tq_hmm_mstep_theta<M>(sums, a.N, theta);
@@ -174,7 +60,7 @@ extern "C" int tq_hmm_mstep(const tq_hmm_mstep_args* a, void* stream) {
     tq_set_error("tq_hmm_mstep: N must be positive and it non-negative");
     return TQ_ERR_ARG;
   }
-  if (!tq_hmm_states("tq_hmm_mstep", a->U, a->B)) return TQ_ERR_ARG;
+  if (!tq_chain_states_ok("tq_hmm_mstep", a->U, a->B)) return TQ_ERR_ARG;
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_hmm_mstep_kernel<MM>), dim3(1), dim3(TQ_SMOOTH_MSTEP_THREADS), 0,
                                                   (hipStream_t)stream, *a));
   return tq_launch_status("tq_hmm_mstep_kernel");
@@ -194,15 +80,9 @@ extern "C" int tq_hmm_viterbi(const tq_hmm_viterbi_args* a, void* stream) {
     tq_set_error("tq_hmm_viterbi: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->N < 1 || a->F < 1 || a->F > TQ_SMOOTH_MAX_F) {
-    tq_set_error("tq_hmm_viterbi: N and F must be positive and F at most 65536");
+  if (!tq_chain_frames_ok("tq_hmm_viterbi", a->N, a->F) || !tq_chain_states_ok("tq_hmm_viterbi", a->U, a->B) ||
+      !tq_chain_prior_ok("tq_hmm_viterbi", a->prior))
     return TQ_ERR_ARG;
-  }
-  if (!tq_hmm_states("tq_hmm_viterbi", a->U, a->B)) return TQ_ERR_ARG;
-  if (!(a->prior > 0.0 && a->prior < 1.0)) {
-    tq_set_error("tq_hmm_viterbi: prior must lie in (0, 1)");
-    return TQ_ERR_ARG;
-  }
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_hmm_viterbi_kernel<MM>), dim3((unsigned)((a->N + 63) / 64)),
                                                   dim3(64), 0, (hipStream_t)stream, *a));
   return tq_launch_status("tq_hmm_viterbi_kernel");
@@ -298,7 +178,7 @@ extern "C" int tq_hmm_count(const tq_hmm_count_args* a, void* stream) {
     tq_set_error("tq_hmm_count: N, F and S must be positive and F at most 65536");
     return TQ_ERR_ARG;
   }
-  if (!tq_hmm_states("tq_hmm_count", a->U, a->B)) return TQ_ERR_ARG;
+  if (!tq_chain_states_ok("tq_hmm_count", a->U, a->B)) return TQ_ERR_ARG;
   const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
   if (grid.y > 65535u) {
     tq_set_error("tq_hmm_count: S too large");
@@ -404,7 +284,7 @@ extern "C" int tq_chain_dwell(const tq_chain_dwell_args* a, void* stream) {
     tq_set_error("tq_chain_dwell: N, F and S must be positive, F at most 65536 and total non-negative");
     return TQ_ERR_ARG;
   }
-  if (!tq_hmm_states("tq_chain_dwell", a->U, a->B)) return TQ_ERR_ARG;
+  if (!tq_chain_states_ok("tq_chain_dwell", a->U, a->B)) return TQ_ERR_ARG;
   const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
   if (grid.y > 65535u) {
     tq_set_error("tq_chain_dwell: S too large");
@@ -470,7 +350,7 @@ extern "C" int tq_hmm_estimate(const tq_hmm_estimate_args* a, void* stream) {
     tq_set_error("tq_hmm_estimate: S too large");
     return TQ_ERR_ARG;
   }
-  if (!tq_hmm_states("tq_hmm_estimate", a->U, a->B)) return TQ_ERR_ARG;
+  if (!tq_chain_states_ok("tq_hmm_estimate", a->U, a->B)) return TQ_ERR_ARG;
   TQ_HMM_SWITCH_M(a->U + a->B,
                   hipLaunchKernelGGL((tq_hmm_estimate_kernel<MM>), dim3((unsigned)a->S), dim3(64), 0, (hipStream_t)stream, *a));
   return tq_launch_status("tq_hmm_estimate_kernel");

@@ -30,6 +30,54 @@ static inline int tq_launch_status(const char* what) {
     default: { constexpr int KK = 4; __VA_ARGS__; } break;           \
   }
 
+// ---- the hidden-Markov entry points (tq_hmm.hip, tq_multistart.hip, tq_joint.hip) ---------------------------------------
+// runs `...` with the compile-time constant MM = M, which tq_chain_states_ok has checked to be 2, 3 or 4
+#define TQ_HMM_SWITCH_M(M, ...)  \
+  switch (M) {                   \
+    case 2: {                    \
+      constexpr int MM = 2;      \
+      __VA_ARGS__;               \
+    } break;                     \
+    case 3: {                    \
+      constexpr int MM = 3;      \
+      __VA_ARGS__;               \
+    } break;                     \
+    default: {                   \
+      constexpr int MM = 4;      \
+      __VA_ARGS__;               \
+    } break;                     \
+  }
+
+// Argument checks: true, or false with the error text "<who>: <what>", who = the entry point
+#define TQ_STR_(x) #x
+#define TQ_STR(x) TQ_STR_(x)
+static inline bool tq_chain_require(bool ok, const char* who, const char* what) {
+  if (ok) return true;
+  char buf[160];
+  snprintf(buf, sizeof(buf), "%s: %s", who, what);
+  tq_set_error(buf);
+  return false;
+}
+static inline bool tq_chain_frames_ok(const char* who, int N, int F) {
+  return tq_chain_require(N >= 1 && F >= 1 && F <= TQ_SMOOTH_MAX_F, who,
+                          "N and F must be positive and F at most " TQ_STR(TQ_SMOOTH_MAX_F));
+}
+static inline bool tq_chain_states_ok(const char* who, int U, int B) {
+  return tq_chain_require(U >= 1 && B >= 1 && U + B <= TQ_HMM_MAX_STATES, who,
+                          "U and B must be at least 1 and U + B at most " TQ_STR(TQ_HMM_MAX_STATES));
+}
+static inline bool tq_chain_replicas_ok(const char* who, int R) {
+  return tq_chain_require(R >= 1 && R <= TQ_MULTISTART_MAX, who, "R must be at least 1 and at most " TQ_STR(TQ_MULTISTART_MAX));
+}
+// written so that a NaN fails; the joint chain has two
+static inline bool tq_chain_prior_ok(const char* who, double prior) {
+  return tq_chain_require(prior > 0.0 && prior < 1.0, who, "prior must lie in (0, 1)");
+}
+static inline bool tq_chain_priors_ok(const char* who, double prior_a, double prior_b) {
+  return tq_chain_require(prior_a > 0.0 && prior_a < 1.0 && prior_b > 0.0 && prior_b < 1.0, who,
+                          "prior_a and prior_b must lie in (0, 1)");
+}
+
 // torch.optim.Adam settings a fit kernel supports (written so that a NaN fails)
 static inline bool tq_adam_settings_ok(double lr, double beta1, double beta2, double eps) {
   return lr > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0;

@@ -2,13 +2,12 @@
 // inline bodies.  The hidden state is s = z_a + 2 z_b (0 neither bound, 1 only a, 2 only b, 3 both), theta = (A row-major
 // (4, 4), rho (4)) with the layout, floor and renormalisation of tq_hmm_model<4>, and the emission of a state is the
 // product of the two channels' evidence, l_f(s) = l^a_f(s & 1) l^b_f(s >> 1):
-//   * the chain with its two priors and the emission of a frame;
-//   * what one lane of the E-step does with its chunk of frames: the chunk product and the two sweeps of tq_hmm.h with
-//     that emission.  These are written out beside tq_hmm.h's instead of turning its bodies into templates over the
-//     emission, so that tq_hmm.h is not touched and every kernel built from it keeps its machine code; whatever does not
-//     see the emission -- TqHmmMat and its products, the floor, the prefix and suffix vectors -- is tq_hmm.h's;
-//   * the M-step under one of five structures of A, closed forms in the margins of the summed pair counts;
-//   * the Viterbi path of a row with four emission logarithms per frame.
+//   * the chain with its two priors, and the emission of a frame and its logarithm as the callables TqJointEmit and
+//     TqJointLogEmit;
+//   * the M-step under one of five structures of A, closed forms in the margins of the summed pair counts.
+// The chunk product, the two sweeps and the Viterbi row are tq_hmm.h's tq_chain_* templates at M = 4, given TqJointModel
+// as the chain and these callables: the joint chain has no sweep text of its own, and tq_joint_chunk, tq_joint_sweeps and
+// tq_joint_viterbi_row are one-line names for those calls.
 // The __global__ wrappers are in tq_joint.hip; the test suite runs the same bodies from a g++ build.
 #pragma once
 #include "tq_multistart.h"
@@ -46,131 +45,41 @@ TQ_HD void tq_joint_emission(const TqJointModel& m, float pa, float pb, double* 
   l[3] = a1 * b1;
 }
 
-// ---- a lane's chunk product and sweeps: tq_hmm_chunk, tq_hmm_forward and tq_hmm_backward with the joint emission --------
+// the emission of frame f of one row, as the tq_chain_* bodies of tq_hmm.h take it
+struct TqJointEmit {
+  const TqJointModel& m;
+  const float *pa, *pb;
+  TQ_HD void operator()(int f, double* l) const { tq_joint_emission(m, pa[f], pb[f], l); }
+};
+
+// ll[s] = log l^a(s & 1) + log l^b(s >> 1): four logarithms per frame, for tq_chain_viterbi_row
+struct TqJointLogEmit {
+  const TqJointModel& m;
+  const float *pa, *pb;
+  TQ_HD void operator()(int f, double* ll) const {
+    double a0, a1, b0, b1;
+    tq_smooth_evidence(m.eva, pa[f], a0, a1);
+    tq_smooth_evidence(m.evb, pb[f], b0, b1);
+    const double la0 = log(a0), la1 = log(a1), lb0 = log(b0), lb1 = log(b1);
+    ll[0] = la0 + lb0;
+    ll[1] = la1 + lb0;
+    ll[2] = la0 + lb1;
+    ll[3] = la1 + lb1;
+  }
+};
+
+// tq_hmm.h's bodies under their names for the joint chain on one row's p_a and p_b: one line each, nothing of their own
 TQ_HD TqHmmMat<TQ_JOINT_M> tq_joint_chunk(const TqJointModel& m, const float* pa, const float* pb, int lo, int hi) {
-  constexpr int M = TQ_JOINT_M;
-  TqHmmMat<M> c = tq_hmm_identity<M>();
-  for (int f = lo; f < hi; ++f) {
-    double l[M];
-    tq_joint_emission(m, pa[f], pb[f], l);
-    TqHmmMat<M> t;
-#pragma unroll
-    for (int i = 0; i < M; ++i)
-#pragma unroll
-      for (int j = 0; j < M; ++j) {
-        double s = c.m[i][0] * m.A[0][j];
-#pragma unroll
-        for (int k = 1; k < M; ++k) s += c.m[i][k] * m.A[k][j];
-        t.m[i][j] = (f == 0 ? m.rho[j] : s) * l[j];
-      }
-    tq_hmm_rescale(t);
-    c = t;
-  }
-  return c;
+  return tq_chain_chunk<TQ_JOINT_M>(m, TqJointEmit{m, pa, pb}, lo, hi);
 }
-
-// writes a_f into filt[f * 4 ..]; returns the lane's sum of log c_f
-TQ_HD double tq_joint_forward(const TqJointModel& m, const float* pa, const float* pb, int lo, int hi, const double* v0,
-                              double* filt) {
-  constexpr int M = TQ_JOINT_M;
-  double v[M], mant = 1.0;
-  int expo = 0;
-#pragma unroll
-  for (int i = 0; i < M; ++i) v[i] = v0[i];
-  for (int f = lo; f < hi; ++f) {
-    double l[M], u[M], c = 0.0;
-    tq_joint_emission(m, pa[f], pb[f], l);
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-      double s = v[0] * m.A[0][j];
-#pragma unroll
-      for (int k = 1; k < M; ++k) s += v[k] * m.A[k][j];
-      u[j] = (f == 0 ? m.rho[j] : s) * l[j];
-      c += u[j];
-    }
-    const double r = 1.0 / c;
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-      v[j] = u[j] * r;
-      filt[(int64_t)f * M + j] = v[j];
-    }
-    int e;
-    mant = frexp(mant * c, &e);
-    expo += e;
-  }
-  return log(mant) + (double)expo * 0.69314718055994530942;
-}
-
-// acc[i * 4 + j] += E n_ij of the pairs (g - 1, g) with g in the lane's frames; acc[16 + i] = gamma_0(i) in the lane that
-// owns frame 0.  GAMMA = false stores no gamma_g and does not read `gam`; the sums are the same.
-template <bool GAMMA>
-TQ_HD void tq_joint_backward(const TqJointModel& m, const float* pa, const float* pb, int lo, int hi, const double* b0,
-                             const double* v, const double* filt, double* gam, double* acc) {
-  constexpr int M = TQ_JOINT_M;
-  double b[M];
-#pragma unroll
-  for (int i = 0; i < M; ++i) b[i] = b0[i];
-  for (int g = hi - 1; g >= lo; --g) {
-    double r[M], s = 0.0;
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      r[i] = filt[(int64_t)g * M + i] * b[i];
-      s += r[i];
-    }
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      r[i] /= s;
-      if constexpr (GAMMA) gam[(int64_t)g * M + i] = r[i];
-    }
-    if (g == 0) {
-#pragma unroll
-      for (int i = 0; i < M; ++i) acc[M * M + i] = r[i];
-      break;
-    }
-    double l[M], w[M], x[M][M], tot = 0.0;
-    tq_joint_emission(m, pa[g], pb[g], l);
-#pragma unroll
-    for (int j = 0; j < M; ++j) w[j] = l[j] * b[j];
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      const double pi = g > lo ? filt[(int64_t)(g - 1) * M + i] : v[i];  // a_{g-1}(i)
-      double rs = 0.0;
-#pragma unroll
-      for (int j = 0; j < M; ++j) {
-        x[i][j] = pi * m.A[i][j] * w[j];
-        rs += x[i][j];
-      }
-      tot += rs;
-    }
-    const double rt = 1.0 / tot;
-#pragma unroll
-    for (int i = 0; i < M; ++i)
-#pragma unroll
-      for (int j = 0; j < M; ++j) acc[i * M + j] += x[i][j] * rt;
-    double bs = 0.0;
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      double t = m.A[i][0] * w[0];
-#pragma unroll
-      for (int j = 1; j < M; ++j) t += m.A[i][j] * w[j];
-      b[i] = t;
-      bs += t;
-    }
-    int e;
-    (void)frexp(bs, &e);
-#pragma unroll
-    for (int i = 0; i < M; ++i) b[i] = ldexp(b[i], -e);
-  }
-}
-
-// acc[0 .. 21) of the lane that owns [lo, hi), in the column order of tq_hmm_estep
 template <bool GAMMA>
 TQ_HD void tq_joint_sweeps(const TqJointModel& m, const float* pa, const float* pb, int lo, int hi, const double* v,
                            const double* b, double* filt, double* gam, double* acc) {
-#pragma unroll
-  for (int j = 0; j < TQ_JOINT_COLS; ++j) acc[j] = 0.0;
-  acc[TQ_JOINT_COLS - 1] = tq_joint_forward(m, pa, pb, lo, hi, v, filt);
-  tq_joint_backward<GAMMA>(m, pa, pb, lo, hi, b, v, filt, gam, acc);
+  tq_chain_sweeps<TQ_JOINT_M, GAMMA>(m, TqJointEmit{m, pa, pb}, lo, hi, v, b, filt, gam, acc);
+}
+TQ_HD void tq_joint_viterbi_row(const TqJointModel& m, const float* pa, const float* pb, int F, uint32_t* back,
+                                int64_t stride, uint8_t* path) {
+  tq_chain_viterbi_row<TQ_JOINT_M>(m, TqJointLogEmit{m, pa, pb}, F, back, stride, path);
 }
 
 // ---- M-step -----------------------------------------------------------------------------------------------------------
@@ -218,75 +127,4 @@ TQ_HD void tq_joint_mstep_theta(const double* sums, int N, int structure, double
 #pragma unroll
   for (int i = 0; i < M; ++i) q[i] = sums[M * M + i] / (double)N;
   tq_hmm_floor<M>(q, theta + M * M);
-}
-
-// ---- Viterbi ----------------------------------------------------------------------------------------------------------
-// tq_hmm_viterbi_row<4> with the emission logarithm of state s formed as log l^a(s & 1) + log l^b(s >> 1): the same
-// relative scores, back-pointer words and tie rule (lowest state).
-TQ_HD void tq_joint_log_emission(const TqJointModel& m, float pa, float pb, double* ll) {
-  double a0, a1, b0, b1;
-  tq_smooth_evidence(m.eva, pa, a0, a1);
-  tq_smooth_evidence(m.evb, pb, b0, b1);
-  const double la0 = log(a0), la1 = log(a1), lb0 = log(b0), lb1 = log(b1);
-  ll[0] = la0 + lb0;
-  ll[1] = la1 + lb0;
-  ll[2] = la0 + lb1;
-  ll[3] = la1 + lb1;
-}
-
-TQ_HD void tq_joint_viterbi_row(const TqJointModel& m, const float* pa, const float* pb, int F, uint32_t* back,
-                                int64_t stride, uint8_t* path) {
-  constexpr int M = TQ_JOINT_M;
-  double la[M][M], d[M], ll[M];
-#pragma unroll
-  for (int i = 0; i < M; ++i)
-#pragma unroll
-    for (int j = 0; j < M; ++j) la[i][j] = log(m.A[i][j]);
-  tq_joint_log_emission(m, pa[0], pb[0], ll);
-  const double s00 = log(m.rho[0]) + ll[0];
-  d[0] = 0.0;
-#pragma unroll
-  for (int i = 1; i < M; ++i) d[i] = (log(m.rho[i]) + ll[i]) - s00;
-  uint32_t word = 0;
-  for (int f = 1; f < F; ++f) {
-    tq_joint_log_emission(m, pa[f], pb[f], ll);
-    double s[M];
-    uint32_t bits = 0;
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-      double best = la[0][j];
-      uint32_t bp = 0;
-#pragma unroll
-      for (int i = 1; i < M; ++i) {
-        const double cand = d[i] + la[i][j];
-        if (cand > best) {
-          best = cand;
-          bp = (uint32_t)i;
-        }
-      }
-      s[j] = best + ll[j];
-      bits |= bp << (2 * j);
-    }
-#pragma unroll
-    for (int j = 1; j < M; ++j) d[j] = s[j] - s[0];
-    word |= bits << (8 * (f & 3));
-    if ((f & 3) == 3 || f == F - 1) {
-      back[(int64_t)(f >> 2) * stride] = word;
-      word = 0;
-    }
-  }
-  uint32_t z = 0;
-  double best = 0.0;
-#pragma unroll
-  for (int i = 1; i < M; ++i)
-    if (d[i] > best) {
-      best = d[i];
-      z = (uint32_t)i;
-    }
-  path[F - 1] = (uint8_t)z;
-  for (int f = F - 1; f >= 1; --f) {
-    if ((f & 3) == 3 || f == F - 1) word = back[(int64_t)(f >> 2) * stride];
-    z = (word >> (8 * (f & 3) + 2 * z)) & 3u;
-    path[f - 1] = (uint8_t)z;
-  }
 }

@@ -5,51 +5,17 @@
 // the joint filt with (U, B) = (2, 2).  No atomics, no workgroup waits on another, every loop bounded by F, N or R.
 #include <hip/hip_runtime.h>
 
-#include "tq_dpp.h"
+#include "tq_chain_dev.h"
 #include "tq_host.h"
 #include "tq_joint.h"
 
-static bool tq_joint_priors(const char* who, double prior_a, double prior_b) {
-  if (prior_a > 0.0 && prior_a < 1.0 && prior_b > 0.0 && prior_b < 1.0) return true;
-  char buf[120];
-  snprintf(buf, sizeof(buf), "%s: prior_a and prior_b must lie in (0, 1)", who);
-  tq_set_error(buf);
-  return false;
-}
-
-static bool tq_joint_replicas(const char* who, int R) {
-  if (R >= 1 && R <= TQ_MULTISTART_MAX) return true;
-  char buf[120];
-  snprintf(buf, sizeof(buf), "%s: R must be at least 1 and at most %d", who, TQ_MULTISTART_MAX);
-  tq_set_error(buf);
-  return false;
-}
-
-// ---- E-step: one wave (= one workgroup) per (row, replica), L = ceil(F / 64) consecutive frames per lane ----------------
-// the shuffles of tq_hmm.hip (device only)
-__device__ __forceinline__ TqHmmMat<TQ_JOINT_M> tq_joint_shfl_up(const TqHmmMat<TQ_JOINT_M>& x, int d) {
-  TqHmmMat<TQ_JOINT_M> r;
-#pragma unroll
-  for (int i = 0; i < TQ_JOINT_M; ++i)
-#pragma unroll
-    for (int j = 0; j < TQ_JOINT_M; ++j) r.m[i][j] = __shfl_up(x.m[i][j], d, 64);
-  return r;
-}
-__device__ __forceinline__ TqHmmMat<TQ_JOINT_M> tq_joint_shfl_down(const TqHmmMat<TQ_JOINT_M>& x, int d) {
-  TqHmmMat<TQ_JOINT_M> r;
-#pragma unroll
-  for (int i = 0; i < TQ_JOINT_M; ++i)
-#pragma unroll
-    for (int j = 0; j < TQ_JOINT_M; ++j) r.m[i][j] = __shfl_down(x.m[i][j], d, 64);
-  return r;
-}
-
-// The geometry, the scans and the sweeps of tq_multistart_estep_kernel<4> with the joint emission.  The test of `active` is
-// uniform over the workgroup and comes before the first shuffle, so an inactive replica's waves leave whole and write
-// nothing.  GAMMA = false stores no gamma and never forms its address.
+// ---- E-step: one wave (= one workgroup) per (row, replica) ----------------------------------------------------------------
+// tq_chain_estep_row at M = 4 with the addressing of tq_multistart_estep_kernel<4> and the joint emission.  The test of
+// `active` is uniform over the workgroup and comes before the first shuffle, so an inactive replica's waves leave whole and
+// write nothing.  GAMMA = false stores no gamma and never forms its address.
 template <bool GAMMA>
 __global__ __launch_bounds__(64) void tq_joint_estep_kernel(const tq_joint_estep_args a) {
-  constexpr int M = TQ_JOINT_M, COLS = TQ_JOINT_COLS;
+  constexpr int M = TQ_JOINT_M;
   const int n = blockIdx.x, r = blockIdx.y, lane = threadIdx.x;
   if (a.active && a.active[r] == 0) return;
   const int F = a.F;
@@ -58,43 +24,7 @@ __global__ __launch_bounds__(64) void tq_joint_estep_kernel(const tq_joint_estep
   double* filt = a.filt + tq_multistart_filt_at<M>(r, n, a.N, F);
   double* gam = GAMMA ? a.gamma + tq_multistart_filt_at<M>(r, n, a.N, F) : nullptr;
   const TqJointModel m = tq_joint_model(a.theta + tq_multistart_theta_at<M>(r), a.prior_a, a.prior_b);
-  int lo, hi;
-  tq_smooth_lane_range(lane, F, lo, hi);
-
-  const TqHmmMat<M> c = tq_joint_chunk(m, pa, pb, lo, hi);
-  double v[M], b[M];
-  {
-    TqHmmMat<M> pre = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const TqHmmMat<M> left = tq_joint_shfl_up(pre, d);
-      if (lane >= d) pre = tq_hmm_mul(left, pre);
-    }
-    pre = tq_joint_shfl_up(pre, 1);
-    if (lane == 0) pre = tq_hmm_identity<M>();
-    tq_hmm_prefix_vector(pre, v);
-  }
-  {
-    TqHmmMat<M> suf = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const TqHmmMat<M> right = tq_joint_shfl_down(suf, d);
-      if (lane + d < 64) suf = tq_hmm_mul(suf, right);
-    }
-    suf = tq_joint_shfl_down(suf, 1);
-    if (lane == 63) suf = tq_hmm_identity<M>();
-    tq_hmm_suffix_vector(suf, b);
-  }
-
-  double acc[COLS];
-  tq_joint_sweeps<GAMMA>(m, pa, pb, lo, hi, v, b, filt, gam, acc);
-#pragma unroll
-  for (int j = 0; j < COLS; ++j) acc[j] = tq_group_sum<64>(acc[j]);  // every lane is back here
-  if (lane == 0) {
-    double* out = a.rows + tq_multistart_row_at<M>(r, n, a.N);
-#pragma unroll
-    for (int j = 0; j < COLS; ++j) out[j] = acc[j];
-  }
+  tq_chain_estep_row<M, GAMMA>(m, TqJointEmit{m, pa, pb}, F, lane, filt, gam, a.rows + tq_multistart_row_at<M>(r, n, a.N));
 }
 
 extern "C" int tq_joint_estep(const tq_joint_estep_args* a, void* stream) {
@@ -102,11 +32,9 @@ extern "C" int tq_joint_estep(const tq_joint_estep_args* a, void* stream) {
     tq_set_error("tq_joint_estep: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->N < 1 || a->F < 1 || a->F > TQ_SMOOTH_MAX_F) {
-    tq_set_error("tq_joint_estep: N and F must be positive and F at most 65536");
+  if (!tq_chain_frames_ok("tq_joint_estep", a->N, a->F) || !tq_chain_replicas_ok("tq_joint_estep", a->R) ||
+      !tq_chain_priors_ok("tq_joint_estep", a->prior_a, a->prior_b))
     return TQ_ERR_ARG;
-  }
-  if (!tq_joint_replicas("tq_joint_estep", a->R) || !tq_joint_priors("tq_joint_estep", a->prior_a, a->prior_b)) return TQ_ERR_ARG;
   const dim3 grid((unsigned)a->N, (unsigned)a->R);
   if (a->gamma) {
     hipLaunchKernelGGL((tq_joint_estep_kernel<true>), grid, dim3(64), 0, (hipStream_t)stream, *a);
@@ -116,37 +44,16 @@ extern "C" int tq_joint_estep(const tq_joint_estep_args* a, void* stream) {
   return tq_launch_status("tq_joint_estep_kernel");
 }
 
-// ---- M-step: one workgroup per replica; thread t sums rows t, t + 256, ..., then a fixed tree in LDS --------------------
-// The sums and the tree of tq_hmm_mstep_kernel<4>, so the totals have its bits; thread 0 then applies the structure.
+// ---- M-step: one workgroup per replica; tq_chain_reduce_rows, then thread 0 applies the structure -------------------------
 __global__ __launch_bounds__(TQ_SMOOTH_MSTEP_THREADS) void tq_joint_mstep_kernel(const tq_joint_mstep_args a) {
   constexpr int M = TQ_JOINT_M, COLS = TQ_JOINT_COLS;
   __shared__ double part[COLS][TQ_SMOOTH_MSTEP_THREADS];
-  const int t = threadIdx.x, r = blockIdx.x;
+  const int r = blockIdx.x;
   if (a.active && a.active[r] == 0) return;  // the whole workgroup, before its first barrier
-  const double* rows = a.rows + tq_multistart_row_at<M>(r, 0, a.N);
-  double s[COLS];
-#pragma unroll
-  for (int j = 0; j < COLS; ++j) s[j] = 0.0;
-  for (int n = t; n < a.N; n += TQ_SMOOTH_MSTEP_THREADS) {
-    const double* row = rows + (int64_t)n * COLS;
-#pragma unroll
-    for (int j = 0; j < COLS; ++j) s[j] += row[j];
-  }
-#pragma unroll
-  for (int j = 0; j < COLS; ++j) part[j][t] = s[j];
-  __syncthreads();
-  for (int h = TQ_SMOOTH_MSTEP_THREADS / 2; h > 0; h >>= 1) {
-    if (t < h) {
-#pragma unroll
-      for (int j = 0; j < COLS; ++j) part[j][t] += part[j][t + h];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    double sums[COLS], theta[TQ_JOINT_THETA];
+  double sums[COLS];
+  if (tq_chain_reduce_rows<COLS>(a.rows + tq_multistart_row_at<M>(r, 0, a.N), a.N, part, sums)) {
+    double theta[TQ_JOINT_THETA];
     double* th = a.theta + tq_multistart_theta_at<M>(r);
-#pragma unroll
-    for (int j = 0; j < COLS; ++j) sums[j] = part[j][0];
 #pragma unroll
     for (int j = 0; j < TQ_JOINT_THETA; ++j) theta[j] = th[j];
     tq_joint_mstep_theta(sums, a.N, a.structure[r], theta);
@@ -169,7 +76,7 @@ extern "C" int tq_joint_mstep(const tq_joint_mstep_args* a, void* stream) {
     tq_set_error("tq_joint_mstep: T must exceed it (the trace of a replica has T entries)");
     return TQ_ERR_ARG;
   }
-  if (!tq_joint_replicas("tq_joint_mstep", a->R)) return TQ_ERR_ARG;
+  if (!tq_chain_replicas_ok("tq_joint_mstep", a->R)) return TQ_ERR_ARG;
   for (int r = 0; r < a->R; ++r)
     if (!tq_joint_structure_ok(a->structure[r])) {
       tq_set_error("tq_joint_mstep: structure must be one of TQ_JOINT_INDEPENDENT .. TQ_JOINT_FULL (0 .. 4) for every replica");
@@ -192,11 +99,8 @@ extern "C" int tq_joint_viterbi(const tq_joint_viterbi_args* a, void* stream) {
     tq_set_error("tq_joint_viterbi: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->N < 1 || a->F < 1 || a->F > TQ_SMOOTH_MAX_F) {
-    tq_set_error("tq_joint_viterbi: N and F must be positive and F at most 65536");
+  if (!tq_chain_frames_ok("tq_joint_viterbi", a->N, a->F) || !tq_chain_priors_ok("tq_joint_viterbi", a->prior_a, a->prior_b))
     return TQ_ERR_ARG;
-  }
-  if (!tq_joint_priors("tq_joint_viterbi", a->prior_a, a->prior_b)) return TQ_ERR_ARG;
   hipLaunchKernelGGL(tq_joint_viterbi_kernel, dim3((unsigned)((a->N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, *a);
   return tq_launch_status("tq_joint_viterbi_kernel");
 }

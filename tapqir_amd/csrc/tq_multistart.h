@@ -1,10 +1,9 @@
 // tq_multistart.h -- R replicas of the chain of tq_hmm.h fitted side by side (`smooth --restarts`),
 // host+device inline bodies, templated on the number of states M = U + B in {2, 3, 4}:
 //   * where replica r keeps its theta, its rows and its scratch of a_f;
-//   * what one lane of the batched E-step does after the two scans: the sweeps of tq_hmm.h with no gamma stored;
 //   * the topology mask `allow` (bit i * M + j set: A_ij is free), its check, and the M-step under it.
-// Everything else -- the chain, the emission, the chunk products, the floor -- is tq_hmm.h's, so that a replica computes
-// what tq_hmm_estep and tq_hmm_mstep compute from the same theta.  The __global__ wrappers are in tq_multistart.hip; the
+// Everything else -- the chain, the emission, the chunk products, the sweeps (tq_chain_sweeps with no gamma stored), the
+// floor -- is tq_hmm.h's, so that a replica computes what tq_hmm_estep and tq_hmm_mstep compute from the same theta.  The __global__ wrappers are in tq_multistart.hip; the
 // test suite runs the same bodies from a g++ build.
 #pragma once
 #include "tq_hmm.h"
@@ -23,17 +22,11 @@ TQ_HD int64_t tq_multistart_filt_at(int r, int n, int N, int F) {
   return ((int64_t)r * N + n) * F * M;
 }
 
-// ---- E-step: a lane's two sweeps ----------------------------------------------------------------------------------------
-// acc[0 .. TQ_HMM_COLS(M)) of the lane that owns [lo, hi): v = a_{lo-1} of its exclusive prefix, b = beta_{hi-1} of its
-// exclusive suffix, filt the row's scratch of a_f.  The sums of tq_hmm_estep_kernel, bit for bit.
+// ---- E-step: a lane's two sweeps, tq_chain_sweeps for the class chain with no gamma stored -------------------------------
 template <int M>
 TQ_HD void tq_multistart_sweeps(const TqHmmModel<M>& m, const float* pr, int lo, int hi, const double* v, const double* b,
                                 double* filt, double* acc) {
-  constexpr int COLS = TQ_HMM_COLS(M);
-#pragma unroll
-  for (int j = 0; j < COLS; ++j) acc[j] = 0.0;
-  acc[COLS - 1] = tq_hmm_forward(m, pr, lo, hi, v, filt);
-  tq_hmm_backward<M, false>(m, pr, lo, hi, b, v, filt, nullptr, acc);
+  tq_chain_sweeps<M, false>(m, TqHmmEmit<M>{m, pr}, lo, hi, v, b, filt, nullptr, acc);
 }
 
 // ---- topology -----------------------------------------------------------------------------------------------------------

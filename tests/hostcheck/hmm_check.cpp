@@ -2,80 +2,26 @@
 // suite: the E-step with the device's ownership of frames by 64 lanes and the device's scan order over an array of 64, the
 // M-step with the device's strided sums and tree, the Viterbi row, the backward sampler and the estimate.
 // With -DHMM_CHECK_MAIN it is a program of its own (the sanitizer run of DESIGN.md section 22).
-#include "../../tapqir_amd/csrc/tq_hmm.h"
-
 #include <vector>
 
+#include "chain_host.h"
+
 namespace {
-
-// the butterfly of tq_group_sum<64>: after the six exchanges every lane holds the sum; lane 0's is returned
-double wave_sum(const double* v) {
-  double a[64], b[64];
-  for (int i = 0; i < 64; ++i) a[i] = v[i];
-  for (int d = 1; d < 64; d <<= 1) {
-    for (int i = 0; i < 64; ++i) b[i] = a[i] + a[i ^ d];
-    for (int i = 0; i < 64; ++i) a[i] = b[i];
-  }
-  return a[0];
-}
-
-template <int M>
-void estep_row(const TqHmmModel<M>& m, const float* pr, int F, double* filt, double* gam, double* row) {
-  constexpr int COLS = TQ_HMM_COLS(M);
-  static TqHmmMat<M> pre[64], suf[64], old[64];
-  int lo[64], hi[64];
-  for (int k = 0; k < 64; ++k) {
-    tq_smooth_lane_range(k, F, lo[k], hi[k]);
-    pre[k] = suf[k] = tq_hmm_chunk(m, pr, lo[k], hi[k]);
-  }
-  for (int d = 1; d < 64; d <<= 1) {  // the kernel's Hillis-Steele steps: all lanes read, then all lanes write
-    for (int k = 0; k < 64; ++k) old[k] = pre[k];
-    for (int k = d; k < 64; ++k) pre[k] = tq_hmm_mul(old[k - d], old[k]);
-  }
-  for (int d = 1; d < 64; d <<= 1) {
-    for (int k = 0; k < 64; ++k) old[k] = suf[k];
-    for (int k = 0; k + d < 64; ++k) suf[k] = tq_hmm_mul(old[k], old[k + d]);
-  }
-  static double acc[COLS][64];
-  for (int k = 0; k < 64; ++k) {
-    const TqHmmMat<M> e = k == 0 ? tq_hmm_identity<M>() : pre[k - 1];
-    const TqHmmMat<M> s = k == 63 ? tq_hmm_identity<M>() : suf[k + 1];
-    double v[M], b[M], a[COLS];
-    for (int j = 0; j < COLS; ++j) a[j] = 0.0;
-    tq_hmm_prefix_vector(e, v);
-    tq_hmm_suffix_vector(s, b);
-    a[COLS - 1] = tq_hmm_forward(m, pr, lo[k], hi[k], v, filt);
-    tq_hmm_backward(m, pr, lo[k], hi[k], b, v, filt, gam, a);
-    for (int j = 0; j < COLS; ++j) acc[j][k] = a[j];
-  }
-  for (int j = 0; j < COLS; ++j) row[j] = wave_sum(acc[j]);
-}
 
 template <int M>
 void estep(const float* p, int N, int F, const double* theta, int U, double prior, double* filt, double* gamma,
            double* rows) {
   const TqHmmModel<M> m = tq_hmm_model<M>(theta, U, prior);
   for (int64_t n = 0; n < N; ++n)
-    estep_row<M>(m, p + n * F, F, filt + n * F * M, gamma + n * F * M, rows + n * TQ_HMM_COLS(M));
+    estep_row<M, true>(m, TqHmmEmit<M>{m, p + n * F}, F, filt + n * F * M, gamma + n * F * M, rows + n * TQ_HMM_COLS(M));
 }
 
-// the M-step kernel: thread t sums rows t, t + 256, ...; the tree halves 256 partial sums; theta in place, returns loglik
+// the M-step kernel: theta in place, returns loglik
 template <int M>
 double mstep(const double* rows, int N, double* theta, double* sums) {
-  constexpr int COLS = TQ_HMM_COLS(M);
-  static double part[COLS][TQ_SMOOTH_MSTEP_THREADS];
-  for (int t = 0; t < TQ_SMOOTH_MSTEP_THREADS; ++t)
-    for (int j = 0; j < COLS; ++j) {
-      double s = 0.0;
-      for (int n = t; n < N; n += TQ_SMOOTH_MSTEP_THREADS) s += rows[(int64_t)n * COLS + j];
-      part[j][t] = s;
-    }
-  for (int h = TQ_SMOOTH_MSTEP_THREADS / 2; h > 0; h >>= 1)
-    for (int t = 0; t < h; ++t)
-      for (int j = 0; j < COLS; ++j) part[j][t] += part[j][t + h];
-  for (int j = 0; j < COLS; ++j) sums[j] = part[j][0];
+  reduce_rows<TQ_HMM_COLS(M)>(rows, N, sums);
   tq_hmm_mstep_theta<M>(sums, N, theta);
-  return sums[COLS - 1];
+  return sums[TQ_HMM_COLS(M) - 1];
 }
 
 template <int M>
@@ -144,24 +90,6 @@ void estimate(const int32_t* trans, int S, int N, int resample, uint64_t seed, i
 }
 
 }  // namespace
-
-#define HK_SWITCH_M(M, ...)   \
-  switch (M) {                \
-    case 2: {                 \
-      constexpr int MM = 2;   \
-      __VA_ARGS__;            \
-    } break;                  \
-    case 3: {                 \
-      constexpr int MM = 3;   \
-      __VA_ARGS__;            \
-    } break;                  \
-    case 4: {                 \
-      constexpr int MM = 4;   \
-      __VA_ARGS__;            \
-    } break;                  \
-    default:                  \
-      break;                  \
-  }
 
 extern "C" {
 

@@ -3,53 +3,12 @@
 // replica layout, and the batched M-step with the device's strided sums, tree and topology mask.  An inactive replica is
 // skipped where the device's workgroups return.
 // With -DMULTISTART_CHECK_MAIN it is a program of its own (the sanitizer run of DESIGN.md section 26).
-#include "../../tapqir_amd/csrc/tq_multistart.h"
-
 #include <vector>
 
+#include "../../tapqir_amd/csrc/tq_multistart.h"
+#include "chain_host.h"
+
 namespace {
-
-// the butterfly of tq_group_sum<64>: after the six exchanges every lane holds the sum; lane 0's is returned
-double wave_sum(const double* v) {
-  double a[64], b[64];
-  for (int i = 0; i < 64; ++i) a[i] = v[i];
-  for (int d = 1; d < 64; d <<= 1) {
-    for (int i = 0; i < 64; ++i) b[i] = a[i] + a[i ^ d];
-    for (int i = 0; i < 64; ++i) a[i] = b[i];
-  }
-  return a[0];
-}
-
-// one workgroup of tq_multistart_estep_kernel
-template <int M>
-void estep_row(const TqHmmModel<M>& m, const float* pr, int F, double* filt, double* row) {
-  constexpr int COLS = TQ_HMM_COLS(M);
-  static TqHmmMat<M> pre[64], suf[64], old[64];
-  int lo[64], hi[64];
-  for (int k = 0; k < 64; ++k) {
-    tq_smooth_lane_range(k, F, lo[k], hi[k]);
-    pre[k] = suf[k] = tq_hmm_chunk(m, pr, lo[k], hi[k]);
-  }
-  for (int d = 1; d < 64; d <<= 1) {  // the kernel's Hillis-Steele steps: all lanes read, then all lanes write
-    for (int k = 0; k < 64; ++k) old[k] = pre[k];
-    for (int k = d; k < 64; ++k) pre[k] = tq_hmm_mul(old[k - d], old[k]);
-  }
-  for (int d = 1; d < 64; d <<= 1) {
-    for (int k = 0; k < 64; ++k) old[k] = suf[k];
-    for (int k = 0; k + d < 64; ++k) suf[k] = tq_hmm_mul(old[k], old[k + d]);
-  }
-  static double acc[COLS][64];
-  for (int k = 0; k < 64; ++k) {
-    const TqHmmMat<M> e = k == 0 ? tq_hmm_identity<M>() : pre[k - 1];
-    const TqHmmMat<M> s = k == 63 ? tq_hmm_identity<M>() : suf[k + 1];
-    double v[M], b[M], a[COLS];
-    tq_hmm_prefix_vector(e, v);
-    tq_hmm_suffix_vector(s, b);
-    tq_multistart_sweeps(m, pr, lo[k], hi[k], v, b, filt, a);
-    for (int j = 0; j < COLS; ++j) acc[j][k] = a[j];
-  }
-  for (int j = 0; j < COLS; ++j) row[j] = wave_sum(acc[j]);
-}
 
 template <int M>
 void estep(const float* p, int N, int F, const double* theta, int R, int U, double prior, const int32_t* active, double* filt,
@@ -58,7 +17,8 @@ void estep(const float* p, int N, int F, const double* theta, int R, int U, doub
     if (active && active[r] == 0) continue;
     const TqHmmModel<M> m = tq_hmm_model<M>(theta + tq_multistart_theta_at<M>(r), U, prior);
     for (int n = 0; n < N; ++n)
-      estep_row<M>(m, p + (int64_t)n * F, F, filt + tq_multistart_filt_at<M>(r, n, N, F), rows + tq_multistart_row_at<M>(r, n, N));
+      estep_row<M, false>(m, TqHmmEmit<M>{m, p + (int64_t)n * F}, F, filt + tq_multistart_filt_at<M>(r, n, N, F), nullptr,
+                          rows + tq_multistart_row_at<M>(r, n, N));
   }
 }
 
@@ -67,45 +27,16 @@ template <int M>
 void mstep(const double* rows, int N, int R, int T, int it, uint32_t allow, const int32_t* active, double* theta,
            double* trace) {
   constexpr int COLS = TQ_HMM_COLS(M);
-  static double part[COLS][TQ_SMOOTH_MSTEP_THREADS];
   for (int r = 0; r < R; ++r) {
     if (active && active[r] == 0) continue;
-    const double* rr = rows + tq_multistart_row_at<M>(r, 0, N);
-    for (int t = 0; t < TQ_SMOOTH_MSTEP_THREADS; ++t)
-      for (int j = 0; j < COLS; ++j) {
-        double s = 0.0;
-        for (int n = t; n < N; n += TQ_SMOOTH_MSTEP_THREADS) s += rr[(int64_t)n * COLS + j];
-        part[j][t] = s;
-      }
-    for (int h = TQ_SMOOTH_MSTEP_THREADS / 2; h > 0; h >>= 1)
-      for (int t = 0; t < h; ++t)
-        for (int j = 0; j < COLS; ++j) part[j][t] += part[j][t + h];
     double sums[COLS];
-    for (int j = 0; j < COLS; ++j) sums[j] = part[j][0];
+    reduce_rows<COLS>(rows + tq_multistart_row_at<M>(r, 0, N), N, sums);
     tq_multistart_mstep_theta<M>(sums, N, allow, theta + tq_multistart_theta_at<M>(r));
     trace[(int64_t)r * T + it] = sums[COLS - 1];
   }
 }
 
 }  // namespace
-
-#define HK_SWITCH_M(M, ...)   \
-  switch (M) {                \
-    case 2: {                 \
-      constexpr int MM = 2;   \
-      __VA_ARGS__;            \
-    } break;                  \
-    case 3: {                 \
-      constexpr int MM = 3;   \
-      __VA_ARGS__;            \
-    } break;                  \
-    case 4: {                 \
-      constexpr int MM = 4;   \
-      __VA_ARGS__;            \
-    } break;                  \
-    default:                  \
-      break;                  \
-  }
 
 extern "C" {
 

@@ -164,14 +164,16 @@ def _active_ptr(active):
     return a, a.ctypes.data
 
 
-def host_estep(lib, p, thetas, U, B, prior, active=None, rows=None):
-    """The g++ batched E-step: rows (R, N, M^2 + M + 1), written into ``rows`` when given (NaN-filled otherwise)."""
+def host_estep(lib, p, thetas, U, B, prior, active=None, rows=None, filt=None):
+    """The g++ batched E-step: rows (R, N, M^2 + M + 1), written into ``rows`` when given (NaN-filled otherwise); ``filt``
+    (R, N, F, M) float64 receives the scratch of a_f when given."""
     M = U + B
     p = np.ascontiguousarray(p, dtype=np.float32)
     thetas = np.ascontiguousarray(thetas, dtype=np.float64)
     (N, F), R = p.shape, len(thetas)
     rows = np.full((R, N, cols(M)), np.nan) if rows is None else rows
-    filt = np.empty((R, N, F, M))
+    filt = np.empty((R, N, F, M)) if filt is None else filt
+    assert filt.shape == (R, N, F, M) and filt.dtype == np.float64 and filt.flags.c_contiguous
     keep, ptr = _active_ptr(active)
     lib.hk_multistart_estep(p.ctypes.data, N, F, thetas.ctypes.data, R, U, B, prior, ptr, filt.ctypes.data, rows.ctypes.data)
     return rows
