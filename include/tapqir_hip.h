@@ -913,6 +913,81 @@ typedef struct {
 int tq_multistart_mstep(const tq_multistart_mstep_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * A mixture of G chains over the AOIs (`tapqir_amd smooth --populations G`): AOI n belongs to
+ * population g with weight phi_g, and every population is a chain theta_g of the same (U, B) and topology.  P starts are
+ * fitted side by side; population g of start p is replica r = p * G + g of the section above, and the E-step is
+ * tq_multistart_estep with R = P * G, unchanged (the caller expands `active` from P to P * G entries).  With
+ * L_g[n] = the loglik column of rows[p, g, n] and phi read floored at TQ_SMOOTH_RMIN and renormalised:
+ *   ev[n]   = log sum_g phi_g e^{L_g[n]}, as max + log sum exp(. - max) with g ascending
+ *   w[g, n] = exp(log phi_g + L_g[n] - ev[n]), evaluated as the g-th term of that sum over the sum
+ * Every entry point returns TQ_ERR_ARG, before anything touches the device, for what the tq_hmm_* / tq_multistart_* pair
+ * of the same name refuses, for G < 1 or G > TQ_MIXTURE_MAX_POP, and the M-step for P < 1, P * G > TQ_MULTISTART_MAX or
+ * T <= it.
+ *
+ * tq_mixture_mstep: grid P, one workgroup per start.  Writes sum_n ev[n] into trace[p * T + it], and for every population
+ *   A_ij = sum_n w E n_ij / sum_j sum_n w E n_ij (a state without weighted occupancy keeps its row; `allow` as in
+ *   tq_multistart_mstep), rho = sum_n w gamma_0 / sum_n w (a population whose weights sum to 0 keeps theta_g), both floored
+ *   as tq_hmm_mstep floors them, and phi_g = sum_n w / N floored at TQ_SMOOTH_RMIN and renormalised.  The sums run in the
+ *   fixed order of tq_hmm_mstep, one population after the other: no atomics, two runs give the same bits, and G = 1 gives
+ *   the theta and the trace of tq_multistart_mstep bit for bit.  An inactive start keeps everything.
+ * ------------------------------------------------------------------------------------- */
+#define TQ_MIXTURE_MAX_POP 4
+typedef struct {
+  const double* rows;          /* (P, G, N, TQ_HMM_COLS(M)) of tq_multistart_estep with R = P * G */
+  double* theta;               /* (P, G, M * M + M) in / out; device memory */
+  double* phi;                 /* (P, G) in / out; device memory */
+  double* trace;               /* (P, T): trace[p * T + it] out, the mixture log evidence */
+  double* resp;                /* (P, G, N) out: w at the theta and phi the rows were computed with; or NULL */
+  double* evidence;            /* (P, N) out: ev; or NULL */
+  const int32_t* active;       /* (P); device memory; or NULL */
+  int32_t N, it;
+  int32_t T, P;                /* entries of a start's trace, T > it; starts */
+  int32_t G;                   /* populations */
+  int32_t U, B;
+  uint32_t allow;              /* topology mask, M * M bits, shared by the populations */
+} tq_mixture_mstep_args;
+
+int tq_mixture_mstep(const tq_mixture_mstep_args* a, void* stream);
+
+/* tq_mixture_count: S posterior rasters of every row, each with a population of its own.  Row (s, n) first draws
+ *   g = the largest g with u < sum_{g' >= g} resp[g', n], or 0, u the first uniform of Philox stream (seed, step = s, site
+ *   0xA05, elem = n); then it is the row tq_hmm_count draws from filt[g, n] under theta[g] with the same seed (site 0xA04).
+ *   With G = 1 the outputs are tq_hmm_count's bit for bit.  pop[s, n] = g; the other outputs as there. */
+typedef struct {
+  const double* filt;          /* (G, N, F, M) of tq_hmm_estep, population by population */
+  const double* theta;         /* (G, M * M + M); device memory */
+  const double* resp;          /* (G, N) of tq_mixture_mstep */
+  int32_t* counts;             /* (S, N, TQ_RATES_COLS) out; 16-byte aligned */
+  int32_t* trans;              /* (S, N, M * M) out; or NULL */
+  uint8_t* pop;                /* (S, N) out */
+  uint8_t* raster;             /* (S, N, F) out; or NULL */
+  int32_t N, F, S;
+  int32_t G;
+  int32_t U, B;
+  uint64_t seed;
+} tq_mixture_count_args;
+
+int tq_mixture_count(const tq_mixture_count_args* a, void* stream);
+
+/* tq_mixture_estimate: tq_hmm_estimate per population, with its a(s, k):
+ *   totals[s, g, i, j] = sum_{k < N} trans[s, a(s, k), i, j] [pop[s, a(s, k)] = g] (int64), members[s, g] = the number of
+ *   drawn AOIs in g, estimand = totals over their row sums as IEEE double division (a zero denominator gives NaN). */
+typedef struct {
+  const int32_t* trans;        /* (S, N, M * M) of tq_mixture_count */
+  const uint8_t* pop;          /* (S, N) of tq_mixture_count */
+  int64_t* totals;             /* (S, G, M * M) out */
+  int64_t* members;            /* (S, G) out */
+  double* estimand;            /* (S, G, M * M) out */
+  int32_t N, S;
+  int32_t G;
+  int32_t U, B;
+  int32_t resample;            /* 0: pooled; 1: bootstrap over AOIs */
+  uint64_t seed;               /* resample = 1 only */
+} tq_mixture_estimate_args;
+
+int tq_mixture_estimate(const tq_mixture_estimate_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Two colour channels as one chain (`tapqir_amd smooth --joint A,B`).  Channels a and b of one
  * cosmos fit, hidden state s = z_a + 2 z_b: 0 neither bound, 1 only a, 2 only b, 3 both.
  *   theta = (A row-major (4, 4), rho (4)): 20 doubles in device memory, read floored at TQ_SMOOTH_RMIN and renormalised as

@@ -754,13 +754,14 @@ def rates(
         raise typer.Exit(1)
 
 
-def _smooth_multistart_options(U, B, restarts, restart_seed, forbid, logger):
+def _smooth_multistart_options(U, B, restarts, restart_seed, forbid, logger, mixture=False):
     """The checks of ``--restarts``, ``--restart-seed`` and ``--forbid`` of `smooth`, made where ``--ci`` is checked (after
-    the model, before ``--cpu``).  Returns ``{"restarts", "seed", "allow"}``, allow an (M, M) list of booleans."""
+    the model, before ``--cpu``).  Returns ``{"restarts", "seed", "allow"}``, allow an (M, M) list of booleans.  A mixture
+    (``--populations``) has several optima at (1, 1) too, so it takes the options there."""
     import re
 
     M = U + B
-    if (U, B) == (1, 1):
+    if (U, B) == (1, 1) and not mixture:
         logger.error("smooth: --restarts, --restart-seed and --forbid need a chain of more than two states "
                      "(--unbound-states, --bound-states): the two-state EM has one optimum and one topology")
         raise typer.Exit(1)
@@ -872,6 +873,118 @@ def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci
             out["loglik_trace"].append(fit["trace"].cpu())
         torch.save(out, cd / f"{stem}.tpqr")
         logger.info(f"Saved the smoothed posterior in {stem}.tpqr file")
+    except HipExtensionError:
+        logger.exception("smooth failed: it needs an AMD GPU (--cuda) and the built HIP library")
+        raise typer.Exit(1)
+
+
+def _smooth_mixture_options(populations, U, B, joint, structure, restarts, restart_seed, forbid, logger):
+    """The checks of ``--populations`` of `smooth`, made where ``--ci`` is checked (after the model, before ``--cpu``).
+    Returns None for one population, else ``{"populations", "restarts", "seed", "allow"}``."""
+    if not 1 <= populations <= 4:
+        logger.error(f"smooth: --populations must lie in 1 .. 4, got {populations}")
+        raise typer.Exit(1)
+    if populations == 1:
+        return None
+    if joint is not None or structure is not None:
+        logger.error("smooth: --populations does not go with --joint / --structure: the joint chain is fitted to all AOIs")
+        raise typer.Exit(1)
+    if (restarts + 1) * populations > 64:
+        logger.error(f"smooth: (--restarts + 1) * --populations must be at most 64, got ({restarts} + 1) * {populations}")
+        raise typer.Exit(1)
+    return {"populations": populations,
+            **_smooth_multistart_options(U, B, restarts, restart_seed, forbid, logger, mixture=True)}
+
+
+def _smooth_mixture(m, mask, cd, logger, U, B, mixture, num_iter, tol, num_samples, ci, bootstrap, seed, progress_bar):
+    """`smooth --populations G`: every channel fitted by ``mixture_fit`` as a mixture of G chains of
+    (U, B) states over the on-target AOIs.  Writes ``<model>_smooth-u<U>b<B>g<G>.tpqr`` and, per channel,
+    ``<model>_smooth-u<U>b<B>g<G>-channel<c>.csv``; no other file is touched.  AOIs outside the mask keep the fit's z_probs
+    and have NaN state and population probabilities and population 255.
+
+    The CSV has, per population g, its weight, every entry of its A, the mean dwell of every state and the class-level kon
+    and koff: ``EM`` is the fitted value, ``Mean`` and the interval come from posterior rasters that draw a population for
+    every AOI (the share of AOIs drawn into g; the quotients of the state pairs of those AOIs)."""
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.exceptions import HipExtensionError
+    from tapqir_amd.utils.mle_analysis import (estimand_summary, hmm_n_params, mixture_estimate, mixture_fit, mixture_sample,
+                                               mixture_viterbi)
+
+    data, M, G = m.data, U + B, mixture["populations"]
+    stem = f"{m.name}_smooth-u{U}b{B}g{G}"
+    pct = f"{ci * 100:g}%"
+    topology = torch.tensor(mixture["allow"], dtype=torch.bool)
+    z_raw = m.params["z_probs"][: data.N, :, :, 1].float()  # (N, F, C)
+    out = {"z_probs": z_raw.clone(), "z_map": z_raw > 0.5, "state_probs": torch.full((*z_raw.shape, M), float("nan")),
+           "population_probs": torch.full((data.N, G, data.C), float("nan"), dtype=torch.float64),
+           "population_map": torch.full((data.N, data.C), 255, dtype=torch.uint8),
+           "theta": torch.zeros(data.C, G, M * M + M, dtype=torch.float64), "phi": torch.zeros(data.C, G, dtype=torch.float64),
+           "log_evidence": torch.full((data.N, data.C), float("nan"), dtype=torch.float64),
+           "bic": torch.zeros(data.C, dtype=torch.float64), "n_params": G * hmm_n_params(topology) + G - 1, "loglik_trace": [],
+           "restart_logliks": torch.zeros(data.C, mixture["restarts"] + 1, dtype=torch.float64), "topology": topology,
+           "prior": torch.zeros(data.C, dtype=torch.float64), "mask": mask, "unbound": U, "bound": B, "populations": G}
+    try:
+        dev = torch.device("cuda")
+        for c in range(data.C):
+            logger.info(f"Channel #{c} ({data.channels[c]})")
+            prior = float(torch.as_tensor(m.params["pi"]["Mean"]).reshape(-1, 2)[c, 1])
+            p = z_raw[:, :, c][mask].to(dev)
+            chan_seed = c if seed is None else seed
+            fit = mixture_fit(p, prior, U, B, populations=G, restarts=mixture["restarts"], seed=mixture["seed"],
+                              allow=topology, num_iter=num_iter, tol=tol, progress_bar=progress_bar)
+            best = fit["best"]
+            logger.info(f"EM of {G} populations of {U} unbound and {B} bound states from {mixture['restarts'] + 1} start"
+                        f"{'s' if mixture['restarts'] else ''}: log evidence = {fit['loglik']:.6f}, mixture BIC = "
+                        f"{fit['bic']:.6f} ({fit['n_params']} parameters; the lower, the better) after "
+                        f"{fit['iterations'][best]} iterations, weights {', '.join(f'{x:.4f}' for x in fit['phi'].tolist())}")
+            logger.info("compare this BIC with that of `smooth --bound-states` (or --unbound-states) without --populations: "
+                        "populations are molecules that differ, more states are one kind of molecule that switches")
+            if not fit["converged"][best]:
+                logger.warning(f"smooth: the EM did not converge to --tol {tol:g} within {fit['iterations'][best]} iterations")
+            thetas, resp = fit["thetas"], fit["resp"]
+            vit = mixture_viterbi(p, thetas, resp, prior, U, B)
+            sample = mixture_sample(fit["filt"], thetas, resp, U, B, num_samples, seed=chan_seed, trans=True)
+            est = mixture_estimate(sample["trans"], sample["pop"], G, bootstrap=bootstrap, seed=chan_seed)
+            tot = est["totals"].double()  # (S, G, M, M)
+            drawn = {"kon": tot[:, :, :U, U:].sum((2, 3)) / tot[:, :, :U].sum((2, 3)),
+                     "koff": tot[:, :, U:, :U].sum((2, 3)) / tot[:, :, U:].sum((2, 3))}
+            share = est["members"].double() / est["members"].sum(1, keepdim=True).double()
+            results = pd.DataFrame(columns=["EM", "Mean", f"{pct} LL", f"{pct} UL"], dtype=float)
+            for g in range(G):
+                A = thetas[g, : M * M].reshape(M, M).cpu()
+                row = estimand_summary(share[:, g], ci)
+                results.loc[f"g{g}_phi"] = [fit["phi"][g].item(), row["mean"], row["ll"], row["ul"]]
+                for i in range(M):
+                    for j in range(M):
+                        row = estimand_summary(est["A"][:, g, i, j], ci)
+                        results.loc[f"g{g}_A{i}{j}"] = [A[i, j].item(), row["mean"], row["ll"], row["ul"]]
+                for i in range(M):  # mean dwell of state i in frames, 1 / (1 - A_ii)
+                    row = estimand_summary(1.0 / (1.0 - est["A"][:, g, i, i]), ci)
+                    results.loc[f"g{g}_dwell{i}"] = [1.0 / (1.0 - A[i, i].item()), row["mean"], row["ll"], row["ul"]]
+                pairs = fit["pair_sums"][g].cpu()
+                em = {"kon": (pairs[:U, U:].sum() / pairs[:U].sum()).item(), "koff": (pairs[U:, :U].sum() / pairs[U:].sum()).item()}
+                for rate in ("kon", "koff"):
+                    row = estimand_summary(drawn[rate][:, g], ci)
+                    results.loc[f"g{g}_{rate}"] = [em[rate], row["mean"], row["ll"], row["ul"]]
+            results.to_csv(cd / f"{stem}-channel{c}.csv")
+            logger.info(f"Saved the weights, transition matrices, dwells and rates of the populations in {stem}-channel{c}.csv "
+                        f"file")
+            out["z_probs"][:, :, c][mask] = fit["gamma"][..., U:].sum(-1).float().cpu()
+            out["state_probs"][:, :, c][mask] = fit["gamma"].float().cpu()
+            out["z_map"][:, :, c][mask] = (vit["path"] >= U).cpu()
+            out["population_probs"][:, :, c][mask] = resp.T.cpu()
+            out["population_map"][:, c][mask] = vit["population_map"].to(torch.uint8).cpu()
+            out["theta"][c] = thetas.cpu()
+            out["phi"][c] = fit["phi"].cpu()
+            out["log_evidence"][:, c][mask] = fit["evidence"].cpu()
+            out["bic"][c] = fit["bic"]
+            out["prior"][c] = prior
+            out["loglik_trace"].append(fit["trace"].cpu())
+            out["restart_logliks"][c] = fit["logliks"]
+        torch.save(out, cd / f"{stem}.tpqr")
+        logger.info(f"Saved the smoothed posterior of the mixture in {stem}.tpqr file")
     except HipExtensionError:
         logger.exception("smooth failed: it needs an AMD GPU (--cuda) and the built HIP library")
         raise typer.Exit(1)
@@ -1021,6 +1134,7 @@ def smooth(
     restarts: int = typer.Option(0, "--restarts", min=0, max=63, help="Random starts of the EM fitted next to the default start; the best one is kept"),
     restart_seed: int = typer.Option(0, "--restart-seed", help="Seed of the random starts"),
     forbid: Optional[List[str]] = typer.Option(None, "--forbid", help="i-j: fix the transition from state i to state j at the floor, 1e-9 (repeatable)"),
+    populations: int = typer.Option(1, "--populations", help="Populations of AOIs, each with a chain of its own (1 to 4): a mixture of chains"),
     joint: Optional[str] = typer.Option(None, "--joint", help="A,B: smooth the colour channels A and B together as one chain of four states"),
     structure: Optional[str] = typer.Option(None, "--structure", help="With --joint: auto (the lowest BIC, the default), independent, a-drives-b, b-drives-a, coupled or full"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
@@ -1051,6 +1165,13 @@ def smooth(
     ``a-drives-b``, ``b-drives-a``, ``coupled``, ``full`` -- side by side; the BIC ranks them and ``--structure`` forces one.
     Only ``<model>_smooth-joint<A><B>.tpqr`` and ``<model>_smooth-joint<A><B>.csv`` are written: the matrix, the on and off
     rates of each channel given the partner's state, and their ratios.
+
+    With ``--populations G`` (2 to 4) the AOIs are a mixture of G populations, each with a chain of its own of the same
+    ``--unbound-states`` / ``--bound-states``: molecules that differ -- an inactive fraction, two
+    conformers -- where more bound states model one kind of molecule that switches; compare the BICs.  ``--restarts``,
+    ``--restart-seed`` and ``--forbid`` apply, at (1, 1) too.  Only ``<model>_smooth-u<U>b<B>g<G>.tpqr`` (with every AOI's
+    population probabilities) and ``<model>_smooth-u<U>b<B>g<G>-channel<c>.csv`` (weight, matrix, dwells and rates of
+    every population) are written.
     """
     import pandas as pd
     import torch
@@ -1067,15 +1188,23 @@ def smooth(
     if model.value == "cosmos" and unbound_states + bound_states > 4:
         logger.error(f"smooth: --unbound-states + --bound-states must be at most 4, got {unbound_states} + {bound_states}")
         raise typer.Exit(1)
+    mixture = None
+    if model.value == "cosmos":
+        mixture = _smooth_mixture_options(populations, unbound_states, bound_states, joint, structure, restarts, restart_seed,
+                                          forbid, logger)
     pair = None
     if model.value == "cosmos" and (joint is not None or structure is not None):
         pair = _smooth_joint_options(joint, structure, unbound_states, bound_states, restarts, restart_seed, forbid, logger)
     multistart = None
-    if model.value == "cosmos" and (restarts or restart_seed or forbid):
+    if model.value == "cosmos" and mixture is None and (restarts or restart_seed or forbid):
         multistart = _smooth_multistart_options(unbound_states, bound_states, restarts, restart_seed, forbid, logger)
     m, mask, progress_bar = _kinetics_inputs("smooth", model, cuda, progress_bar)
     if pair is not None:
         _smooth_joint(m, mask, cd, logger, pair, num_iter, tol, num_samples, ci, bootstrap, seed, progress_bar)
+        return
+    if mixture is not None:
+        _smooth_mixture(m, mask, cd, logger, unbound_states, bound_states, mixture, num_iter, tol, num_samples, ci, bootstrap,
+                        seed, progress_bar)
         return
     if (unbound_states, bound_states) != (1, 1):
         _smooth_multistate(m, mask, cd, logger, unbound_states, bound_states, num_iter, tol, num_samples, ci, bootstrap,

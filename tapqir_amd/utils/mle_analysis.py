@@ -30,7 +30,12 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
 * ``hmm_dwell_sample`` / ``hmm_dwell_intervals``: the outputs of ``smooth_dwell_sample`` / ``smooth_dwell_intervals`` for
   the class rasters of ``hmm_sample``, walked as they are drawn (``tq_chain_dwell``);
 * ``hmm_random_starts`` / ``hmm_fit_restarts``: the EM of ``hmm_fit`` from several starts fitted side by side, under an
-  optional topology of forbidden transitions, and the best of them (``tq_multistart_estep``, ``tq_multistart_mstep``).
+  optional topology of forbidden transitions, and the best of them (``tq_multistart_estep``, ``tq_multistart_mstep``);
+* ``mixture_default_start`` / ``mixture_random_starts`` / ``mixture_mstep`` / ``mixture_fit`` / ``mixture_sample`` /
+  ``mixture_estimate`` / ``mixture_viterbi``: a mixture of G such chains over the AOIs -- static heterogeneity, every AOI
+  belonging to one population -- fitted by EM from several starts side by side, with the responsibilities, the BIC,
+  posterior rasters that draw a population each, and the transition matrix of every population
+  (``tq_multistart_estep``, ``tq_mixture_mstep``, ``tq_mixture_count``, ``tq_mixture_estimate``).
 
 Two colour channels smoothed together as one chain (``smooth --joint``) are in ``tapqir_amd/utils/joint_analysis.py``.
 
@@ -41,7 +46,7 @@ import ctypes as C
 
 import torch
 
-from tapqir_amd import _lib, _lib_hmm, _lib_multistart, _lib_rates, _lib_smooth
+from tapqir_amd import _lib, _lib_hmm, _lib_mixture, _lib_multistart, _lib_rates, _lib_smooth
 from tapqir_amd.exceptions import HipExtensionError
 
 ADAM_BETAS = (0.9, 0.999)
@@ -857,6 +862,22 @@ def hmm_n_params(allow):
     return int(allow.sum()) - M + (M - 1)
 
 
+def _hmm_draw_start(rng, M, free):
+    """One random start (M * M + M,) from ``rng``, in the order of draws that ``hmm_random_starts`` documents."""
+    import numpy as np
+
+    A = np.zeros((M, M))
+    for i in range(M):
+        leave = 10.0 ** rng.uniform(-2.5, -0.3)
+        js = [j for j in range(M) if j != i and free[i, j]]
+        if js:
+            A[i, js] = leave * rng.dirichlet(np.ones(len(js)))
+            A[i, i] = 1.0 - leave
+        else:
+            A[i, i] = 1.0
+    return np.concatenate([A.ravel(), rng.dirichlet(np.ones(M))])
+
+
 def hmm_random_starts(unbound, bound, restarts, seed=0, allow=None):
     """``restarts`` + 1 starts of the EM as (restarts + 1, M * M + M) float64 on the host, theta = (A row-major, rho).
 
@@ -883,16 +904,7 @@ def hmm_random_starts(unbound, bound, restarts, seed=0, allow=None):
     out[0] = np.concatenate([A.ravel(), rho.numpy()])
     rng = np.random.default_rng(seed)
     for r in range(1, restarts + 1):
-        A = np.zeros((M, M))
-        for i in range(M):
-            leave = 10.0 ** rng.uniform(-2.5, -0.3)
-            js = [j for j in range(M) if j != i and free[i, j]]
-            if js:
-                A[i, js] = leave * rng.dirichlet(np.ones(len(js)))
-                A[i, i] = 1.0 - leave
-            else:
-                A[i, i] = 1.0
-        out[r] = np.concatenate([A.ravel(), rng.dirichlet(np.ones(M))])
+        out[r] = _hmm_draw_start(rng, M, free)
     return torch.from_numpy(out)
 
 
@@ -1062,3 +1074,286 @@ def hmm_fit_restarts(p, prior, unbound, bound, restarts=8, seed=0, allow=None, s
             "loglik": loglik, "n_params": n_params, "bic": -2.0 * loglik + n_params * math.log(N * F), "order": order,
             "best": best, "logliks": logliks, "thetas": thetas, "traces": trace[:, : max(iterations)], "starts": starts,
             "allow": free[idx][:, idx]}
+
+
+# ---- a mixture of chains over the AOIs (`smooth --populations`) ------------------------------------
+def _mixture_pops(who, populations):
+    G = int(populations)
+    if not 1 <= G <= _lib_mixture.MIXTURE_MAX_POP:
+        raise ValueError(f"{who}: populations must lie in 1 .. {_lib_mixture.MIXTURE_MAX_POP}, got {populations}")
+    return G
+
+
+def mixture_n_params(allow, populations):
+    """Free parameters of a mixture of G chains of the topology ``allow``: G chains of ``hmm_n_params`` and G - 1 weights."""
+    return populations * hmm_n_params(allow) + populations - 1
+
+
+def mixture_default_start(unbound, bound, populations, allow=None):
+    """The deterministic default start of ``mixture_fit`` as (thetas (G, M * M + M), phi (G,)) float64 on the host:
+    population g is ``hmm_default_start`` with every off-diagonal entry of A divided by 4^g and the diagonal set to 1 minus
+    the row's off-diagonal sum, so population g leaves its states 4^g times more slowly; rho and phi are uniform.  With
+    ``allow`` the forbidden entries are zeroed and their rows renormalised, as ``hmm_random_starts`` does it."""
+    import numpy as np
+
+    U, B, M = _hmm_states("mixture_default_start", unbound, bound)
+    G = _mixture_pops("mixture_default_start", populations)
+    free = hmm_allow(allow, M, "mixture_default_start").numpy()
+    A0, rho = hmm_default_start(U, B)
+    thetas = np.zeros((G, M * M + M))
+    for g in range(G):
+        A = A0.numpy().copy()
+        for i in range(M):
+            A[i, i] = 0.0
+            A[i] = A[i] / 4.0 ** g
+            A[i, i] = 1.0 - A[i].sum()
+            if not free[i].all():
+                A[i] = A[i] * free[i] / (A[i] * free[i]).sum()
+        thetas[g] = np.concatenate([A.ravel(), rho.numpy()])
+    return torch.from_numpy(thetas), torch.full((G,), 1.0 / G, dtype=torch.float64)
+
+
+def mixture_random_starts(unbound, bound, populations, restarts, seed=0, allow=None):
+    """``restarts`` + 1 starts of the mixture EM as (thetas (P, G, M * M + M), phi (P, G)) float64 on the host.  Start 0 is
+    ``mixture_default_start``.  Starts 1 ... come from ``numpy.random.default_rng(seed)``: for every population in turn
+    the draws of a start of ``hmm_random_starts``, and after the G chains of a start ``phi = rng.dirichlet(ones(G))``.
+    P * G is at most 64."""
+    import numpy as np
+
+    U, B, M = _hmm_states("mixture_random_starts", unbound, bound)
+    G = _mixture_pops("mixture_random_starts", populations)
+    restarts = int(restarts)
+    if restarts < 0 or (restarts + 1) * G > _lib_multistart.MULTISTART_MAX:
+        raise ValueError(f"mixture_random_starts: (restarts + 1) * populations must lie in 1 .. "
+                         f"{_lib_multistart.MULTISTART_MAX}, got restarts = {restarts} and populations = {G}")
+    free = hmm_allow(allow, M, "mixture_random_starts").numpy()
+    thetas, phi = np.zeros((restarts + 1, G, M * M + M)), np.zeros((restarts + 1, G))
+    t0, f0 = mixture_default_start(U, B, G, free)
+    thetas[0], phi[0] = t0.numpy(), f0.numpy()
+    rng = np.random.default_rng(seed)
+    for p in range(1, restarts + 1):
+        for g in range(G):
+            thetas[p, g] = _hmm_draw_start(rng, M, free)
+        phi[p] = rng.dirichlet(np.ones(G))
+    return torch.from_numpy(thetas), torch.from_numpy(phi)
+
+
+def mixture_mstep(rows, thetas, phi, trace, it=0, unbound=1, bound=1, allow=None, active=None, resp=None, evidence=None):
+    """One launch of ``tq_mixture_mstep``: for each of P starts, the G chains ``thetas`` (P, G, M * M + M) and the weights
+    ``phi`` (P, G), both in place, from ``rows`` (P, G, N, M * M + M + 1) -- ``multistart_estep`` of the P * G chains -- with
+    every AOI weighted by its responsibility, under the topology ``allow``; the mixture log evidence goes into
+    ``trace[p, it]``, trace (P, T).  ``resp`` (P, G, N) and ``evidence`` (P, N), when given, receive the responsibilities
+    and the per-AOI log evidence at the thetas and phi the rows were computed with.  A start with ``active[p] == 0`` keeps
+    everything.  Returns ``thetas``."""
+    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
+        raise HipExtensionError("mixture_mstep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states("mixture_mstep", unbound, bound)
+    cols = _lib_hmm.hmm_cols(M)
+    if (rows.ndim != 4 or rows.shape[3] != cols or 0 in rows.shape or rows.dtype != torch.float64 or not rows.is_contiguous()
+            or rows.shape[1] > _lib_mixture.MIXTURE_MAX_POP or rows.shape[0] * rows.shape[1] > _lib_multistart.MULTISTART_MAX):
+        raise ValueError(f"mixture_mstep: rows must be contiguous float64 (P, G, N, {cols}) with G <= "
+                         f"{_lib_mixture.MIXTURE_MAX_POP} and P * G <= {_lib_multistart.MULTISTART_MAX}")
+    P, G, N = rows.shape[:3]
+    it = int(it)
+    for name, x, ok in (("thetas", thetas, lambda x: x.shape == (P, G, M * M + M)), ("phi", phi, lambda x: x.shape == (P, G)),
+                        ("trace", trace, lambda x: x.ndim == 2 and x.shape[0] == P and 0 <= it < x.shape[1]),
+                        ("resp", resp, lambda x: x.shape == (P, G, N)), ("evidence", evidence, lambda x: x.shape == (P, N))):
+        if x is None and name in ("resp", "evidence"):
+            continue
+        if (not isinstance(x, torch.Tensor) or x.device != rows.device or x.dtype != torch.float64 or not x.is_contiguous()
+                or not ok(x)):
+            raise ValueError(f"mixture_mstep: {name} must be contiguous float64 on the device of rows: thetas ({P}, {G}, "
+                             f"{M * M + M}), phi ({P}, {G}), trace ({P}, T) with 0 <= it < T, resp ({P}, {G}, {N}), "
+                             f"evidence ({P}, {N})")
+    active = _multistart_active("mixture_mstep", active, P, rows.device)
+    bits = _lib_multistart.allow_bits(hmm_allow(allow, M, "mixture_mstep").tolist())
+    a = _lib_mixture.MixtureMstepArgs(rows=_lib.ptr(rows), theta=_lib.ptr(thetas), phi=_lib.ptr(phi), trace=_lib.ptr(trace),
+                                      resp=_lib.ptr(resp), evidence=_lib.ptr(evidence), active=_lib.ptr(active), N=N, it=it,
+                                      T=trace.shape[1], P=P, G=G, U=U, B=B, allow=bits)
+    _lib.check(_lib_mixture.lib().tq_mixture_mstep(C.byref(a), _stream(rows.device)), "tq_mixture_mstep")
+    return thetas
+
+
+def mixture_fit(p, prior, unbound=1, bound=1, populations=2, restarts=0, seed=0, allow=None, num_iter=200, tol=1e-9,
+                chunk=50, progress_bar=None, starts=None):
+    """EM fit of a mixture of ``populations`` chains of ``unbound`` + ``bound`` hidden states to the rows of ``p`` (N, F):
+    AOI n belongs to population g with weight phi_g and follows the chain theta_g throughout -- static heterogeneity,
+    where ``hmm_fit`` with more bound states models a molecule that switches.  P = ``restarts`` + 1 starts
+    (``mixture_random_starts``, or ``starts`` = (thetas (P, G, .), phi (P, G)), normalised as ``hmm_fit`` normalises its
+    start) are fitted side by side: an iteration is one ``multistart_estep`` of the P * G chains and one
+    ``mixture_mstep``, driven by ``multistart_em`` with the stopping rule of ``hmm_fit`` per start on the mixture log
+    evidence.  A closing E-step gives every start's evidence; the best start is the largest, a tie going to the lowest
+    index.  For the winner, ``hmm_estep`` per population gives ``filt`` and ``gamma``, the states of each population are
+    put in ``hmm_canonical_order``, and the populations in descending phi (a tie: the lower index first).
+
+    Returns ``thetas`` (G, M * M + M), ``phi`` (G,), ``resp`` (G, N), ``evidence`` (N,), ``loglik``, ``n_params`` =
+    G (free entries of A - M + M - 1) + G - 1, ``bic`` = -2 loglik + n_params log(N F), ``trace``, ``logliks`` (P,) on the
+    host, ``gamma`` (N, F, M) = sum_g resp gamma_g, ``gammas`` and ``filt`` (G, N, F, M), ``population_map`` (N,), ``best``,
+    the lists ``iterations`` and ``converged`` (P,), ``traces`` (P, T), ``allows`` (G, M, M), ``orders``, and ``pair_sums``
+    (G, M, M): the expected state pairs of every population, its AOIs weighted by their responsibilities."""
+    import math
+
+    num_iter = int(num_iter)
+    U, B, M = _hmm_states("mixture_fit", unbound, bound)
+    G = _mixture_pops("mixture_fit", populations)
+    free = hmm_allow(allow, M, "mixture_fit")
+    if starts is None:
+        starts = mixture_random_starts(U, B, G, restarts, seed, free)
+    th0 = torch.as_tensor(starts[0], dtype=torch.float64).detach().cpu()
+    ph0 = torch.as_tensor(starts[1], dtype=torch.float64).detach().cpu()
+    W = M * M + M
+    if (num_iter < 1 or th0.ndim != 3 or th0.shape[1:] != (G, W) or ph0.shape != (th0.shape[0], G) or th0.shape[0] < 1
+            or th0.shape[0] * G > _lib_multistart.MULTISTART_MAX or not bool((th0 >= 0).all()) or not bool((ph0 >= 0).all())):
+        raise ValueError(f"mixture_fit: num_iter must be positive, starts non-negative (P, {G}, {W}) and (P, {G}) with "
+                         f"1 <= P * {G} <= {_lib_multistart.MULTISTART_MAX}")
+    P = th0.shape[0]
+    A, rho = th0[..., : M * M].reshape(P * G, M, M), th0[..., M * M:].reshape(P * G, M)
+    if not bool((A.sum(2) > 0).all()) or not bool((rho.sum(1) > 0).all()) or not bool((ph0.sum(1) > 0).all()):
+        raise ValueError("mixture_fit: every row of A, every rho and every phi of starts must have a positive sum")
+    if not isinstance(p, torch.Tensor) or p.device.type != "cuda":
+        raise HipExtensionError("mixture_fit runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    thetas = torch.stack([torch.cat([(A[r] / A[r].sum(1, keepdim=True)).reshape(-1), rho[r] / rho[r].sum()])
+                          for r in range(P * G)]).to(p.device)  # (P * G, W): the replicas of multistart_estep
+    phi = torch.stack([ph0[q] / ph0[q].sum() for q in range(P)]).to(p.device)
+    p, N, F, _, prior, U, B, M = _hmm_inputs("mixture_fit", p, thetas[0], prior, U, B)
+    R = P * G
+    if R * N * F * M * 8 > MULTISTART_SCRATCH_BYTES:
+        raise ValueError(f"mixture_fit: the scratch of R = {R} chains, N = {N} rows, F = {F} frames and M = {M} states takes "
+                         f"{R * N * F * M * 8} bytes, more than {MULTISTART_SCRATCH_BYTES}: use fewer restarts")
+    dev = p.device
+    rows = torch.empty(R, N, _lib_hmm.hmm_cols(M), dtype=torch.float64, device=dev)
+    scratch = torch.empty(R, N, F, M, dtype=torch.float64, device=dev)
+    trace = torch.full((P, num_iter), float("nan"), dtype=torch.float64, device=dev)
+    active = torch.ones(P, dtype=torch.int32, device=dev)
+    active_r = torch.ones(R, dtype=torch.int32, device=dev)
+    rows4, thetas3 = rows.view(P, G, N, -1), thetas.view(P, G, W)
+
+    def estep():
+        active_r.view(P, G).copy_(active[:, None])  # a population is a replica: active (P) expanded to (P * G)
+        multistart_estep(p, thetas, prior, U, B, active_r, rows, scratch)
+
+    iterations, converged = multistart_em(
+        estep, lambda it: mixture_mstep(rows4, thetas3, phi, trace, it, U, B, free, active), trace, active, num_iter, tol,
+        chunk, progress_bar)
+    multistart_estep(p, thetas, prior, U, B, None, rows, scratch)
+    del scratch
+    closing = torch.full((P, 1), float("nan"), dtype=torch.float64, device=dev)
+    resp = torch.empty(P, G, N, dtype=torch.float64, device=dev)
+    evidence = torch.empty(P, N, dtype=torch.float64, device=dev)
+    mixture_mstep(rows4, thetas3.clone(), phi.clone(), closing, 0, U, B, free, None, resp, evidence)
+    logliks = closing[:, 0].cpu()
+    finite = torch.where(torch.isnan(logliks), torch.full_like(logliks, -math.inf), logliks)
+    best = min(q for q in range(P) if finite[q] == finite.max())
+
+    weights = phi[best].cpu()
+    pops = sorted(range(G), key=lambda g: -weights[g].item())  # stable: a tie keeps the lower index first
+    out = {"thetas": [], "filt": [], "gammas": [], "allows": [], "orders": [], "pairs": []}
+    for g in pops:
+        theta = thetas3[best, g].clone()
+        one = _hmm_estep(p, N, F, theta, prior, U, B, _hmm_buffers(N, F, M, dev))
+        order = hmm_canonical_order(theta, U, B)
+        one = hmm_permute(order, M, theta=theta, **one)
+        idx = torch.as_tensor(order, dtype=torch.int64)
+        out["pairs"].append((resp[best, g][:, None] * one["rows"][:, : M * M]).sum(0).reshape(M, M))
+        out["thetas"].append(one["theta"])
+        out["filt"].append(one["filt"])
+        out["gammas"].append(one["gamma"])
+        out["allows"].append(free[idx][:, idx])
+        out["orders"].append(order)
+    ix = torch.as_tensor(pops, dtype=torch.int64, device=dev)
+    resp_best = resp[best][ix].contiguous()
+    gammas = torch.stack(out["gammas"])
+    loglik = logliks[best].item()
+    n_params = mixture_n_params(free, G)
+    return {"thetas": torch.stack(out["thetas"]), "phi": phi[best][ix].contiguous(), "resp": resp_best,
+            "evidence": evidence[best].contiguous(), "loglik": loglik, "n_params": n_params,
+            "bic": -2.0 * loglik + n_params * math.log(N * F), "trace": trace[best, : iterations[best]],
+            "logliks": logliks, "gamma": (resp_best[:, :, None, None] * gammas).sum(0), "gammas": gammas,
+            "filt": torch.stack(out["filt"]), "population_map": resp_best.argmax(0), "best": best,
+            "iterations": iterations, "converged": converged, "traces": trace[:, : max(iterations)],
+            "allows": torch.stack(out["allows"]), "orders": out["orders"], "populations": pops,
+            "pair_sums": torch.stack(out["pairs"])}
+
+
+def _mixture_chains(who, filt, thetas, resp, unbound, bound):
+    """``filt`` (G, N, F, M), ``thetas`` (G, M * M + M) and ``resp`` (G, N) as contiguous float64 on one device."""
+    if not isinstance(filt, torch.Tensor) or filt.device.type != "cuda":
+        raise HipExtensionError(f"{who} runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states(who, unbound, bound)
+    if (filt.ndim != 4 or 0 in filt.shape or filt.shape[3] != M or filt.dtype != torch.float64
+            or filt.shape[0] > _lib_mixture.MIXTURE_MAX_POP or filt.shape[2] > _lib_smooth.SMOOTH_MAX_F):
+        raise ValueError(f"{who}: filt must be float64 (G, N, F, {M}) with 1 <= G <= {_lib_mixture.MIXTURE_MAX_POP}, N >= 1 "
+                         f"and 1 <= F <= {_lib_smooth.SMOOTH_MAX_F}, got {filt.dtype} {tuple(filt.shape)}")
+    G, N, F = filt.shape[:3]
+    for name, x, shape in (("thetas", thetas, (G, M * M + M)), ("resp", resp, (G, N))):
+        if (not isinstance(x, torch.Tensor) or x.device != filt.device or x.dtype != torch.float64 or x.shape != shape):
+            raise ValueError(f"{who}: {name} must be float64 {shape} on the device of filt")
+    return filt.contiguous(), thetas.contiguous(), resp.contiguous(), U, B, M, G, N, F
+
+
+def mixture_sample(filt, thetas, resp, unbound, bound, num_samples, seed=0, trans=False, raster=False):
+    """``num_samples`` posterior rasters of the mixture: every row (s, n) first draws its population from ``resp[:, n]``
+    and is then the row ``hmm_sample`` draws from ``filt[g]`` under ``thetas[g]`` with the same seed.
+
+    Returns ``"counts"`` (S, N, 4) int32 as ``hmm_sample`` does, ``"pop"`` (S, N) uint8, and with ``trans`` / ``raster``
+    the state-pair counts (S, N, M * M) int32 and the hidden states (S, N, F) uint8.  With one population the outputs
+    are those of ``hmm_sample``, bit for bit."""
+    filt, thetas, resp, U, B, M, G, N, F = _mixture_chains("mixture_sample", filt, thetas, resp, unbound, bound)
+    S = int(num_samples)
+    if S < 1:
+        raise ValueError(f"mixture_sample: num_samples must be at least 1, got {num_samples}")
+    dev = filt.device
+    out = {"counts": torch.empty(S, N, _lib_rates.RATES_COLS, dtype=torch.int32, device=dev),
+           "pop": torch.empty(S, N, dtype=torch.uint8, device=dev)}
+    if trans:
+        out["trans"] = torch.empty(S, N, M * M, dtype=torch.int32, device=dev)
+    if raster:
+        out["raster"] = torch.empty(S, N, F, dtype=torch.uint8, device=dev)
+    a = _lib_mixture.MixtureCountArgs(filt=_lib.ptr(filt), theta=_lib.ptr(thetas), resp=_lib.ptr(resp),
+                                      counts=_lib.ptr(out["counts"]), trans=_lib.ptr(out.get("trans")),
+                                      pop=_lib.ptr(out["pop"]), raster=_lib.ptr(out.get("raster")), N=N, F=F, S=S, G=G, U=U, B=B,
+                                      seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib_mixture.lib().tq_mixture_count(C.byref(a), _stream(dev)), "tq_mixture_count")
+    return out
+
+
+def mixture_estimate(trans, pop, populations, bootstrap=False, seed=0):
+    """``hmm_estimate`` per population: from ``trans`` (S, N, M * M) and ``pop`` (S, N) of ``mixture_sample``, pooled over
+    the AOIs a raster put into population g, or with ``bootstrap=True`` over the AOIs ``hmm_estimate`` draws for the same
+    ``seed``.  Returns ``"A"`` (S, G, M, M) float64 (NaN rows for a state no member visited), ``"totals"`` (S, G, M, M) and
+    ``"members"`` (S, G) int64, on the device."""
+    import math
+
+    if not isinstance(trans, torch.Tensor) or trans.device.type != "cuda":
+        raise HipExtensionError("mixture_estimate runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    G = _mixture_pops("mixture_estimate", populations)
+    M = math.isqrt(trans.shape[2]) if trans.ndim == 3 else 0
+    if (trans.ndim != 3 or M * M != trans.shape[2] or not 2 <= M <= _lib_hmm.HMM_MAX_STATES or trans.dtype != torch.int32
+            or 0 in trans.shape or not isinstance(pop, torch.Tensor) or pop.device != trans.device
+            or pop.dtype != torch.uint8 or pop.shape != trans.shape[:2]):
+        raise ValueError(f"mixture_estimate: trans must be int32 (S, N, M * M) with S, N >= 1 and M in 2 .. "
+                         f"{_lib_hmm.HMM_MAX_STATES}, and pop uint8 (S, N) on its device")
+    trans, pop = trans.contiguous(), pop.contiguous()
+    S, N = trans.shape[:2]
+    totals = torch.empty(S, G, M, M, dtype=torch.int64, device=trans.device)
+    members = torch.empty(S, G, dtype=torch.int64, device=trans.device)
+    est = torch.empty(S, G, M, M, dtype=torch.float64, device=trans.device)
+    a = _lib_mixture.MixtureEstimateArgs(trans=_lib.ptr(trans), pop=_lib.ptr(pop), totals=_lib.ptr(totals),
+                                         members=_lib.ptr(members), estimand=_lib.ptr(est), N=N, S=S, G=G, U=1, B=M - 1,
+                                         resample=1 if bootstrap else 0, seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib_mixture.lib().tq_mixture_estimate(C.byref(a), _stream(trans.device)), "tq_mixture_estimate")
+    return {"A": est, "totals": totals, "members": members}
+
+
+def mixture_viterbi(p, thetas, resp, prior, unbound=1, bound=1):
+    """``hmm_viterbi`` under every population's chain; every AOI takes the path of its most probable population (the first
+    of equal responsibilities).  Returns ``{"path"}`` (N, F) uint8 in hidden states and ``{"population_map"}`` (N,)."""
+    if not isinstance(p, torch.Tensor) or p.device.type != "cuda":
+        raise HipExtensionError("mixture_viterbi runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states("mixture_viterbi", unbound, bound)
+    if (not isinstance(thetas, torch.Tensor) or thetas.ndim != 2 or not 1 <= thetas.shape[0] <= _lib_mixture.MIXTURE_MAX_POP
+            or not isinstance(resp, torch.Tensor) or resp.shape != (thetas.shape[0], p.shape[0])):
+        raise ValueError("mixture_viterbi: thetas must be (G, M * M + M) and resp (G, N)")
+    paths = torch.stack([hmm_viterbi(p, thetas[g], prior, U, B) for g in range(thetas.shape[0])])  # (G, N, F)
+    pop = resp.argmax(0)
+    return {"path": paths[pop, torch.arange(p.shape[0], device=p.device)], "population_map": pop}
