@@ -987,6 +987,47 @@ typedef struct {
 
 int tq_mixture_estimate(const tq_mixture_estimate_args* a, void* stream);
 
+/* tq_population_dwell: the rasters of tq_mixture_count walked into dwell-time intervals and first-binding frames as they
+ * are drawn (`dwelltime --smooth --populations G` / `ttfb --smooth --populations G`); neither a raster
+ * nor the state pairs are stored.
+ * Row (s, n) is, population for population and state for state, the row tq_mixture_count draws for the same filt, theta,
+ * resp, U, B, G and seed: the same population draw (Philox stream (seed, step = s, site 0xA05, elem = n), the tails of
+ * resp[., n]), then the same stream (site 0xA04), order of draws, floor of theta_g, thresholds and double compare under
+ * theta[g] and filt[g, n] -- so one seed gives `smooth --populations G` and the two kinetics commands rasters of the same
+ * mixture.  The class z = (state >= U) of every frame goes through the walker of tq_chain_dwell, and the outputs are
+ * tq_chain_dwell's for that class raster, with the histograms kept apart by the row's drawn population:
+ *   mode TQ_DWELL_COUNT: counts[s, n] = number of intervals of the row; pop[s, n] = g; every interior interval
+ *     (low_or_high 0 / 1) of dwell time d adds 1 to hist_unbound[s, g, d] / hist_bound[s, g, d] (the caller zeroes both
+ *     histograms); and, when tau is not NULL, tau[s, n] = the smallest f with a bound state, or F if there is none.
+ *   mode TQ_DWELL_EMIT: the same draws again into the table `intervals` of tq_chain_dwell's EMIT, under its rules: the k-th
+ *     run a row closes is written at offsets[s, n] + counts[s, n] - 1 - k; a position outside
+ *     [offsets[s, n], min(offsets[s, n] + counts[s, n], total)) is dropped, never written; total = 0 launches nothing.  The
+ *     table keeps its TQ_DWELL_COLS columns: the population of a row is pop[s, n] of the COUNT launch.
+ * With G = 1 every output is tq_chain_dwell's bit for bit.
+ * TQ_ERR_ARG, before anything touches the device, for what tq_chain_dwell refuses (a NULL required pointer of the mode --
+ * resp always, pop in COUNT --, N, F or S < 1, F > TQ_SMOOTH_MAX_F, S > 65535 * 64, total < 0, an unknown mode, U or B < 1 or
+ * U + B > TQ_HMM_MAX_STATES), and for G < 1 or G > TQ_MIXTURE_MAX_POP. */
+typedef struct {
+  const double* filt;          /* (G, N, F, M) of tq_hmm_estep, population by population */
+  const double* theta;         /* (G, M * M + M); device memory */
+  const double* resp;          /* (G, N) of tq_mixture_mstep */
+  int32_t* counts;             /* (S, N) out (COUNT), in (EMIT) */
+  uint8_t* pop;                /* (S, N) out (COUNT) */
+  int32_t* hist_bound;         /* (S, G, F) in/out (COUNT): interior bound runs by drawn population and dwell time */
+  int32_t* hist_unbound;       /* (S, G, F) in/out (COUNT): interior unbound runs by drawn population and dwell time */
+  float* tau;                  /* (S, N) out (COUNT): integer-valued first-binding frames in [0, F]; or NULL */
+  const int64_t* offsets;      /* (S, N) in (EMIT): exclusive scan of counts */
+  int32_t* intervals;          /* (TQ_DWELL_COLS, total) out (EMIT) */
+  int64_t total;               /* EMIT: number of intervals (the column stride) */
+  int32_t N, F, S;
+  int32_t G;
+  int32_t U, B;                /* unbound and bound states, M = U + B */
+  int32_t mode;                /* TQ_DWELL_COUNT or TQ_DWELL_EMIT */
+  uint64_t seed;
+} tq_population_dwell_args;
+
+int tq_population_dwell(const tq_population_dwell_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Two colour channels as one chain (`tapqir_amd smooth --joint A,B`).  Channels a and b of one
  * cosmos fit, hidden state s = z_a + 2 z_b: 0 neither bound, 1 only a, 2 only b, 3 both.

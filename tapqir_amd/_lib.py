@@ -222,6 +222,7 @@ EXPORTS = [
     "tq_multistart_estep", "tq_multistart_mstep",  # ... tapqir_amd/_lib_multistart.py
     "tq_joint_estep", "tq_joint_mstep", "tq_joint_viterbi",  # ... tapqir_amd/_lib_joint.py
     "tq_mixture_mstep", "tq_mixture_count", "tq_mixture_estimate",  # ... tapqir_amd/_lib_mixture.py
+    "tq_population_dwell",
 ]
 
 _lib = None

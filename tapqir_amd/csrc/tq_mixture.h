@@ -4,7 +4,8 @@
 //     tq_multistart.h, so that the E-step is tq_multistart_estep as it stands;
 //   * the weights phi as they are read, the evidence and the responsibilities of one AOI from its G logliks;
 //   * the M-step of one population from its weighted sums under the topology mask;
-//   * the sampler's draw of an AOI's population.
+//   * the sampler's draw of an AOI's population;
+//   * where the interior-run histograms of a sample's population start (tq_population_dwell).
 // With G = 1 every body reduces to its single-chain counterpart bit for bit: phi reads as 1, its logarithm is 0, the
 // evidence is L + 0, the responsibility exp(0) / 1, and a product with 1.0 is exact, fused or not.
 // The __global__ wrappers are in tq_mixture.hip; the test suite runs the same bodies from a g++ build.
@@ -107,3 +108,9 @@ TQ_HD int tq_mixture_population(uint64_t seed, int s, int n, const double* resp,
   }
   return pop;
 }
+
+// ---- sampler walked into intervals (tq_population_dwell) -------------------------------------------
+// The draws are tq_mixture_population and then TqHmmDraws / tq_hmm_thresholds / tq_hmm_label under theta_g, the walk is
+// TqChainDwellRow / tq_chain_dwell_frame / tq_chain_dwell_finish of tq_hmm.h; only the layout is new: the F bins of sample
+// s and drawn population g in histograms of shape (S, G, F).
+TQ_HD int64_t tq_population_hist_at(int s, int g, int G, int F) { return ((int64_t)s * G + g) * F; }

@@ -1,8 +1,9 @@
 // tq_mixture.hip -- a mixture of G <= 4 chains of tq_hmm.h over the AOIs on the device (`smooth --populations G`,
 // DESIGN.md section 29; bodies in tq_mixture.h): the M-step that weights every AOI by its responsibility, on a grid of one
-// workgroup per start; the backward sampler that draws a population with every raster; and the per-population estimate
-// of A.  The E-step is tq_multistart_estep with R = P * G.  No atomics, no workgroup waits on another, every loop bounded
-// by N, F, S or G.
+// workgroup per start; the backward sampler that draws a population with every raster; the same sampler walked into
+// dwell-time intervals and first-binding frames (tq_population_dwell, section 30); and the per-population estimate of A.
+// The E-step is tq_multistart_estep with R = P * G.  No atomics but the integer histogram bins of tq_population_dwell, no
+// workgroup waits on another, every loop bounded by N, F, S or G.
 #include <hip/hip_runtime.h>
 
 #include "tq_dpp.h"
@@ -219,6 +220,130 @@ extern "C" int tq_mixture_count(const tq_mixture_count_args* a, void* stream) {
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_mixture_count_kernel<MM>), grid, dim3(64),
                                                   (size_t)a->G * 64 * MM * (MM - 1) * sizeof(double), (hipStream_t)stream, *a));
   return tq_launch_status("tq_mixture_count_kernel");
+}
+
+// ---- backward sampler walked into intervals: the geometry, the staging and the draws of tq_mixture_count_kernel ---------
+// Row (s, n) is the raster that kernel draws, population for population and state for state (tq_mixture_population, then
+// TqHmmDraws against qbuf[g][j]); here its class z = (state >= U) is walked, as it is drawn, into runs of equal labels as
+// tq_chain_dwell_kernel walks them (tq_chain_dwell_frame), and neither a raster nor the state pairs are kept.  EMIT = false:
+// per-row interval counts, the drawn population, the first-binding frame, and the interior-run histograms of the row's
+// population (integer atomics: order-free, so deterministic); EMIT = true: the same draws again, the k-th run a row closes
+// written at tq_smooth_emit_slot.  Addresses diverge by population, control flow does not; inactive lanes reach every
+// barrier and touch no memory but the staging; every loop is bounded by F or G.  M = 4 writes its quotients to LDS as
+// they come, as tq_chain_dwell_kernel does.
+template <int M, bool EMIT>
+__global__ __launch_bounds__(64) void tq_population_dwell_kernel(const tq_population_dwell_args a) {
+  constexpr int T = M * (M - 1);
+  extern __shared__ double qbuf[];  // [G][64][T]
+  __shared__ TqHmmModel<M> mods[TQ_MIXTURE_MAX_POP];
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const int s = blockIdx.y * 64 + lane;
+  const bool active = s < a.S;
+  const int F = a.F, U = a.U, G = a.G, N = a.N;
+  const int64_t row = (int64_t)s * N + n;
+  if (lane < G) mods[lane] = tq_hmm_model<M>(a.theta + tq_multistart_theta_at<M>(lane), U, 0.5);  // the prior is in filt
+
+  const int g = active ? tq_mixture_population(a.seed, s, n, a.resp + n, N, G) : 0;  // g < G
+  int32_t* hb = EMIT || !active ? nullptr : a.hist_bound + tq_population_hist_at(s, g, G, F);
+  int32_t* hu = EMIT || !active ? nullptr : a.hist_unbound + tq_population_hist_at(s, g, G, F);
+  const int64_t total = a.total;
+  int64_t o = 0;
+  int count = 0;
+  if (EMIT && active) {
+    o = a.offsets[row];
+    count = a.counts[row];
+  }
+
+  TqHmmDraws draws;
+  tq_hmm_draws_begin(draws, a.seed, s, n);
+  TqChainDwellRow r;
+  tq_chain_dwell_begin(r, F);
+  TqDwellInterval iv;
+  int closed = 0;  // runs closed so far
+
+  auto emit = [&](const TqDwellInterval& v) {
+    if (EMIT) {
+      const int64_t pos = tq_smooth_emit_slot(o, count, closed, total);
+      if (pos >= 0) tq_smooth_emit_row(a.intervals, total, pos, s, n, v);
+    } else if (v.low_or_high == 0 || v.low_or_high == 1) {
+      atomicAdd((v.z ? hb : hu) + (v.stop + 1 - v.start), 1);  // an interior run is shorter than F
+    }
+    ++closed;
+  };
+  __syncthreads();
+
+  for (int f0 = (F - 1) & ~63; f0 >= 0; f0 -= 64) {
+    const int cnt = min(64, F - f0);
+    if (lane < cnt) {
+      for (int gp = 0; gp < G; ++gp) {
+        const double* fr = a.filt + tq_multistart_filt_at<M>(gp, n, N, F) + (int64_t)(f0 + lane) * M;
+        double* q = qbuf + (gp * 64 + lane) * T;
+        double af[M];
+#pragma unroll
+        for (int i = 0; i < M; ++i) af[i] = fr[i];
+        if constexpr (M == 4) {
+          tq_hmm_thresholds(mods[gp], af, f0 + lane == F - 1, q);
+        } else {
+          double t[T];
+          tq_hmm_thresholds(mods[gp], af, f0 + lane == F - 1, t);
+#pragma unroll
+          for (int k = 0; k < T; ++k) q[k] = t[k];
+        }
+      }
+    }
+    __syncthreads();
+    if (active) {
+      for (int j = cnt - 1; j >= 0; --j) {
+        const int f = f0 + j;
+        const double u = tq_hmm_draws_next(draws, F - 1 - f);
+        if (tq_chain_dwell_frame<M>(r, u, qbuf + (g * 64 + j) * T, f, F, U, iv)) emit(iv);
+      }
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  tq_chain_dwell_finish(r, iv);
+  emit(iv);
+  if (!EMIT) {
+    a.counts[row] = closed;
+    a.pop[row] = (uint8_t)g;
+    if (a.tau) a.tau[row] = (float)r.tau;
+  }
+}
+
+extern "C" int tq_population_dwell(const tq_population_dwell_args* a, void* stream) {
+  if (!a || !a->filt || !a->theta || !a->resp || !a->counts) {
+    tq_set_error("tq_population_dwell: NULL required pointer");
+    return TQ_ERR_ARG;
+  }
+  if (a->mode == TQ_DWELL_COUNT ? (!a->pop || !a->hist_bound || !a->hist_unbound)
+                                : (a->mode != TQ_DWELL_EMIT || !a->offsets || (a->total > 0 && !a->intervals))) {
+    tq_set_error(a->mode == TQ_DWELL_COUNT || a->mode == TQ_DWELL_EMIT ? "tq_population_dwell: NULL required pointer"
+                                                                       : "tq_population_dwell: unknown mode");
+    return TQ_ERR_ARG;
+  }
+  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F || a->total < 0) {
+    tq_set_error("tq_population_dwell: N, F and S must be positive, F at most 65536 and total non-negative");
+    return TQ_ERR_ARG;
+  }
+  if (!tq_chain_states_ok("tq_population_dwell", a->U, a->B) || !tq_mixture_pops_ok("tq_population_dwell", a->G))
+    return TQ_ERR_ARG;
+  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
+  if (grid.y > 65535u) {
+    tq_set_error("tq_population_dwell: S too large");
+    return TQ_ERR_ARG;
+  }
+  if (a->mode == TQ_DWELL_COUNT) {
+    TQ_HMM_SWITCH_M(a->U + a->B,
+                    hipLaunchKernelGGL((tq_population_dwell_kernel<MM, false>), grid, dim3(64),
+                                       (size_t)a->G * 64 * MM * (MM - 1) * sizeof(double), (hipStream_t)stream, *a));
+  } else {
+    if (a->total == 0) return TQ_OK;
+    TQ_HMM_SWITCH_M(a->U + a->B,
+                    hipLaunchKernelGGL((tq_population_dwell_kernel<MM, true>), grid, dim3(64),
+                                       (size_t)a->G * 64 * MM * (MM - 1) * sizeof(double), (hipStream_t)stream, *a));
+  }
+  return tq_launch_status("tq_population_dwell_kernel");
 }
 
 // ---- estimate: one wave (= one workgroup) per posterior sample ----------------------------------------------------------

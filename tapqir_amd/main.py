@@ -337,36 +337,50 @@ def _kinetics_inputs(command, model, cuda, progress_bar):
     return m, mask, progress_bar
 
 
-def _chain_states(command, model, cuda, smooth, U, B, logger):
-    """The checks of ``--unbound-states`` / ``--bound-states`` of `ttfb` and `dwelltime`: the bound on their sum where
-    `smooth` checks it (after the model, before ``--cpu``), and, once the model and ``--cpu`` have passed, that a chain
-    other than (1, 1) comes with ``--smooth``."""
+def _chain_states(command, model, cuda, smooth, U, B, logger, G=1):
+    """The checks of ``--unbound-states`` / ``--bound-states`` / ``--populations`` of `ttfb` and `dwelltime`: the bound on
+    the sum of the states and the range of the populations where `smooth` checks them (after the model, before ``--cpu``),
+    and, once the model and ``--cpu`` have passed, that a chain other than (1, 1) or more than one population comes with
+    ``--smooth``."""
     if model.value != "cosmos":
         return
     if U + B > 4:
         logger.error(f"{command}: --unbound-states + --bound-states must be at most 4, got {U} + {B}")
         raise typer.Exit(1)
+    if not 1 <= G <= 4:
+        logger.error(f"{command}: --populations must lie in 1 .. 4, got {G}")
+        raise typer.Exit(1)
     if cuda and not smooth and (U, B) != (1, 1):
         logger.error(f"{command}: --unbound-states and --bound-states need --smooth: they choose the chain of `smooth` "
                      f"whose rasters are sampled")
         raise typer.Exit(1)
+    if cuda and not smooth and G > 1:
+        logger.error(f"{command}: --populations needs --smooth: it chooses the mixture of `smooth --populations` whose "
+                     f"rasters are sampled")
+        raise typer.Exit(1)
 
 
-def _smooth_suffix(U, B):
-    """What follows ``smooth`` in the file names of a chain: nothing for the two-state chain, ``-u<U>b<B>`` otherwise."""
+def _smooth_suffix(U, B, G=1):
+    """What follows ``smooth`` in the file names of a chain: nothing for the two-state chain, ``-u<U>b<B>`` otherwise, and
+    ``-u<U>b<B>g<G>`` for a mixture of G > 1 populations at any (U, B)."""
+    if G > 1:
+        return f"-u{U}b{B}g{G}"
     return "" if (U, B) == (1, 1) else f"-u{U}b{B}"
 
 
-def _smoothed_posterior(command, cd, name, mask, logger, U=1, B=1):
-    """``<name>_smooth.tpqr`` (``<name>_smooth-u<U>b<B>.tpqr`` for a chain other than (1, 1)) for the ``--smooth`` switch
-    of `ttfb` and `dwelltime`: the chain of every channel (``theta``, ``prior``), the smoothed ``z_probs`` and the Viterbi
-    path ``z_map``.  Exits with status 1 when the file is missing or was written for another selection of AOIs."""
+def _smoothed_posterior(command, cd, name, mask, logger, U=1, B=1, G=1):
+    """``<name>_smooth.tpqr`` (``<name>_smooth-u<U>b<B>.tpqr`` for a chain other than (1, 1), ``<name>_smooth-u<U>b<B>g<G>.tpqr``
+    for a mixture of G > 1 populations) for the ``--smooth`` switch of `ttfb` and `dwelltime`: the chain of every channel
+    (``theta``, ``prior``), the smoothed ``z_probs`` and the Viterbi path ``z_map``.  Exits with status 1 when the file is
+    missing or was written for another selection of AOIs."""
     import torch
 
     from tapqir_amd.utils.safe_load import load_tpqr
 
-    path = cd / f"{name}_smooth{_smooth_suffix(U, B)}.tpqr"
+    path = cd / f"{name}_smooth{_smooth_suffix(U, B, G)}.tpqr"
     again = "smooth" if (U, B) == (1, 1) else f"smooth --unbound-states {U} --bound-states {B}"
+    if G > 1:
+        again += f" --populations {G}"
     if not path.is_file():
         logger.error(f"{command} --smooth needs {path.name}: run `{again}` first")
         raise typer.Exit(1)
@@ -389,6 +403,41 @@ def _smoothed_filter(sm, c, p_bound, U=1, B=1):
     if (U, B) == (1, 1):
         return smooth_estep(p_bound, theta, float(sm["prior"][c]))["filt"], theta
     return hmm_estep(p_bound, theta, float(sm["prior"][c]), U, B)["filt"], theta
+
+
+def _mixture_filter(sm, c, p_bound, mask, U, B, logger):
+    """The inputs of the mixture's backward sampler for channel ``c`` from the file of `smooth --populations`: the filtered
+    marginals under every population's chain (one E-step per population on the fit's ``p_bound`` at the stored theta_g and
+    prior), the chains and the responsibilities of the on-target AOIs.  Returns (filt (G, N, F, M), thetas (G, M * M + M),
+    resp (G, N)) on the device of ``p_bound``, and logs the stored weights."""
+    import torch
+
+    from tapqir_amd.utils.mle_analysis import hmm_estep
+
+    logger.info(f"rasters of the mixture of {sm['theta'][c].shape[0]} populations fitted by `smooth`, weights "
+                + ", ".join(f"{x:.4f}" for x in sm["phi"][c].tolist()))
+    thetas = sm["theta"][c].to(device=p_bound.device, dtype=torch.float64).contiguous()
+    prior = float(sm["prior"][c])
+    filt = torch.stack([hmm_estep(p_bound, thetas[g], prior, U, B)["filt"] for g in range(thetas.shape[0])])
+    resp = sm["population_probs"][:, :, c][mask].T.to(device=p_bound.device, dtype=torch.float64).contiguous()
+    return filt, thetas, resp
+
+
+def _finite_summary(rows):
+    """``_summary_table`` over the finite values of every row (a sample in which a population has no member, or none that
+    bound, has no value there); a row without any finite value is NaN."""
+    import pandas as pd
+    import torch
+
+    tables = []
+    for label, values in rows:
+        x = values[torch.isfinite(values)]
+        if x.numel():
+            tables.append(_summary_table([(label, x)]))
+        else:
+            tables.append(pd.DataFrame({"Mean": [float("nan")], "95% LL": [float("nan")], "95% UL": [float("nan")]},
+                                       index=[label]))
+    return pd.concat(tables)
 
 
 def _summary_table(rows):
@@ -453,6 +502,40 @@ def _ttfb_plots(cd, stem, c, z_masked, sdx, r_type, Tmax, fb_mean, fb_ll, fb_ul,
     logger.info(f"Saved data plots in {stem}-plot-channel{c}.png file")
 
 
+def _ttfb_populations(cd, stem, c, split, G, Tmax, Af, logger):
+    """``<stem>-populations-channel<c>.csv`` of `ttfb --smooth --populations G`: mean and 95% HPDI over the samples (those in
+    which the population has a member, for the last two a member that bound) of, per population g, ``g<g>_share`` (AOIs
+    drawn into g), ``g<g>_never_bound`` (of those, the share with no bound frame), ``g<g>_first_binding`` (mean
+    first-binding frame of those that bound), and the cumulative fraction bound of the AOIs of g at every frame t,
+    ``g<g>_fraction_bound_<t>``: the columns of the fraction-bound file, one row per frame.  Logs the fitted ``Af`` next to
+    the mixture's estimate of the active fraction, sum_g share_g (1 - never_bound_g)."""
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.utils.mle_analysis import hpdi_columns
+
+    host = {k: v.cpu() for k, v in split.items()}
+    table = _finite_summary((f"g{g}_{key}", host[key][:, g]) for g in range(G)
+                            for key in ("share", "never_bound", "first_binding"))
+    curves = []
+    for g in range(G):
+        fb = host["fraction_bound"][:, g][host["share"][:, g] > 0]  # (samples with a member, Tmax)
+        if fb.shape[0]:
+            ll, ul = hpdi_columns(fb, 0.95)
+            block = {"Mean": fb.mean(0).numpy(), "95% LL": ll.numpy(), "95% UL": ul.numpy()}
+        else:
+            block = {name: torch.full((Tmax,), float("nan")).numpy() for name in ("Mean", "95% LL", "95% UL")}
+        curves.append(pd.DataFrame(block, index=[f"g{g}_fraction_bound_{t}" for t in range(Tmax)]))
+    pd.concat([table, *curves]).to_csv(cd / f"{stem}-populations-channel{c}.csv")
+    logger.info(f"Saved the share, the never-bound share, the mean first-binding frame and the fraction bound of every "
+                f"population in {stem}-populations-channel{c}.csv file")
+    active = (host["share"] * (1.0 - torch.nan_to_num(host["never_bound"], nan=1.0))).sum(1)
+    logger.info(f"active fraction: fitted Af = {Af:.4f}; the mixture's rasters give sum_g share_g (1 - never-bound share of "
+                f"g) = {active.mean().item():.4f} (per population: "
+                + ", ".join(f"g{g} {table.loc[f'g{g}_share', 'Mean']:.4f} x (1 - {table.loc[f'g{g}_never_bound', 'Mean']:.4f})"
+                            for g in range(G)) + ")")
+
+
 @app.command()
 def ttfb(
     model: avail_models = typer.Option("cosmos", help="Tapqir model"),
@@ -463,6 +546,7 @@ def ttfb(
     smooth: bool = typer.Option(False, "--smooth", help="Sample the rasters of the chain fitted by `smooth`"),
     unbound_states: int = typer.Option(1, "--unbound-states", min=1, help="Hidden states that look unbound (z = 0)"),
     bound_states: int = typer.Option(1, "--bound-states", min=1, help="Hidden states that look bound (z = 1); at most 4 in all"),
+    populations: int = typer.Option(1, "--populations", help="Populations of AOIs, each with a chain of its own (1 to 4): a mixture of chains"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -481,6 +565,16 @@ def ttfb(
     are rasters of the same chain at the same seed as those behind ``<model>_smooth-u<U>b<B>-channel<c>.csv``, but not bit
     for bit: the filtered marginals are computed again at the stored chain, and a draw whose uniform lies within rounding
     of a threshold can fall on the other side.
+
+    With ``--smooth --populations G`` (2 to 4) the rasters are those of the mixture of G chains that `smooth` fitted with
+    the same ``--populations`` and state options (``<model>_smooth-u<U>b<B>g<G>.tpqr``): every raster draws a population for
+    every AOI from its responsibilities and then that population's chain, and the files are named
+    ``<model>_ttfb-smooth-u<U>b<B>g<G>-...``.  The same caveat holds: the rasters of the same mixture
+    at the same seed as those behind ``<model>_smooth-u<U>b<B>g<G>-channel<c>.csv``, not bit for bit.  The (ka, kns, Af)
+    fit is pooled over all AOIs; ``...-populations-channel<c>.csv`` adds, per population, the share of AOIs drawn into it,
+    the share of those never bound, the mean first-binding frame of those that bound and the cumulative fraction bound,
+    and the fitted Af is logged next to the mixture's own estimate of the active fraction.  There are no per-population
+    ttfb fits: the members of a population change from sample to sample, and the fit takes rectangular data.
     """
     import pandas as pd
     import torch
@@ -488,16 +582,17 @@ def ttfb(
     from tapqir_amd.exceptions import HipExtensionError
     from tapqir_amd.utils.imscroll import time_to_first_binding
     from tapqir_amd.utils.mle_analysis import (fraction_bound, fraction_bound_fit, hmm_dwell_sample, hpdi_columns,
-                                               smooth_dwell_sample, ttfb_fit, ttfb_sample)
+                                               mixture_dwell_sample, population_first_binding, smooth_dwell_sample,
+                                               ttfb_fit, ttfb_sample)
 
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
-    U, B = unbound_states, bound_states
-    _chain_states("ttfb", model, cuda, smooth, U, B, logger)
+    U, B, G = unbound_states, bound_states, populations
+    _chain_states("ttfb", model, cuda, smooth, U, B, logger, G)
     m, mask, progress_bar = _kinetics_inputs("ttfb", model, cuda, progress_bar)
     data = m.data
-    sm = _smoothed_posterior("ttfb", cd, m.name, mask, logger, U, B) if smooth else None
-    stem = f"{m.name}_ttfb-smooth{_smooth_suffix(U, B)}" if smooth else f"{m.name}_ttfb"
+    sm = _smoothed_posterior("ttfb", cd, m.name, mask, logger, U, B, G) if smooth else None
+    stem = f"{m.name}_ttfb-smooth{_smooth_suffix(U, B, G)}" if smooth else f"{m.name}_ttfb"
     if smooth:
         z = sm["z_map"].float() if binary else sm["z_probs"].float()
     else:
@@ -513,7 +608,11 @@ def ttfb(
             sdx = torch.argsort(time_to_first_binding(z_masked), descending=True)
 
             p_bound = m.params["z_probs"][: data.N, :, c, 1][mask].float().to(dev)
-            if smooth and (U, B) != (1, 1):  # seed c: the default of `smooth`
+            drawn = None
+            if smooth and G > 1:  # seed c: the default of `smooth`
+                drawn = mixture_dwell_sample(*_mixture_filter(sm, c, p_bound, mask, U, B, logger), U, B, num_samples, seed=c)
+                tau = drawn["tau"]
+            elif smooth and (U, B) != (1, 1):  # seed c: the default of `smooth`
                 tau = hmm_dwell_sample(*_smoothed_filter(sm, c, p_bound, U, B), U, B, num_samples, seed=c)["tau"]
             elif smooth:  # seed c: the default of `smooth`, so these are the rasters of its rate table
                 tau = smooth_dwell_sample(*_smoothed_filter(sm, c, p_bound), num_samples, seed=c)["tau"]
@@ -540,6 +639,9 @@ def ttfb(
             logger.info(f"Saved fit data in {stem}-fraction-bound-channel{c}.csv file")
             _ttfb_plots(cd, stem, c, z_masked.cpu(), sdx.cpu(), r_type, Tmax, fb_mean.numpy(), fb_ll.numpy(),
                         fb_ul.numpy(), best_fit.numpy(), logger)
+            if drawn is not None:
+                _ttfb_populations(cd, stem, c, population_first_binding(tau, drawn["pop"], G, Tmax), G, Tmax,
+                                  results.loc["Af", "Mean"], logger)
     except HipExtensionError:
         logger.exception("ttfb failed: it needs an AMD GPU (--cuda) and the built HIP library")
         raise typer.Exit(1)
@@ -572,6 +674,50 @@ def _dwell_plot(cd, stem, c, kind, map_dt, A, k, t_max, logger):
     logger.info(f"Saved {kind} dwell-time histograms in {stem}-{kind}-histogram-channel{c}.png file")
 
 
+def _dwell_population_fits(cd, stem, c, sample, G, K, num_iter, kinds, z_map, population_map, progress_bar, logger):
+    """The fits of `dwelltime --smooth --populations G` for one channel: for every kind, one K-exponential fit per
+    population from ``sample["hist_<kind>"][:, g]`` -- the interior intervals of the AOIs a sample drew into g -- written
+    together as ``<stem>-<rate>-channel<c>.csv`` with rows ``g<g>_A<i>`` and ``g<g>_<rate><i>``, and one histogram per
+    population, ``<stem>-g<g>-<kind>-histogram-channel<c>.png``, of the Viterbi paths ``z_map`` (N, F) of the AOIs whose
+    ``population_map`` is g.  A sample in which g has no interior interval of the kind is left out of that fit and logged;
+    a kind no sample has for g is skipped with a warning."""
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.utils.imscroll import count_intervals
+    from tapqir_amd.utils.mle_analysis import dwell_csr_from_hist, dwell_fit
+
+    for kind, rate, title, host_dwell_times in kinds:
+        logger.info(f"{title} calculation ...")
+        tables = []
+        for g in range(G):
+            hist = sample[f"hist_{kind}"][:, g].contiguous()
+            keep = hist.sum(1) > 0
+            n_out = int((~keep).sum())
+            if n_out == hist.shape[0]:
+                logger.warning(f"dwelltime: no posterior sample has an interior {kind} interval in population {g}: its "
+                               f"{rate} is not fitted")
+                continue
+            if n_out:
+                logger.info(f"population {g}: {n_out} of {hist.shape[0]} posterior samples have no interior {kind} interval "
+                            f"and are left out of the {rate} fit")
+            hist = hist[keep]
+            fit = dwell_fit(dwell_csr_from_hist(hist), K, lr=5e-3, n_steps=num_iter, progress_bar=progress_bar)
+            results = _summary_table(pair for i in range(K) for pair in (
+                (f"g{g}_A{i}", fit["A"][:, i].cpu()), (f"g{g}_{rate}{i}", fit["k"][:, i].cpu())))
+            tables.append(results)
+            A_mean = [results.loc[f"g{g}_A{i}", "Mean"] for i in range(K)]
+            k_mean = [results.loc[f"g{g}_{rate}{i}", "Mean"] for i in range(K)]
+            t_max = int(torch.nonzero(hist.sum(0)).max().item())  # the largest sampled dwell time
+            members = (population_map == g).cpu()
+            map_dt = (host_dwell_times(count_intervals(z_map[members][None].cpu().numpy())) if bool(members.any())
+                      else torch.zeros(0).numpy())
+            _dwell_plot(cd, f"{stem}-g{g}", c, kind, map_dt, A_mean, k_mean, t_max, logger)
+        if tables:
+            pd.concat(tables).to_csv(cd / f"{stem}-{rate}-channel{c}.csv")
+            logger.info(f"Saved {title.lower()} parameters of the populations in {stem}-{rate}-channel{c}.csv file")
+
+
 @app.command()
 def dwelltime(
     model: avail_models = typer.Option("cosmos", help="Tapqir model"),
@@ -582,6 +728,7 @@ def dwelltime(
     smooth: bool = typer.Option(False, "--smooth", help="Sample the rasters of the chain fitted by `smooth`"),
     unbound_states: int = typer.Option(1, "--unbound-states", min=1, help="Hidden states that look unbound (z = 0)"),
     bound_states: int = typer.Option(1, "--bound-states", min=1, help="Hidden states that look bound (z = 1); at most 4 in all"),
+    populations: int = typer.Option(1, "--populations", help="Populations of AOIs, each with a chain of its own (1 to 4): a mixture of chains"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -603,6 +750,15 @@ def dwelltime(
     They are rasters of the same chain at the same seed as those behind ``<model>_smooth-u<U>b<B>-channel<c>.csv``, but not
     bit for bit: the filtered marginals are computed again at the stored chain, and a draw whose uniform lies within
     rounding of a threshold can fall on the other side.
+
+    With ``--smooth --populations G`` (2 to 4) the rasters are those of the mixture of G chains that `smooth` fitted with
+    the same ``--populations`` and state options (``<model>_smooth-u<U>b<B>g<G>.tpqr``): every raster draws a population for
+    every AOI from its responsibilities and then that population's chain.  The interval table gains the column
+    ``population``, every population has its own K-exponential fits (rows ``g<g>_A<i>`` and ``g<g>_koff<i>`` / ``g<g>_kon<i>``)
+    from the interior intervals of the AOIs drawn into it, and its own histograms, of the Viterbi paths of the AOIs whose
+    most probable population it is; the files are named ``<model>_dwelltime-smooth-u<U>b<B>g<G>-...`` (DESIGN.md section
+    30).  The same caveat holds: the rasters of the same mixture at the same seed as those behind
+    ``<model>_smooth-u<U>b<B>g<G>-channel<c>.csv``, not bit for bit.
     """
     import torch
 
@@ -610,8 +766,8 @@ def dwelltime(
     from tapqir_amd.exceptions import HipExtensionError
     from tapqir_amd.utils.imscroll import bound_dwell_times, count_intervals, unbound_dwell_times
     from tapqir_amd.utils.mle_analysis import (dwell_csr_from_hist, dwell_fit, dwell_intervals, dwell_sample,
-                                               hmm_dwell_intervals, hmm_dwell_sample, smooth_dwell_intervals,
-                                               smooth_dwell_sample)
+                                               hmm_dwell_intervals, hmm_dwell_sample, mixture_dwell_intervals,
+                                               mixture_dwell_sample, smooth_dwell_intervals, smooth_dwell_sample)
 
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
@@ -619,8 +775,8 @@ def dwelltime(
     if model.value == "cosmos" and not 1 <= K <= _lib.DWELL_KMAX:
         logger.error(f"dwelltime: -K must be between 1 and {_lib.DWELL_KMAX}, got {K}")
         raise typer.Exit(1)
-    U, B = unbound_states, bound_states
-    _chain_states("dwelltime", model, cuda, smooth, U, B, logger)
+    U, B, G = unbound_states, bound_states, populations
+    _chain_states("dwelltime", model, cuda, smooth, U, B, logger, G)
     m, mask, progress_bar = _kinetics_inputs("dwelltime", model, cuda, progress_bar)
     try:
         from scipy.io import savemat
@@ -628,8 +784,8 @@ def dwelltime(
         savemat = None
 
     data = m.data
-    sm = _smoothed_posterior("dwelltime", cd, m.name, mask, logger, U, B) if smooth else None
-    stem = f"{m.name}_dwelltime-smooth{_smooth_suffix(U, B)}" if smooth else f"{m.name}_dwelltime"
+    sm = _smoothed_posterior("dwelltime", cd, m.name, mask, logger, U, B, G) if smooth else None
+    stem = f"{m.name}_dwelltime-smooth{_smooth_suffix(U, B, G)}" if smooth else f"{m.name}_dwelltime"
     if smooth:
         z_map = sm["z_map"]
     else:
@@ -640,7 +796,11 @@ def dwelltime(
         for c in range(data.C):
             logger.info(f"Channel #{c} ({data.channels[c]})")
             p_bound = m.params["z_probs"][: data.N, :, c, 1][mask].float().to(dev)
-            if smooth and (U, B) != (1, 1):  # seed c: the default of `smooth`
+            if smooth and G > 1:  # seed c: the default of `smooth`
+                chains = _mixture_filter(sm, c, p_bound, mask, U, B, logger)
+                sample = mixture_dwell_sample(*chains, U, B, num_samples, seed=c)
+                intervals = mixture_dwell_intervals(*chains, U, B, num_samples, seed=c, sample=sample)
+            elif smooth and (U, B) != (1, 1):  # seed c: the default of `smooth`
                 filt, theta = _smoothed_filter(sm, c, p_bound, U, B)
                 sample = hmm_dwell_sample(filt, theta, U, B, num_samples, seed=c)
                 intervals = hmm_dwell_intervals(filt, theta, U, B, num_samples, seed=c, sample=sample)
@@ -659,6 +819,10 @@ def dwelltime(
             else:
                 logger.info("scipy is not available: the .mat file of the intervals is not written")
 
+            if smooth and G > 1:
+                _dwell_population_fits(cd, stem, c, sample, G, K, num_iter, kinds, z_map[mask, :, c],
+                                       sm["population_map"][:, c][mask], progress_bar, logger)
+                continue
             for kind, rate, title, host_dwell_times in kinds:
                 logger.info(f"{title} calculation ...")
                 hist = sample[f"hist_{kind}"]

@@ -35,7 +35,11 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
   ``mixture_estimate`` / ``mixture_viterbi``: a mixture of G such chains over the AOIs -- static heterogeneity, every AOI
   belonging to one population -- fitted by EM from several starts side by side, with the responsibilities, the BIC,
   posterior rasters that draw a population each, and the transition matrix of every population
-  (``tq_multistart_estep``, ``tq_mixture_mstep``, ``tq_mixture_count``, ``tq_mixture_estimate``).
+  (``tq_multistart_estep``, ``tq_mixture_mstep``, ``tq_mixture_count``, ``tq_mixture_estimate``);
+* ``mixture_dwell_sample`` / ``mixture_dwell_intervals`` / ``population_first_binding``: the outputs of ``hmm_dwell_sample``
+  / ``hmm_dwell_intervals`` for the class rasters of ``mixture_sample``, walked as they are drawn, with the histograms kept
+  apart by the population every row drew, and the first-binding frames split by population (``tq_population_dwell``;
+  ``population_first_binding`` is host-side torch on S x N numbers and runs anywhere).
 
 Two colour channels smoothed together as one chain (``smooth --joint``) are in ``tapqir_amd/utils/joint_analysis.py``.
 
@@ -500,16 +504,23 @@ def smooth_sample(filt, theta, num_samples, seed=0, raster=False):
 
 
 # ---- dwell times and first binding of the smoothed chain (`dwelltime --smooth`, `ttfb --smooth`) ----
-def _walk_count(launch, S, N, F, dev):
-    """Launch A of a sampler that walks its rasters as it draws them (``tq_smooth_dwell``, ``tq_chain_dwell``):
-    ``launch(**fields)`` fills the argument block's remaining fields and calls the entry point."""
+def _walk_count(launch, S, N, F, dev, populations=None):
+    """Launch A of a sampler that walks its rasters as it draws them (``tq_smooth_dwell``, ``tq_chain_dwell``,
+    ``tq_population_dwell``): ``launch(**fields)`` fills the argument block's remaining fields and calls the entry point.
+    With ``populations`` = G the histograms are (S, G, F) and the launch also fills ``pop`` (S, N) uint8."""
     counts = torch.empty(S, N, dtype=torch.int32, device=dev)
-    hb = torch.zeros(S, F, dtype=torch.int32, device=dev)
-    hu = torch.zeros(S, F, dtype=torch.int32, device=dev)
+    shape = (S, F) if populations is None else (S, populations, F)
+    hb = torch.zeros(shape, dtype=torch.int32, device=dev)
+    hu = torch.zeros(shape, dtype=torch.int32, device=dev)
     tau = torch.empty(S, N, dtype=torch.float32, device=dev)
+    out = {"hist_bound": hb, "hist_unbound": hu, "counts": counts, "tau": tau}
+    extra = {}
+    if populations is not None:
+        out["pop"] = torch.empty(S, N, dtype=torch.uint8, device=dev)
+        extra["pop"] = _lib.ptr(out["pop"])
     launch(counts=_lib.ptr(counts), hist_bound=_lib.ptr(hb), hist_unbound=_lib.ptr(hu), tau=_lib.ptr(tau),
-           mode=_lib.DWELL_COUNT)
-    return {"hist_bound": hb, "hist_unbound": hu, "counts": counts, "tau": tau}
+           mode=_lib.DWELL_COUNT, **extra)
+    return out
 
 
 def _walk_emit(who, launch, sample, S, N, dev):
@@ -1315,6 +1326,81 @@ def mixture_sample(filt, thetas, resp, unbound, bound, num_samples, seed=0, tran
                                       seed=int(seed) & (2**64 - 1))
     _lib.check(_lib_mixture.lib().tq_mixture_count(C.byref(a), _stream(dev)), "tq_mixture_count")
     return out
+
+
+# ---- dwell times and first binding of the mixture's rasters --------------------------------------
+def _population_dwell_launch(filt, thetas, resp, U, B, G, S, N, F, seed):
+    def launch(**fields):
+        a = _lib_mixture.PopulationDwellArgs(filt=_lib.ptr(filt), theta=_lib.ptr(thetas), resp=_lib.ptr(resp), N=N, F=F, S=S,
+                                             G=G, U=U, B=B, seed=int(seed) & (2**64 - 1), **fields)
+        _lib.check(_lib_mixture.lib().tq_population_dwell(C.byref(a), _stream(filt.device)), "tq_population_dwell")
+
+    return launch
+
+
+def _mixture_dwell_inputs(who, filt, thetas, resp, unbound, bound, num_samples):
+    filt, thetas, resp, U, B, M, G, N, F = _mixture_chains(who, filt, thetas, resp, unbound, bound)
+    S = int(num_samples)
+    if S < 1:
+        raise ValueError(f"{who}: num_samples must be at least 1, got {num_samples}")
+    return filt, thetas, resp, U, B, G, S, N, F
+
+
+def mixture_dwell_sample(filt, thetas, resp, unbound, bound, num_samples, seed=0):
+    """``hmm_dwell_sample`` for the mixture of chains: launch A of the interval sampler on the class rasters
+    ``mixture_sample(filt, thetas, resp, unbound, bound, num_samples, seed, raster=True)["raster"] >= unbound``, walked as
+    they are drawn with the population every row draws; neither the rasters nor the state pairs are stored.
+
+    Returns ``"hist_bound"`` / ``"hist_unbound"`` (S, G, F) int32 -- the interior runs of the rows a sample drew into
+    population g, by dwell time; ``hist[:, g]`` goes to ``dwell_csr_from_hist`` / ``dwell_fit`` --, ``"counts"`` (S, N)
+    int32, ``"tau"`` (S, N) float32 and ``"pop"`` (S, N) uint8, the population of ``mixture_sample``.  With one population
+    the outputs are those of ``hmm_dwell_sample``, bit for bit."""
+    filt, thetas, resp, U, B, G, S, N, F = _mixture_dwell_inputs("mixture_dwell_sample", filt, thetas, resp, unbound, bound,
+                                                                 num_samples)
+    return _walk_count(_population_dwell_launch(filt, thetas, resp, U, B, G, S, N, F, seed), S, N, F, filt.device, G)
+
+
+def mixture_dwell_intervals(filt, thetas, resp, unbound, bound, num_samples, seed=0, sample=None):
+    """``hmm_dwell_intervals`` for the mixture of chains: launch A (or its result ``sample`` from ``mixture_dwell_sample``
+    with the same arguments), the exclusive scan of the row counts, and launch B.  Returns the DataFrame of
+    ``dwell_intervals`` and an int64 column ``population``: ``sample["pop"][posterior_sample, aoi]``."""
+    given = num_samples if sample is None else sample["counts"].shape[0]
+    filt, thetas, resp, U, B, G, S, N, F = _mixture_dwell_inputs("mixture_dwell_intervals", filt, thetas, resp, unbound,
+                                                                 bound, given)
+    launch = _population_dwell_launch(filt, thetas, resp, U, B, G, S, N, F, seed)
+    if sample is None:
+        sample = _walk_count(launch, S, N, F, filt.device, G)
+    pop = sample.get("pop")
+    if not isinstance(pop, torch.Tensor) or pop.shape != (S, N) or pop.dtype != torch.uint8 or pop.device != filt.device:
+        raise ValueError(f"mixture_dwell_intervals: sample['pop'] must be uint8 ({S}, {N}) on the device of filt")
+    table = _walk_emit("mixture_dwell_intervals", launch, sample, S, N, filt.device)
+    host = pop.cpu().numpy().astype("int64")
+    table["population"] = host[table["posterior_sample"].to_numpy(), table["aoi"].to_numpy()]
+    return table
+
+
+def population_first_binding(tau, pop, populations, Tmax):
+    """The first-binding frames ``tau`` (S, N) of ``mixture_dwell_sample`` split by the drawn populations ``pop`` (S, N), per
+    sample and population, float64 on the device of ``tau``: ``"share"`` (S, G), the share of AOIs drawn into g;
+    ``"never_bound"`` (S, G), the share of those with tau = Tmax; ``"first_binding"`` (S, G), the mean tau of those that
+    bound; ``"fraction_bound"`` (S, G, Tmax), ``fraction_bound`` over the AOIs of g.  NaN where a sample has no AOI in g (or
+    none that bound)."""
+    G = _mixture_pops("population_first_binding", populations)
+    t = tau.to(torch.float64)
+    S, N = t.shape
+    member = (pop.to(torch.int64)[:, None, :] == torch.arange(G, device=pop.device)[None, :, None]).to(torch.float64)
+    n_g = member.sum(2)  # (S, G)
+    never = member * (t == Tmax).to(torch.float64)[:, None, :]
+    bound = member - never
+    nan = torch.full_like(n_g, float("nan"))
+    first = torch.where(bound.sum(2) > 0, (bound * t[:, None, :]).sum(2) / bound.sum(2).clamp(min=1), nan)
+    counts = torch.zeros(S, G, Tmax + 1, dtype=torch.float64, device=t.device)
+    idx = tau.to(torch.int64).clamp(0, Tmax)[:, None, :].expand(S, G, N)
+    counts.scatter_add_(2, idx, member)
+    below = torch.cumsum(counts, 2) - counts
+    fb = torch.where(n_g[..., None] > 0, below[..., :Tmax] / n_g.clamp(min=1)[..., None], nan[..., None])
+    return {"share": n_g / N, "never_bound": torch.where(n_g > 0, never.sum(2) / n_g.clamp(min=1), nan),
+            "first_binding": first, "fraction_bound": fb}
 
 
 def mixture_estimate(trans, pop, populations, bootstrap=False, seed=0):
