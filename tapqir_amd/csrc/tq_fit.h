@@ -1,12 +1,27 @@
 // tq_fit.h -- what a per-sample Adam fit is made of, shared by the fit kernels of tq_kinetics.hip and tq_dwell.hip
-// (host+device inline bodies): torch.optim.Adam on parameters held in registers and -- device
-// only -- the wave sum of a step's sufficient statistics.  Each kernel keeps its own data pass and its own
+// (host+device inline bodies): the exponential of an unconstrained rate, torch.optim.Adam on parameters held in registers
+// and -- device only -- the wave sum of a step's sufficient statistics.  Each kernel keeps its own data pass and its own
 // consts / accumulate / grad / loss.
 #pragma once
 #include "tq_math.h"
 #if defined(__HIPCC__)
 #include "tq_dpp.h"
 #endif
+
+// e^x of an unconstrained rate parameter.  TQ_FEXP on the device rounds x log2(e) to float before v_exp_f32: up to half an
+// ulp of the exponent, |x| 2^-24 ln 2 relative in e^x (3e-7 at x = log 0.002, five float32 eps), and a gradient whose
+// terms cancel (k sum tau against a count) magnifies it by the cancellation.  Here the part l of the product that the
+// rounding lost goes back in as 2^h (1 + l ln 2), which leaves the instruction's own 1 ulp.  Once per step, not per point.
+TQ_HD float tq_fit_exp(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float h = x * TQ_LOG2E;
+  const float l = fmaf(x, TQ_LOG2E, -h) + x * 1.92596299112661747e-08f;  // log2(e) - (float)log2(e)
+  const float e = TQ_FEXP2(h);
+  return fmaf(e, l * 0.69314718055994530942f, e);
+#else
+  return expf(x);
+#endif
+}
 
 // torch.optim.Adam (betas, eps, bias correction; no weight decay / amsgrad) on one parameter, float32 as torch does it:
 // m.lerp_(g, 1 - beta1); v = v beta2 + (1 - beta2) g^2; p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)

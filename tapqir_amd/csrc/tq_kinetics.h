@@ -6,6 +6,7 @@
 // The __global__ wrappers are in tq_kinetics.hip; the test suite runs the same bodies from a g++ build.
 #pragma once
 #include "../../include/tapqir_hip.h"
+#include "tq_fit.h"
 #include "tq_math.h"
 
 #define TQ_TTFB_SITE 0xA00u  // Philox site id of the sampler's uniforms: stream (seed, step = s, site, elem = n)
@@ -90,8 +91,8 @@ struct TqTtfbK {
 
 TQ_HD TqTtfbK tq_ttfb_consts(float lka, float lkns, float c) {
   TqTtfbK k;
-  k.ka = TQ_FEXP(lka);
-  k.kns = TQ_FEXP(lkns);
+  k.ka = tq_fit_exp(lka);  // the gradient sets k sum tau against counts: see tq_fit_exp
+  k.kns = tq_fit_exp(lkns);
   k.Af = tq_sigmoid(c);
   k.rk1 = 1.0f / (k.ka + k.kns);
   k.lk0 = lkns;
