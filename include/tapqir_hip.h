@@ -94,6 +94,8 @@ typedef struct {
                                   images[ai * F * C * P * P] (a window of a data set that does not fit the device: the host
                                   streams the AOIs of a batch in, dataset.py:140-151 does the same per minibatch); every other
                                   array stays dataset-indexed.  Gathered batches (ndx given) of the 16-lane kernel */
+  const uint16_t* images_il16; /* the 16-bit interleaved copy of tq_images_interleave_u16_n, or NULL (= fp32 tiles).  Read by the
+                                  fused launch of a cosmos step only (tq_cosmos_args.images_il16); tq_ksmogn_log_prob ignores it */
 } tq_ksmogn_args;
 
 int tq_ksmogn_log_prob(const tq_ksmogn_args* a, void* stream);
@@ -160,6 +162,15 @@ int tq_images_interleave(const float* images, float* images_il, int64_t U, int32
 /* the same for tiles of `npix` floats (crosstalk: one (C, P, P) tile per AOI-frame) */
 int64_t tq_interleaved_floats_n(int64_t U, int32_t npix);
 int tq_images_interleave_n(const float* images, float* images_il, int64_t U, int32_t npix, void* stream);
+/* The same layout with 2 bytes per pixel, for images that are integers in [0, 65535] (camera counts: glimpse files hold
+ * int16 + 2^15, the simulator floors): group q of four pixels of the 64 units of a block is one contiguous 512-byte row,
+ *   out[(((u / 64) * npix4 + q) * 64 + (u % 64)) * 4 + e] = (uint16_t) pixel 4q + e of unit u,
+ * padded as the fp32 copy is (zeros behind the last pixel and behind the last unit of the last block).  `out` must hold
+ * tq_interleaved_u16_n(U, npix) uint16_t.  *inexact (a device word that the caller has zeroed) is set to 1 if any pixel v
+ * fails v == (float)(uint16_t)v -- a fraction, a negative value, one above 65535, a NaN -- and is left alone otherwise;
+ * the copy is then not a copy of the images and must not be used. */
+int64_t tq_interleaved_u16_n(int64_t U, int32_t npix);
+int tq_images_interleave_u16_n(const float* images, uint16_t* out, int64_t U, int32_t npix, int32_t* inexact, void* stream);
 
 /* Per-unit data statistics for a single camera offset `offset[0]` (device scalar): with v = D - offset,
  *   pixstats[0][u] = sum_pix v,  pixstats[1][u] = sum_pix ln v,  pixstats[2][u] = #pixels with v <= 0
@@ -283,6 +294,11 @@ typedef struct {
   void* pu_scratch;            /* tq_cosmos_pu_scratch_bytes(pu_scratch_tiles) bytes, or NULL: one ticket counter per split tile,
                                   zeroed once by the caller and never reset (four tickets per tile and launch), then the
                                   partial sums [tile][part][value][lane] */
+  const uint16_t* images_il16; /* fused launch (TQ_PIXEL_FUSED_UNIT): the 16-bit interleaved copy of the images
+                                  (tq_images_interleave_u16_n, its flag read back as 0), or NULL.  Given, the packed pixel loop
+                                  streams it instead of images_il -- 2 instead of 4 bytes per pixel, the same bits out, since a
+                                  16-bit integer converts to fp32 exactly; images_il must be given all the same (the scalar loop
+                                  of a tile with a small background / gain reads it).  Every other launch ignores it */
 } tq_cosmos_args;
 #define TQ_SUBSAMPLE_MAX 65536
 

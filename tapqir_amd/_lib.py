@@ -37,6 +37,7 @@ class KsmognArgs(C.Structure):
         ("P", C.c_int32), ("K", C.c_int32), ("O", C.c_int32),
         ("nb_full", C.c_int32), ("il_min_units", C.c_int32),
         ("scale", C.c_float), ("pixel_mode", C.c_int32), ("images_by_slot", C.c_int32),
+        ("images_il16", C.c_void_p),
     ]
 
 
@@ -66,6 +67,7 @@ class CosmosArgs(C.Structure):
         ("pixel_mode", C.c_int32), ("tail_kind", C.c_int32), ("sync", C.c_void_p), ("sync_value", C.c_int32),
         ("images_by_slot", C.c_int32), ("next_ndx", C.c_void_p), ("next_fdx", C.c_void_p),
         ("pu_split", C.c_int32), ("pu_scratch_tiles", C.c_int32), ("pu_scratch", C.c_void_p),
+        ("images_il16", C.c_void_p),
     ]
 
 
@@ -207,6 +209,7 @@ DWELL_LDS_PAIRS = 2048          # TQ_DWELL_LDS_PAIRS
 EXPORTS = [
     "tq_version", "tq_last_error", "tq_ksmogn_log_prob", "tq_ksmogn_crosstalk_log_prob", "tq_crosstalk_param_count",
     "tq_interleaved_floats", "tq_interleaved_floats_n", "tq_images_interleave_n", "tq_images_interleave", "tq_image_stats",
+    "tq_interleaved_u16_n", "tq_images_interleave_u16_n",
     "tq_globals_size", "tq_gbase_size", "tq_cosmos_nblk", "tq_cosmos_param_count",
     "tq_cosmos_sample_globals", "tq_cosmos_sample_locals", "tq_cosmos_elbo_grads",
     "tq_cosmos_globals_grad", "tq_cosmos_adam", "tq_cosmos_adam_catchup", "tq_cosmos_step", "tq_cosmos_step_overlapped", "tq_cosmos_tail", "tq_cosmos_tail_reduced", "tq_cosmos_sample_locals_range",
@@ -260,6 +263,10 @@ def load():
     lib.tq_interleaved_floats_n.argtypes = [C.c_int64, C.c_int32]
     lib.tq_images_interleave_n.restype = C.c_int
     lib.tq_images_interleave_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    lib.tq_interleaved_u16_n.restype = C.c_int64
+    lib.tq_interleaved_u16_n.argtypes = [C.c_int64, C.c_int32]
+    lib.tq_images_interleave_u16_n.restype = C.c_int
+    lib.tq_images_interleave_u16_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     lib.tq_images_interleave.restype = C.c_int
     lib.tq_images_interleave.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     lib.tq_image_stats.restype = C.c_int

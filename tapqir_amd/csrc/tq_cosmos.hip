@@ -172,6 +172,7 @@ static tq_ksmogn_args cosmos_ksmogn_args(const tq_cosmos_args* a, float** pix_en
   const int64_t B = tq_batch_units(*a), U = tq_num_units(*a);
   tq_ksmogn_args k = {};
   k.images = a->images; k.images_il = a->images_il; k.xy = a->xy; k.ndx = a->ndx; k.fdx = a->fdx;
+  k.images_il16 = a->images_il16;
   k.nb_full = a->Nt;
   k.pixstats = a->pixstats;
   k.stats_stride = U;
@@ -230,25 +231,32 @@ static int launch_likelihood(const tq_cosmos_args* a, void* stream) {
   return tq_ksmogn_log_prob(&k, stream);
 }
 
-// The (K, P) instances of tq_pixel_unit_kernel: runs `...` with the compile-time constants KK = K (1 or 2) and PP = P (14 or
-// 20), which tq_fused_pixel_unit has checked (not TQ_SWITCH_K: the kernel exists for K <= 2 only)
-#define TQ_SWITCH_PU(K, P, ...)                                             \
-  switch (2 * ((K) != 1) + ((P) != 14)) {                                   \
-    case 0: { constexpr int KK = 1, PP = 14; __VA_ARGS__; } break;          \
-    case 1: { constexpr int KK = 1, PP = 20; __VA_ARGS__; } break;          \
-    case 2: { constexpr int KK = 2, PP = 14; __VA_ARGS__; } break;          \
-    default: { constexpr int KK = 2, PP = 20; __VA_ARGS__; } break;         \
+// The (K, P, tile format) instances of tq_pixel_unit_kernel: runs `...` with the compile-time constants KK = K (1 or 2) and
+// PP = P (14 or 20), which tq_fused_pixel_unit has checked (not TQ_SWITCH_K: the kernel exists for K <= 2 only), and
+// FF = TQ_TILE_U16 where U16 says that the step brings the 16-bit copy of the tiles (images_il16), else TQ_TILE_F32
+#define TQ_SWITCH_PU(K, P, U16, ...)                                                            \
+  switch (4 * ((U16) != 0) + 2 * ((K) != 1) + ((P) != 14)) {                                    \
+    case 0: { constexpr int KK = 1, PP = 14, FF = TQ_TILE_F32; __VA_ARGS__; } break;            \
+    case 1: { constexpr int KK = 1, PP = 20, FF = TQ_TILE_F32; __VA_ARGS__; } break;            \
+    case 2: { constexpr int KK = 2, PP = 14, FF = TQ_TILE_F32; __VA_ARGS__; } break;            \
+    case 3: { constexpr int KK = 2, PP = 20, FF = TQ_TILE_F32; __VA_ARGS__; } break;            \
+    case 4: { constexpr int KK = 1, PP = 14, FF = TQ_TILE_U16; __VA_ARGS__; } break;            \
+    case 5: { constexpr int KK = 1, PP = 20, FF = TQ_TILE_U16; __VA_ARGS__; } break;            \
+    case 6: { constexpr int KK = 2, PP = 14, FF = TQ_TILE_U16; __VA_ARGS__; } break;            \
+    default: { constexpr int KK = 2, PP = 20, FF = TQ_TILE_U16; __VA_ARGS__; } break;           \
   }
 
-// Split tiles of the fused launch (tq_step_rows.h).  Waves of the (K, P) instance that the device holds at a time: asked once.
-extern "C" int32_t tq_cosmos_pu_slots(int32_t K, int32_t P) {
-  static int cache[2][2] = {{-1, -1}, {-1, -1}};
+// Split tiles of the fused launch (tq_step_rows.h).  Waves of the (K, P, tile format) instance that the device holds at a time:
+// asked once.  The exported form answers for the fp32 tiles; the 16-bit instances are built to the same register counts
+// (DESIGN.md section 4), and a launch that should find more slots than its caller sized pu_scratch for splits nothing.
+static int32_t tq_pu_slots(int32_t K, int32_t P, bool u16) {
+  static int cache[2][2][2] = {{{-1, -1}, {-1, -1}}, {{-1, -1}, {-1, -1}}};
   if (K < 1 || K > 2 || (P != 14 && P != 20)) return 0;
-  int& slots = cache[K - 1][P == 20];
+  int& slots = cache[u16][K - 1][P == 20];
   if (slots < 0) {
     int per_cu = 0, dev = 0, cus = 0;
     hipError_t e;
-    TQ_SWITCH_PU(K, P, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tq_pixel_unit_kernel<KK, PP>, 64, 0));
+    TQ_SWITCH_PU(K, P, u16, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tq_pixel_unit_kernel<KK, PP, FF>, 64, 0));
     if (e == hipSuccess) e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) {
@@ -259,6 +267,7 @@ extern "C" int32_t tq_cosmos_pu_slots(int32_t K, int32_t P) {
   }
   return slots;
 }
+extern "C" int32_t tq_cosmos_pu_slots(int32_t K, int32_t P) { return tq_pu_slots(K, P, false); }
 // pu_split = -1: the last round of tiles, where it is at most an eighth full.  Below one full round nothing is split.
 // Measured on 2048 slots: a split tile costs ~0.035 us of launch time and the round it removes ~11 us, so the
 // split pays below ~320 tiles (r = 106: -7.6 us; r = 506, a quarter of the slots: +6 us); an eighth keeps a margin.
@@ -274,6 +283,7 @@ static int launch_pixel_unit(const tq_cosmos_args* a, void* stream) {
   const int64_t B = tq_batch_units(*a);
   const tq_ksmogn_args k = cosmos_ksmogn_args(a);
   const int64_t ntiles = (B + 63) / 64;
+  const bool u16 = a->images_il16 != nullptr;  // the packed loop streams the 16-bit copy of the tiles
   int nsplit = 0;
   if (a->pu_split > 0) {
     nsplit = (int)(a->pu_split < ntiles ? a->pu_split : ntiles);
@@ -282,12 +292,12 @@ static int launch_pixel_unit(const tq_cosmos_args* a, void* stream) {
       return TQ_ERR_ARG;
     }
   } else if (a->pu_split < 0 && a->pu_scratch) {
-    nsplit = tq_cosmos_pu_split_auto(ntiles, tq_cosmos_pu_slots(a->K, a->P));
+    nsplit = tq_cosmos_pu_split_auto(ntiles, tq_pu_slots(a->K, a->P, u16));
     if (nsplit > a->pu_scratch_tiles) nsplit = 0;
   }
   const dim3 grid((unsigned)(ntiles + (TQ_PU_PARTS - 1) * (int64_t)nsplit)), block(64);
   hipStream_t st = (hipStream_t)stream;
-  TQ_SWITCH_PU(a->K, a->P, hipLaunchKernelGGL((tq_pixel_unit_kernel<KK, PP>), grid, block, 0, st, k, *a, B, nsplit));
+  TQ_SWITCH_PU(a->K, a->P, u16, hipLaunchKernelGGL((tq_pixel_unit_kernel<KK, PP, FF>), grid, block, 0, st, k, *a, B, nsplit));
   return tq_launch_status("tq_pixel_unit_kernel");
 }
 

@@ -40,6 +40,9 @@ __device__ __forceinline__ T tq_group_sum(T v) {
 // two FP32 values per lane that the compiler maps onto packed instructions (two operations per lane and issue slot)
 typedef float tq_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ tq_f2 tq2(float a) { return (tq_f2){a, a}; }
+// a * b + c with ONE rounding, whatever the compiler would have chosen for the expression (a product that feeds two sums is
+// fused into one, both or neither depending on the code around it)
+__device__ __forceinline__ tq_f2 tq2_fma(tq_f2 a, tq_f2 b, tq_f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ tq_f2 tq2_rcp(tq_f2 a) { return (tq_f2){__builtin_amdgcn_rcpf(a.x), __builtin_amdgcn_rcpf(a.y)}; }
 __device__ __forceinline__ tq_f2 tq2_log2(tq_f2 a) { return (tq_f2){__builtin_amdgcn_logf(a.x), __builtin_amdgcn_logf(a.y)}; }
 __device__ __forceinline__ tq_f2 tq2_exp2(tq_f2 a) { return (tq_f2){__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)}; }

@@ -381,6 +381,36 @@ __global__ __launch_bounds__(256) void tq_interleave_kernel(const float* __restr
   reinterpret_cast<float4*>(out)[t] = v;
 }
 
+// The same layout with 2 bytes per pixel (one uint2 of the output per thread); *inexact = 1 where a pixel is not an integer
+// in [0, 65535].  Every thread that finds one stores the same value: a plain vector store, no atomic.
+__global__ __launch_bounds__(256) void tq_interleave_u16_kernel(const float* __restrict__ images, uint2* __restrict__ out,
+                                                                int32_t* inexact, const int64_t U, const int npix,
+                                                                const int64_t total4) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total4) return;
+  const int npix4 = (npix + 3) >> 2;
+  const int lane = (int)(t & 63);
+  const int64_t rowq = t >> 6;
+  const int q = (int)(rowq % npix4);
+  const int64_t u = (rowq / npix4) * 64 + lane;
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  bool bad = false;
+  if (u < U) {
+    const float* tile = images + u * npix;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int p = 4 * q + e;
+      if (p < npix) {
+        const float v = tile[p];
+        w[e] = (uint32_t)fminf(fmaxf(v, 0.0f), 65535.0f);  // (a NaN gives 0)
+        bad |= !(v == (float)w[e]);
+      }
+    }
+  }
+  out[t] = make_uint2(w[0] | (w[1] << 16), w[2] | (w[3] << 16));
+  if (bad) *inexact = 1;
+}
+
 // Per-unit data statistics of the single-offset path: [0][u] = sum (D - delta), [1][u] = sum ln(D - delta),
 // [2][u] = number of pixels with D <= delta.  One wave per unit, sums in double.
 __global__ __launch_bounds__(256) void tq_image_stats_kernel(const float* __restrict__ images, const float* offset,
@@ -416,7 +446,7 @@ __global__ __launch_bounds__(256) void tq_image_stats_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
 extern "C" const char* tq_last_error(void) { return g_err; }
-extern "C" int tq_version(void) { return 103; }
+extern "C" int tq_version(void) { return 104; }
 void tq_set_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
 
 template <int K, bool ONE>
@@ -524,6 +554,20 @@ extern "C" int tq_images_interleave_n(const float* images, float* images_il, int
   hipLaunchKernelGGL(tq_interleave_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      images, images_il, U, npix, total4);
   return tq_launch_status("tq_interleave_kernel");
+}
+
+extern "C" int64_t tq_interleaved_u16_n(int64_t U, int32_t npix) { return tq_interleaved_floats_n(U, npix); }
+
+extern "C" int tq_images_interleave_u16_n(const float* images, uint16_t* out, int64_t U, int32_t npix, int32_t* inexact,
+                                          void* stream) {
+  if (!images || !out || !inexact || U < 1 || npix < 4) {
+    tq_set_error("tq_images_interleave_u16_n: bad argument");
+    return TQ_ERR_ARG;
+  }
+  const int64_t total4 = tq_interleaved_u16_n(U, npix) / 4;
+  hipLaunchKernelGGL(tq_interleave_u16_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     images, reinterpret_cast<uint2*>(out), inexact, U, npix, total4);
+  return tq_launch_status("tq_interleave_u16_kernel");
 }
 
 extern "C" int tq_images_interleave(const float* images, float* images_il, int64_t U, int32_t P, void* stream) {

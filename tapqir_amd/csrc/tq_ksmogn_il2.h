@@ -145,8 +145,10 @@ __device__ __forceinline__ void tq_pixel_pair(TqPixAcc2<K, P, COLACC>& A, tq_f2 
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       if (COLACC) {
-        A.col[k][ip] += q[k] * spot[k];
-        A.S0r[k] = first_in_row ? q[k] * spot[k] : A.S0r[k] + q[k] * spot[k];
+        // explicit multiply-adds: the product feeds two sums, and into which of them it is fused must not depend on the
+        // instance (tile format, whole or split tile) -- the two tile formats give the same bits
+        A.col[k][ip] = tq2_fma(q[k], spot[k], A.col[k][ip]);
+        A.S0r[k] = first_in_row ? q[k] * spot[k] : tq2_fma(q[k], spot[k], A.S0r[k]);
       } else {
         const tq_f2 aq = q[k] * spot[k];
         A.S0r[k] = first_in_row ? aq : A.S0r[k] + aq;
@@ -200,8 +202,14 @@ struct TqWholeTile {
 // returns false the wave is done and so is this routine (it returns false); where it returns true, A and sum_gy hold the
 // sums of the whole tile and the wave finishes the tile.  The scalar loop of a tile with a small alpha is not shared out:
 // range.whole_tile() says which ONE of the tile's waves runs all of it (the test is the same in all of them).
+//
+// FMT, the format in which the packed loop streams the tiles: TQ_TILE_F32 reads images_il (a float4 per group of four pixels),
+// TQ_TILE_U16 reads images_il16 (tq_images_interleave_u16_n: the same layout with 2 bytes per pixel, a uint2 per group), for
+// images that are integers in [0, 65535].  A 16-bit integer converts to fp32 exactly and everything behind `v` is the same
+// code, so the two formats give the same bits.  The scalar loop of a tile with a small alpha reads images_il in both.
 #define TQ_PIXOUT(K) ((1 << (K)) + 2 + 4 * (K))
-template <int K, int P, bool BWD, class Range = TqWholeTile>
+enum TqTileFmt : int { TQ_TILE_F32 = 0, TQ_TILE_U16 = 1 };
+template <int K, int P, bool BWD, class Range = TqWholeTile, int FMT = TQ_TILE_F32>
 __device__ __forceinline__ bool tq_il2_lane(const tq_ksmogn_args& a, const int64_t B, float* OUT = nullptr,
                                             const int64_t tile = blockIdx.x, const Range range = Range()) {
   static_assert(P % 2 == 0 && (P * P) % 4 == 0, "packed kernel needs an even tile side");
@@ -213,11 +221,16 @@ __device__ __forceinline__ bool tq_il2_lane(const tq_ksmogn_args& a, const int64
   constexpr bool COLACC = BWD && (K * P <= 28);
   constexpr bool PINNED = BWD && K == 2;  // prefetches fenced in place + first body peeled (see run_body)
   constexpr bool SPLIT = Range::SPLIT;
+  constexpr bool U16 = FMT == TQ_TILE_U16;
+  using Group = std::conditional_t<U16, uint2, float4>;  // four pixels of the packed loop
   const int64_t i_raw = tile * 64 + threadIdx.x;  // one wave per workgroup: no barriers, finest dispatch granularity
   const bool live = i_raw < B;
   const int64_t i = live ? i_raw : (B - 1);
   // idle lanes of the last workgroup read the LAST tile too: the interleaved buffer ends with its 64-tile block
   const float4* src = reinterpret_cast<const float4*>(a.images_il) + ((i >> 6) * npix4) * 64 + (i & 63);
+  const Group* psrc;  // the same group of the format the packed loop streams
+  if constexpr (U16) psrc = reinterpret_cast<const uint2*>(a.images_il16) + ((i >> 6) * npix4) * 64 + (i & 63);
+  else psrc = src;
 
   const float g = a.gain[0];
   const float rg = TQ_FRCP(g);
@@ -288,14 +301,14 @@ __device__ __forceinline__ bool tq_il2_lane(const tq_ksmogn_args& a, const int64
       body_begin = range.body_begin;
       body_end = range.body_end;
     }
-    float4 ring[G];
+    Group ring[G];
 #pragma unroll
-    for (int j = 0; j < G; ++j) ring[j] = src[(SPLIT ? body_begin * G : 0) * 64 + j * 64];
+    for (int j = 0; j < G; ++j) ring[j] = psrc[(SPLIT ? body_begin * G : 0) * 64 + j * 64];
     // one loop body = R rows; MORE: the groups of the next body are fetched as those of this one retire
     // (the last body is peeled so that the prefetches are unconditional and stay where they are written)
     auto run_body = [&](const int body, auto more_tag) {
       constexpr bool MORE = decltype(more_tag)::value;
-      const float4* nxt = src + (int64_t)(body + 1) * G * 64;
+      const Group* nxt = psrc + (int64_t)(body + 1) * G * 64;
 #pragma unroll
       for (int rr = 0; rr < R; ++rr) {
         const float fj = (float)(body * R + rr);
@@ -310,7 +323,7 @@ __device__ __forceinline__ bool tq_il2_lane(const tq_ksmogn_args& a, const int64
         for (int ip = 0; ip < P / 2; ++ip) {
           const int pair = rr * (P / 2) + ip;  // pair index within the body (compile-time after unrolling)
           const int gi = pair >> 1;            // float4 group within the body
-          const float4 d4 = ring[gi];
+          const Group d4 = ring[gi];
           // v = D - delta is taken BEFORE the group is re-loaded, and (backward kernel) the load is fenced in place:
           // the old registers are dead at the load, which writes the next body's group straight into them.  A refill
           // hoisted above the last use of its registers costs a copy at the end of the body, and that copy waits for
@@ -319,7 +332,17 @@ __device__ __forceinline__ bool tq_il2_lane(const tq_ksmogn_args& a, const int64
           // compiler derives are exact: vmcnt(6) before each group) this is worth 1-8 % of the K = 2 backward launch,
           // depending on the box; the forward kernels do not profit and the K = 1 backward kernel would lose its
           // fourth wave per SIMD (130 registers), so they keep the plain form (PINNED).
-          const tq_f2 v = ((pair & 1) ? (tq_f2){d4.z, d4.w} : (tq_f2){d4.x, d4.y}) - off0;
+          tq_f2 D;
+          if constexpr (U16) {
+            const uint32_t w = (pair & 1) ? d4.y : d4.x;  // two pixels, the left one in the low half
+            D = (tq_f2){(float)(w & 0xffffu), (float)(w >> 16)};
+            // opaque from here on, as a loaded float is: what the compiler knows about a converted 16-bit integer (its range,
+            // that it is no NaN) must not shape the arithmetic behind it differently from the fp32 instance's
+            asm volatile("" : "+v"(D));
+          } else {
+            D = (pair & 1) ? (tq_f2){d4.z, d4.w} : (tq_f2){d4.x, d4.y};
+          }
+          const tq_f2 v = D - off0;
           if (MORE && (pair & 1)) {
             if (PINNED) __builtin_amdgcn_sched_barrier(0);
             ring[gi] = nxt[gi * 64];
@@ -335,8 +358,8 @@ __device__ __forceinline__ bool tq_il2_lane(const tq_ksmogn_args& a, const int64
 #pragma unroll
           for (int k = 0; k < K; ++k) {
             if (!COLACC) A.S0[k] += A.S0r[k];
-            A.Sy[k] += A.S0r[k] * dyk[k];
-            A.Syy[k] += A.S0r[k] * (dyk[k] * dyk[k]);
+            A.Sy[k] = tq2_fma(A.S0r[k], tq2(dyk[k]), A.Sy[k]);  // (explicit: see tq_pixel_pair)
+            A.Syy[k] = tq2_fma(A.S0r[k], tq2(dyk[k] * dyk[k]), A.Syy[k]);
           }
         }
       }

@@ -185,7 +185,9 @@ __device__ __forceinline__ void tq_pu_part_bodies(int q, int* begin, int* end) {
   *end = (q + 1) * PER < NB ? (q + 1) * PER : NB;
 }
 
-template <int K, int P>
+// FMT (TqTileFmt): the format in which the packed pixel loop streams the tiles -- fp32 from images_il, or 16-bit integers
+// from images_il16 where the caller has that copy (tq_il2_lane: the same bits either way, half the tile bytes).
+template <int K, int P, int FMT = TQ_TILE_F32>
 __global__ __launch_bounds__(64, 2) void tq_pixel_unit_kernel(const tq_ksmogn_args k, const tq_cosmos_args a, const int64_t B,
                                                               const int nsplit) {
   float pixv[TQ_PIXOUT(K)];
@@ -202,9 +204,9 @@ __global__ __launch_bounds__(64, 2) void tq_pixel_unit_kernel(const tq_ksmogn_ar
     sp.slabs = (uint64_t*)((int32_t*)a.pu_scratch + tq_pu_counter_words(a.pu_scratch_tiles)) +
                (int64_t)s * (TQ_PU_PARTS * TQ_PU_PAIRS * 64);
     tile = ((B + 63) >> 6) - nsplit + s;
-    if (!tq_il2_lane<K, P, true, TqSplitPart>(k, B, pixv, tile, sp)) return;
+    if (!tq_il2_lane<K, P, true, TqSplitPart, FMT>(k, B, pixv, tile, sp)) return;
   } else {
-    tq_il2_lane<K, P, true>(k, B, pixv, tile);
+    tq_il2_lane<K, P, true, TqWholeTile, FMT>(k, B, pixv, tile);
   }
   const int64_t i = tile * 64 + threadIdx.x;
   const uint32_t FC = (uint32_t)(a.F * a.C);

@@ -160,6 +160,13 @@ class CosmosEngine:
         ps = os.environ.get("TAPQIR_AMD_PU_SPLIT", "auto")
         self.pu_split = -1 if ps == "auto" else int(ps)
         self._pu_scratch, self._pu_scratch_tiles = None, 0
+        # the fused launch streams the tiles as 16-bit integers where the images are integers in [0, 65535] (tq_cosmos_args.
+        # images_il16, built when a step first takes the fused route: _tile16); TAPQIR_AMD_TILE16=auto|0 fixes it for A/B timing
+        t16 = os.environ.get("TAPQIR_AMD_TILE16", "auto")
+        if t16 not in ("auto", "0"):
+            raise ValueError(f"TAPQIR_AMD_TILE16={t16!r}: expected auto or 0")
+        self.tile16 = t16 != "0"
+        self.images_il16, self._tile16_tried = None, False
         self._sync = torch.zeros(_lib.SYNC_WORDS, dtype=torch.int32, device=dev)  # tickets, flags; diagnostic stamps of a TQ_MB_STAMPS build
         self._sync_value = 0
 
@@ -185,6 +192,25 @@ class CosmosEngine:
         _lib.check(self.lib.tq_images_interleave_n(_lib.ptr(self.images), _lib.ptr(out), tiles, npix, self._stream()),
                    "tq_images_interleave_n")
         return out
+
+    def _tile16(self):
+        """The 16-bit interleaved copy of the tiles for the fused launch (tq_cosmos_args.images_il16), built by the library
+        when a step first takes that route and kept only if every pixel is an integer in [0, 65535] (one read-back of the
+        library's flag); None otherwise, with TAPQIR_AMD_TILE16=0, and for engines without the fp32 interleaved copy, which
+        stays resident beside it (2 more bytes per pixel of device memory)."""
+        if self._tile16_tried or not self.tile16:
+            return self.images_il16
+        self._tile16_tried = True
+        if self.images_il is None or self.crosstalk:
+            return None
+        tiles, npix = self.Nt * self.F * self.C, self.P * self.P
+        out = torch.empty(int(self.lib.tq_interleaved_u16_n(tiles, npix)), dtype=torch.uint16, device=self.device)
+        inexact = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.tq_images_interleave_u16_n(_lib.ptr(self.images), _lib.ptr(out), tiles, npix, _lib.ptr(inexact),
+                                                       self._stream()), "tq_images_interleave_u16_n")
+        if int(inexact.item()) == 0:
+            self.images_il16 = out
+        return self.images_il16
 
     def _image_stats(self, U):
         _lib.check(self.lib.tq_image_stats(_lib.ptr(self.images), _lib.ptr(self.offset_samples), _lib.ptr(self.pixstats),
@@ -534,6 +560,7 @@ class CosmosEngine:
         a = self._core_args()
         a.images, a.xy, a.is_ontarget, a.aoi_mask = p(self.images), p(self.xy), p(self.is_ontarget), p(self._mask_arg)
         a.images_il = p(self.images_il)
+        a.images_il16 = p(self.images_il16)  # (None until a step has taken the fused route: _fuse)
         a.pixstats = p(self.pixstats)
         a.ndx, a.fdx = p(ndx), p(fdx)
         a.offset_samples, a.offset_logits = p(self.offset_samples), p(self.offset_logits)
@@ -634,6 +661,11 @@ class CosmosEngine:
         tq_fused_pixel_unit of tq_cosmos.hip asks the same of a step's arguments.)"""
         return (self.pipelined_tail and not self.crosstalk and self.K <= 2 and self.O == 1 and self.P in (14, 20)
                 and self.Nt * self.F * self.C >= self.il_min_units and self.F * self.C >= 256)
+
+    def _fuse(self, a):
+        """Step `a` takes the fused launch: with the 16-bit tiles where the engine has them (built at the first such step)."""
+        a.pixel_mode = _lib.PIXEL_FUSED_UNIT
+        a.images_il16 = _lib.ptr(self._tile16())
 
     def _route(self, nb, fb, allreduce):
         """The launch sequence of a step of nb AOIs x fb frames (step() and step_subsampled() both ask here):
@@ -791,7 +823,7 @@ class CosmosEngine:
             self._adam_catchup(a, 0)
         self._finish_pending()
         if self.fuse_unit and not a.zero_grad and self._fusable():
-            a.pixel_mode = _lib.PIXEL_FUSED_UNIT
+            self._fuse(a)
         prev = self._tail_args
         _lib.check(self.lib.tq_cosmos_step_overlapped(C.byref(a), None if prev is None else C.byref(prev), self._stream()),
                    "tq_cosmos_step_overlapped")
@@ -839,7 +871,7 @@ class CosmosEngine:
             else:
                 self.call("cosmos_sample_globals", a)
         if a.fuse_adam and not a.zero_grad and self.fuse_unit and self._fusable():
-            a.pixel_mode = _lib.PIXEL_FUSED_UNIT
+            self._fuse(a)
         self.call("cosmos_elbo_grads", a)
         handle = allreduce(self.gsum) if allreduce is not None else None
         if handle is not None and hasattr(handle, "wait") and a.fuse_adam:
