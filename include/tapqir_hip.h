@@ -1045,6 +1045,74 @@ typedef struct {
 int tq_population_dwell(const tq_population_dwell_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Dwell times with the open last run (`tapqir_amd dwelltime --censored`).  A run of a kind (bound,
+ * z = 1; unbound, z = 0) is used when it opens inside the record (start_frame > 0).  If it also closes inside it
+ * (low_or_high 0 / 1, what the COUNT launches put into their histograms) it is a complete dwell of d frames with the term
+ * log sum_j A_j k_j exp(-k_j d).  If it is still open at frame F - 1 (low_or_high == z + 2) it is right-censored after d
+ * seen frames -- d - 1 stays and nothing else -- with the term log sum_j A_j exp(-k_j (d - 1)); d = 1 carries no
+ * information.  First runs (start_frame == 0, a run that spans the record included) are used by neither.
+ *
+ * tq_dwell_censored_hist: the histograms of the open last runs from the interval table that any of the four EMIT launches
+ * wrote.  One lane per table row; every row with low_or_high 2 / 3 and start_frame > 0 adds 1 to
+ * cens_unbound[s, g, dwell_time] / cens_bound[s, g, dwell_time], g = pop[s, n] (the pop of tq_population_dwell's COUNT
+ * launch) or 0 without pop.  The caller zeroes both histograms.  Integer atomics: the result is deterministic.  A row whose
+ * entries are out of range adds nothing.  total == 0 is TQ_OK without a launch.  TQ_ERR_ARG, before anything touches the
+ * device, for a NULL histogram (or table with total > 0), S, N or F < 1, total < 0, G outside 1 .. 4, or G > 1 without pop.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const int32_t* intervals;    /* (TQ_DWELL_COLS, total): the table of an EMIT launch, on the device */
+  const uint8_t* pop;          /* (S, N) drawn population of every row, or NULL (G = 1) */
+  int32_t* cens_bound;         /* (S, G, F) in/out: open last bound runs by drawn population and dwell time */
+  int32_t* cens_unbound;       /* (S, G, F) in/out: open last unbound runs by drawn population and dwell time */
+  int64_t total;               /* number of intervals (the column stride) */
+  int32_t S, N, F;
+  int32_t G;                   /* populations, 1 .. 4 */
+} tq_dwell_censored_hist_args;
+
+int tq_dwell_censored_hist(const tq_dwell_censored_hist_args* a, void* stream);
+
+/* tq_dwell_censored_fit: tq_dwell_fit with a second CSR list per row, (cvalues[i], cweights[i]), crow_ptr[s] <= i <
+ * crow_ptr[s + 1], of right-censored times t >= 0 (t = d - 1) with their multiplicities.  The loss of row s is
+ *   -sum_i w_i log sum_j A_j k_j exp(-k_j t_i) - sum_i wc_i log sum_j A_j exp(-k_j tc_i),
+ * and everything else -- parameters, state layout (S, 6 K), step0 / n_steps chunking (bitwise equal to one launch), the
+ * loss of the last step, Adam -- is tq_dwell_fit's.  At K = 1 the maximiser is k = n / (sum w t + sum wc tc).  One wave per
+ * row: a row is staged in LDS when stage_lds != 0 and its complete and censored pairs together are at most
+ * TQ_DWELL_LDS_PAIRS, otherwise both lists are read from L2 every step.  With every censored row empty, state and loss
+ * are tq_dwell_fit's bit for bit.  TQ_ERR_ARG for what tq_dwell_fit refuses, and for a NULL censored list (an empty one
+ * still needs valid pointers). */
+typedef struct {
+  const float* values;         /* (nnz) dwell times > 0 of the complete runs */
+  const float* weights;        /* (nnz) multiplicities */
+  const int64_t* row_ptr;      /* (S + 1) */
+  const float* cvalues;        /* (cnnz) censored times >= 0: seen frames - 1 */
+  const float* cweights;       /* (cnnz) multiplicities */
+  const int64_t* crow_ptr;     /* (S + 1) */
+  float* state;                /* (S, 6 K) in/out: log k[K], a[K], exp_avg[2K], exp_avg_sq[2K] */
+  float* loss;                 /* (S) out or NULL: loss at the last step of the launch, before its update */
+  int32_t S, K;                /* 1 <= K <= TQ_DWELL_KMAX */
+  int32_t step0;               /* Adam steps completed before this launch */
+  int32_t n_steps;             /* Adam steps of this launch (>= 1) */
+  int32_t stage_lds;           /* 1: stage rows in LDS when they fit; 0: always read them from L2 */
+  double lr, beta1, beta2, eps;
+} tq_dwell_censored_fit_args;
+
+int tq_dwell_censored_fit(const tq_dwell_censored_fit_args* a, void* stream);
+
+/* tq_dwell_survival: the product-limit (Kaplan-Meier) estimate of every row.  hist[r, d] complete runs and cens[r, d]
+ * open last runs of d frames; surv[r, 0] = 1 and surv[r, t] = prod_{u = 1 .. t} (Y_u - h_u) / Y_u, a factor of 1 where
+ * Y_u = 0, with Y_u = sum_{d >= u} h_d + sum_{d >= u + 1} c_d: an open run of d frames is at risk up to d - 1, the
+ * convention of the fit.  Each factor is one float64 division of two integers, so a curve that reaches 0 (Y_u = h_u) or
+ * stays at 1 does so exactly.  One wave per row.  TQ_ERR_ARG for a NULL pointer, R or F < 1 or F > TQ_SMOOTH_MAX_F. */
+typedef struct {
+  const int32_t* hist;         /* (R, F) complete runs by dwell time */
+  const int32_t* cens;         /* (R, F) open last runs by seen frames */
+  double* surv;                /* (R, F) out */
+  int32_t R, F;
+} tq_dwell_survival_args;
+
+int tq_dwell_survival(const tq_dwell_survival_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Two colour channels as one chain (`tapqir_amd smooth --joint A,B`).  Channels a and b of one
  * cosmos fit, hidden state s = z_a + 2 z_b: 0 neither bound, 1 only a, 2 only b, 3 both.
  *   theta = (A row-major (4, 4), rho (4)): 20 doubles in device memory, read floored at TQ_SMOOTH_RMIN and renormalised as

@@ -718,6 +718,86 @@ def _dwell_population_fits(cd, stem, c, sample, G, K, num_iter, kinds, z_map, po
             logger.info(f"Saved {title.lower()} parameters of the populations in {stem}-{rate}-channel{c}.csv file")
 
 
+def _dwell_censored_fits(cd, stem, c, sample, cens, G, K, num_iter, kinds, progress_bar, logger):
+    """The fits of `dwelltime --censored` for one channel.  For every kind, and every population g
+    of ``G`` (None: no populations), one K-exponential fit per posterior sample of the complete interior runs
+    ``sample["hist_<kind>"]`` with the open last runs ``cens["cens_<kind>"]`` as right-censored observations, written as
+    ``<stem>-censored-<rate>-channel<c>.csv`` with the rows of the fit without the switch; and per kind (and population,
+    ``<stem>-g<g>-censored-...``) the Kaplan-Meier survival of every sample with the fitted survival at the mean
+    parameters, as ``...-censored-<kind>-survival-channel<c>.csv`` and ``.png``.  A sample (or a population of one) without
+    a complete interval of the kind is left out and logged; a kind no sample has is skipped with a warning."""
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.utils.censored_analysis import (dwell_censored_fit, dwell_csr_from_censored_hist, dwell_survival,
+                                                    mixture_survival)
+    from tapqir_amd.utils.mle_analysis import dwell_csr_from_hist, hpdi_columns
+
+    for kind, rate, title, _ in kinds:
+        logger.info(f"{title} calculation with the open last runs ...")
+        tables = []
+        for g in (range(G) if G else (None,)):
+            hist, open_runs = sample[f"hist_{kind}"], cens[f"cens_{kind}"]
+            if g is not None:
+                hist, open_runs = hist[:, g].contiguous(), open_runs[:, g].contiguous()
+            who, pre, gstem = ("", "", stem) if g is None else (f" in population {g}", f"g{g}_", f"{stem}-g{g}")
+            keep = hist.sum(1) > 0
+            n_out = int((~keep).sum())
+            if n_out == hist.shape[0]:
+                logger.warning(f"dwelltime: no posterior sample has an interior {kind} interval{who}: {rate} is not fitted")
+                continue
+            if n_out:
+                logger.info(f"{n_out} of {hist.shape[0]} posterior samples have no interior {kind} interval{who} and are "
+                            f"left out of the {rate} fit")
+            hist, open_runs = hist[keep], open_runs[keep]
+            logger.info(f"{int(hist.sum())} complete and {int(open_runs[:, 2:].sum())} open {kind} intervals{who} enter "
+                        f"the {rate} fit")
+            fit = dwell_censored_fit(dwell_csr_from_hist(hist), dwell_csr_from_censored_hist(open_runs), K, lr=5e-3,
+                                     n_steps=num_iter, progress_bar=progress_bar)
+            results = _summary_table(pair for i in range(K) for pair in (
+                (f"{pre}A{i}", fit["A"][:, i].cpu()), (f"{pre}{rate}{i}", fit["k"][:, i].cpu())))
+            tables.append(results)
+            A_mean = [results.loc[f"{pre}A{i}", "Mean"] for i in range(K)]
+            k_mean = [results.loc[f"{pre}{rate}{i}", "Mean"] for i in range(K)]
+
+            t_max = int(torch.nonzero(hist.sum(0) + open_runs.sum(0)).max().item())  # the largest sampled dwell time
+            surv = dwell_survival(hist, open_runs)[:, : t_max + 1].cpu()
+            ll, ul = hpdi_columns(surv, 0.95)
+            mean = surv.mean(0)
+            fitted = mixture_survival(A_mean, k_mean, torch.arange(t_max + 1))
+            name = f"{gstem}-censored-{kind}-survival-channel{c}"
+            pd.DataFrame(data={"time": torch.arange(t_max + 1).numpy(), "best fit": fitted.numpy(),
+                               "survival mean": mean.numpy(), "survival 95% ll": ll.numpy(),
+                               "survival 95% ul": ul.numpy()}).to_csv(cd / f"{name}.csv")
+            logger.info(f"Saved {kind} survival curves in {name}.csv file")
+            _survival_plot(cd, name, c, kind, mean.numpy(), ll.numpy(), ul.numpy(), fitted.numpy(), logger)
+        if tables:
+            pd.concat(tables).to_csv(cd / f"{stem}-censored-{rate}-channel{c}.csv")
+            logger.info(f"Saved {title.lower()} parameters in {stem}-censored-{rate}-channel{c}.csv file")
+
+
+def _survival_plot(cd, name, c, kind, mean, ll, ul, fitted, logger):
+    """Kaplan-Meier band of the posterior samples with the fitted survival over it (`dwelltime --censored`)."""
+    mpl, plt = _pyplot()
+    if plt is None:
+        logger.warning("matplotlib is not available: the survival plots are not drawn")
+        return
+    import numpy as np
+
+    fig, ax = plt.subplots()
+    t = np.arange(mean.shape[0])
+    ax.fill_between(t, ll, ul, alpha=0.3, step="post")
+    ax.step(t, mean, where="post")
+    ax.plot(t, fitted, "k-")
+    ax.set_ylim(0, 1.02)
+    ax.set_xlabel("Time interval (frame)")
+    ax.set_ylabel("Fraction of dwells longer than t")
+    ax.set_title(f"{kind.capitalize()} dwell survival channel {c}")
+    plt.savefig(cd / f"{name}.png", dpi=600)
+    plt.close(fig)
+    logger.info(f"Saved {kind} survival plot in {name}.png file")
+
+
 @app.command()
 def dwelltime(
     model: avail_models = typer.Option("cosmos", help="Tapqir model"),
@@ -729,6 +809,7 @@ def dwelltime(
     unbound_states: int = typer.Option(1, "--unbound-states", min=1, help="Hidden states that look unbound (z = 0)"),
     bound_states: int = typer.Option(1, "--bound-states", min=1, help="Hidden states that look bound (z = 1); at most 4 in all"),
     populations: int = typer.Option(1, "--populations", help="Populations of AOIs, each with a chain of its own (1 to 4): a mixture of chains"),
+    censored: bool = typer.Option(False, "--censored", help="Count the run still open at the last frame as a right-censored dwell"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -759,11 +840,22 @@ def dwelltime(
     most probable population it is; the files are named ``<model>_dwelltime-smooth-u<U>b<B>g<G>-...`` (DESIGN.md section
     30).  The same caveat holds: the rasters of the same mixture at the same seed as those behind
     ``<model>_smooth-u<U>b<B>g<G>-channel<c>.csv``, not bit for bit.
+
+    With ``--censored``, in any of the forms above, a run that opened inside the record and is still open at the last frame
+    enters the fit as a right-censored dwell (d seen frames: d - 1 stays, the term ``log sum_j A_j exp(-k_j (d - 1))``)
+    instead of being dropped, which removes the bias towards short dwells of slow complexes in short records.  First runs
+    (``start_frame == 0``, a run that spans the record included) stay out: their start was not observed, and the first
+    unbound run is `ttfb`'s subject.  The interval files are written as without the switch; the rate tables go to
+    ``<stem>-censored-<rate>-channel<c>.csv`` and, per kind (and population), the Kaplan-Meier survival of the samples with
+    the fitted survival to ``...-censored-<kind>-survival-channel<c>.csv`` and ``.png``.  The MAP raster's histogram is not
+    drawn: it holds interior runs only, and a correct fit would look wrong next to it.  The files of the fit without the
+    switch are neither written nor touched.
     """
     import torch
 
     from tapqir_amd import _lib
     from tapqir_amd.exceptions import HipExtensionError
+    from tapqir_amd.utils.censored_analysis import dwell_censored_hist
     from tapqir_amd.utils.imscroll import bound_dwell_times, count_intervals, unbound_dwell_times
     from tapqir_amd.utils.mle_analysis import (dwell_csr_from_hist, dwell_fit, dwell_intervals, dwell_sample,
                                                hmm_dwell_intervals, hmm_dwell_sample, mixture_dwell_intervals,
@@ -799,18 +891,27 @@ def dwelltime(
             if smooth and G > 1:  # seed c: the default of `smooth`
                 chains = _mixture_filter(sm, c, p_bound, mask, U, B, logger)
                 sample = mixture_dwell_sample(*chains, U, B, num_samples, seed=c)
-                intervals = mixture_dwell_intervals(*chains, U, B, num_samples, seed=c, sample=sample)
+                intervals = mixture_dwell_intervals(*chains, U, B, num_samples, seed=c, sample=sample,
+                                                    device_table=censored)
             elif smooth and (U, B) != (1, 1):  # seed c: the default of `smooth`
                 filt, theta = _smoothed_filter(sm, c, p_bound, U, B)
                 sample = hmm_dwell_sample(filt, theta, U, B, num_samples, seed=c)
-                intervals = hmm_dwell_intervals(filt, theta, U, B, num_samples, seed=c, sample=sample)
+                intervals = hmm_dwell_intervals(filt, theta, U, B, num_samples, seed=c, sample=sample,
+                                                device_table=censored)
             elif smooth:  # seed c: the default of `smooth`, so these are the rasters of its rate table
                 filt, theta = _smoothed_filter(sm, c, p_bound)
                 sample = smooth_dwell_sample(filt, theta, num_samples, seed=c)
-                intervals = smooth_dwell_intervals(filt, theta, num_samples, seed=c, sample=sample)
+                intervals = smooth_dwell_intervals(filt, theta, num_samples, seed=c, sample=sample,
+                                                   device_table=censored)
             else:
                 sample = dwell_sample(p_bound, num_samples, seed=c)
-                intervals = dwell_intervals(p_bound, num_samples, seed=c, sample=sample)
+                intervals = dwell_intervals(p_bound, num_samples, seed=c, sample=sample, device_table=censored)
+            if censored:  # the open last runs, counted from the table while it is still on the device
+                intervals, table = intervals
+                mixture = smooth and G > 1
+                cens = dwell_censored_hist(table, num_samples, p_bound.shape[0], p_bound.shape[1],
+                                           pop=sample["pop"] if mixture else None, populations=G if mixture else None)
+                del table
             intervals.to_pickle(cd / f"{stem}-intervals-channel{c}.pkl")
             logger.info(f"Saved time intervals in {stem}-intervals-channel{c}.pkl file")
             if savemat is not None:
@@ -819,6 +920,10 @@ def dwelltime(
             else:
                 logger.info("scipy is not available: the .mat file of the intervals is not written")
 
+            if censored:
+                _dwell_censored_fits(cd, stem, c, sample, cens, G if smooth and G > 1 else None, K, num_iter, kinds,
+                                     progress_bar, logger)
+                continue
             if smooth and G > 1:
                 _dwell_population_fits(cd, stem, c, sample, G, K, num_iter, kinds, z_map[mask, :, c],
                                        sm["population_map"][:, c][mask], progress_bar, logger)

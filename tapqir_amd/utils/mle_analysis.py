@@ -41,7 +41,8 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
   apart by the population every row drew, and the first-binding frames split by population (``tq_population_dwell``;
   ``population_first_binding`` is host-side torch on S x N numbers and runs anywhere).
 
-Two colour channels smoothed together as one chain (``smooth --joint``) are in ``tapqir_amd/utils/joint_analysis.py``.
+Two colour channels smoothed together as one chain (``smooth --joint``) are in ``tapqir_amd/utils/joint_analysis.py``, the
+open last run as a right-censored dwell (``dwelltime --censored``) in ``tapqir_amd/utils/censored_analysis.py``.
 
 There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
 """
@@ -191,15 +192,13 @@ def dwell_sample(p_bound, num_samples, seed=0):
     return {"hist_bound": hb, "hist_unbound": hu, "counts": counts}
 
 
-def dwell_intervals(p_bound, num_samples, seed=0, sample=None):
+def dwell_intervals(p_bound, num_samples, seed=0, sample=None, device_table=False):
     """The interval table of ``num_samples`` posterior rasters (``count_intervals(z_sample)`` of the reference): launch A
     (or its result ``sample`` from ``dwell_sample`` with the same arguments), an exclusive scan of the row counts, and
     launch B, which draws the same bits again and writes every row's intervals at its offset.  Returns a DataFrame with
-    the columns of ``tapqir_amd.utils.imscroll.INTERVAL_COLUMNS``, int64, in (sample, AOI, frame) order."""
-    import pandas as pd
-
-    from tapqir_amd.utils.imscroll import INTERVAL_COLUMNS
-
+    the columns of ``tapqir_amd.utils.imscroll.INTERVAL_COLUMNS``, int64, in (sample, AOI, frame) order.  With
+    ``device_table`` it returns ``(DataFrame, table)``, table the (DWELL_COLS, total) int32 device tensor launch B wrote
+    (what ``censored_analysis.dwell_censored_hist`` reads)."""
     given = num_samples if sample is None else sample["counts"].shape[0]
     p, N, F, seed = _sampler_inputs("dwell_intervals", p_bound, given, seed)
     if sample is None:
@@ -213,8 +212,19 @@ def dwell_intervals(p_bound, num_samples, seed=0, sample=None):
     a = _lib.DwellSampleArgs(p=_lib.ptr(p), offsets=_lib.ptr(offsets), intervals=_lib.ptr(cols), total=total, N=N, F=F,
                              S=S, mode=_lib.DWELL_EMIT, seed=seed)
     _lib.check(_lib.load().tq_dwell_sample(C.byref(a), _stream(p.device)), "tq_dwell_sample")
+    return _interval_frame(cols, total, device_table)
+
+
+def _interval_frame(cols, total, device_table=False):
+    """The DataFrame of the first ``total`` columns of the device table ``cols`` (DWELL_COLS, max(total, 1)) int32; with
+    ``device_table`` also that part of the table itself, still on the device."""
+    import pandas as pd
+
+    from tapqir_amd.utils.imscroll import INTERVAL_COLUMNS
+
     host = cols[:, :total].to(torch.int64).cpu().numpy()
-    return pd.DataFrame({name: host[i] for i, name in enumerate(INTERVAL_COLUMNS)})
+    frame = pd.DataFrame({name: host[i] for i, name in enumerate(INTERVAL_COLUMNS)})
+    return (frame, cols[:, :total]) if device_table else frame
 
 
 def dwell_csr_from_hist(hist):
@@ -523,13 +533,9 @@ def _walk_count(launch, S, N, F, dev, populations=None):
     return out
 
 
-def _walk_emit(who, launch, sample, S, N, dev):
+def _walk_emit(who, launch, sample, S, N, dev, device_table=False):
     """The exclusive scan of the row counts of launch A and launch B of the same sampler; the DataFrame of
-    ``dwell_intervals``."""
-    import pandas as pd
-
-    from tapqir_amd.utils.imscroll import INTERVAL_COLUMNS
-
+    ``dwell_intervals`` (with ``device_table``, the pair it returns then)."""
     counts = sample["counts"].contiguous()
     if counts.shape != (S, N) or counts.dtype != torch.int32 or counts.device != dev:
         raise ValueError(f"{who}: sample['counts'] must be int32 ({S}, {N}) on the device of filt")
@@ -538,8 +544,7 @@ def _walk_emit(who, launch, sample, S, N, dev):
     total = int(csum[-1].item())
     cols = torch.empty(_lib.DWELL_COLS, max(total, 1), dtype=torch.int32, device=dev)
     launch(counts=_lib.ptr(counts), offsets=_lib.ptr(offsets), intervals=_lib.ptr(cols), total=total, mode=_lib.DWELL_EMIT)
-    host = cols[:, :total].to(torch.int64).cpu().numpy()
-    return pd.DataFrame({name: host[i] for i, name in enumerate(INTERVAL_COLUMNS)})
+    return _interval_frame(cols, total, device_table)
 
 
 def _smooth_dwell_launch(filt, theta, S, N, F, seed):
@@ -562,18 +567,18 @@ def smooth_dwell_sample(filt, theta, num_samples, seed=0):
     return _walk_count(_smooth_dwell_launch(filt, theta, S, N, F, seed), S, N, F, filt.device)
 
 
-def smooth_dwell_intervals(filt, theta, num_samples, seed=0, sample=None):
+def smooth_dwell_intervals(filt, theta, num_samples, seed=0, sample=None, device_table=False):
     """The interval table of the rasters of ``smooth_sample(filt, theta, num_samples, seed)``: launch A (or its result
     ``sample`` from ``smooth_dwell_sample`` with the same arguments), an exclusive scan of the row counts, and launch B,
     which draws the same bits again and writes every row's intervals, last run first, back from the end of the row's
     slice.  Returns the DataFrame of ``dwell_intervals``: the columns of ``tapqir_amd.utils.imscroll.INTERVAL_COLUMNS``,
-    int64, in (sample, AOI, frame) order."""
+    int64, in (sample, AOI, frame) order; with ``device_table`` the pair ``dwell_intervals`` returns then."""
     given = num_samples if sample is None else sample["counts"].shape[0]
     filt, theta, S, N, F = _smooth_sample_inputs("smooth_dwell_intervals", filt, theta, given)
     launch = _smooth_dwell_launch(filt, theta, S, N, F, seed)
     if sample is None:
         sample = _walk_count(launch, S, N, F, filt.device)
-    return _walk_emit("smooth_dwell_intervals", launch, sample, S, N, filt.device)
+    return _walk_emit("smooth_dwell_intervals", launch, sample, S, N, filt.device, device_table)
 
 
 # ---- hidden Markov smoothing with several states per class (`smooth --bound-states`, DESIGN.md section 22) ---------------
@@ -805,16 +810,17 @@ def hmm_dwell_sample(filt, theta, unbound, bound, num_samples, seed=0):
     return _walk_count(_chain_dwell_launch(filt, theta, U, B, S, N, F, seed), S, N, F, filt.device)
 
 
-def hmm_dwell_intervals(filt, theta, unbound, bound, num_samples, seed=0, sample=None):
+def hmm_dwell_intervals(filt, theta, unbound, bound, num_samples, seed=0, sample=None, device_table=False):
     """``smooth_dwell_intervals`` for the chain in hidden states: launch A (or its result ``sample`` from
     ``hmm_dwell_sample`` with the same arguments), the exclusive scan of the row counts, and launch B.  Returns the
-    DataFrame of ``dwell_intervals``; ``z`` is the class of a run, not its hidden state."""
+    DataFrame of ``dwell_intervals``; ``z`` is the class of a run, not its hidden state.  With ``device_table`` the pair
+    ``dwell_intervals`` returns then."""
     given = num_samples if sample is None else sample["counts"].shape[0]
     filt, theta, U, B, M, S, N, F = _hmm_sample_inputs("hmm_dwell_intervals", filt, theta, unbound, bound, given)
     launch = _chain_dwell_launch(filt, theta, U, B, S, N, F, seed)
     if sample is None:
         sample = _walk_count(launch, S, N, F, filt.device)
-    return _walk_emit("hmm_dwell_intervals", launch, sample, S, N, filt.device)
+    return _walk_emit("hmm_dwell_intervals", launch, sample, S, N, filt.device, device_table)
 
 
 def hmm_estimate(trans, bootstrap=False, seed=0):
@@ -1360,10 +1366,11 @@ def mixture_dwell_sample(filt, thetas, resp, unbound, bound, num_samples, seed=0
     return _walk_count(_population_dwell_launch(filt, thetas, resp, U, B, G, S, N, F, seed), S, N, F, filt.device, G)
 
 
-def mixture_dwell_intervals(filt, thetas, resp, unbound, bound, num_samples, seed=0, sample=None):
+def mixture_dwell_intervals(filt, thetas, resp, unbound, bound, num_samples, seed=0, sample=None, device_table=False):
     """``hmm_dwell_intervals`` for the mixture of chains: launch A (or its result ``sample`` from ``mixture_dwell_sample``
     with the same arguments), the exclusive scan of the row counts, and launch B.  Returns the DataFrame of
-    ``dwell_intervals`` and an int64 column ``population``: ``sample["pop"][posterior_sample, aoi]``."""
+    ``dwell_intervals`` and an int64 column ``population``: ``sample["pop"][posterior_sample, aoi]``.  With
+    ``device_table`` the pair ``dwell_intervals`` returns then (the device table keeps its DWELL_COLS columns)."""
     given = num_samples if sample is None else sample["counts"].shape[0]
     filt, thetas, resp, U, B, G, S, N, F = _mixture_dwell_inputs("mixture_dwell_intervals", filt, thetas, resp, unbound,
                                                                  bound, given)
@@ -1373,9 +1380,10 @@ def mixture_dwell_intervals(filt, thetas, resp, unbound, bound, num_samples, see
     pop = sample.get("pop")
     if not isinstance(pop, torch.Tensor) or pop.shape != (S, N) or pop.dtype != torch.uint8 or pop.device != filt.device:
         raise ValueError(f"mixture_dwell_intervals: sample['pop'] must be uint8 ({S}, {N}) on the device of filt")
-    table = _walk_emit("mixture_dwell_intervals", launch, sample, S, N, filt.device)
+    table = _walk_emit("mixture_dwell_intervals", launch, sample, S, N, filt.device, device_table)
+    frame = table[0] if device_table else table
     host = pop.cpu().numpy().astype("int64")
-    table["population"] = host[table["posterior_sample"].to_numpy(), table["aoi"].to_numpy()]
+    frame["population"] = host[frame["posterior_sample"].to_numpy(), frame["aoi"].to_numpy()]
     return table
 
 
