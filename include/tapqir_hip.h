@@ -1185,6 +1185,51 @@ typedef struct {
 
 int tq_joint_viterbi(const tq_joint_viterbi_args* a, void* stream);
 
+/* tq_pair_dwell: the rasters of tq_hmm_count at (U, B) = (2, 2) on the joint filt, walked into the dwell-time intervals and
+ * first-binding frames of one channel as they are drawn, every run with the other channel's state at its two ends
+ * (`dwelltime --smooth --joint A,B` / `ttfb --smooth --joint A,B`); neither a raster nor the state
+ * pairs are stored.
+ * Row (s, n) is, state for state, the row tq_hmm_count draws at (U, B) = (2, 2) for the same filt, theta and seed: the same
+ * Philox stream (seed, step = s, site 0xA04, elem = n), the same order of draws (u_0 for frame F - 1, then downwards, four
+ * uniforms to a Philox block), the same floor of theta, thresholds t(i) and double compare -- so one seed gives
+ * `smooth --joint A,B` and the two kinetics commands rasters of the same chain, and both values of `which` at one seed
+ * describe the same rasters.  `which` chooses the channel whose runs are walked: 0 is channel a (bit 0 of the state
+ * s = z_a + 2 z_b), 1 is channel b (bit 1); the other channel is the partner.  The class z = (state >> which) & 1 goes
+ * through the walker of tq_chain_dwell; with q(f) the partner's class at frame f, a run over [start, stop] has the partner
+ * code  bit 0 = q(start), bit 1 = q(start - 1) (0 when start = 0), bit 2 = q(stop), bit 3 = q(stop + 1) (0 when
+ * stop = F - 1).
+ *   mode TQ_DWELL_COUNT: counts[s, n] = number of intervals of the row; every interior interval (low_or_high 0 / 1) of
+ *     dwell time d adds 1 to hist_unbound[s, q(start), d] / hist_bound[s, q(start), d] (the caller zeroes both histograms);
+ *     when tau is not NULL, tau[s, n] = the smallest f with z = 1, or F if there is none; when tau_after is not NULL,
+ *     tau_after[s, n] = the smallest f >= tau[s, n] with q(f) = 1, or F if there is none or tau[s, n] = F.
+ *   mode TQ_DWELL_EMIT: the same draws again into the table `intervals` of tq_chain_dwell's EMIT, under its rules: ascending
+ *     in start_frame within a row, the k-th run a row closes is written at offsets[s, n] + counts[s, n] - 1 - k; a position
+ *     outside [offsets[s, n], min(offsets[s, n] + counts[s, n], total)) is dropped, never written; total = 0 launches
+ *     nothing.  The table keeps its TQ_DWELL_COLS columns; partner[pos] receives the partner code of the run at pos.
+ * With which = 1, counts, tau, the table and the histograms summed over q are tq_chain_dwell's at (2, 2) bit for bit.
+ * TQ_ERR_ARG, before anything touches the device, for what tq_chain_dwell refuses (a NULL required pointer of the mode --
+ * partner in EMIT with total > 0 among them --, N, F or S < 1, F > TQ_SMOOTH_MAX_F, S > 65535 * 64, total < 0, an unknown
+ * mode), and for `which` outside {0, 1}. */
+typedef struct {
+  const double* filt;          /* (N, F, 4) of tq_joint_estep at R = 1 */
+  const double* theta;         /* (20); device memory */
+  int32_t* counts;             /* (S, N) out (COUNT), in (EMIT) */
+  int32_t* hist_bound;         /* (S, 2, F) in/out (COUNT): interior bound runs by q(start) and dwell time */
+  int32_t* hist_unbound;       /* (S, 2, F) in/out (COUNT): interior unbound runs by q(start) and dwell time */
+  float* tau;                  /* (S, N) out (COUNT): integer-valued first-binding frames in [0, F]; or NULL */
+  float* tau_after;            /* (S, N) out (COUNT): the partner's first bound frame from tau on, in [0, F]; or NULL */
+  const int64_t* offsets;      /* (S, N) in (EMIT): exclusive scan of counts */
+  int32_t* intervals;          /* (TQ_DWELL_COLS, total) out (EMIT) */
+  uint8_t* partner;            /* (total) out (EMIT): partner code of every interval */
+  int64_t total;               /* EMIT: number of intervals (the column stride) */
+  int32_t N, F, S;
+  int32_t which;               /* 0: the runs of channel a; 1: those of channel b */
+  int32_t mode;                /* TQ_DWELL_COUNT or TQ_DWELL_EMIT */
+  uint64_t seed;
+} tq_pair_dwell_args;
+
+int tq_pair_dwell(const tq_pair_dwell_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame

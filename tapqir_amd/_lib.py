@@ -224,6 +224,7 @@ EXPORTS = [
     "tq_chain_dwell",
     "tq_multistart_estep", "tq_multistart_mstep",  # ... tapqir_amd/_lib_multistart.py
     "tq_joint_estep", "tq_joint_mstep", "tq_joint_viterbi",  # ... tapqir_amd/_lib_joint.py
+    "tq_pair_dwell",
     "tq_mixture_mstep", "tq_mixture_count", "tq_mixture_estimate",  # ... tapqir_amd/_lib_mixture.py
     "tq_population_dwell",
     "tq_dwell_censored_hist", "tq_dwell_censored_fit", "tq_dwell_survival",  # ... tapqir_amd/_lib_censored.py

@@ -1,7 +1,8 @@
 """
 ctypes mirrors of the two-channel chain entry points of ``libtapqir_hip.so`` (``tq_joint_estep`` / ``tq_joint_mstep`` /
-``tq_joint_viterbi``, include/tapqir_hip.h).  Import this module as a module (``from tapqir_amd import _lib_joint``);
-``lib()`` returns the library of ``tapqir_amd._lib.load()`` with the three prototypes bound.
+``tq_joint_viterbi`` / ``tq_pair_dwell``, include/tapqir_hip.h).  Import this module as a module
+(``from tapqir_amd import _lib_joint``); ``lib()`` returns the library of ``tapqir_amd._lib.load()`` with the prototypes
+bound.
 """
 
 import ctypes as C
@@ -45,6 +46,17 @@ class JointViterbiArgs(C.Structure):
     ]
 
 
+class PairDwellArgs(C.Structure):
+    """``tq_pair_dwell_args`` (include/tapqir_hip.h); ``mode`` is ``_lib.DWELL_COUNT`` or ``_lib.DWELL_EMIT``."""
+
+    _fields_ = [
+        ("filt", C.c_void_p), ("theta", C.c_void_p), ("counts", C.c_void_p), ("hist_bound", C.c_void_p),
+        ("hist_unbound", C.c_void_p), ("tau", C.c_void_p), ("tau_after", C.c_void_p), ("offsets", C.c_void_p),
+        ("intervals", C.c_void_p), ("partner", C.c_void_p), ("total", C.c_int64),
+        ("N", C.c_int32), ("F", C.c_int32), ("S", C.c_int32), ("which", C.c_int32), ("mode", C.c_int32), ("seed", C.c_uint64),
+    ]
+
+
 def structure_array(structures):
     """The ``structure`` field of ``tq_joint_mstep_args`` of a list of ids: the first len(structures) entries, zeros after."""
     ids = [int(s) for s in structures]
@@ -52,9 +64,9 @@ def structure_array(structures):
 
 
 def bind(lib):
-    """Set the prototypes of the three entry points on a loaded library; returns it."""
+    """Set the prototypes of the entry points on a loaded library; returns it."""
     for name, args in (("tq_joint_estep", JointEstepArgs), ("tq_joint_mstep", JointMstepArgs),
-                       ("tq_joint_viterbi", JointViterbiArgs)):
+                       ("tq_joint_viterbi", JointViterbiArgs), ("tq_pair_dwell", PairDwellArgs)):
         fn = getattr(lib, name)
         fn.argtypes = [C.POINTER(args), C.c_void_p]
         fn.restype = C.c_int

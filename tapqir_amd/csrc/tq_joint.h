@@ -4,7 +4,9 @@
 // product of the two channels' evidence, l_f(s) = l^a_f(s & 1) l^b_f(s >> 1):
 //   * the chain with its two priors, and the emission of a frame and its logarithm as the callables TqJointEmit and
 //     TqJointLogEmit;
-//   * the M-step under one of five structures of A, closed forms in the margins of the summed pair counts.
+//   * the M-step under one of five structures of A, closed forms in the margins of the summed pair counts;
+//   * a row of the backward sampler walked, as it is drawn, into the runs of one channel, each with the other channel's
+//     state at its two ends (tq_pair_dwell).
 // The chunk product, the two sweeps and the Viterbi row are tq_hmm.h's tq_chain_* templates at M = 4, given TqJointModel
 // as the chain and these callables: the joint chain has no sweep text of its own, and tq_joint_chunk, tq_joint_sweeps and
 // tq_joint_viterbi_row are one-line names for those calls.
@@ -128,3 +130,62 @@ TQ_HD void tq_joint_mstep_theta(const double* sums, int N, int structure, double
   for (int i = 0; i < M; ++i) q[i] = sums[M * M + i] / (double)N;
   tq_hmm_floor<M>(q, theta + M * M);
 }
+
+// ---- backward sampler walked into one channel's intervals (tq_pair_dwell) ---------------------------
+// The draws are TqHmmDraws / tq_hmm_thresholds<4> / tq_hmm_label<4> of tq_hmm.h, so row (s, n) is the row tq_hmm_count
+// draws at (U, B) = (2, 2); the walk is TqSmoothWalk on the class z = (state >> which) & 1, channel a for which = 0 and
+// channel b for which = 1.  New here is the partner q = (state >> (which ^ 1)) & 1: a run over [start, stop] gets the code
+//   bit 0 = q(start), bit 1 = q(start - 1) (0 when start = 0), bit 2 = q(stop), bit 3 = q(stop + 1) (0 when stop = F - 1).
+// The row comes from frame F - 1 downwards: bits 2 and 3 are known when the run opens, bits 0 and 1 when it closes.
+struct TqPairDwellRow {
+  TqChainDwellRow c;  // the walker, the state of the frame after the current one, the lowest frame seen with z = 1
+  int qnext;          // q of the frame after the current one
+  int open;           // bits 2 and 3 of the open run
+  int qlow;           // the lowest frame seen with q = 1, or F
+  int tau_after;      // qlow as it stood when the lowest frame with z = 1 was passed: the smallest f >= tau with q = 1, or F
+};
+
+TQ_HD void tq_pair_dwell_begin(TqPairDwellRow& r, int F) {
+  tq_chain_dwell_begin(r.c, F);
+  r.qnext = 0;
+  r.open = 0;
+  r.qlow = F;
+  r.tau_after = F;
+}
+
+// Frame f with its uniform u and the twelve thresholds t of tq_hmm_thresholds<4> for that frame: draws the joint state as
+// the sampler of tq_hmm_count does, and returns 1 and fills `out` and `code` when the frame closes the run of channel
+// `which` that began at f + 1.
+TQ_HD int tq_pair_dwell_frame(TqPairDwellRow& r, double u, const double* t, int f, int F, int which, TqDwellInterval& out,
+                              int& code) {
+  constexpr int M = TQ_JOINT_M;
+  const bool last = f == F - 1;
+  const int state = tq_hmm_label<M>(u, t + (last ? 0 : r.c.next) * (M - 1));
+  const int z = (state >> which) & 1, q = (state >> (which ^ 1)) & 1;
+  r.c.next = state;
+  if (q) r.qlow = f;
+  if (z) {
+    r.c.tau = f;
+    r.tau_after = r.qlow;
+  }
+  int closed = 0;
+  if (last) {
+    tq_smooth_walk_begin(r.c.w, F, z);
+    r.open = q << 2;
+  } else if (tq_smooth_walk_step(r.c.w, f, z, out)) {
+    closed = 1;
+    code = r.open | r.qnext | (q << 1);  // the closed run began at f + 1
+    r.open = (q << 2) | (r.qnext << 3);  // the run that opens here stops at f
+  }
+  r.qnext = q;
+  return closed;
+}
+
+// the run still open after frame 0: it starts the record, so bit 1 is 0
+TQ_HD void tq_pair_dwell_finish(const TqPairDwellRow& r, TqDwellInterval& out, int& code) {
+  tq_chain_dwell_finish(r.c, out);
+  code = r.open | r.qnext;
+}
+
+// the F bins of sample s and partner state q at the run's start, in histograms of shape (S, 2, F)
+TQ_HD int64_t tq_pair_hist_at(int s, int q, int F) { return ((int64_t)s * 2 + q) * F; }

@@ -337,19 +337,33 @@ def _kinetics_inputs(command, model, cuda, progress_bar):
     return m, mask, progress_bar
 
 
-def _chain_states(command, model, cuda, smooth, U, B, logger, G=1):
-    """The checks of ``--unbound-states`` / ``--bound-states`` / ``--populations`` of `ttfb` and `dwelltime`: the bound on
-    the sum of the states and the range of the populations where `smooth` checks them (after the model, before ``--cpu``),
-    and, once the model and ``--cpu`` have passed, that a chain other than (1, 1) or more than one population comes with
-    ``--smooth``."""
+def _joint_pair(command, joint, logger):
+    """The value of ``--joint A,B`` of `smooth`, `dwelltime` and `ttfb`: two different channel indices (A, B), or exit
+    status 1."""
+    import re
+
+    match = re.fullmatch(r"\s*(\d+)\s*,\s*(\d+)\s*", joint)
+    if not match or int(match.group(1)) == int(match.group(2)):
+        logger.error(f"{command}: --joint takes A,B with two different channel indices, got {joint!r}")
+        raise typer.Exit(1)
+    return int(match.group(1)), int(match.group(2))
+
+
+def _chain_states(command, model, cuda, smooth, U, B, logger, G=1, joint=None, censored=False):
+    """The checks of ``--unbound-states`` / ``--bound-states`` / ``--populations`` / ``--joint`` of `ttfb` and `dwelltime`:
+    the bound on the sum of the states, the range of the populations and the value of ``--joint`` where `smooth` checks
+    them (after the model, before ``--cpu``), and, once the model and ``--cpu`` have passed, that a chain other than
+    (1, 1), more than one population or a joint chain comes with ``--smooth``; then what ``--joint`` does not go with.
+    Returns the pair (A, B) of ``--joint``, or None."""
     if model.value != "cosmos":
-        return
+        return None
     if U + B > 4:
         logger.error(f"{command}: --unbound-states + --bound-states must be at most 4, got {U} + {B}")
         raise typer.Exit(1)
     if not 1 <= G <= 4:
         logger.error(f"{command}: --populations must lie in 1 .. 4, got {G}")
         raise typer.Exit(1)
+    pair = None if joint is None else _joint_pair(command, joint, logger)
     if cuda and not smooth and (U, B) != (1, 1):
         logger.error(f"{command}: --unbound-states and --bound-states need --smooth: they choose the chain of `smooth` "
                      f"whose rasters are sampled")
@@ -358,6 +372,23 @@ def _chain_states(command, model, cuda, smooth, U, B, logger, G=1):
         logger.error(f"{command}: --populations needs --smooth: it chooses the mixture of `smooth --populations` whose "
                      f"rasters are sampled")
         raise typer.Exit(1)
+    if pair is None:
+        return None
+    if cuda and not smooth:
+        logger.error(f"{command}: --joint needs --smooth: it chooses the chain of `smooth --joint` whose rasters are sampled")
+        raise typer.Exit(1)
+    if (U, B) != (1, 1):
+        logger.error(f"{command}: --joint samples the chain of two two-state channels: it does not go with --unbound-states / "
+                     f"--bound-states other than 1 and 1")
+        raise typer.Exit(1)
+    if G > 1:
+        logger.error(f"{command}: --joint does not go with --populations: the joint chain is fitted to all AOIs")
+        raise typer.Exit(1)
+    if censored:
+        logger.error(f"{command}: --joint does not go with --censored: the censored histograms are not split by the "
+                     f"partner's state")
+        raise typer.Exit(1)
+    return pair
 
 
 def _smooth_suffix(U, B, G=1):
@@ -421,6 +452,50 @@ def _mixture_filter(sm, c, p_bound, mask, U, B, logger):
     filt = torch.stack([hmm_estep(p_bound, thetas[g], prior, U, B)["filt"] for g in range(thetas.shape[0])])
     resp = sm["population_probs"][:, :, c][mask].T.to(device=p_bound.device, dtype=torch.float64).contiguous()
     return filt, thetas, resp
+
+
+def _joint_posterior(command, cd, m, mask, pair, logger):
+    """``<name>_smooth-joint<A><B>.tpqr`` for the ``--smooth --joint A,B`` switch of `ttfb` and `dwelltime`: the joint chain
+    (``theta``, ``prior``) of `smooth --joint A,B`.  Exits with status 1 when the data lacks a channel of the pair, the
+    file is missing or was written for another pair or another selection of AOIs."""
+    import torch
+
+    from tapqir_amd.utils.safe_load import load_tpqr
+
+    a, b = pair
+    C = m.data.C
+    if a >= C or b >= C:
+        logger.error(f"{command}: --joint {a},{b} needs channels {a} and {b}, the data has {C} channel{'s' if C != 1 else ''}")
+        raise typer.Exit(1)
+    path = cd / f"{m.name}_smooth-joint{a}{b}.tpqr"
+    if not path.is_file():
+        logger.error(f"{command} --smooth --joint needs {path.name}: run `smooth --joint {a},{b}` first")
+        raise typer.Exit(1)
+    sm = load_tpqr(path)
+    if tuple(int(c) for c in sm["channels"]) != (a, b):
+        logger.error(f"{command} --smooth --joint: {path.name} was written for the channels {tuple(sm['channels'])}: run "
+                     f"`smooth --joint {a},{b}` again")
+        raise typer.Exit(1)
+    if sm["mask"].shape != mask.shape or not torch.equal(sm["mask"].bool(), mask):
+        logger.error(f"{command} --smooth --joint: {path.name} was written for another mask of on-target AOIs than the data "
+                     f"has now: run `smooth --joint {a},{b}` again")
+        raise typer.Exit(1)
+    return sm
+
+
+def _joint_filter(sm, m, mask, pair, dev, logger):
+    """The inputs of the joint chain's backward sampler from the file of `smooth --joint`: one E-step on the two channels'
+    p(z = 1) of the fit at the stored theta and priors.  Returns (filt (N, F, 4), theta (20,)) on ``dev``."""
+    import torch
+
+    from tapqir_amd.utils.joint_analysis import joint_estep
+
+    a, b = pair
+    logger.info(f"rasters of the joint chain of channels #{a} and #{b} fitted by `smooth --joint` (structure {sm['chosen']})")
+    theta = sm["theta"].to(device=dev, dtype=torch.float64).reshape(1, -1).contiguous()
+    p_a, p_b = (m.params["z_probs"][: m.data.N, :, c, 1][mask].float().to(dev) for c in (a, b))
+    filt = joint_estep(p_a, p_b, theta, float(sm["prior"][0]), float(sm["prior"][1]))["filt"][0]
+    return filt, theta[0]
 
 
 def _finite_summary(rows):
@@ -536,6 +611,37 @@ def _ttfb_populations(cd, stem, c, split, G, Tmax, Af, logger):
                             for g in range(G)) + ")")
 
 
+def _ttfb_joint(cd, m, mask, sm, pair, num_samples, logger):
+    """`ttfb --smooth --joint A,B`: the order of arrival of the two channels from posterior rasters
+    of the joint chain, both channels walked at the seed A.  Writes ``<model>_ttfb-smooth-joint<A><B>-order.csv`` alone: the
+    rows of ``joint_arrival_order`` with A as the lead (``a_*``) and with B as the lead (``b_*``), mean and 95% HPDI over
+    the samples in which the quantity exists."""
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.utils.joint_analysis import ORDER_NAMES, joint_arrival_order, joint_dwell_sample
+    from tapqir_amd.utils.mle_analysis import hpdi_columns
+
+    a, b = pair
+    stem = f"{m.name}_ttfb-smooth-joint{a}{b}"
+    F = m.data.F
+    filt, theta = _joint_filter(sm, m, mask, pair, torch.device("cuda"), logger)
+    drawn = [joint_dwell_sample(filt, theta, which, num_samples, seed=a) for which in (0, 1)]  # seed A: `smooth --joint`'s
+    rows = {}
+    for lead, label in ((0, "a"), (1, "b")):
+        order = joint_arrival_order(drawn[lead]["tau"], drawn[lead]["tau_after"], drawn[1 - lead]["tau"], F)
+        for key in ORDER_NAMES:
+            x = order[key].cpu()
+            x = x[torch.isfinite(x)]
+            if x.numel():
+                ll, ul = hpdi_columns(x[:, None], 0.95)
+                rows[f"{label}_{key}"] = [x.mean().item(), ll.item(), ul.item()]
+            else:
+                rows[f"{label}_{key}"] = [float("nan")] * 3
+    pd.DataFrame.from_dict(rows, orient="index", columns=["Mean", "95% LL", "95% UL"]).to_csv(cd / f"{stem}-order.csv")
+    logger.info(f"Saved the order of arrival of channels #{a} and #{b} in {stem}-order.csv file")
+
+
 @app.command()
 def ttfb(
     model: avail_models = typer.Option("cosmos", help="Tapqir model"),
@@ -547,6 +653,7 @@ def ttfb(
     unbound_states: int = typer.Option(1, "--unbound-states", min=1, help="Hidden states that look unbound (z = 0)"),
     bound_states: int = typer.Option(1, "--bound-states", min=1, help="Hidden states that look bound (z = 1); at most 4 in all"),
     populations: int = typer.Option(1, "--populations", help="Populations of AOIs, each with a chain of its own (1 to 4): a mixture of chains"),
+    joint: Optional[str] = typer.Option(None, "--joint", help="A,B: the order of arrival of the colour channels A and B from the chain of `smooth --joint A,B`"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -575,6 +682,18 @@ def ttfb(
     the share of those never bound, the mean first-binding frame of those that bound and the cumulative fraction bound,
     and the fitted Af is logged next to the mixture's own estimate of the active fraction.  There are no per-population
     ttfb fits: the members of a population change from sample to sample, and the fit takes rectangular data.
+
+    With ``--smooth --joint A,B`` the rasters are those of the chain of four joint states that `smooth --joint A,B` chose
+    (``<model>_smooth-joint<A><B>.tpqr``), both channels walked in the same rasters, and only
+    ``<model>_ttfb-smooth-joint<A><B>-order.csv`` is written: with A as the lead (rows ``a_*``) and
+    with B as the lead (``b_*``), per sample the share of AOIs in which the lead binds (``binds``); of those, the shares in
+    which the partner is there at that frame (``together``), arrives later (``later``) or never does (``never``); the mean
+    delay of the late arrivals (``mean_delay``); the partner's probability per frame of arriving once the lead is there
+    (``k_after``) and from the start of the record (``k_base``), both as events over frames at risk with right censoring;
+    and their ``ratio``.  There is no (ka, kns, Af) fit: it takes one observation window for all AOIs, and here the window
+    after the lead's arrival differs from AOI to AOI.  The rasters are those of the same chain at the same seed as the
+    ones behind ``<model>_smooth-joint<A><B>.csv``, not bit for bit: the filtered marginals are computed again at the
+    stored chain.  ``--joint`` does not go with state or population options.
     """
     import pandas as pd
     import torch
@@ -588,9 +707,16 @@ def ttfb(
     cd = DEFAULTS["cd"]
     logger = logging.getLogger("tapqir")
     U, B, G = unbound_states, bound_states, populations
-    _chain_states("ttfb", model, cuda, smooth, U, B, logger, G)
+    pair = _chain_states("ttfb", model, cuda, smooth, U, B, logger, G, joint)
     m, mask, progress_bar = _kinetics_inputs("ttfb", model, cuda, progress_bar)
     data = m.data
+    if pair is not None:
+        try:
+            _ttfb_joint(cd, m, mask, _joint_posterior("ttfb", cd, m, mask, pair, logger), pair, num_samples, logger)
+        except HipExtensionError:
+            logger.exception("ttfb failed: it needs an AMD GPU (--cuda) and the built HIP library")
+            raise typer.Exit(1)
+        return
     sm = _smoothed_posterior("ttfb", cd, m.name, mask, logger, U, B, G) if smooth else None
     stem = f"{m.name}_ttfb-smooth{_smooth_suffix(U, B, G)}" if smooth else f"{m.name}_ttfb"
     if smooth:
@@ -798,6 +924,56 @@ def _survival_plot(cd, name, c, kind, mean, ll, ul, fitted, logger):
     logger.info(f"Saved {kind} survival plot in {name}.png file")
 
 
+def _dwell_joint(cd, m, mask, sm, pair, K, num_samples, num_iter, kinds, savemat, progress_bar, logger):
+    """`dwelltime --smooth --joint A,B`: for each channel c of the pair, the runs of c in posterior
+    rasters of the joint chain (seed A for both, so both tables describe the same rasters), written as
+    ``<model>_dwelltime-smooth-joint<A><B>-intervals-channel<c>.pkl`` / ``.mat`` with the partner's state at the ends of
+    every run, and for every kind one K-exponential fit per partner state q at the run's first frame from
+    ``sample["hist_<kind>"][:, q]``, written together as ``...-<rate>-channel<c>.csv`` with rows ``q<q>_A<i>`` and
+    ``q<q>_<rate><i>``.  A sample without an interior interval of the kind for q is left out of that fit and logged; a
+    kind no sample has for q is skipped with a warning.  No plots."""
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.utils.joint_analysis import joint_dwell_intervals, joint_dwell_sample
+    from tapqir_amd.utils.mle_analysis import dwell_csr_from_hist, dwell_fit
+
+    a, b = pair
+    stem = f"{m.name}_dwelltime-smooth-joint{a}{b}"
+    filt, theta = _joint_filter(sm, m, mask, pair, torch.device("cuda"), logger)
+    for which, c in enumerate(pair):
+        logger.info(f"Channel #{c} ({m.data.channels[c]}), partner #{pair[1 - which]}")
+        sample = joint_dwell_sample(filt, theta, which, num_samples, seed=a)  # seed A: the default of `smooth --joint`
+        intervals = joint_dwell_intervals(filt, theta, which, num_samples, seed=a, sample=sample)
+        intervals.to_pickle(cd / f"{stem}-intervals-channel{c}.pkl")
+        logger.info(f"Saved time intervals in {stem}-intervals-channel{c}.pkl file")
+        if savemat is not None:
+            savemat(cd / f"{stem}-intervals-channel{c}.mat", intervals.to_dict("list"))
+            logger.info(f"Saved time intervals in {stem}-intervals-channel{c}.mat file")
+        else:
+            logger.info("scipy is not available: the .mat file of the intervals is not written")
+        for kind, rate, title, _ in kinds:
+            logger.info(f"{title} calculation by the partner's state ...")
+            tables = []
+            for q in (0, 1):
+                hist = sample[f"hist_{kind}"][:, q].contiguous()
+                keep = hist.sum(1) > 0
+                n_out = int((~keep).sum())
+                if n_out == hist.shape[0]:
+                    logger.warning(f"dwelltime: no posterior sample has an interior {kind} interval that starts with the "
+                                   f"partner at {q}: its {rate} is not fitted")
+                    continue
+                if n_out:
+                    logger.info(f"partner at {q}: {n_out} of {hist.shape[0]} posterior samples have no interior {kind} "
+                                f"interval and are left out of the {rate} fit")
+                fit = dwell_fit(dwell_csr_from_hist(hist[keep]), K, lr=5e-3, n_steps=num_iter, progress_bar=progress_bar)
+                tables.append(_summary_table(row for i in range(K) for row in (
+                    (f"q{q}_A{i}", fit["A"][:, i].cpu()), (f"q{q}_{rate}{i}", fit["k"][:, i].cpu()))))
+            if tables:
+                pd.concat(tables).to_csv(cd / f"{stem}-{rate}-channel{c}.csv")
+                logger.info(f"Saved {title.lower()} parameters by the partner's state in {stem}-{rate}-channel{c}.csv file")
+
+
 @app.command()
 def dwelltime(
     model: avail_models = typer.Option("cosmos", help="Tapqir model"),
@@ -810,6 +986,7 @@ def dwelltime(
     bound_states: int = typer.Option(1, "--bound-states", min=1, help="Hidden states that look bound (z = 1); at most 4 in all"),
     populations: int = typer.Option(1, "--populations", help="Populations of AOIs, each with a chain of its own (1 to 4): a mixture of chains"),
     censored: bool = typer.Option(False, "--censored", help="Count the run still open at the last frame as a right-censored dwell"),
+    joint: Optional[str] = typer.Option(None, "--joint", help="A,B: the dwell times of the colour channels A and B by each other's state, from the chain of `smooth --joint A,B`"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -850,6 +1027,17 @@ def dwelltime(
     the fitted survival to ``...-censored-<kind>-survival-channel<c>.csv`` and ``.png``.  The MAP raster's histogram is not
     drawn: it holds interior runs only, and a correct fit would look wrong next to it.  The files of the fit without the
     switch are neither written nor touched.
+
+    With ``--smooth --joint A,B`` the rasters are those of the chain of four joint states that `smooth --joint A,B` chose
+    (``<model>_smooth-joint<A><B>.tpqr``), and each channel c of the pair is walked in the same rasters with the other
+    channel as its partner.  ``<model>_dwelltime-smooth-joint<A><B>-intervals-channel<c>`` gains the
+    columns ``partner_start``, ``partner_before``, ``partner_stop`` and ``partner_after``: the partner's state at the first
+    frame of the run, the frame before it, its last frame and the frame after it, -1 where the record has no such frame.
+    Every kind has one K-exponential fit per partner state q at the first frame of the run, rows ``q<q>_A<i>`` and
+    ``q<q>_koff<i>`` / ``q<q>_kon<i>`` of ``...-koff-channel<c>.csv`` / ``...-kon-channel<c>.csv``.  There are no plots.
+    The rasters are those of the same chain at the same seed as the ones behind ``<model>_smooth-joint<A><B>.csv``, not
+    bit for bit: the filtered marginals are computed again at the stored chain.  ``--joint`` does not go with state or
+    population options or with ``--censored``, whose histograms are not split by the partner's state.
     """
     import torch
 
@@ -868,7 +1056,7 @@ def dwelltime(
         logger.error(f"dwelltime: -K must be between 1 and {_lib.DWELL_KMAX}, got {K}")
         raise typer.Exit(1)
     U, B, G = unbound_states, bound_states, populations
-    _chain_states("dwelltime", model, cuda, smooth, U, B, logger, G)
+    pair = _chain_states("dwelltime", model, cuda, smooth, U, B, logger, G, joint, censored)
     m, mask, progress_bar = _kinetics_inputs("dwelltime", model, cuda, progress_bar)
     try:
         from scipy.io import savemat
@@ -876,13 +1064,21 @@ def dwelltime(
         savemat = None
 
     data = m.data
+    kinds = (("bound", "koff", "Off-rate", bound_dwell_times), ("unbound", "kon", "On-rate", unbound_dwell_times))
+    if pair is not None:
+        try:
+            _dwell_joint(cd, m, mask, _joint_posterior("dwelltime", cd, m, mask, pair, logger), pair, K, num_samples, num_iter,
+                         kinds, savemat, progress_bar, logger)
+        except HipExtensionError:
+            logger.exception("dwelltime failed: it needs an AMD GPU (--cuda) and the built HIP library")
+            raise typer.Exit(1)
+        return
     sm = _smoothed_posterior("dwelltime", cd, m.name, mask, logger, U, B, G) if smooth else None
     stem = f"{m.name}_dwelltime-smooth{_smooth_suffix(U, B, G)}" if smooth else f"{m.name}_dwelltime"
     if smooth:
         z_map = sm["z_map"]
     else:
         z_map = m.params["z_map"][: data.N] if "z_map" in m.params else None
-    kinds = (("bound", "koff", "Off-rate", bound_dwell_times), ("unbound", "kon", "On-rate", unbound_dwell_times))
     try:
         dev = torch.device("cuda")
         for c in range(data.C):
@@ -1270,10 +1466,7 @@ def _smooth_joint_options(joint, structure, U, B, restarts, restart_seed, forbid
     if joint is None:
         logger.error("smooth: --structure needs --joint A,B")
         raise typer.Exit(1)
-    match = re.fullmatch(r"\s*(\d+)\s*,\s*(\d+)\s*", joint)
-    if not match or int(match.group(1)) == int(match.group(2)):
-        logger.error(f"smooth: --joint takes A,B with two different channel indices, got {joint!r}")
-        raise typer.Exit(1)
+    a, b = _joint_pair("smooth", joint, logger)
     if (U, B) != (1, 1):
         logger.error("smooth: --joint smooths two two-state channels together: it does not go with --unbound-states / "
                      "--bound-states other than 1 and 1")
@@ -1285,7 +1478,7 @@ def _smooth_joint_options(joint, structure, U, B, restarts, restart_seed, forbid
     if structure is not None and structure != "auto" and structure not in names:
         logger.error(f"smooth: --structure takes auto, {', '.join(names)}; got {structure!r}")
         raise typer.Exit(1)
-    return {"a": int(match.group(1)), "b": int(match.group(2)), "structure": None if structure in (None, "auto") else structure}
+    return {"a": a, "b": b, "structure": None if structure in (None, "auto") else structure}
 
 
 def _smooth_joint(m, mask, cd, logger, pair, num_iter, tol, num_samples, ci, bootstrap, seed, progress_bar):

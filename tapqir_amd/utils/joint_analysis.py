@@ -8,6 +8,10 @@ product of the two channels' evidence.  Five structures of A state the scientifi
 ``hmm_fit_restarts`` (``multistart_em``) on ``tq_joint_estep`` / ``tq_joint_mstep``; the BIC ranks them.  The backward
 sampler and the estimate of A are ``hmm_sample`` / ``hmm_estimate`` at (2, 2) on the joint ``filt``.
 
+``joint_dwell_sample`` / ``joint_dwell_intervals`` walk the rasters of that sampler, as they are drawn, into the runs of one
+channel with the other channel's state at their ends (``tq_pair_dwell``), and ``joint_arrival_order``
+turns the first-binding frames into the order of arrival (host-side torch on S x N numbers; it runs anywhere).
+
 The states are identified by their emissions, so nothing is reordered after a fit.  Everything runs on the HIP device;
 there is no CPU fallback.
 """
@@ -20,13 +24,16 @@ import torch
 from tapqir_amd import _lib, _lib_joint, _lib_smooth
 from tapqir_amd._lib_multistart import MULTISTART_MAX
 from tapqir_amd.exceptions import HipExtensionError
-from tapqir_amd.utils.mle_analysis import (MULTISTART_SCRATCH_BYTES, _multistart_active, _multistart_inputs,
-                                           _sampler_inputs, _stream, multistart_em)
+from tapqir_amd.utils.mle_analysis import (MULTISTART_SCRATCH_BYTES, _hmm_sample_inputs, _multistart_active,
+                                           _multistart_inputs, _sampler_inputs, _stream, _walk_count, _walk_emit,
+                                           multistart_em)
 
 STRUCTURE_NAMES = tuple(name for name, _ in _lib_joint.STRUCTURES)
 M, THETA, COLS = _lib_joint.JOINT_STATES, _lib_joint.JOINT_THETA, _lib_joint.JOINT_COLS
 RATE_NAMES = ("kon_a|b0", "kon_a|b1", "koff_a|b0", "koff_a|b1", "kon_b|a0", "kon_b|a1", "koff_b|a0", "koff_b|a1")
 RATIO_NAMES = ("kon_a ratio", "koff_a ratio", "kon_b ratio", "koff_b ratio")
+PARTNER_COLUMNS = ("partner_start", "partner_before", "partner_stop", "partner_after")  # bits 0 .. 3 of the partner code
+ORDER_NAMES = ("binds", "together", "later", "never", "mean_delay", "k_after", "k_base", "ratio")
 
 
 def joint_structure_id(structure):
@@ -242,3 +249,101 @@ def joint_fit(p_a, p_b, prior_a, prior_b, structures=STRUCTURE_NAMES, start=None
              "trace": host_trace[r, : iterations[r]]} for r, s in enumerate(ids)]
     return {"fits": fits, "best": best, "chosen": chosen, "theta": thetas[k].clone(), "filt": out["filt"][k].clone(),
             "gamma": out["gamma"][k].clone(), "rows": rows[k].clone()}
+
+
+# ---- dwell times and first binding of one channel of the joint chain -----------------------------
+def _pair_dwell_launch(filt, theta, which, S, N, F, seed):
+    def launch(**fields):
+        a = _lib_joint.PairDwellArgs(filt=_lib.ptr(filt), theta=_lib.ptr(theta), N=N, F=F, S=S, which=which,
+                                     seed=int(seed) & (2**64 - 1), **fields)
+        _lib.check(_lib_joint.lib().tq_pair_dwell(C.byref(a), _stream(filt.device)), "tq_pair_dwell")
+
+    return launch
+
+
+def _pair_dwell_inputs(who, filt, theta, which, num_samples):
+    filt, theta, _, _, _, S, N, F = _hmm_sample_inputs(who, filt, theta, 2, 2, num_samples)
+    if which not in (0, 1):
+        raise ValueError(f"{who}: which must be 0 (the runs of channel a) or 1 (those of channel b), got {which!r}")
+    return filt, theta, int(which), S, N, F
+
+
+def joint_dwell_sample(filt, theta, which, num_samples, seed=0):
+    """``hmm_dwell_sample`` for one channel of the joint chain: launch A of the interval sampler on the rasters
+    ``hmm_sample(filt, theta, 2, 2, num_samples, seed, raster=True)["raster"]``, walked as they are drawn at the level of
+    ``z = (state >> which) & 1`` -- channel a for ``which`` = 0, channel b for 1 -- with the partner
+    ``q = (state >> (1 - which)) & 1`` beside it.  ``filt`` (N, F, 4) is that of ``joint_estep`` at one theta (20,).
+
+    Returns ``"hist_bound"`` / ``"hist_unbound"`` (S, 2, F) int32 -- the interior runs by the partner's state q at the
+    run's first frame and by dwell time; ``hist[:, q]`` goes to ``dwell_csr_from_hist`` / ``dwell_fit`` --, ``"counts"``
+    (S, N) int32, ``"tau"`` (S, N) float32, the first frame with z = 1 or F, and ``"tau_after"`` (S, N) float32, the
+    partner's first bound frame from ``tau`` on, or F (also where ``tau`` is F).  Both values of ``which`` at one seed
+    describe the same rasters."""
+    filt, theta, which, S, N, F = _pair_dwell_inputs("joint_dwell_sample", filt, theta, which, num_samples)
+    return _walk_count(_pair_dwell_launch(filt, theta, which, S, N, F, seed), S, N, F, filt.device, partner=True)
+
+
+def joint_dwell_intervals(filt, theta, which, num_samples, seed=0, sample=None, device_table=False):
+    """``hmm_dwell_intervals`` for one channel of the joint chain: launch A (or its result ``sample`` from
+    ``joint_dwell_sample`` with the same arguments), the exclusive scan of the row counts, and launch B.  Returns the
+    DataFrame of ``dwell_intervals`` and four int64 columns, the partner's state at the run's first frame
+    (``partner_start``), at the frame before it (``partner_before``), at its last frame (``partner_stop``) and at the frame
+    after it (``partner_after``); -1 where that frame does not exist.  With ``device_table`` the pair ``dwell_intervals``
+    returns then, the DataFrame with the four columns."""
+    given = num_samples if sample is None else sample["counts"].shape[0]
+    filt, theta, which, S, N, F = _pair_dwell_inputs("joint_dwell_intervals", filt, theta, which, given)
+    launch = _pair_dwell_launch(filt, theta, which, S, N, F, seed)
+    if sample is None:
+        sample = _walk_count(launch, S, N, F, filt.device, partner=True)
+    out, codes = _walk_emit("joint_dwell_intervals", launch, sample, S, N, filt.device, device_table, partner=True)
+    table = out[0] if device_table else out
+    code = codes.cpu().numpy().astype("int64")
+    exists = (None, table["start_frame"].to_numpy() > 0, None, table["stop_frame"].to_numpy() < F - 1)
+    for bit, name in enumerate(PARTNER_COLUMNS):
+        value = (code >> bit) & 1
+        table[name] = value if exists[bit] is None else value * exists[bit] - (~exists[bit])
+    return out
+
+
+def joint_arrival_order(tau_lead, tau_after, tau_partner, F):
+    """The order of arrival of two channels from first-binding frames, per posterior sample: ``tau_lead`` and ``tau_after``
+    (S, N) of ``joint_dwell_sample`` for the lead channel, ``tau_partner`` (S, N) the partner's own first-binding frame
+    (``tau`` of the other ``which``), ``F`` the number of frames.  Plain torch on the device of ``tau_lead``; it runs on the
+    host as well.  With d = tau_after - tau_lead, defined where the lead binds, returns a dict of (S,) float64 tensors:
+
+    * ``binds``: the share of rows in which the lead binds (tau_lead < F);
+    * ``together`` / ``later`` / ``never``: of those, the shares with d = 0, with d > 0 and the partner following
+      (tau_after < F), and with the partner never following (tau_after = F); they sum to 1;
+    * ``mean_delay``: the mean d over the rows of ``later``;
+    * ``k_after`` = |E| / (sum_E d + sum_C (F - 1 - tau_lead)), E the rows of ``later`` and C those of ``never``;
+    * ``k_base`` = |E0| / (sum_E0 tau_partner + |C0| (F - 1)), E0 = {0 < tau_partner < F}, C0 = {tau_partner = F};
+    * ``ratio`` = k_after / k_base.
+
+    The two k are the maximum-likelihood per-frame probabilities of a geometric waiting time with right censoring: events
+    over frames at risk, for the partner's arrival after the lead has arrived and for its arrival from the start of the
+    record.  A zero denominator gives NaN."""
+    lead, after, own = (torch.as_tensor(x).to(torch.float64) for x in (tau_lead, tau_after, tau_partner))
+    if lead.ndim != 2 or after.shape != lead.shape or own.shape != lead.shape:
+        raise ValueError(f"joint_arrival_order: three (S, N) tensors of one shape, got {tuple(lead.shape)}, "
+                         f"{tuple(after.shape)} and {tuple(own.shape)}")
+    F = int(F)
+    bound = lead < F
+    d = after - lead
+    events = bound & (d > 0) & (after < F)
+    censored = bound & (after == F)
+    n_bound = bound.sum(1).to(torch.float64)
+
+    def quotient(num, den):
+        return torch.where(den > 0, num / den.clamp(min=1e-300), torch.full_like(den, float("nan")))
+
+    def total(x, where):
+        return (x * where).sum(1)
+
+    n_events = events.sum(1).to(torch.float64)
+    k_after = quotient(n_events, total(d, events) + total(F - 1 - lead, censored))
+    base_events, base_censored = (own > 0) & (own < F), own == F
+    k_base = quotient(base_events.sum(1).to(torch.float64), total(own, base_events) + base_censored.sum(1).to(torch.float64) * (F - 1))
+    return {"binds": n_bound / lead.shape[1], "together": quotient((bound & (d == 0)).sum(1).to(torch.float64), n_bound),
+            "later": quotient(n_events, n_bound), "never": quotient(censored.sum(1).to(torch.float64), n_bound),
+            "mean_delay": quotient(total(d, events), n_events), "k_after": k_after, "k_base": k_base,
+            "ratio": quotient(k_after, k_base)}

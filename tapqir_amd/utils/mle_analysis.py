@@ -41,7 +41,8 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
   apart by the population every row drew, and the first-binding frames split by population (``tq_population_dwell``;
   ``population_first_binding`` is host-side torch on S x N numbers and runs anywhere).
 
-Two colour channels smoothed together as one chain (``smooth --joint``) are in ``tapqir_amd/utils/joint_analysis.py``, the
+Two colour channels smoothed together as one chain (``smooth --joint``), with the dwell times of one channel by the other's
+state and the order of arrival (``dwelltime`` / ``ttfb --smooth --joint``), are in ``tapqir_amd/utils/joint_analysis.py``, the
 open last run as a right-censored dwell (``dwelltime --censored``) in ``tapqir_amd/utils/censored_analysis.py``.
 
 There is no CPU path: every entry point raises ``HipExtensionError`` off the device.
@@ -514,12 +515,13 @@ def smooth_sample(filt, theta, num_samples, seed=0, raster=False):
 
 
 # ---- dwell times and first binding of the smoothed chain (`dwelltime --smooth`, `ttfb --smooth`) ----
-def _walk_count(launch, S, N, F, dev, populations=None):
+def _walk_count(launch, S, N, F, dev, populations=None, partner=False):
     """Launch A of a sampler that walks its rasters as it draws them (``tq_smooth_dwell``, ``tq_chain_dwell``,
-    ``tq_population_dwell``): ``launch(**fields)`` fills the argument block's remaining fields and calls the entry point.
-    With ``populations`` = G the histograms are (S, G, F) and the launch also fills ``pop`` (S, N) uint8."""
+    ``tq_population_dwell``, ``tq_pair_dwell``): ``launch(**fields)`` fills the argument block's remaining fields and calls
+    the entry point.  With ``populations`` = G the histograms are (S, G, F) and the launch also fills ``pop`` (S, N) uint8;
+    with ``partner`` they are (S, 2, F) and it also fills ``tau_after`` (S, N) float32."""
     counts = torch.empty(S, N, dtype=torch.int32, device=dev)
-    shape = (S, F) if populations is None else (S, populations, F)
+    shape = (S, 2, F) if partner else (S, F) if populations is None else (S, populations, F)
     hb = torch.zeros(shape, dtype=torch.int32, device=dev)
     hu = torch.zeros(shape, dtype=torch.int32, device=dev)
     tau = torch.empty(S, N, dtype=torch.float32, device=dev)
@@ -528,14 +530,18 @@ def _walk_count(launch, S, N, F, dev, populations=None):
     if populations is not None:
         out["pop"] = torch.empty(S, N, dtype=torch.uint8, device=dev)
         extra["pop"] = _lib.ptr(out["pop"])
+    if partner:
+        out["tau_after"] = torch.empty(S, N, dtype=torch.float32, device=dev)
+        extra["tau_after"] = _lib.ptr(out["tau_after"])
     launch(counts=_lib.ptr(counts), hist_bound=_lib.ptr(hb), hist_unbound=_lib.ptr(hu), tau=_lib.ptr(tau),
            mode=_lib.DWELL_COUNT, **extra)
     return out
 
 
-def _walk_emit(who, launch, sample, S, N, dev, device_table=False):
+def _walk_emit(who, launch, sample, S, N, dev, device_table=False, partner=False):
     """The exclusive scan of the row counts of launch A and launch B of the same sampler; the DataFrame of
-    ``dwell_intervals`` (with ``device_table``, the pair it returns then)."""
+    ``dwell_intervals`` (with ``device_table``, the pair it returns then).  With ``partner`` launch B also fills one uint8
+    per interval, and the result is the pair of that and those ``total`` codes on the device."""
     counts = sample["counts"].contiguous()
     if counts.shape != (S, N) or counts.dtype != torch.int32 or counts.device != dev:
         raise ValueError(f"{who}: sample['counts'] must be int32 ({S}, {N}) on the device of filt")
@@ -543,8 +549,14 @@ def _walk_emit(who, launch, sample, S, N, dev, device_table=False):
     offsets = (csum - counts.reshape(-1)).contiguous()
     total = int(csum[-1].item())
     cols = torch.empty(_lib.DWELL_COLS, max(total, 1), dtype=torch.int32, device=dev)
-    launch(counts=_lib.ptr(counts), offsets=_lib.ptr(offsets), intervals=_lib.ptr(cols), total=total, mode=_lib.DWELL_EMIT)
-    return _interval_frame(cols, total, device_table)
+    extra = {}
+    if partner:
+        codes = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        extra["partner"] = _lib.ptr(codes)
+    launch(counts=_lib.ptr(counts), offsets=_lib.ptr(offsets), intervals=_lib.ptr(cols), total=total, mode=_lib.DWELL_EMIT,
+           **extra)
+    frame = _interval_frame(cols, total, device_table)
+    return (frame, codes[:total]) if partner else frame
 
 
 def _smooth_dwell_launch(filt, theta, S, N, F, seed):
