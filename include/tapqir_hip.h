@@ -1231,6 +1231,70 @@ typedef struct {
 int tq_pair_dwell(const tq_pair_dwell_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Bootstrap refits of the chain over AOIs (`tapqir_amd smooth --refit R`): R replicas of the EM of
+ * tq_multistart_estep / tq_multistart_mstep, each on a resample of the N AOIs with replacement.  A resample is a weight
+ * per AOI -- how often it was drawn -- so p stays shared and no row is gathered: the E-step leaves out the (replica, AOI)
+ * pairs of weight 0, and the M-step multiplies every row by its weight.  theta, rows, the scratch, `active`, `allow` and
+ * the trace have the layouts of the tq_multistart_* section; weights is (R, N) int32 in device memory, non-negative, every
+ * row's sum below 2^31.
+ * Every entry point returns TQ_ERR_ARG, before anything touches the device, for what the tq_multistart_* entry point of the
+ * same role refuses and for a NULL `weights`; tq_refit_weights for N < 1, R < 1 or R > TQ_MULTISTART_MAX, first < 0 or
+ * first + R > 2^31 - 1.
+ *
+ * tq_refit_weights: weights[r, n] = #{ i < N : a(first + r, i) = n }, a(s, i) the resample of tq_rates_estimate and
+ *   tq_hmm_estimate for sample s at the same seed (Philox site 0xA02, the same formula), so one seed resamples the same
+ *   AOIs everywhere; `first` lets the host work in batches without changing any replica's draw.  Grid R, one workgroup
+ *   per replica: it zeroes its row itself -- the caller need not -- and counts with integer atomics, whose result does
+ *   not depend on their order.  Every row sums to N.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t* weights;            /* (R, N) out */
+  int32_t N, R;
+  int32_t first;               /* replica r is sample first + r of the stream */
+  uint64_t seed;
+} tq_refit_weights_args;
+
+int tq_refit_weights(const tq_refit_weights_args* a, void* stream);
+
+/* tq_refit_estep: tq_multistart_estep on the grid (N, R) with the weights.  The workgroup of a pair with
+ * weights[r, n] == 0, like that of a replica with active[r] == 0, returns before its first shuffle and writes nothing:
+ * rows[r, n] and filt[r, n] keep what they held.  Where the weight is positive it writes the bits of tq_multistart_estep. */
+typedef struct {
+  const float* p;              /* (N, F) p(z = 1) of the fit, shared by the replicas */
+  const double* theta;         /* (R, M * M + M); device memory */
+  double* filt;                /* (R, N, F, M) scratch */
+  double* rows;                /* (R, N, TQ_HMM_COLS(M)) out, where weights[r, n] > 0 */
+  const int32_t* active;       /* (R); device memory; or NULL: every replica runs */
+  const int32_t* weights;      /* (R, N); device memory */
+  int32_t N, F, R;
+  int32_t U, B;                /* unbound and bound states, M = U + B */
+  double prior;
+} tq_refit_estep_args;
+
+int tq_refit_estep(const tq_refit_estep_args* a, void* stream);
+
+/* tq_refit_mstep: grid R, one workgroup per replica.  sums_j = sum_n weights[r, n] rows[r, n, j] and
+ * W = sum_n weights[r, n], thread t taking rows t, t + 256, ... and a fixed tree after it -- the order of additions of
+ * tq_multistart_mstep; a row of weight 0 is skipped and never read, so it may hold anything, NaN included.  Then the
+ * M-step of tq_multistart_mstep under `allow` with W in the place of N, into theta[r], and the weighted log evidence
+ * sum_n weights[r, n] loglik_n into trace[r * T + it].  With every weight 1 theta and the trace are those of
+ * tq_multistart_mstep bit for bit.  W = 0 leaves A[r] as it is and sets rho[r] uniform.  An inactive replica keeps
+ * theta[r] and writes no trace entry. */
+typedef struct {
+  const double* rows;          /* (R, N, TQ_HMM_COLS(M)) of tq_refit_estep */
+  double* theta;               /* (R, M * M + M) in / out; device memory */
+  double* trace;               /* (R, T): trace[r * T + it] out */
+  const int32_t* active;       /* (R); device memory; or NULL */
+  const int32_t* weights;      /* (R, N); device memory */
+  int32_t N, it;
+  int32_t T, R;                /* entries of a replica's trace, T > it; replicas */
+  int32_t U, B;
+  uint32_t allow;              /* topology mask, M * M bits */
+} tq_refit_mstep_args;
+
+int tq_refit_mstep(const tq_refit_mstep_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame
  * decode of GlimpseDataset.__getitem__ (168-186: big-endian int16 + 2^15) and the offset-region value counts

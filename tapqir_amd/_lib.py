@@ -228,6 +228,7 @@ EXPORTS = [
     "tq_mixture_mstep", "tq_mixture_count", "tq_mixture_estimate",  # ... tapqir_amd/_lib_mixture.py
     "tq_population_dwell",
     "tq_dwell_censored_hist", "tq_dwell_censored_fit", "tq_dwell_survival",  # ... tapqir_amd/_lib_censored.py
+    "tq_refit_weights", "tq_refit_estep", "tq_refit_mstep",  # ... tapqir_amd/_lib_refit.py
 ]
 
 _lib = None

@@ -1245,11 +1245,12 @@ def _smooth_multistart_options(U, B, restarts, restart_seed, forbid, logger, mix
 
 
 def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci, bootstrap, seed, progress_bar,
-                       multistart=None):
+                       multistart=None, refit=None):
     """`smooth` with U + B > 2 hidden states: ``<model>_smooth-u<U>b<B>.tpqr`` and, per channel,
     ``<model>_smooth-u<U>b<B>-channel<c>.csv``.  AOIs outside the mask keep the fit's z_probs and have NaN state
     probabilities and state 255.  With ``multistart`` (``--restarts`` / ``--forbid``, section 26) every channel is fitted
-    by ``hmm_fit_restarts`` and the file gains ``restart_logliks``, ``restart_best`` and ``topology``."""
+    by ``hmm_fit_restarts`` and the file gains ``restart_logliks``, ``restart_best`` and ``topology``.  With ``refit``
+    (``--refit``, section 33) the files of ``_smooth_refit`` are written next to them."""
     import pandas as pd
     import torch
 
@@ -1275,6 +1276,7 @@ def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci
                     "restart_logliks": torch.zeros(data.C, multistart["restarts"] + 1, dtype=torch.float64),
                     "restart_best": torch.zeros(data.C, dtype=torch.int64),
                     "topology_by_channel": torch.ones(data.C, M, M, dtype=torch.bool)})
+    refits = []
     try:
         dev = torch.device("cuda")
         for c in range(data.C):
@@ -1336,11 +1338,71 @@ def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci
             out["prior"][c] = prior
             out["bic"][c] = fit["bic"]
             out["loglik_trace"].append(fit["trace"].cpu())
+            if refit:
+                # the topology in the canonical order of the states, as theta is
+                allow = fit["allow"] if multistart is not None else None
+                refits.append(_smooth_refit(cd, stem, c, p, prior, theta, U, B, refit, allow, num_iter, tol, ci, progress_bar,
+                                            logger))
         torch.save(out, cd / f"{stem}.tpqr")
         logger.info(f"Saved the smoothed posterior in {stem}.tpqr file")
+        if refit:
+            _smooth_refit_save(cd, stem, refits, refit, U, B, logger)
     except HipExtensionError:
         logger.exception("smooth failed: it needs an AMD GPU (--cuda) and the built HIP library")
         raise typer.Exit(1)
+
+
+def _smooth_refit(cd, stem, c, p, prior, theta, U, B, refit, allow, num_iter, tol, ci, progress_bar, logger):
+    """`smooth --refit R` for one channel: ``hmm_fit_refits`` from the fitted ``theta`` (M * M + M)
+    and ``<stem>-refit-channel<c>.csv`` with the row labels of the channel CSV -- every A_ij, every state's mean dwell
+    1 / (1 - A_ii), the class-level kon and koff from the expected pair counts, as `smooth` forms them -- and the columns
+    EM (replica 0: the data as they are), Mean, SE (the standard deviation) and the percentile interval over the refits
+    that met ``--tol``.  Returns the result of ``hmm_fit_refits``."""
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.utils.mle_analysis import estimand_summary, hmm_fit_refits
+
+    M, R = U + B, refit["refits"]
+    fit = hmm_fit_refits(p, prior, theta, U, B, R, seed=refit["seed"], allow=allow, num_iter=num_iter, tol=tol,
+                         progress_bar=progress_bar)
+    A, pairs = fit["thetas"][:, : M * M].reshape(R + 1, M, M), fit["pairs"]
+    values = {f"A{i}{j}": A[:, i, j] for i in range(M) for j in range(M)}
+    values.update({f"dwell{i}": 1.0 / (1.0 - A[:, i, i]) for i in range(M)})
+    values["kon"] = pairs[:, :U, U:].sum((1, 2)) / pairs[:, :U].sum((1, 2))
+    values["koff"] = pairs[:, U:, :U].sum((1, 2)) / pairs[:, U:].sum((1, 2))
+    keep = torch.tensor(fit["converged"][1:], dtype=torch.bool)
+    left_out = R - int(keep.sum())
+    logger.info(f"{R} refits of the chain on resampled AOIs (seed {refit['seed']}): {left_out} did not converge to --tol "
+                f"{tol:g} within {num_iter} iterations and {'are' if left_out != 1 else 'is'} left out of the summary")
+    if not fit["converged"][0]:
+        logger.warning(f"smooth: the refit of the data as they are did not converge to --tol {tol:g} within {num_iter} "
+                       f"iterations")
+    pct = f"{ci * 100:g}%"
+    results = pd.DataFrame(columns=["EM", "Mean", "SE", f"{pct} LL", f"{pct} UL"], dtype=float)
+    for name, x in values.items():
+        x = x.double()
+        kept = x[1:][keep]
+        row = estimand_summary(kept, ci)
+        se = kept[torch.isfinite(kept)].std().item() if int(torch.isfinite(kept).sum()) > 1 else float("nan")
+        results.loc[name] = [x[0].item(), row["mean"], se, row["ll"], row["ul"]]
+    results.to_csv(cd / f"{stem}-refit-channel{c}.csv")
+    logger.info(f"Saved the standard errors and intervals of the refits in {stem}-refit-channel{c}.csv file")
+    return fit
+
+
+def _smooth_refit_save(cd, stem, fits, refit, U, B, logger):
+    """``<stem>-refit.tpqr``: per channel the refitted chains, their weighted log evidences and pair counts, the iteration
+    counts and the converged flags; the seed and R."""
+    import torch
+
+    out = {"thetas": torch.stack([f["thetas"] for f in fits]), "logliks": torch.stack([f["logliks"] for f in fits]),
+           "pairs": torch.stack([f["pairs"] for f in fits]),
+           "converged": torch.tensor([f["converged"] for f in fits], dtype=torch.bool),
+           "iterations": torch.tensor([f["iterations"] for f in fits], dtype=torch.int64),
+           "seed": refit["seed"], "refits": refit["refits"], "unbound": U, "bound": B}
+    torch.save(out, cd / f"{stem}-refit.tpqr")
+    logger.info(f"Saved the refitted chains in {stem}-refit.tpqr file")
 
 
 def _smooth_mixture_options(populations, U, B, joint, structure, restarts, restart_seed, forbid, logger):
@@ -1599,6 +1661,8 @@ def smooth(
     populations: int = typer.Option(1, "--populations", help="Populations of AOIs, each with a chain of its own (1 to 4): a mixture of chains"),
     joint: Optional[str] = typer.Option(None, "--joint", help="A,B: smooth the colour channels A and B together as one chain of four states"),
     structure: Optional[str] = typer.Option(None, "--structure", help="With --joint: auto (the lowest BIC, the default), independent, a-drives-b, b-drives-a, coupled or full"),
+    refit: int = typer.Option(0, "--refit", min=0, max=4096, help="Bootstrap refits of the chain over AOIs: the standard error and interval of the EM values"),
+    refit_seed: int = typer.Option(0, "--refit-seed", help="Seed of the resamples of --refit"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -1634,6 +1698,13 @@ def smooth(
     ``--restart-seed`` and ``--forbid`` apply, at (1, 1) too.  Only ``<model>_smooth-u<U>b<B>g<G>.tpqr`` (with every AOI's
     population probabilities) and ``<model>_smooth-u<U>b<B>g<G>-channel<c>.csv`` (weight, matrix, dwells and rates of
     every population) are written.
+
+    With ``--refit R`` (1 to 4096) the EM of the single chain, at any (U, B) and under ``--forbid``, is run again from the
+    fitted values on R resamples of the AOIs with replacement (``--refit-seed``), side by side.  The
+    ``Mean`` / ``LL`` / ``UL`` of the channel CSV come from rasters drawn at the fitted chain and leave the uncertainty of
+    the chain itself out; ``<model>_smooth<suffix>-refit-channel<c>.csv`` has, for the same rows, the EM value, the mean,
+    the standard error and the percentile interval over the refits, and ``<model>_smooth<suffix>-refit.tpqr`` every
+    refitted chain.  No other file changes.  ``--refit`` does not go with ``--joint`` or ``--populations``.
     """
     import pandas as pd
     import torch
@@ -1649,6 +1720,10 @@ def smooth(
         raise typer.Exit(1)
     if model.value == "cosmos" and unbound_states + bound_states > 4:
         logger.error(f"smooth: --unbound-states + --bound-states must be at most 4, got {unbound_states} + {bound_states}")
+        raise typer.Exit(1)
+    if model.value == "cosmos" and refit and (joint is not None or structure is not None or populations != 1):
+        logger.error("smooth: --refit does not go with --joint or --populations: their M-steps (structure constraints, "
+                     "responsibilities) have no weighted form yet")
         raise typer.Exit(1)
     mixture = None
     if model.value == "cosmos":
@@ -1670,7 +1745,7 @@ def smooth(
         return
     if (unbound_states, bound_states) != (1, 1):
         _smooth_multistate(m, mask, cd, logger, unbound_states, bound_states, num_iter, tol, num_samples, ci, bootstrap,
-                           seed, progress_bar, multistart)
+                           seed, progress_bar, multistart, refit and {"refits": refit, "seed": refit_seed})
         return
     data = m.data
     pct = f"{ci * 100:g}%"
@@ -1679,6 +1754,7 @@ def smooth(
            "log_evidence": torch.full((data.N, data.C), float("nan"), dtype=torch.float64),
            "theta": torch.zeros(data.C, 3, dtype=torch.float64), "prior": torch.zeros(data.C, dtype=torch.float64),
            "loglik_trace": [], "mask": mask}
+    refits = []
     try:
         dev = torch.device("cuda")
         for c in range(data.C):
@@ -1712,8 +1788,14 @@ def smooth(
             out["theta"][c] = theta.cpu()
             out["prior"][c] = prior
             out["loglik_trace"].append(fit["trace"].cpu())
+            if refit:  # the general kernels at U = B = 1 from (A, rho) of (kon, koff, pi0)
+                start = torch.tensor([1.0 - kon, kon, koff, 1.0 - koff, 1.0 - pi0, pi0], dtype=torch.float64)
+                refits.append(_smooth_refit(cd, f"{m.name}_smooth", c, p, prior, start, 1, 1,
+                                            {"refits": refit, "seed": refit_seed}, None, num_iter, tol, ci, progress_bar, logger))
         torch.save(out, cd / f"{m.name}_smooth.tpqr")
         logger.info(f"Saved the smoothed posterior in {m.name}_smooth.tpqr file")
+        if refit:
+            _smooth_refit_save(cd, f"{m.name}_smooth", refits, {"refits": refit, "seed": refit_seed}, 1, 1, logger)
     except HipExtensionError:
         logger.exception("smooth failed: it needs an AMD GPU (--cuda) and the built HIP library")
         raise typer.Exit(1)

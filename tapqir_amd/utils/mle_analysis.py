@@ -31,6 +31,9 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
   the class rasters of ``hmm_sample``, walked as they are drawn (``tq_chain_dwell``);
 * ``hmm_random_starts`` / ``hmm_fit_restarts``: the EM of ``hmm_fit`` from several starts fitted side by side, under an
   optional topology of forbidden transitions, and the best of them (``tq_multistart_estep``, ``tq_multistart_mstep``);
+* ``refit_weights`` / ``refit_estep`` / ``refit_mstep`` / ``hmm_fit_refits``: the non-parametric bootstrap of that EM fit
+  over the AOIs -- every resample a weight per AOI, the refits side by side from the fitted theta -- for the uncertainty
+  of theta itself (``tq_refit_weights``, ``tq_refit_estep``, ``tq_refit_mstep``);
 * ``mixture_default_start`` / ``mixture_random_starts`` / ``mixture_mstep`` / ``mixture_fit`` / ``mixture_sample`` /
   ``mixture_estimate`` / ``mixture_viterbi``: a mixture of G such chains over the AOIs -- static heterogeneity, every AOI
   belonging to one population -- fitted by EM from several starts side by side, with the responsibilities, the BIC,
@@ -52,7 +55,7 @@ import ctypes as C
 
 import torch
 
-from tapqir_amd import _lib, _lib_hmm, _lib_mixture, _lib_multistart, _lib_rates, _lib_smooth
+from tapqir_amd import _lib, _lib_hmm, _lib_mixture, _lib_multistart, _lib_rates, _lib_refit, _lib_smooth
 from tapqir_amd.exceptions import HipExtensionError
 
 ADAM_BETAS = (0.9, 0.999)
@@ -1103,6 +1106,158 @@ def hmm_fit_restarts(p, prior, unbound, bound, restarts=8, seed=0, allow=None, s
             "loglik": loglik, "n_params": n_params, "bic": -2.0 * loglik + n_params * math.log(N * F), "order": order,
             "best": best, "logliks": logliks, "thetas": thetas, "traces": trace[:, : max(iterations)], "starts": starts,
             "allow": free[idx][:, idx]}
+
+
+# ---- bootstrap refits of the chain over AOIs (`smooth --refit`) -------------------------------------
+def refit_weights(N, refits, seed=0, first=0, device="cuda"):
+    """One launch of ``tq_refit_weights``: (``refits``, N) int32 on ``device``, row r the number of times each of the N
+    AOIs is drawn by sample ``first`` + r of the bootstrap over AOIs of ``rates_estimate`` / ``hmm_estimate`` at the same
+    ``seed``.  Every row sums to N; ``first`` batches the rows without changing any of them."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise HipExtensionError("refit_weights runs on the HIP device only (no CPU fallback): pass a cuda device")
+    N, R, first = int(N), int(refits), int(first)
+    if N < 1 or not 1 <= R <= _lib_multistart.MULTISTART_MAX or first < 0 or first + R > 2**31 - 1:
+        raise ValueError(f"refit_weights: N must be positive, 1 <= refits <= {_lib_multistart.MULTISTART_MAX} and first "
+                         f"non-negative, got N = {N}, refits = {R}, first = {first}")
+    weights = torch.empty(R, N, dtype=torch.int32, device=device)
+    a = _lib_refit.RefitWeightsArgs(weights=_lib.ptr(weights), N=N, R=R, first=first, seed=int(seed) & (2**64 - 1))
+    _lib.check(_lib_refit.lib().tq_refit_weights(C.byref(a), _stream(weights.device)), "tq_refit_weights")
+    return weights
+
+
+def _refit_weights_arg(who, weights, R, N, device):
+    if (not isinstance(weights, torch.Tensor) or weights.device != device or weights.dtype != torch.int32
+            or weights.shape != (R, N) or not weights.is_contiguous()):
+        raise ValueError(f"{who}: weights must be contiguous int32 ({R}, {N}) on the device of the data")
+    return weights
+
+
+def refit_estep(p, thetas, weights, prior, unbound=1, bound=1, active=None, rows=None, scratch=None):
+    """One launch of ``tq_refit_estep``: ``multistart_estep`` that leaves out every pair (replica r, AOI n) with
+    ``weights[r, n] == 0``, weights (R, N) int32 on the device.  The rows and the scratch of such a pair keep what they
+    held (a fresh ``rows`` holds zeros there); where the weight is positive the rows are those of ``multistart_estep``
+    bit for bit.  Returns ``rows`` (R, N, M * M + M + 1)."""
+    if not isinstance(p, torch.Tensor) or p.device.type != "cuda":
+        raise HipExtensionError("refit_estep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states("refit_estep", unbound, bound)
+    thetas = _multistart_inputs("refit_estep", thetas, (M * M + M,), "thetas")
+    R = thetas.shape[0]
+    p, N, F, _, prior, U, B, M = _hmm_inputs("refit_estep", p, thetas[0], prior, U, B)
+    active = _multistart_active("refit_estep", active, R, p.device)
+    weights = _refit_weights_arg("refit_estep", weights, R, N, p.device)
+    if rows is None:
+        rows = torch.zeros(R, N, _lib_hmm.hmm_cols(M), dtype=torch.float64, device=p.device)
+    if scratch is None:
+        scratch = torch.empty(R, N, F, M, dtype=torch.float64, device=p.device)
+    for name, x, shape in (("rows", rows, (R, N, _lib_hmm.hmm_cols(M))), ("scratch", scratch, (R, N, F, M))):
+        if x.shape != shape or x.dtype != torch.float64 or x.device != p.device or not x.is_contiguous():
+            raise ValueError(f"refit_estep: {name} must be contiguous float64 {shape} on the device of p")
+    a = _lib_refit.RefitEstepArgs(p=_lib.ptr(p), theta=_lib.ptr(thetas), filt=_lib.ptr(scratch), rows=_lib.ptr(rows),
+                                  active=_lib.ptr(active), weights=_lib.ptr(weights), N=N, F=F, R=R, U=U, B=B, prior=prior)
+    _lib.check(_lib_refit.lib().tq_refit_estep(C.byref(a), _stream(p.device)), "tq_refit_estep")
+    return rows
+
+
+def refit_mstep(rows, thetas, weights, trace, it=0, unbound=1, bound=1, allow=None, active=None):
+    """One launch of ``tq_refit_mstep``: ``multistart_mstep`` with row n of replica r counted ``weights[r, n]`` times and
+    the sum of the weights in the place of N; ``trace[r, it]`` receives the weighted log evidence.  A row of weight 0 is
+    never read.  With all weights 1 ``thetas`` and ``trace`` are those of ``multistart_mstep`` bit for bit.  Returns
+    ``thetas``."""
+    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
+        raise HipExtensionError("refit_mstep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states("refit_mstep", unbound, bound)
+    if rows.ndim != 3 or rows.shape[1] < 1:
+        raise ValueError(f"refit_mstep: rows must be (R, N, {_lib_hmm.hmm_cols(M)}) with N >= 1")
+    rows = _multistart_inputs("refit_mstep", rows, (rows.shape[1], _lib_hmm.hmm_cols(M)), "rows")
+    R, N = rows.shape[:2]
+    it = int(it)
+    for name, x, ok in (("thetas", thetas, lambda x: x.shape == (R, M * M + M)),
+                        ("trace", trace, lambda x: x.ndim == 2 and x.shape[0] == R and 0 <= it < x.shape[1])):
+        if (not isinstance(x, torch.Tensor) or x.device != rows.device or x.dtype != torch.float64 or not x.is_contiguous()
+                or not ok(x)):
+            raise ValueError(f"refit_mstep: {name} must be contiguous float64 on the device of rows, thetas "
+                             f"({R}, {M * M + M}) and trace ({R}, T) with 0 <= it < T")
+    active = _multistart_active("refit_mstep", active, R, rows.device)
+    weights = _refit_weights_arg("refit_mstep", weights, R, N, rows.device)
+    bits = _lib_multistart.allow_bits(hmm_allow(allow, M, "refit_mstep").tolist())
+    a = _lib_refit.RefitMstepArgs(rows=_lib.ptr(rows), theta=_lib.ptr(thetas), trace=_lib.ptr(trace), active=_lib.ptr(active),
+                                  weights=_lib.ptr(weights), N=N, it=it, T=trace.shape[1], R=R, U=U, B=B, allow=bits)
+    _lib.check(_lib_refit.lib().tq_refit_mstep(C.byref(a), _stream(rows.device)), "tq_refit_mstep")
+    return thetas
+
+
+REFIT_MAX = 4096  # the largest `refits` of hmm_fit_refits
+
+
+def hmm_fit_refits(p, prior, theta_hat, unbound, bound, refits, seed=0, allow=None, num_iter=200, tol=1e-9, chunk=50,
+                   progress_bar=None):
+    """Non-parametric bootstrap of the EM fit over the AOIs: ``refits`` + 1 fits of the chain of ``hmm_fit`` to the rows
+    of ``p`` (N, F), all warm-started at ``theta_hat`` (M * M + M,), under the topology ``allow``.
+
+    Replica 0 has every weight 1: the data as they are, fitted by the same kernels, the like-for-like reference point of
+    the others.  Replica r >= 1 is the resample of N AOIs with replacement that ``rates_estimate`` / ``hmm_estimate`` draw
+    for sample r - 1 at the same ``seed`` (``refit_weights(N, ., seed, first=r - 1)``), as a weight per AOI.  The replicas
+    are fitted in batches of at most 64 by ``multistart_em`` -- its freezing and its stopping rule, applied to the
+    weighted log evidence -- on ``refit_estep`` / ``refit_mstep``; a replica's result does not depend on its batch.  Every
+    refitted theta is put in the order of ``hmm_canonical_order``.
+
+    Returns ``thetas`` (refits + 1, M * M + M) and ``logliks`` (refits + 1,) -- the weighted log evidence at the final
+    theta -- and ``pairs`` (refits + 1, M, M) -- the weighted expected number of frame pairs in states (i, j) there, whose
+    class blocks give kon and koff as `smooth` defines them -- float64 on the host, in the canonical order;
+    ``traces`` (refits + 1, num_iter) in the order the EM ran in, with NaN after a replica's stop, ``orders`` (the
+    permutation applied to every replica's theta), the lists ``iterations`` and ``converged``, ``seed`` and ``refits``."""
+    num_iter, refits = int(num_iter), int(refits)
+    U, B, M = _hmm_states("hmm_fit_refits", unbound, bound)
+    free = hmm_allow(allow, M, "hmm_fit_refits")
+    if num_iter < 1 or not 0 <= refits <= REFIT_MAX:
+        raise ValueError(f"hmm_fit_refits: num_iter must be positive and refits lie in 0 .. {REFIT_MAX}, got {num_iter} "
+                         f"and {refits}")
+    if not isinstance(p, torch.Tensor) or p.device.type != "cuda":
+        raise HipExtensionError("hmm_fit_refits runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    start = torch.as_tensor(theta_hat, dtype=torch.float64).detach().reshape(-1).to(p.device)
+    p, N, F, start, prior, U, B, M = _hmm_inputs("hmm_fit_refits", p, start, prior, U, B)
+    dev, batch = p.device, _lib_multistart.MULTISTART_MAX
+    if min(refits + 1, batch) * N * F * M * 8 > MULTISTART_SCRATCH_BYTES:
+        raise ValueError(f"hmm_fit_refits: the scratch of a batch of {min(refits + 1, batch)} replicas, N = {N} rows, F = {F} "
+                         f"frames and M = {M} states takes more than {MULTISTART_SCRATCH_BYTES} bytes")
+    out_thetas, out_ll, pairs, traces, orders, iterations, converged = [], [], [], [], [], [], []
+    for g0 in range(0, refits + 1, batch):  # replicas g0 .. g0 + R - 1
+        R = min(batch, refits + 1 - g0)
+        if g0 == 0:
+            parts = [torch.ones(1, N, dtype=torch.int32, device=dev)]
+            if R > 1:
+                parts.append(refit_weights(N, R - 1, seed, 0, dev))
+            weights = torch.cat(parts).contiguous()
+        else:
+            weights = refit_weights(N, R, seed, g0 - 1, dev)
+        thetas = start.reshape(1, -1).repeat(R, 1).contiguous()
+        rows = torch.zeros(R, N, _lib_hmm.hmm_cols(M), dtype=torch.float64, device=dev)
+        scratch = torch.empty(R, N, F, M, dtype=torch.float64, device=dev)
+        trace = torch.full((R, num_iter), float("nan"), dtype=torch.float64, device=dev)
+        active = torch.ones(R, dtype=torch.int32, device=dev)
+        its, conv = multistart_em(
+            lambda: refit_estep(p, thetas, weights, prior, U, B, active, rows, scratch),
+            lambda it: refit_mstep(rows, thetas, weights, trace, it, U, B, free, active), trace, active, num_iter, tol,
+            chunk, progress_bar)
+        refit_estep(p, thetas, weights, prior, U, B, None, rows, scratch)
+        ll = rows[:, :, -1]
+        out_ll.append(torch.where(weights > 0, weights.double() * ll, torch.zeros_like(ll)).sum(1).cpu())
+        drawn = (weights > 0)[:, :, None]  # a row of weight 0 was never written: left out, not multiplied by 0
+        pair = torch.where(drawn, weights.double()[:, :, None] * rows[:, :, : M * M], torch.zeros_like(rows[:, :, : M * M]))
+        pair = pair.sum(1).reshape(R, M, M).cpu()
+        host = thetas.cpu()
+        orders += [hmm_canonical_order(host[r], U, B) for r in range(R)]
+        for r, order in zip(range(R), orders[g0:]):
+            out_thetas.append(hmm_permute(order, M, theta=host[r])["theta"])
+            pairs.append(pair[r][order][:, order])
+        traces.append(trace.cpu())
+        iterations += its
+        converged += conv
+        del scratch
+    return {"thetas": torch.stack(out_thetas), "logliks": torch.cat(out_ll), "pairs": torch.stack(pairs),
+            "traces": torch.cat(traces), "orders": orders,
+            "iterations": iterations, "converged": converged, "seed": int(seed), "refits": refits}
 
 
 # ---- a mixture of chains over the AOIs (`smooth --populations`, DESIGN.md section 29) ------------------------------------
