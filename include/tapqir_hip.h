@@ -1295,6 +1295,84 @@ typedef struct {
 int tq_refit_mstep(const tq_refit_mstep_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The continuous-time hidden Markov chain on the frame timestamps (`tapqir_amd smooth --timed`): the
+ * chain of the tq_hmm_* section with a generator Q in the place of the per-frame matrix A.  The transition from frame f to
+ * f + 1 is exp(Q d_f), d_f the gap between their stamps, so the record need not be equally spaced.
+ *   theta = (Q row-major (M, M), rho (M)): M * M + M doubles in device memory, Q per unit of the gaps.  Every reader
+ *           ignores the stored diagonal, takes a free off-diagonal as max(q_ij, TQ_SMOOTH_RMIN), a forbidden one (cleared
+ *           bit of `allow`, the mask of tq_multistart_mstep; its diagonal bits are not read) as exactly 0, sets
+ *           q_ii = -sum_j q_ij, and floors and renormalises rho as tq_hmm_estep does.
+ *   d     = the D distinct gaps, positive and finite, and cls (F - 1) int32 the class of every gap: the gap between frames
+ *           f and f + 1 is d[cls[f]].  The host scales the gaps so that their median is 1; the floor of a rate then means
+ *           what the floor of a transition probability means per frame.
+ *   P (D, M, M) and K (D, M, M, M, M): P[k] = exp(Q d[k]) and K[k][a][b][i][j] = int_0^d[k] P_ai(s) P_jb(d[k] - s) ds, so
+ *           that sum_b P[k][a][b] = 1 and sum_i K[k][a][b][i][i] = d[k] P[k][a][b].
+ * Every entry point returns TQ_ERR_ARG, before anything touches the device, for a NULL required pointer, U or B < 1,
+ * U + B > TQ_HMM_MAX_STATES, D < 1 (tables, E-step), an `allow` with a bit beyond M * M or a row without a set bit;
+ * tq_timed_table for a gap of d_host that is not finite and positive; tq_timed_estep for N or F < 1, F > TQ_SMOOTH_MAX_F, a
+ * prior outside (0, 1), a NULL cls or cls_host where F > 1, or an entry of cls_host outside [0, D); tq_timed_mstep for
+ * N < 1, it < 0 or T <= it.  d_host and cls_host are the host's copies of d and cls: the checks read them, the kernels the
+ * device's.
+ *
+ * tq_timed_table: one thread per (class, i, j), which carries P and the M x M matrix K[k][.][.][i][j] through a Taylor
+ *   series of the uniformised chain at d / 2^s and s squarings of the pair (P, K); no thread waits on another and there
+ *   are no atomics, so two runs give the same bits.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const double* theta;         /* M * M + M; device memory */
+  const double* d;             /* (D) gaps; device memory */
+  const double* d_host;        /* (D) the same gaps; host memory */
+  double* P;                   /* (D, M, M) out */
+  double* K;                   /* (D, M, M, M, M) out */
+  int32_t D;
+  int32_t U, B;                /* unbound and bound states, M = U + B */
+  uint32_t allow;              /* topology mask, M * M bits */
+} tq_timed_table_args;
+
+int tq_timed_table(const tq_timed_table_args* a, void* stream);
+
+/* tq_timed_estep: tq_hmm_estep -- grid N, one wave per row, its lane ranges, scans, sweeps and lane sums -- with the
+ * transition into frame f read from P[cls[f - 1]].  filt and gamma are those of tq_hmm_estep; gamma may be NULL, and the
+ * rows are then the same bits.  rows[n] keeps TQ_HMM_COLS(M) columns: slot i * M + j, i != j, holds E N_ij, the expected
+ * number of jumps from i to j (0 for a forbidden pair, whatever K holds there); slot i * M + i holds E T_i, the expected
+ * time in state i, in the unit of d; then gamma_0 (M) and the row's log evidence.  With a = a_f, w = l_{f+1} o beta_{f+1}
+ * and c_ab = a_a w_b / sum_ab a_a P_ab w_b, gap f adds sum_ab c_ab K[a][b][i][i] to E T_i and q_ij sum_ab c_ab K[a][b][i][j]
+ * to E N_ij: nothing is divided by P_ab.  F = 1 has no gap and writes gamma_0 and the log evidence only. */
+typedef struct {
+  const float* p;              /* (N, F) p(z = 1) of the fit */
+  const double* theta;         /* M * M + M; device memory */
+  const double* P;             /* (D, M, M) of tq_timed_table at the same theta */
+  const double* K;             /* (D, M, M, M, M) of tq_timed_table */
+  const int32_t* cls;          /* (F - 1); device memory */
+  const int32_t* cls_host;     /* (F - 1) the same indices; host memory */
+  double* filt;                /* (N, F, M) out */
+  double* gamma;               /* (N, F, M) out, or NULL */
+  double* rows;                /* (N, TQ_HMM_COLS(M)) out */
+  int32_t N, F, D;
+  int32_t U, B;
+  uint32_t allow;              /* topology mask, M * M bits */
+  double prior;
+} tq_timed_estep_args;
+
+int tq_timed_estep(const tq_timed_estep_args* a, void* stream);
+
+/* tq_timed_mstep: one workgroup, the order of additions of tq_hmm_mstep.  q_ij = sum_n E N_ij / sum_n E T_i floored at
+ * TQ_SMOOTH_RMIN for a free pair, exactly 0 for a forbidden one, and the stored diagonal minus the row's sum; a state with
+ * sum_n E T_i = 0 keeps its free rates.  rho = the mean gamma_0, floored and renormalised; the summed log evidence goes to
+ * trace[it]. */
+typedef struct {
+  const double* rows;          /* (N, TQ_HMM_COLS(M)) of tq_timed_estep */
+  double* theta;               /* M * M + M in / out; device memory */
+  double* trace;               /* (T): trace[it] out */
+  int32_t N, it;
+  int32_t T;                   /* entries of the trace, T > it */
+  int32_t U, B;
+  uint32_t allow;              /* topology mask, M * M bits */
+} tq_timed_mstep_args;
+
+int tq_timed_mstep(const tq_timed_mstep_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Input side: AOI extraction from raw Glimpse frames.
  * Replaces the per-frame / per-AOI loop of read_glimpse (tapqir/imscroll/glimpse_reader.py:358-392), the frame
  * decode of GlimpseDataset.__getitem__ (168-186: big-endian int16 + 2^15) and the offset-region value counts

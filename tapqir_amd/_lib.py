@@ -229,6 +229,7 @@ EXPORTS = [
     "tq_population_dwell",
     "tq_dwell_censored_hist", "tq_dwell_censored_fit", "tq_dwell_survival",  # ... tapqir_amd/_lib_censored.py
     "tq_refit_weights", "tq_refit_estep", "tq_refit_mstep",  # ... tapqir_amd/_lib_refit.py
+    "tq_timed_table", "tq_timed_estep", "tq_timed_mstep",  # ... tapqir_amd/_lib_timed.py
 ]
 
 _lib = None

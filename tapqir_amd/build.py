@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libtapqir_hip.so")
 SOURCES = ["tq_ksmogn.hip", "tq_xtalk.hip", "tq_cosmos.hip", "tq_glimpse.hip", "tq_aux.hip", "tq_kinetics.hip", "tq_dwell.hip",
            "tq_quantile.hip", "tq_rates.hip", "tq_smooth.hip", "tq_hmm.hip", "tq_multistart.hip", "tq_joint.hip", "tq_mixture.hip",
-           "tq_censored.hip", "tq_refit.hip"]
+           "tq_censored.hip", "tq_refit.hip", "tq_timed.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed"]
 
 

@@ -1223,13 +1223,18 @@ def _smooth_multistart_options(U, B, restarts, restart_seed, forbid, logger, mix
     """The checks of ``--restarts``, ``--restart-seed`` and ``--forbid`` of `smooth`, made where ``--ci`` is checked (after
     the model, before ``--cpu``).  Returns ``{"restarts", "seed", "allow"}``, allow an (M, M) list of booleans.  A mixture
     (``--populations``) has several optima at (1, 1) too, so it takes the options there."""
-    import re
-
     M = U + B
     if (U, B) == (1, 1) and not mixture:
         logger.error("smooth: --restarts, --restart-seed and --forbid need a chain of more than two states "
                      "(--unbound-states, --bound-states): the two-state EM has one optimum and one topology")
         raise typer.Exit(1)
+    return {"restarts": restarts, "seed": restart_seed, "allow": _smooth_forbid(M, forbid, logger)}
+
+
+def _smooth_forbid(M, forbid, logger):
+    """The values of ``--forbid`` of `smooth` as an (M, M) list of booleans, True where the transition is free."""
+    import re
+
     allow = [[True] * M for _ in range(M)]
     for item in forbid or []:
         match = re.fullmatch(r"(\d+)-(\d+)", item.strip())
@@ -1241,7 +1246,7 @@ def _smooth_multistart_options(U, B, restarts, restart_seed, forbid, logger, mix
     if not all(any(row) for row in allow):
         logger.error("smooth: --forbid leaves a state without a free transition")
         raise typer.Exit(1)
-    return {"restarts": restarts, "seed": restart_seed, "allow": allow}
+    return allow
 
 
 def _smooth_multistate(m, mask, cd, logger, U, B, num_iter, tol, num_samples, ci, bootstrap, seed, progress_bar,
@@ -1643,6 +1648,94 @@ def _smooth_joint(m, mask, cd, logger, pair, num_iter, tol, num_samples, ci, boo
         raise typer.Exit(1)
 
 
+def _smooth_timed(m, mask, cd, logger, U, B, allow, frame_time, time_scale, num_iter, tol, progress_bar):
+    """`smooth --timed`: the continuous-time chain on the frames' time stamps --
+    ``data.ttb * time_scale``, or ``arange(F) * frame_time`` -- fitted by ``timed_fit`` next to the per-frame chain of
+    ``hmm_fit`` at the same (U, B).  Writes ``<model>_smooth-timed<suffix>.tpqr`` and, per channel,
+    ``<model>_smooth-timed<suffix>-channel<c>.csv`` with the rates in 1 / s; no other file is touched."""
+    import pandas as pd
+    import torch
+
+    from tapqir_amd.exceptions import HipExtensionError
+    from tapqir_amd.utils.mle_analysis import hmm_fit, timed_fit, timed_gaps
+
+    data, M = m.data, U + B
+    stem = f"{m.name}_smooth-timed{_smooth_suffix(U, B)}"
+    if frame_time is not None:
+        if not frame_time > 0.0:
+            logger.error(f"smooth: --frame-time must be positive, got {frame_time}")
+            raise typer.Exit(1)
+        times = (torch.arange(data.F, dtype=torch.float64) * frame_time)[:, None].expand(data.F, data.C).clone()
+    elif getattr(data, "ttb", None) is None:
+        logger.error("smooth: --timed needs the time stamps of the frames: data.tpqr has no ttb (written by `glimpse`); "
+                     "give --frame-time SECONDS for an equally spaced record")
+        raise typer.Exit(1)
+    else:
+        times = torch.as_tensor(data.ttb).double().reshape(data.F, -1)[:, : data.C] * time_scale
+    for c in range(data.C):
+        try:
+            timed_gaps(times[:, c])
+        except ValueError:
+            logger.error(f"smooth: the time stamps of channel {c} are not finite and strictly increasing")
+            raise typer.Exit(1)
+    topology = torch.tensor(allow, dtype=torch.bool)
+    z_raw = m.params["z_probs"][: data.N, :, :, 1].float()  # (N, F, C)
+    out = {"z_probs": z_raw.clone(), "state_probs": torch.full((*z_raw.shape, M), float("nan")), "z_map": z_raw > 0.5,
+           "log_evidence": torch.full((data.N, data.C), float("nan"), dtype=torch.float64),
+           "theta": torch.zeros(data.C, M * M + M, dtype=torch.float64), "prior": torch.zeros(data.C, dtype=torch.float64),
+           "times": times, "bic": torch.zeros(data.C, dtype=torch.float64), "n_params": 0, "loglik_trace": [],
+           "log_evidence_per_frame": torch.zeros(data.C, dtype=torch.float64), "mask": mask, "unbound": U, "bound": B,
+           "topology_by_channel": torch.ones(data.C, M, M, dtype=torch.bool)}
+    try:
+        dev = torch.device("cuda")
+        for c in range(data.C):
+            logger.info(f"Channel #{c} ({data.channels[c]})")
+            prior = float(torch.as_tensor(m.params["pi"]["Mean"]).reshape(-1, 2)[c, 1])
+            p = z_raw[:, :, c][mask].to(dev)
+            fit = timed_fit(p, prior, times[:, c], U, B, allow=topology, num_iter=num_iter, tol=tol, progress_bar=progress_bar)
+            frame = hmm_fit(p, prior, U, B, num_iter=num_iter, tol=tol, progress_bar=progress_bar)
+            logger.info(f"Continuous-time EM with {U} unbound and {B} bound states: log evidence = {fit['loglik']:.6f}, BIC = "
+                        f"{fit['bic']:.6f} ({fit['n_params']} parameters) after {fit['iterations']} iterations")
+            logger.info(f"Per-frame EM on the same data: log evidence = {frame['loglik']:.6f} ({frame['n_params']} parameters); "
+                        f"the time stamps gain {fit['loglik'] - frame['loglik']:+.6f}")
+            for name, f in (("continuous-time", fit), ("per-frame", frame)):
+                if not f["converged"]:
+                    logger.warning(f"smooth: the {name} EM did not converge to --tol {tol:g} within {f['iterations']} "
+                                   f"iterations")
+            theta = fit["theta"].cpu()
+            Q = theta[: M * M].reshape(M, M)
+            sums = fit["rows"][:, : M * M].sum(0).reshape(M, M).cpu()  # jumps off the diagonal, seconds on it
+            jumps = sums - torch.diag(sums.diagonal())
+            results = pd.DataFrame(columns=["EM"], dtype=float)
+            for i in range(M):
+                for j in range(M):
+                    if i != j:
+                        results.loc[f"q{i}{j}"] = [Q[i, j].item()]
+            for i in range(M):  # mean dwell of state i in seconds, -1 / q_ii
+                results.loc[f"dwell{i}"] = [(-1.0 / Q[i, i]).item()]
+            results.loc["kon"] = [(jumps[:U, U:].sum() / sums.diagonal()[:U].sum()).item()]
+            results.loc["koff"] = [(jumps[U:, :U].sum() / sums.diagonal()[U:].sum()).item()]
+            results.to_csv(cd / f"{stem}-channel{c}.csv")
+            logger.info(f"Saved the rates (1 / s) and dwells (s) in {stem}-channel{c}.csv file")
+            smoothed = fit["gamma"][..., U:].sum(-1).float().cpu()
+            out["z_probs"][:, :, c][mask] = smoothed
+            out["state_probs"][:, :, c][mask] = fit["gamma"].float().cpu()
+            out["z_map"][:, :, c][mask] = smoothed > 0.5
+            out["log_evidence"][:, c][mask] = fit["rows"][:, -1].cpu()
+            out["theta"][c] = theta
+            out["prior"][c] = prior
+            out["bic"][c] = fit["bic"]
+            out["n_params"] = fit["n_params"]
+            out["loglik_trace"].append(fit["trace"].cpu())
+            out["log_evidence_per_frame"][c] = frame["loglik"]
+            out["topology_by_channel"][c] = fit["allow"]  # in the canonical order of the states, as theta is
+        torch.save(out, cd / f"{stem}.tpqr")
+        logger.info(f"Saved the smoothed posterior in {stem}.tpqr file")
+    except HipExtensionError:
+        logger.exception("smooth failed: it needs an AMD GPU (--cuda) and the built HIP library")
+        raise typer.Exit(1)
+
+
 @app.command()
 def smooth(
     model: avail_models = typer.Option("cosmos", help="Tapqir model"),
@@ -1663,6 +1756,9 @@ def smooth(
     structure: Optional[str] = typer.Option(None, "--structure", help="With --joint: auto (the lowest BIC, the default), independent, a-drives-b, b-drives-a, coupled or full"),
     refit: int = typer.Option(0, "--refit", min=0, max=4096, help="Bootstrap refits of the chain over AOIs: the standard error and interval of the EM values"),
     refit_seed: int = typer.Option(0, "--refit-seed", help="Seed of the resamples of --refit"),
+    timed: bool = typer.Option(False, "--timed", help="Fit a continuous-time chain on the frames' time stamps: rates in 1/s for records that are not equally spaced"),
+    frame_time: Optional[float] = typer.Option(None, "--frame-time", help="With --timed: seconds between frames of an equally spaced record, in the place of the stamps of data.tpqr"),
+    time_scale: float = typer.Option(0.001, "--time-scale", help="With --timed: seconds per unit of the time stamps of data.tpqr (Glimpse writes milliseconds)"),
     no_input: bool = typer.Option(False, "--no-input", help="Accepted for compatibility (there are no prompts)."),
     progress_bar=None,
 ):
@@ -1705,6 +1801,17 @@ def smooth(
     the chain itself out; ``<model>_smooth<suffix>-refit-channel<c>.csv`` has, for the same rows, the EM value, the mean,
     the standard error and the percentile interval over the refits, and ``<model>_smooth<suffix>-refit.tpqr`` every
     refitted chain.  No other file changes.  ``--refit`` does not go with ``--joint`` or ``--populations``.
+
+    With ``--timed`` the chain runs in continuous time on the time stamps of the frames: a generator
+    Q in the place of the per-frame matrix, the transition over a gap d its exponential exp(Q d), fitted by EM.  Records
+    whose frame interval changes, that pause for a reagent exchange or that drop frames are not equally spaced, and a
+    per-frame matrix is then the wrong model.  The stamps are ``ttb`` of ``data.tpqr`` times ``--time-scale`` (seconds per
+    unit; Glimpse writes milliseconds), or ``--frame-time SECONDS`` apart.  Runs at any ``--unbound-states`` /
+    ``--bound-states`` and under ``--forbid`` (a forbidden rate is exactly 0), and fits the per-frame chain next to it: the
+    difference of the two log evidences says whether the time stamps matter for the record.  Only
+    ``<model>_smooth-timed<suffix>.tpqr`` and ``<model>_smooth-timed<suffix>-channel<c>.csv`` (every rate in 1 / s, every
+    state's mean dwell in s, the class-level kon and koff) are written.  ``--timed`` does not go with ``--restarts``,
+    ``--refit``, ``--joint``, ``--structure`` or ``--populations``.
     """
     import pandas as pd
     import torch
@@ -1725,6 +1832,20 @@ def smooth(
         logger.error("smooth: --refit does not go with --joint or --populations: their M-steps (structure constraints, "
                      "responsibilities) have no weighted form yet")
         raise typer.Exit(1)
+    if model.value == "cosmos" and timed and (restarts or restart_seed or refit or joint is not None or structure is not None
+                                              or populations != 1):
+        logger.error("smooth: --timed does not go with --restarts, --refit, --joint, --structure or --populations: the "
+                     "replicas of those fits run the per-frame kernels")
+        raise typer.Exit(1)
+    if model.value == "cosmos" and not timed and frame_time is not None:
+        logger.error("smooth: --frame-time needs --timed")
+        raise typer.Exit(1)
+    if model.value == "cosmos" and timed:
+        allow = _smooth_forbid(unbound_states + bound_states, forbid, logger)
+        m, mask, progress_bar = _kinetics_inputs("smooth", model, cuda, progress_bar)
+        _smooth_timed(m, mask, cd, logger, unbound_states, bound_states, allow, frame_time, time_scale, num_iter, tol,
+                      progress_bar)
+        return
     mixture = None
     if model.value == "cosmos":
         mixture = _smooth_mixture_options(populations, unbound_states, bound_states, joint, structure, restarts, restart_seed,

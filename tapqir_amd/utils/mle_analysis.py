@@ -42,7 +42,12 @@ tapqir/main.py:926-1384, and the two-state rates of tapqir/utils/imscroll.py:199
 * ``mixture_dwell_sample`` / ``mixture_dwell_intervals`` / ``population_first_binding``: the outputs of ``hmm_dwell_sample``
   / ``hmm_dwell_intervals`` for the class rasters of ``mixture_sample``, walked as they are drawn, with the histograms kept
   apart by the population every row drew, and the first-binding frames split by population (``tq_population_dwell``;
-  ``population_first_binding`` is host-side torch on S x N numbers and runs anywhere).
+  ``population_first_binding`` is host-side torch on S x N numbers and runs anywhere);
+* ``timed_gaps`` / ``timed_tables`` / ``timed_estep`` / ``timed_mstep`` / ``timed_fit``: the chain of ``hmm_fit`` in
+  continuous time on the frames' time stamps -- a generator Q in the place of the per-frame matrix, the transition over a
+  gap d its exponential exp(Q d), the expected jumps and holding times of a discretely observed Markov process in the
+  E-step -- for records that are not equally spaced (``tq_timed_table``, ``tq_timed_estep``, ``tq_timed_mstep``;
+  ``timed_gaps`` is host-side torch and runs anywhere).
 
 Two colour channels smoothed together as one chain (``smooth --joint``), with the dwell times of one channel by the other's
 state and the order of arrival (``dwelltime`` / ``ttfb --smooth --joint``), are in ``tapqir_amd/utils/joint_analysis.py``, the
@@ -55,7 +60,7 @@ import ctypes as C
 
 import torch
 
-from tapqir_amd import _lib, _lib_hmm, _lib_mixture, _lib_multistart, _lib_rates, _lib_refit, _lib_smooth
+from tapqir_amd import _lib, _lib_hmm, _lib_mixture, _lib_multistart, _lib_rates, _lib_refit, _lib_smooth, _lib_timed
 from tapqir_amd.exceptions import HipExtensionError
 
 ADAM_BETAS = (0.9, 0.999)
@@ -1618,3 +1623,212 @@ def mixture_viterbi(p, thetas, resp, prior, unbound=1, bound=1):
     paths = torch.stack([hmm_viterbi(p, thetas[g], prior, U, B) for g in range(thetas.shape[0])])  # (G, N, F)
     pop = resp.argmax(0)
     return {"path": paths[pop, torch.arange(p.shape[0], device=p.device)], "population_map": pop}
+
+
+# ---- the continuous-time chain on the frame timestamps (`smooth --timed`) ---------------------------
+def timed_gaps(times):
+    """The gap classes of the F time stamps ``times``: ``(d, cls, scale)`` with ``scale`` the median gap, ``d`` (D,) float64
+    the distinct gaps over ``scale`` as ``torch.unique`` returns them, and ``cls`` (F - 1,) int32 the class of every gap,
+    all on the host.  At equal spacing D = 1.  One frame has no gap: d = [1], no class, scale 1.  Raises ``ValueError``
+    unless the stamps are finite and strictly increasing."""
+    t = torch.as_tensor(times).detach().cpu().to(torch.float64).reshape(-1)
+    if t.numel() < 1 or not bool(torch.isfinite(t).all()):
+        raise ValueError("timed_gaps: times must be at least one finite time stamp")
+    gaps = t[1:] - t[:-1]
+    if not bool((gaps > 0).all()) or not bool(torch.isfinite(gaps).all()):
+        raise ValueError("timed_gaps: the time stamps must be strictly increasing")
+    if gaps.numel() == 0:
+        return torch.ones(1, dtype=torch.float64), torch.zeros(0, dtype=torch.int32), 1.0
+    scale = gaps.median().item()
+    d, cls = torch.unique(gaps, return_inverse=True)
+    return d / scale, cls.to(torch.int32), scale
+
+
+def _timed_allow(who, allow, M):
+    return _lib_multistart.allow_bits(hmm_allow(allow, M, who).tolist())
+
+
+def _timed_classes(who, d, cls, F, device):
+    """``d`` and ``cls`` of ``timed_gaps`` as (device d, host d, device cls, host cls, D), checked against F frames."""
+    d_host = torch.as_tensor(d).detach().cpu().to(torch.float64).contiguous().reshape(-1)
+    if d_host.numel() < 1 or not bool(torch.isfinite(d_host).all()) or not bool((d_host > 0).all()):
+        raise ValueError(f"{who}: d must be at least one finite positive gap")
+    if cls is None:
+        return d_host.to(device), d_host, None, None, d_host.numel()
+    cls_host = torch.as_tensor(cls).detach().cpu().to(torch.int32).contiguous().reshape(-1)
+    if cls_host.numel() != F - 1 or (F > 1 and not (0 <= int(cls_host.min()) and int(cls_host.max()) < d_host.numel())):
+        raise ValueError(f"{who}: cls must be {F - 1} class indices in [0, {d_host.numel()})")
+    return d_host.to(device), d_host, cls_host.to(device), cls_host, d_host.numel()
+
+
+def _timed_table(theta, d_dev, d_host, D, U, B, bits, P, K):
+    a = _lib_timed.TimedTableArgs(theta=_lib.ptr(theta), d=_lib.ptr(d_dev), d_host=d_host.data_ptr(), P=_lib.ptr(P),
+                                  K=_lib.ptr(K), D=D, U=U, B=B, allow=bits)
+    _lib.check(_lib_timed.lib().tq_timed_table(C.byref(a), _stream(theta.device)), "tq_timed_table")
+
+
+def timed_tables(theta, d, unbound=1, bound=1, allow=None):
+    """One launch of ``tq_timed_table``: for the chain ``theta`` = (Q row-major, rho) (M * M + M float64 on the device, Q per
+    unit of ``d``) and the D gaps ``d``, ``{"P"}`` (D, M, M) = exp(Q d) and ``{"K"}`` (D, M, M, M, M) with
+    K[k, a, b, i, j] = the integral over the gap of P_ai(s) P_jb(d - s).  ``allow`` (M, M) is the topology of
+    ``hmm_allow``: a forbidden rate is read as exactly 0."""
+    if not isinstance(theta, torch.Tensor) or theta.device.type != "cuda":
+        raise HipExtensionError("timed_tables runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states("timed_tables", unbound, bound)
+    theta = _hmm_theta("timed_tables", theta, M, theta.device)
+    bits = _timed_allow("timed_tables", allow, M)
+    d_dev, d_host, _, _, D = _timed_classes("timed_tables", d, None, 0, theta.device)
+    out = {"P": torch.empty(D, M, M, dtype=torch.float64, device=theta.device),
+           "K": torch.empty(D, M, M, M, M, dtype=torch.float64, device=theta.device)}
+    _timed_table(theta, d_dev, d_host, D, U, B, bits, out["P"], out["K"])
+    return out
+
+
+def _timed_estep(p, N, F, theta, P, K, cls_dev, cls_host, D, prior, U, B, bits, out):
+    gamma = out.get("gamma")
+    a = _lib_timed.TimedEstepArgs(p=_lib.ptr(p), theta=_lib.ptr(theta), P=_lib.ptr(P), K=_lib.ptr(K),
+                                  cls=_lib.ptr(cls_dev) if F > 1 else None, cls_host=cls_host.data_ptr() if F > 1 else None,
+                                  filt=_lib.ptr(out["filt"]), gamma=None if gamma is None else _lib.ptr(gamma),
+                                  rows=_lib.ptr(out["rows"]), N=N, F=F, D=D, U=U, B=B, allow=bits, prior=prior)
+    _lib.check(_lib_timed.lib().tq_timed_estep(C.byref(a), _stream(p.device)), "tq_timed_estep")
+    return out
+
+
+def timed_estep(p, theta, tables, cls, prior, unbound=1, bound=1, allow=None, gamma=True):
+    """One launch of ``tq_timed_estep``: ``hmm_estep`` with the transition from frame f to f + 1 read from
+    ``tables["P"][cls[f]]`` (``timed_tables`` at the same ``theta``, ``cls`` of ``timed_gaps``).  Returns ``{"filt",
+    "gamma"}`` (N, F, M) (no ``gamma`` with ``gamma=False``; the rows are the same bits) and ``"rows"`` (N, M * M + M + 1):
+    off the diagonal the expected number of jumps from state i to state j, on it the expected time in state i in the unit
+    of the gaps, then gamma_0 and the log evidence."""
+    p, N, F, theta, prior, U, B, M = _hmm_inputs("timed_estep", p, theta, prior, unbound, bound)
+    bits = _timed_allow("timed_estep", allow, M)
+    P, K = tables["P"], tables["K"]
+    for name, x, tail in (("P", P, (M, M)), ("K", K, (M, M, M, M))):
+        if (not isinstance(x, torch.Tensor) or x.device != p.device or x.dtype != torch.float64 or not x.is_contiguous()
+                or x.ndim != len(tail) + 1 or tuple(x.shape[1:]) != tail or x.shape[0] != P.shape[0] or x.shape[0] < 1):
+            raise ValueError(f"timed_estep: tables[{name!r}] must be contiguous float64 (D, {', '.join(map(str, tail))}) on "
+                             f"the device of p")
+    D = P.shape[0]
+    cls_host = torch.as_tensor(cls).detach().cpu().to(torch.int32).contiguous().reshape(-1)
+    if cls_host.numel() != F - 1 or (F > 1 and not (0 <= int(cls_host.min()) and int(cls_host.max()) < D)):
+        raise ValueError(f"timed_estep: cls must be {F - 1} class indices in [0, {D})")
+    out = _hmm_buffers(N, F, M, p.device)
+    if not gamma:
+        del out["gamma"]
+    return _timed_estep(p, N, F, theta, P, K, cls_host.to(p.device), cls_host, D, prior, U, B, bits, out)
+
+
+def timed_mstep(rows, theta, trace, it=0, unbound=1, bound=1, allow=None):
+    """One launch of ``tq_timed_mstep``: ``theta`` (M * M + M float64, in place) from the summed ``rows`` of
+    ``timed_estep`` -- q_ij = sum E N_ij / sum E T_i, floored at 1e-9 where free and exactly 0 where ``allow`` forbids it,
+    rho the mean gamma_0 -- and the total log evidence of those rows into ``trace[it]``.  Returns ``theta``."""
+    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
+        raise HipExtensionError("timed_mstep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = _hmm_states("timed_mstep", unbound, bound)
+    cols = _lib_hmm.hmm_cols(M)
+    if rows.ndim != 2 or rows.shape[1] != cols or rows.shape[0] < 1 or rows.dtype != torch.float64 or not rows.is_contiguous():
+        raise ValueError(f"timed_mstep: rows must be contiguous float64 (N, {cols}), N >= 1")
+    for name, x, n in (("theta", theta, M * M + M), ("trace", trace, int(it) + 1)):
+        if (not isinstance(x, torch.Tensor) or x.device != rows.device or x.dtype != torch.float64 or x.ndim != 1
+                or x.numel() < n or not x.is_contiguous() or it < 0):
+            raise ValueError(f"timed_mstep: {name} must be a float64 vector of at least {n} values on the device of rows")
+    a = _lib_timed.TimedMstepArgs(rows=_lib.ptr(rows), theta=_lib.ptr(theta), trace=_lib.ptr(trace), N=rows.shape[0],
+                                  it=int(it), T=trace.numel(), U=U, B=B, allow=_timed_allow("timed_mstep", allow, M))
+    _lib.check(_lib_timed.lib().tq_timed_mstep(C.byref(a), _stream(rows.device)), "tq_timed_mstep")
+    return theta
+
+
+def timed_default_start(unbound, bound):
+    """The deterministic default start of ``timed_fit`` as (Q (M, M), rho (M,)) float64: the off-diagonals of
+    ``hmm_default_start``'s A as rates per median gap -- its first order -- and the diagonal minus the row's sum."""
+    A, rho = hmm_default_start(unbound, bound)
+    Q = A.clone()
+    Q.fill_diagonal_(0.0)
+    Q -= torch.diag(Q.sum(1))
+    return Q, rho
+
+
+def timed_canonical_order(theta, unbound, bound):
+    """The permutation (a list: new state k is old state order[k]) that puts the states of each class in ascending exit
+    rate -- the analogue of descending A_ii; equal values keep their order.  The stored diagonal is not read."""
+    U, B, M = _hmm_states("timed_canonical_order", unbound, bound)
+    Q = theta.detach().cpu().reshape(-1)[: M * M].reshape(M, M).clone()
+    Q.fill_diagonal_(0.0)
+    leave = Q.sum(1).tolist()
+    return sorted(range(U), key=lambda i: leave[i]) + sorted(range(U, M), key=lambda i: leave[i])
+
+
+def timed_fit(p, prior, times, unbound=1, bound=1, allow=None, Q0=None, rho0=None, num_iter=200, tol=1e-9, chunk=50,
+              progress_bar=None):
+    """EM fit of a continuous-time chain of ``unbound`` + ``bound`` hidden states to the rows of ``p`` (N, F) observed at the
+    F time stamps ``times``, from (``Q0``, ``rho0``) -- Q0 in rates per unit of ``times`` -- or from
+    ``timed_default_start``.  Every iteration is three launches (tables, E-step, M-step); the chunks, the stopping rule and
+    the closing E-step are those of ``hmm_fit``.  ``allow`` (M, M) forbids transitions: their rates are exactly 0.
+
+    After the fit the states of each class are put in ascending exit rate (``timed_canonical_order``), in every output
+    alike.  Returns ``theta`` (M * M + M,) with Q in **rates per unit of ``times``**, ``gamma``, ``filt`` (N, F, M), ``rows``
+    (N, M * M + M + 1; the expected times in the unit of ``times``), ``trace``, ``iterations``, ``converged``, ``loglik``,
+    ``n_params`` (free off-diagonals + M - 1), ``bic``, ``order``, ``allow`` (in the order of the outputs) and ``scale``
+    (the median gap, the kernels' unit of time)."""
+    import math
+
+    num_iter = int(num_iter)
+    U, B, M = _hmm_states("timed_fit", unbound, bound)
+    free = hmm_allow(allow, M, "timed_fit")
+    d, cls_host, scale = timed_gaps(times)
+    Q, rho = timed_default_start(U, B)
+    if Q0 is not None:
+        Q = torch.as_tensor(Q0, dtype=torch.float64).cpu() * scale
+    if rho0 is not None:
+        rho = torch.as_tensor(rho0, dtype=torch.float64).cpu()
+    off = ~torch.eye(M, dtype=torch.bool)
+    if (num_iter < 1 or Q.shape != (M, M) or rho.shape != (M,) or not bool((Q[off] >= 0).all()) or not bool((rho >= 0).all())
+            or not bool(torch.isfinite(Q).all()) or not float(rho.sum()) > 0):
+        raise ValueError(f"timed_fit: num_iter must be positive, Q0 ({M}, {M}) with finite non-negative off-diagonal rates and "
+                         f"rho0 ({M},) non-negative with a positive sum")
+    if not isinstance(p, torch.Tensor) or p.device.type != "cuda":
+        raise HipExtensionError("timed_fit runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    Q = torch.where(off & free, Q, torch.zeros_like(Q))
+    Q = Q - torch.diag(Q.sum(1))
+    theta = torch.cat([Q.reshape(-1), rho / rho.sum()]).to(p.device)
+    p, N, F, theta, prior, U, B, M = _hmm_inputs("timed_fit", p, theta, prior, U, B)
+    if cls_host.numel() != F - 1:
+        raise ValueError(f"timed_fit: times must have one stamp per frame, got {cls_host.numel() + 1} for {F} frames")
+    bits = _lib_multistart.allow_bits(free.tolist())
+    d_dev, d_host, cls_dev, cls_host, D = _timed_classes("timed_fit", d, cls_host, F, p.device)
+    P = torch.empty(D, M, M, dtype=torch.float64, device=p.device)
+    K = torch.empty(D, M, M, M, M, dtype=torch.float64, device=p.device)
+    out = _hmm_buffers(N, F, M, p.device)
+    rows_only = {"filt": out["filt"], "rows": out["rows"]}
+    trace = torch.full((num_iter,), float("nan"), dtype=torch.float64, device=p.device)
+    state = {"iterations": 0, "converged": False}
+
+    def em_steps(step0, n):
+        if state["converged"]:
+            return
+        for it in range(step0, step0 + n):
+            _timed_table(theta, d_dev, d_host, D, U, B, bits, P, K)
+            _timed_estep(p, N, F, theta, P, K, cls_dev, cls_host, D, prior, U, B, bits, rows_only)
+            timed_mstep(out["rows"], theta, trace, it, U, B, free)
+        state["iterations"] = step0 + n
+        ll = trace[: step0 + n].cpu()
+        gain = ll[1:] - ll[:-1]
+        state["converged"] = bool((gain <= tol * ll[1:].abs()).any())
+
+    _run_chunks(em_steps, num_iter, chunk, progress_bar)
+    _timed_table(theta, d_dev, d_host, D, U, B, bits, P, K)
+    _timed_estep(p, N, F, theta, P, K, cls_dev, cls_host, D, prior, U, B, bits, out)
+    order = timed_canonical_order(theta, U, B)
+    out = hmm_permute(order, M, theta=theta, **out)
+    ix = torch.as_tensor(order)
+    # back to the unit of `times`: rates over the median gap, expected times times it
+    unit = torch.ones(M * M + M, dtype=torch.float64, device=p.device)
+    unit[: M * M] = 1.0 / scale
+    out["theta"] = out["theta"] * unit
+    rows = out["rows"]
+    diag = torch.arange(M, device=p.device) * (M + 1)
+    rows[:, diag] = rows[:, diag] * scale
+    loglik = rows[:, -1].sum().item()
+    n_params = int(free.sum()) - M + (M - 1)
+    return {**out, "trace": trace[: state["iterations"]], **state, "loglik": loglik, "n_params": n_params,
+            "bic": -2.0 * loglik + n_params * math.log(N * F), "order": order, "allow": free[ix][:, ix], "scale": scale}
