@@ -1,7 +1,8 @@
 // tq_chain_dev.h -- device-only halves of the hidden-Markov kernels over MxM products, shared by tq_hmm.hip,
-// tq_multistart.hip and tq_joint.hip (bodies in tq_hmm.h): the wave shuffles of a product, the two exclusive scans, the
-// E-step of one row by one wave, and the M-step's sum of rows.  Only those three units include it: no header that the g++
-// host build reads may, and tests/hostcheck/chain_host.h is its mirror on arrays.
+// tq_multistart.hip, tq_joint.hip, tq_refit.hip and tq_timed.hip (bodies in tq_hmm.h): the wave shuffles of a product, the
+// two exclusive scans, the E-step of one row by one wave -- whatever the chain: it reaches the bodies as `m`, with what it
+// overloads of tq_chain_step and tq_chain_pair -- and the M-step's sum of rows.  Only .hip units include it: no header
+// that the g++ host build reads may, and tests/hostcheck/chain_host.h is its mirror on arrays.
 #pragma once
 #include <hip/hip_runtime.h>
 

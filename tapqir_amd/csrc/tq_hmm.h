@@ -4,10 +4,14 @@
 //     class, tq_smooth_evidence;
 //   * products of MxM matrices kept in range by powers of two, and what one lane of the E-step does with its chunk of
 //     frames (tq_smooth_lane_range): the chunk product, the forward sweep from the chunk's exclusive prefix, the backward
-//     sweep from its exclusive suffix with the pair marginals.  These tq_chain_* bodies and the Viterbi row see the chain
-//     as anything with A[M][M] and rho[M], and a frame's emission through a callable em(f, l): TqHmmEmit here, TqJointEmit
-//     in tq_joint.h.  Every chain with M x M products runs this one text;
-//   * the M-step of the summed rows, the Viterbi path of a row in hidden states, and the backward sampler's thresholds;
+//     sweep from its exclusive suffix with the pair marginals.  These tq_chain_* bodies see the chain as anything with
+//     rho[M], a frame's emission through a callable em(f, l) -- TqHmmEmit here, TqJointEmit in tq_joint.h, TqTimedEmit in
+//     tq_timed.h -- and ask the chain for two things: the transition into frame f, tq_chain_step, and what the pair
+//     (g - 1, g) adds to a lane's sums, tq_chain_pair.  A chain with A[M][M] gets both from here: one A for every frame,
+//     and the pair marginals.  The timed chain of tq_timed.h overloads both, and of the bodies tq_chain_forward alone,
+//     for the rounding of its normaliser.  Every chain with M x M products runs this text;
+//   * the M-step of the summed rows, the Viterbi path of a row in hidden states (tq_chain_viterbi_row: any chain with
+//     A[M][M] and rho[M], the emission logarithms through a callable), and the backward sampler's thresholds;
 //   * the sampler's uniforms in its order of draws, and a row drawn backwards and walked, as it is drawn, into runs of
 //     equal class (tq_chain_dwell).
 // The two-state bodies of tq_smooth.h stay apart on purpose: their layout differs (filt holds a_f(1) alone, gamma's row
@@ -135,22 +139,62 @@ TQ_HD TqHmmMat<M> tq_hmm_mul(const TqHmmMat<M>& x, const TqHmmMat<M>& y) {
   return r;
 }
 
-// product of M_f = A diag(l_f) over the lane's frames; M_0 has every row equal to rho o l_0, so that every prefix that
-// holds frame 0 has rows proportional to a_f.  No frames: the identity.
+// ---- what the tq_chain_* bodies ask of a chain --------------------------------------------------------------------------
+// tq_chain_step<M>(m, f): the transition into frame f, anything with A(i, j), fetched once per frame.  Frame 0 has none:
+// the bodies ask all the same and discard what they compute from it, so a chain must return something readable there.
+// tq_chain_pair<M>(m, t, a, w, acc): adds to acc[0 .. M * M) what the pair (g - 1, g) contributes, given the transition t
+// into g, a = a_{g-1} and w = l_g o beta_g.
+// These two are for a chain with A[M][M]: one A for every frame, and the pair marginals
+// xi_{g-1}(i, j) ~ a_{g-1}(i) A[i][j] l_g(j) beta_g(j), so that acc[i * M + j] += E n_ij.  A chain of another kind
+// overloads both on its own type (tq_timed.h).
+template <int M>
+struct TqChainStep {
+  const double (&a)[M][M];
+  TQ_HD double A(int i, int j) const { return a[i][j]; }
+};
+
+template <int M, class Chain>
+TQ_HD TqChainStep<M> tq_chain_step(const Chain& m, int) {
+  return TqChainStep<M>{m.A};
+}
+
+template <int M, class Chain, class Step>
+TQ_HD void tq_chain_pair(const Chain&, const Step& t, const double* a, const double* w, double* acc) {
+  double x[M][M], tot = 0.0;
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    double rs = 0.0;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      x[i][j] = a[i] * t.A(i, j) * w[j];
+      rs += x[i][j];
+    }
+    tot += rs;
+  }
+  const double rt = 1.0 / tot;
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) acc[i * M + j] += x[i][j] * rt;
+}
+
+// product of M_f = A_f diag(l_f) over the lane's frames, A_f the transition into f; M_0 has every row equal to rho o l_0,
+// so that every prefix that holds frame 0 has rows proportional to a_f.  No frames: the identity.
 template <int M, class Chain, class Emit>
 TQ_HD TqHmmMat<M> tq_chain_chunk(const Chain& m, const Emit& em, int lo, int hi) {
   TqHmmMat<M> c = tq_hmm_identity<M>();
   for (int f = lo; f < hi; ++f) {
     double l[M];
     em(f, l);
+    const auto a = tq_chain_step<M>(m, f);
     TqHmmMat<M> t;
 #pragma unroll
     for (int i = 0; i < M; ++i)
 #pragma unroll
       for (int j = 0; j < M; ++j) {
-        double s = c.m[i][0] * m.A[0][j];
+        double s = c.m[i][0] * a.A(0, j);
 #pragma unroll
-        for (int k = 1; k < M; ++k) s += c.m[i][k] * m.A[k][j];
+        for (int k = 1; k < M; ++k) s += c.m[i][k] * a.A(k, j);
         t.m[i][j] = (f == 0 ? m.rho[j] : s) * l[j];
       }
     tq_hmm_rescale(t);
@@ -194,11 +238,12 @@ TQ_HD double tq_chain_forward(const Chain& m, const Emit& em, int lo, int hi, co
   for (int f = lo; f < hi; ++f) {
     double l[M], u[M], c = 0.0;
     em(f, l);
+    const auto a = tq_chain_step<M>(m, f);
 #pragma unroll
     for (int j = 0; j < M; ++j) {
-      double s = v[0] * m.A[0][j];
+      double s = v[0] * a.A(0, j);
 #pragma unroll
-      for (int k = 1; k < M; ++k) s += v[k] * m.A[k][j];
+      for (int k = 1; k < M; ++k) s += v[k] * a.A(k, j);
       u[j] = (f == 0 ? m.rho[j] : s) * l[j];
       c += u[j];
     }
@@ -216,9 +261,10 @@ TQ_HD double tq_chain_forward(const Chain& m, const Emit& em, int lo, int hi, co
 }
 
 // Backward sweep over [lo, hi), g = hi - 1 .. lo, from beta_{hi-1} = b0.  Frame g gives gamma_g, and with a_{g-1} -- the
-// lane's own, or v = a_{lo-1} of its prefix -- the pair marginals xi_{g-1}(i, j) ~ a_{g-1}(i) A[i][j] l_g(j) beta_g(j):
-// the pair (g - 1, g) belongs to the lane that owns g.  acc[i * M + j] += E n_ij; acc[M * M + i] = gamma_0(i) in the lane
-// that owns frame 0.  GAMMA = false stores no gamma_g and does not read `gam`; the sums are the same.
+// lane's own, or v = a_{lo-1} of its prefix -- and w = l_g o beta_g what the pair (g - 1, g) adds to acc[0 .. M * M)
+// (tq_chain_pair; the pair marginals unless the chain says otherwise): the pair belongs to the lane that owns g.
+// acc[M * M + i] = gamma_0(i) in the lane that owns frame 0.  GAMMA = false stores no gamma_g and does not read `gam`; the
+// sums are the same.
 template <int M, bool GAMMA, class Chain, class Emit>
 TQ_HD void tq_chain_backward(const Chain& m, const Emit& em, int lo, int hi, const double* b0, const double* v,
                              const double* filt, double* gam, double* acc) {
@@ -242,35 +288,23 @@ TQ_HD void tq_chain_backward(const Chain& m, const Emit& em, int lo, int hi, con
       for (int i = 0; i < M; ++i) acc[M * M + i] = r[i];
       break;
     }
-    double l[M], w[M], x[M][M], tot = 0.0;
+    double l[M], w[M], a[M];
     em(g, l);
+    const auto t = tq_chain_step<M>(m, g);
 #pragma unroll
     for (int j = 0; j < M; ++j) w[j] = l[j] * b[j];
 #pragma unroll
-    for (int i = 0; i < M; ++i) {
-      const double pi = g > lo ? filt[(int64_t)(g - 1) * M + i] : v[i];  // a_{g-1}(i)
-      double rs = 0.0;
-#pragma unroll
-      for (int j = 0; j < M; ++j) {
-        x[i][j] = pi * m.A[i][j] * w[j];
-        rs += x[i][j];
-      }
-      tot += rs;
-    }
-    const double rt = 1.0 / tot;
-#pragma unroll
-    for (int i = 0; i < M; ++i)
-#pragma unroll
-      for (int j = 0; j < M; ++j) acc[i * M + j] += x[i][j] * rt;
-    // beta_{g-1} = A (l_g o beta_g), scaled by a power of two
+    for (int i = 0; i < M; ++i) a[i] = g > lo ? filt[(int64_t)(g - 1) * M + i] : v[i];  // a_{g-1}(i)
+    tq_chain_pair<M>(m, t, a, w, acc);
+    // beta_{g-1} = A_g (l_g o beta_g), scaled by a power of two
     double bs = 0.0;
 #pragma unroll
     for (int i = 0; i < M; ++i) {
-      double t = m.A[i][0] * w[0];
+      double u = t.A(i, 0) * w[0];
 #pragma unroll
-      for (int j = 1; j < M; ++j) t += m.A[i][j] * w[j];
-      b[i] = t;
-      bs += t;
+      for (int j = 1; j < M; ++j) u += t.A(i, j) * w[j];
+      b[i] = u;
+      bs += u;
     }
     int e;
     (void)frexp(bs, &e);

@@ -56,10 +56,7 @@ extern "C" int tq_hmm_mstep(const tq_hmm_mstep_args* a, void* stream) {
     tq_set_error("tq_hmm_mstep: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->N < 1 || a->it < 0) {
-    tq_set_error("tq_hmm_mstep: N must be positive and it non-negative");
-    return TQ_ERR_ARG;
-  }
+  if (!tq_chain_iteration_ok("tq_hmm_mstep", a->N, a->it)) return TQ_ERR_ARG;
   if (!tq_chain_states_ok("tq_hmm_mstep", a->U, a->B)) return TQ_ERR_ARG;
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_hmm_mstep_kernel<MM>), dim3(1), dim3(TQ_SMOOTH_MSTEP_THREADS), 0,
                                                   (hipStream_t)stream, *a));

@@ -30,7 +30,7 @@ static inline int tq_launch_status(const char* what) {
     default: { constexpr int KK = 4; __VA_ARGS__; } break;           \
   }
 
-// ---- the hidden-Markov entry points (tq_hmm.hip, tq_multistart.hip, tq_joint.hip) ---------------------------------------
+// ---- the hidden-Markov entry points (tq_hmm.hip and every chain unit after it) ------------------------------------------
 // runs `...` with the compile-time constant MM = M, which tq_chain_states_ok has checked to be 2, 3 or 4
 #define TQ_HMM_SWITCH_M(M, ...)  \
   switch (M) {                   \
@@ -65,6 +65,20 @@ static inline bool tq_chain_frames_ok(const char* who, int N, int F) {
 static inline bool tq_chain_states_ok(const char* who, int U, int B) {
   return tq_chain_require(U >= 1 && B >= 1 && U + B <= TQ_HMM_MAX_STATES, who,
                           "U and B must be at least 1 and U + B at most " TQ_STR(TQ_HMM_MAX_STATES));
+}
+// an M-step: N rows, iteration `it` of a trace of T entries
+static inline bool tq_chain_iteration_ok(const char* who, int N, int it) {
+  return tq_chain_require(N >= 1 && it >= 0, who, "N must be positive and it non-negative");
+}
+// `whose` says whose trace it is, as the text names it: "the trace of a replica"
+static inline bool tq_chain_trace_ok(const char* who, int it, int T, const char* whose) {
+  char what[120];
+  snprintf(what, sizeof(what), "T must exceed it (%s has T entries)", whose);
+  return tq_chain_require(T > it, who, what);
+}
+// ok = tq_multistart_allow_ok(allow, U + B) of tq_multistart.h, which only the units that take a mask include
+static inline bool tq_chain_allow_ok(const char* who, bool ok) {
+  return tq_chain_require(ok, who, "allow must have no bit beyond M * M and a free entry in every row");
 }
 static inline bool tq_chain_replicas_ok(const char* who, int R) {
   return tq_chain_require(R >= 1 && R <= TQ_MULTISTART_MAX, who, "R must be at least 1 and at most " TQ_STR(TQ_MULTISTART_MAX));

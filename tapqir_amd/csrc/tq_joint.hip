@@ -70,14 +70,9 @@ extern "C" int tq_joint_mstep(const tq_joint_mstep_args* a, void* stream) {
     tq_set_error("tq_joint_mstep: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->N < 1 || a->it < 0) {
-    tq_set_error("tq_joint_mstep: N must be positive and it non-negative");
+  if (!tq_chain_iteration_ok("tq_joint_mstep", a->N, a->it) ||
+      !tq_chain_trace_ok("tq_joint_mstep", a->it, a->T, "the trace of a replica"))
     return TQ_ERR_ARG;
-  }
-  if (a->T <= a->it) {
-    tq_set_error("tq_joint_mstep: T must exceed it (the trace of a replica has T entries)");
-    return TQ_ERR_ARG;
-  }
   if (!tq_chain_replicas_ok("tq_joint_mstep", a->R)) return TQ_ERR_ARG;
   for (int r = 0; r < a->R; ++r)
     if (!tq_joint_structure_ok(a->structure[r])) {

@@ -92,23 +92,16 @@ extern "C" int tq_mixture_mstep(const tq_mixture_mstep_args* a, void* stream) {
     tq_set_error("tq_mixture_mstep: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->N < 1 || a->it < 0) {
-    tq_set_error("tq_mixture_mstep: N must be positive and it non-negative");
+  if (!tq_chain_iteration_ok("tq_mixture_mstep", a->N, a->it) ||
+      !tq_chain_trace_ok("tq_mixture_mstep", a->it, a->T, "the trace of a start"))
     return TQ_ERR_ARG;
-  }
-  if (a->T <= a->it) {
-    tq_set_error("tq_mixture_mstep: T must exceed it (the trace of a start has T entries)");
-    return TQ_ERR_ARG;
-  }
   if (!tq_chain_states_ok("tq_mixture_mstep", a->U, a->B) || !tq_mixture_pops_ok("tq_mixture_mstep", a->G)) return TQ_ERR_ARG;
   if (a->P < 1 || a->P > TQ_MULTISTART_MAX / a->G) {
     tq_set_error("tq_mixture_mstep: P must be at least 1 and P * G at most " TQ_STR(TQ_MULTISTART_MAX));
     return TQ_ERR_ARG;
   }
-  if (!tq_multistart_allow_ok(a->allow, a->U + a->B)) {
-    tq_set_error("tq_mixture_mstep: allow must have no bit beyond M * M and a free entry in every row");
+  if (!tq_chain_allow_ok("tq_mixture_mstep", tq_multistart_allow_ok(a->allow, a->U + a->B)))
     return TQ_ERR_ARG;
-  }
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_mixture_mstep_kernel<MM>), dim3((unsigned)a->P),
                                                   dim3(TQ_SMOOTH_MSTEP_THREADS), 0, (hipStream_t)stream, *a));
   return tq_launch_status("tq_mixture_mstep_kernel");

@@ -61,20 +61,13 @@ extern "C" int tq_multistart_mstep(const tq_multistart_mstep_args* a, void* stre
     tq_set_error("tq_multistart_mstep: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->N < 1 || a->it < 0) {
-    tq_set_error("tq_multistart_mstep: N must be positive and it non-negative");
+  if (!tq_chain_iteration_ok("tq_multistart_mstep", a->N, a->it) ||
+      !tq_chain_trace_ok("tq_multistart_mstep", a->it, a->T, "the trace of a replica"))
     return TQ_ERR_ARG;
-  }
-  if (a->T <= a->it) {
-    tq_set_error("tq_multistart_mstep: T must exceed it (the trace of a replica has T entries)");
-    return TQ_ERR_ARG;
-  }
   if (!tq_chain_states_ok("tq_multistart_mstep", a->U, a->B) || !tq_chain_replicas_ok("tq_multistart_mstep", a->R))
     return TQ_ERR_ARG;
-  if (!tq_multistart_allow_ok(a->allow, a->U + a->B)) {
-    tq_set_error("tq_multistart_mstep: allow must have no bit beyond M * M and a free entry in every row");
+  if (!tq_chain_allow_ok("tq_multistart_mstep", tq_multistart_allow_ok(a->allow, a->U + a->B)))
     return TQ_ERR_ARG;
-  }
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_multistart_mstep_kernel<MM>), dim3((unsigned)a->R),
                                                   dim3(TQ_SMOOTH_MSTEP_THREADS), 0, (hipStream_t)stream, *a));
   return tq_launch_status("tq_multistart_mstep_kernel");

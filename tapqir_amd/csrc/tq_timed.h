@@ -5,11 +5,14 @@
 //   * the tables of one gap class, P = exp(Q d) and K[a][b][i][j] = int_0^d P_ai(s) P_jb(d - s) ds, by a Taylor series of
 //     the uniformised chain at d / 2^s and s squarings of the pair (P, K).  Every term and every product is non-negative,
 //     so nothing cancels; there is no eigendecomposition and no 2M x 2M matrix;
-//   * what one lane of the E-step does with its chunk of frames: the bodies of tq_chain_chunk, tq_chain_forward and
-//     tq_chain_backward of tq_hmm.h with the transition of frame f read from P[cls[f - 1]], and in the backward sweep the
-//     contraction of the rank-one pair posterior with K[cls[g - 1]] in the place of the pair marginals;
+//   * the two things the tq_chain_* bodies of tq_hmm.h ask of a chain: the transition into frame f, read from
+//     P[cls[f - 1]], and what the pair (g - 1, g) adds to a lane's sums, the contraction of the rank-one pair posterior with
+//     K[cls[g - 1]] in the place of the pair marginals;
+//   * the forward sweep, tq_chain_forward overloaded for this chain: the one sweep kept as a text of its own, for the
+//     rounding of the normaliser c_f (see there);
 //   * the M-step of the summed rows: q_ij = sum E N_ij / sum E T_i.
-// The products, their rescaling, the prefix and suffix vectors and the lane ranges are tq_hmm.h's and tq_smooth.h's.
+// The chunk product, the backward sweep, the products, their rescaling, the prefix and suffix vectors and the lane ranges
+// are tq_hmm.h's and tq_smooth.h's.
 // Nothing here divides by a transition probability, so an exact zero in Q or P is safe.
 // The __global__ wrappers are in tq_timed.hip; the test suite runs the same bodies from a g++ build.
 #pragma once
@@ -202,43 +205,44 @@ TQ_HD void tq_timed_table_item(const TqTimedModel<M>& m, const double* d, int k,
   }
 }
 
-// ---- the lane's chunk product and its two sweeps --------------------------------------------------------------------------
-// tq_chain_chunk with the transition into frame f read from P[cls[f - 1]]
-template <int M, class Emit>
-TQ_HD TqHmmMat<M> tq_timed_chunk(const TqTimedModel<M>& m, const Emit& em, const double* P, const int32_t* cls, int lo,
-                                 int hi) {
-  TqHmmMat<M> c = tq_hmm_identity<M>();
-  for (int f = lo; f < hi; ++f) {
-    double l[M];
-    em(f, l);
-    TqHmmMat<M> t;
-    if (f == 0) {
-#pragma unroll
-      for (int i = 0; i < M; ++i)
-#pragma unroll
-        for (int j = 0; j < M; ++j) t.m[i][j] = m.rho[j] * l[j];
-    } else {
-      const double* A = P + (int64_t)cls[f - 1] * (M * M);
-#pragma unroll
-      for (int i = 0; i < M; ++i)
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-          double s = c.m[i][0] * A[j];
-#pragma unroll
-          for (int k = 1; k < M; ++k) s += c.m[i][k] * A[k * M + j];
-          t.m[i][j] = s * l[j];
-        }
-    }
-    tq_hmm_rescale(t);
-    c = t;
-  }
-  return c;
+// ---- the chain as the tq_chain_* bodies of tq_hmm.h take it ---------------------------------------------------------------
+// the model with the tables of its D gap classes and the class of every gap: cls[f - 1] is that of (f - 1, f), and may be
+// NULL where there is one frame
+template <int M>
+struct TqTimedChain : TqTimedModel<M> {
+  const double* P;  // (D, M, M)
+  const double* K;  // (D, M, M, M, M), K[k][a][b][i][j]
+  const int32_t* cls;
+};
+
+template <int M>
+TQ_HD TqTimedChain<M> tq_timed_chain(const double* theta, int U, double prior, uint32_t allow, const double* P,
+                                     const double* K, const int32_t* cls) {
+  return TqTimedChain<M>{tq_timed_model<M>(theta, U, prior, allow), P, K, cls};
 }
 
-// tq_chain_forward with the transition into frame f read from P[cls[f - 1]]
+// one gap class: its index and its P; only the pair sums read its K, so only they form that address
+template <int M>
+struct TqTimedStep {
+  const double* P;
+  int64_t k;
+  TQ_HD double A(int i, int j) const { return P[i * M + j]; }
+};
+
+// the transition into frame f: the tables of class cls[f - 1].  Frame 0 has no gap before it and the bodies discard what
+// they compute there, so it gets class 0's, which exist (D >= 1), and cls[-1] is not read.
+template <int M>
+TQ_HD TqTimedStep<M> tq_chain_step(const TqTimedChain<M>& m, int f) {
+  const int64_t k = f > 0 ? m.cls[f - 1] : 0;
+  return TqTimedStep<M>{m.P + k * (M * M), k};
+}
+
+// The forward sweep, tq_chain_forward for this chain: tq_chain_sweeps finds it by its argument.  It is a text of its own
+// for the rounding of c_f alone.  tq_hmm.h's selects between rho_j and the sum, which leaves the product u_j and the sum
+// c_f in one basic block, and the device build fuses them there into FMAs; here frame 0 is a branch of its own and c_f adds
+// the rounded products.  These are the bits filt and the log evidence of this chain have had from the start, so they stay.
 template <int M, class Emit>
-TQ_HD double tq_timed_forward(const TqTimedModel<M>& m, const Emit& em, const double* P, const int32_t* cls, int lo, int hi,
-                              const double* v0, double* filt) {
+TQ_HD double tq_chain_forward(const TqTimedChain<M>& m, const Emit& em, int lo, int hi, const double* v0, double* filt) {
   double v[M], mant = 1.0;
   int expo = 0;
 #pragma unroll
@@ -250,7 +254,7 @@ TQ_HD double tq_timed_forward(const TqTimedModel<M>& m, const Emit& em, const do
 #pragma unroll
       for (int j = 0; j < M; ++j) u[j] = m.rho[j] * l[j];
     } else {
-      const double* A = P + (int64_t)cls[f - 1] * (M * M);
+      const double* A = m.P + (int64_t)m.cls[f - 1] * (M * M);
 #pragma unroll
       for (int j = 0; j < M; ++j) {
         double s = v[0] * A[j];
@@ -274,95 +278,60 @@ TQ_HD double tq_timed_forward(const TqTimedModel<M>& m, const Emit& em, const do
   return log(mant) + (double)expo * 0.69314718055994530942;
 }
 
-// Backward sweep over [lo, hi), g = hi - 1 .. lo, from beta_{hi-1} = b0: frame g gives gamma_g, and the gap (g - 1, g) of
-// class k = cls[g - 1] -- it belongs to the lane that owns g -- gives, with a = a_{g-1}, w = l_g o beta_g and
-// tot = sum_ab a_a P[k]_ab w_b, the rank-one pair posterior c_ab = a_a w_b / tot over P[k]_ab and
-//   acc[i * M + i] += sum_ab c_ab K[k][a][b][i][i]         (E T_i, the expected time in state i)
-//   acc[i * M + j] += q_ij sum_ab c_ab K[k][a][b][i][j]    (E N_ij, the expected number of jumps; free pairs only)
-// summed over a and b into M * M running sums, one K row of M * M at a time.  A forbidden pair's K is loaded and not used:
-// its slot stays 0 whatever the table holds there.  acc[M * M + i] = gamma_0(i) in the lane that owns frame 0.
-template <int M, bool GAMMA, class Emit>
-TQ_HD void tq_timed_backward(const TqTimedModel<M>& m, const Emit& em, const double* P, const double* K, const int32_t* cls,
-                             int lo, int hi, const double* b0, const double* v, const double* filt, double* gam,
-                             double* acc) {
-  double b[M];
+// The gap (g - 1, g) of class k, with a = a_{g-1}, w = l_g o beta_g and tot = sum_xy a_x P[k]_xy w_y, gives the rank-one pair
+// posterior c_xy = a_x w_y / tot over P[k]_xy and
+//   acc[i * M + i] += sum_xy c_xy K[k][x][y][i][i]         (E T_i, the expected time in state i)
+//   acc[i * M + j] += q_ij sum_xy c_xy K[k][x][y][i][j]    (E N_ij, the expected number of jumps; free pairs only)
+// summed over x and y into M * M running sums, one K row of M * M at a time.  A forbidden pair's K is loaded and not used:
+// its slot stays 0 whatever the table holds there.
+template <int M>
+TQ_HD void tq_chain_pair(const TqTimedChain<M>& m, const TqTimedStep<M>& s, const double* a, const double* w, double* acc) {
+  // t is row i of P[k] w, which tq_chain_backward's beta update forms again in the same statements: once inlined the two
+  // are one computation (the kernels' register counts show it), so it is not carried from here to there by hand
+  double tot = 0.0;
 #pragma unroll
-  for (int i = 0; i < M; ++i) b[i] = b0[i];
-  for (int g = hi - 1; g >= lo; --g) {
-    double r[M], s = 0.0;
+  for (int i = 0; i < M; ++i) {
+    double t = s.A(i, 0) * w[0];
 #pragma unroll
-    for (int i = 0; i < M; ++i) {
-      r[i] = filt[(int64_t)g * M + i] * b[i];
-      s += r[i];
-    }
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      r[i] /= s;
-      if constexpr (GAMMA) gam[(int64_t)g * M + i] = r[i];
-    }
-    if (g == 0) {
-#pragma unroll
-      for (int i = 0; i < M; ++i) acc[M * M + i] = r[i];
-      break;
-    }
-    const int k = cls[g - 1];
-    const double* A = P + (int64_t)k * (M * M);
-    const double* Kk = K + (int64_t)k * (M * M * M * M);
-    double l[M], w[M], a[M], nb[M], tot = 0.0;
-    em(g, l);
-#pragma unroll
-    for (int j = 0; j < M; ++j) w[j] = l[j] * b[j];
-    // beta_{g-1} = P[k] (l_g o beta_g), and tot = a_{g-1} . beta_{g-1} before its scaling
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      a[i] = g > lo ? filt[(int64_t)(g - 1) * M + i] : v[i];
-      double t = A[i * M] * w[0];
-#pragma unroll
-      for (int j = 1; j < M; ++j) t += A[i * M + j] * w[j];
-      nb[i] = t;
-      tot += a[i] * t;
-    }
-    double e[M * M];
-#pragma unroll
-    for (int q = 0; q < M * M; ++q) e[q] = 0.0;
-#pragma unroll
-    for (int x = 0; x < M; ++x)
-#pragma unroll
-      for (int y = 0; y < M; ++y) {
-        const double c = a[x] * w[y];
-        const double* row = Kk + (x * M + y) * (M * M);
-#pragma unroll
-        for (int q = 0; q < M * M; ++q) e[q] += c * row[q];
-      }
-    const double rt = 1.0 / tot;
-#pragma unroll
-    for (int i = 0; i < M; ++i)
-#pragma unroll
-      for (int j = 0; j < M; ++j) {
-        if (i == j)
-          acc[i * M + i] += e[i * M + i] * rt;
-        else
-          acc[i * M + j] += tq_timed_free<M>(m.allow, i, j) ? m.Q[i][j] * (e[i * M + j] * rt) : 0.0;
-      }
-    double bs = 0.0;
-#pragma unroll
-    for (int i = 0; i < M; ++i) bs += nb[i];
-    int ex;
-    (void)frexp(bs, &ex);
-#pragma unroll
-    for (int i = 0; i < M; ++i) b[i] = ldexp(nb[i], -ex);
+    for (int j = 1; j < M; ++j) t += s.A(i, j) * w[j];
+    tot += a[i] * t;
   }
+  const double* Kk = m.K + s.k * (M * M * M * M);
+  double e[M * M];
+#pragma unroll
+  for (int q = 0; q < M * M; ++q) e[q] = 0.0;
+#pragma unroll
+  for (int x = 0; x < M; ++x)
+#pragma unroll
+    for (int y = 0; y < M; ++y) {
+      const double c = a[x] * w[y];
+      const double* row = Kk + (x * M + y) * (M * M);
+#pragma unroll
+      for (int q = 0; q < M * M; ++q) e[q] += c * row[q];
+    }
+  const double rt = 1.0 / tot;
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      if (i == j)
+        acc[i * M + i] += e[i * M + i] * rt;
+      else
+        acc[i * M + j] += tq_timed_free<M>(m.allow, i, j) ? m.Q[i][j] * (e[i * M + j] * rt) : 0.0;
+    }
 }
 
-// acc[0 .. TQ_HMM_COLS(M)) of the lane that owns [lo, hi), as tq_chain_sweeps
+// the shared bodies under the timed chain's earlier names, for a caller that holds the model and the tables apart: one
+// line each, nothing of their own (as tq_hmm_chunk and tq_multistart_sweeps).  The chunk product reads no K.
+template <int M, class Emit>
+TQ_HD TqHmmMat<M> tq_timed_chunk(const TqTimedModel<M>& m, const Emit& em, const double* P, const int32_t* cls, int lo,
+                                 int hi) {
+  return tq_chain_chunk<M>(TqTimedChain<M>{m, P, nullptr, cls}, em, lo, hi);
+}
 template <int M, bool GAMMA, class Emit>
 TQ_HD void tq_timed_sweeps(const TqTimedModel<M>& m, const Emit& em, const double* P, const double* K, const int32_t* cls,
                            int lo, int hi, const double* v, const double* b, double* filt, double* gam, double* acc) {
-  constexpr int COLS = TQ_HMM_COLS(M);
-#pragma unroll
-  for (int j = 0; j < COLS; ++j) acc[j] = 0.0;
-  acc[COLS - 1] = tq_timed_forward<M>(m, em, P, cls, lo, hi, v, filt);
-  tq_timed_backward<M, GAMMA>(m, em, P, K, cls, lo, hi, b, v, filt, gam, acc);
+  tq_chain_sweeps<M, GAMMA>(TqTimedChain<M>{m, P, K, cls}, em, lo, hi, v, b, filt, gam, acc);
 }
 
 // ---- M-step -------------------------------------------------------------------------------------------------------------

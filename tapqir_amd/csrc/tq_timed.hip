@@ -1,8 +1,8 @@
 // tq_timed.hip -- the continuous-time hidden Markov chain on the frame timestamps on the device (`smooth --timed`,
 // DESIGN.md section 34; bodies in tq_timed.h and tq_hmm.h): the tables P = exp(Q d) and K of every gap class, the E-step
-// as the chunked forward-backward of tq_hmm_estep with the transition of a frame read from its gap's class and the
-// expected jumps and holding times in the backward sweep, and the M-step of the summed rows.  No floating-point atomics,
-// no workgroup waits on another, every loop bounded by F, N, TQ_TIMED_ORDER or TQ_TIMED_MAX_SQ.
+// -- the chunked forward-backward of tq_hmm_estep, the same text, with the transition of a frame read from its gap's class
+// and the expected jumps and holding times for the pair marginals -- and the M-step of the summed rows.  No floating-point
+// atomics, no workgroup waits on another, every loop bounded by F, N, TQ_TIMED_ORDER or TQ_TIMED_MAX_SQ.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -31,10 +31,8 @@ extern "C" int tq_timed_table(const tq_timed_table_args* a, void* stream) {
     return TQ_ERR_ARG;
   }
   if (!tq_chain_states_ok("tq_timed_table", a->U, a->B)) return TQ_ERR_ARG;
-  if (!tq_multistart_allow_ok(a->allow, a->U + a->B)) {
-    tq_set_error("tq_timed_table: allow must have no bit beyond M * M and a free entry in every row");
+  if (!tq_chain_allow_ok("tq_timed_table", tq_multistart_allow_ok(a->allow, a->U + a->B)))
     return TQ_ERR_ARG;
-  }
   for (int k = 0; k < a->D; ++k)
     if (!(a->d_host[k] > 0.0) || !isfinite(a->d_host[k])) {
       tq_set_error("tq_timed_table: every gap must be finite and positive");
@@ -48,35 +46,17 @@ extern "C" int tq_timed_table(const tq_timed_table_args* a, void* stream) {
 }
 
 // ---- E-step: one wave (= one workgroup) per row ---------------------------------------------------------------------------
-// tq_chain_estep_row with the bodies of tq_timed.h: the chunk product, the two scans of tq_chain_dev.h, the two sweeps,
-// TQ_HMM_COLS(M) wave sums and lane 0's write.  Every lane takes part in every shuffle.
+// tq_chain_estep_row, as tq_hmm_estep_kernel calls it, given the timed chain: its transition of a frame and its pair sums
+// (tq_timed.h) are what the shared chunk product and backward sweep ask it for; the forward sweep is its overload.
 template <int M, bool GAMMA>
 __global__ __launch_bounds__(64) void tq_timed_estep_kernel(const tq_timed_estep_args a) {
-  constexpr int COLS = TQ_HMM_COLS(M);
   const int n = blockIdx.x, lane = threadIdx.x;
   const int F = a.F;
   const float* pr = a.p + (int64_t)n * F;
   double* filt = a.filt + (int64_t)n * F * M;
   double* gam = GAMMA ? a.gamma + (int64_t)n * F * M : nullptr;
-  const TqTimedModel<M> m = tq_timed_model<M>(a.theta, a.U, a.prior, a.allow);
-  const TqTimedEmit<M> em{m, pr};
-  int lo, hi;
-  tq_smooth_lane_range(lane, F, lo, hi);
-
-  const TqHmmMat<M> c = tq_timed_chunk<M>(m, em, a.P, a.cls, lo, hi);
-  double v[M], b[M];
-  tq_chain_prefix_scan(c, lane, v);
-  tq_chain_suffix_scan(c, lane, b);
-
-  double acc[COLS];
-  tq_timed_sweeps<M, GAMMA>(m, em, a.P, a.K, a.cls, lo, hi, v, b, filt, gam, acc);
-#pragma unroll
-  for (int j = 0; j < COLS; ++j) acc[j] = tq_group_sum<64>(acc[j]);  // every lane is back here
-  if (lane == 0) {
-    double* out = a.rows + (int64_t)n * COLS;
-#pragma unroll
-    for (int j = 0; j < COLS; ++j) out[j] = acc[j];
-  }
+  const TqTimedChain<M> m = tq_timed_chain<M>(a.theta, a.U, a.prior, a.allow, a.P, a.K, a.cls);
+  tq_chain_estep_row<M, GAMMA>(m, TqTimedEmit<M>{m, pr}, F, lane, filt, gam, a.rows + (int64_t)n * TQ_HMM_COLS(M));
 }
 
 extern "C" int tq_timed_estep(const tq_timed_estep_args* a, void* stream) {
@@ -91,10 +71,8 @@ extern "C" int tq_timed_estep(const tq_timed_estep_args* a, void* stream) {
     tq_set_error("tq_timed_estep: D must be positive");
     return TQ_ERR_ARG;
   }
-  if (!tq_multistart_allow_ok(a->allow, a->U + a->B)) {
-    tq_set_error("tq_timed_estep: allow must have no bit beyond M * M and a free entry in every row");
+  if (!tq_chain_allow_ok("tq_timed_estep", tq_multistart_allow_ok(a->allow, a->U + a->B)))
     return TQ_ERR_ARG;
-  }
   if (a->F > 1 && (!a->cls || !a->cls_host)) {
     tq_set_error("tq_timed_estep: NULL cls or cls_host with more than one frame");
     return TQ_ERR_ARG;
@@ -136,19 +114,12 @@ extern "C" int tq_timed_mstep(const tq_timed_mstep_args* a, void* stream) {
     tq_set_error("tq_timed_mstep: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->N < 1 || a->it < 0) {
-    tq_set_error("tq_timed_mstep: N must be positive and it non-negative");
+  if (!tq_chain_iteration_ok("tq_timed_mstep", a->N, a->it) ||
+      !tq_chain_trace_ok("tq_timed_mstep", a->it, a->T, "the trace"))
     return TQ_ERR_ARG;
-  }
-  if (a->T <= a->it) {
-    tq_set_error("tq_timed_mstep: T must exceed it (the trace has T entries)");
-    return TQ_ERR_ARG;
-  }
   if (!tq_chain_states_ok("tq_timed_mstep", a->U, a->B)) return TQ_ERR_ARG;
-  if (!tq_multistart_allow_ok(a->allow, a->U + a->B)) {
-    tq_set_error("tq_timed_mstep: allow must have no bit beyond M * M and a free entry in every row");
+  if (!tq_chain_allow_ok("tq_timed_mstep", tq_multistart_allow_ok(a->allow, a->U + a->B)))
     return TQ_ERR_ARG;
-  }
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_timed_mstep_kernel<MM>), dim3(1), dim3(TQ_SMOOTH_MSTEP_THREADS), 0,
                                                   (hipStream_t)stream, *a));
   return tq_launch_status("tq_timed_mstep_kernel");

@@ -425,18 +425,27 @@ def smooth_estep(p, theta, prior):
     return _smooth_estep(p, N, F, theta, prior, _smooth_buffers(N, F, p.device))
 
 
+def _mstep_inputs(who, rows, theta, trace, it, states=None):
+    """What ``smooth_mstep``, ``hmm_mstep`` and ``timed_mstep`` ask of their arguments: ``rows`` a contiguous float64
+    (N, cols) on the device, ``theta`` and ``trace`` float64 vectors there that hold theta and entry ``it``.  ``states`` =
+    (unbound, bound) of a chain of M states, or None for the two-state chain of ``smooth``.  Returns (U, B, M)."""
+    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
+        raise HipExtensionError(f"{who} runs on the HIP device only (no CPU fallback): pass a cuda tensor")
+    U, B, M = (None, None, None) if states is None else _hmm_states(who, *states)
+    cols, n_theta = (_lib_smooth.SMOOTH_COLS, 3) if states is None else (_lib_hmm.hmm_cols(M), M * M + M)
+    if rows.ndim != 2 or rows.shape[1] != cols or rows.shape[0] < 1 or rows.dtype != torch.float64 or not rows.is_contiguous():
+        raise ValueError(f"{who}: rows must be contiguous float64 (N, {cols}), N >= 1")
+    for name, x, n in (("theta", theta, n_theta), ("trace", trace, int(it) + 1)):
+        if (not isinstance(x, torch.Tensor) or x.device != rows.device or x.dtype != torch.float64 or x.ndim != 1
+                or x.numel() < n or not x.is_contiguous() or it < 0):
+            raise ValueError(f"{who}: {name} must be a float64 vector of at least {n} values on the device of rows")
+    return U, B, M
+
+
 def smooth_mstep(rows, theta, trace, it=0):
     """One launch of ``tq_smooth_mstep``: ``theta`` (3 float64, in place) from the summed ``rows`` of an E-step, and the
     total log-evidence of those rows into ``trace[it]``.  Returns ``theta``."""
-    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
-        raise HipExtensionError("smooth_mstep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
-    if (rows.ndim != 2 or rows.shape[1] != _lib_smooth.SMOOTH_COLS or rows.shape[0] < 1 or rows.dtype != torch.float64
-            or not rows.is_contiguous()):
-        raise ValueError(f"smooth_mstep: rows must be contiguous float64 (N, {_lib_smooth.SMOOTH_COLS}), N >= 1")
-    for name, x, n in (("theta", theta, 3), ("trace", trace, int(it) + 1)):
-        if (not isinstance(x, torch.Tensor) or x.device != rows.device or x.dtype != torch.float64 or x.ndim != 1
-                or x.numel() < n or not x.is_contiguous() or it < 0):
-            raise ValueError(f"smooth_mstep: {name} must be a float64 vector of at least {n} values on the device of rows")
+    _mstep_inputs("smooth_mstep", rows, theta, trace, it)
     a = _lib_smooth.SmoothMstepArgs(rows=_lib.ptr(rows), theta=_lib.ptr(theta), trace=_lib.ptr(trace), N=rows.shape[0],
                                     it=int(it))
     _lib.check(_lib_smooth.lib().tq_smooth_mstep(C.byref(a), _stream(rows.device)), "tq_smooth_mstep")
@@ -463,20 +472,12 @@ def smooth_fit(p, prior, kon=0.5, koff=0.5, init=0.5, num_iter=200, tol=1e-9, ch
     p, N, F, theta, prior = _smooth_inputs("smooth_fit", p, theta, prior)
     out = _smooth_buffers(N, F, p.device)
     trace = torch.full((num_iter,), float("nan"), dtype=torch.float64, device=p.device)
-    state = {"iterations": 0, "converged": False}
 
-    def em_steps(step0, n):
-        if state["converged"]:
-            return
-        for it in range(step0, step0 + n):
-            _smooth_estep(p, N, F, theta, prior, out)
-            smooth_mstep(out["rows"], theta, trace, it)
-        state["iterations"] = step0 + n
-        ll = trace[: step0 + n].cpu()
-        gain = ll[1:] - ll[:-1]
-        state["converged"] = bool((gain <= tol * ll[1:].abs()).any())
+    def step(it):
+        _smooth_estep(p, N, F, theta, prior, out)
+        smooth_mstep(out["rows"], theta, trace, it)
 
-    _run_chunks(em_steps, num_iter, chunk, progress_bar)
+    state = _chain_em(step, trace, num_iter, tol, chunk, progress_bar)
     _smooth_estep(p, N, F, theta, prior, out)
     return {"theta": theta, **out, "trace": trace[: state["iterations"]], **state}
 
@@ -656,16 +657,7 @@ def hmm_estep(p, theta, prior, unbound=1, bound=1):
 def hmm_mstep(rows, theta, trace, it=0, unbound=1, bound=1):
     """One launch of ``tq_hmm_mstep``: ``theta`` (M * M + M float64, in place) from the summed ``rows`` of an E-step, and
     the total log-evidence of those rows into ``trace[it]``.  Returns ``theta``."""
-    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
-        raise HipExtensionError("hmm_mstep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
-    U, B, M = _hmm_states("hmm_mstep", unbound, bound)
-    cols = _lib_hmm.hmm_cols(M)
-    if rows.ndim != 2 or rows.shape[1] != cols or rows.shape[0] < 1 or rows.dtype != torch.float64 or not rows.is_contiguous():
-        raise ValueError(f"hmm_mstep: rows must be contiguous float64 (N, {cols}), N >= 1")
-    for name, x, n in (("theta", theta, M * M + M), ("trace", trace, int(it) + 1)):
-        if (not isinstance(x, torch.Tensor) or x.device != rows.device or x.dtype != torch.float64 or x.ndim != 1
-                or x.numel() < n or not x.is_contiguous() or it < 0):
-            raise ValueError(f"hmm_mstep: {name} must be a float64 vector of at least {n} values on the device of rows")
+    U, B, M = _mstep_inputs("hmm_mstep", rows, theta, trace, it, (unbound, bound))
     a = _lib_hmm.HmmMstepArgs(rows=_lib.ptr(rows), theta=_lib.ptr(theta), trace=_lib.ptr(trace), N=rows.shape[0], it=int(it),
                               U=U, B=B)
     _lib.check(_lib_hmm.lib().tq_hmm_mstep(C.byref(a), _stream(rows.device)), "tq_hmm_mstep")
@@ -738,20 +730,12 @@ def hmm_fit(p, prior, unbound=1, bound=1, A0=None, rho0=None, num_iter=200, tol=
     p, N, F, theta, prior, U, B, M = _hmm_inputs("hmm_fit", p, theta, prior, U, B)
     out = _hmm_buffers(N, F, M, p.device)
     trace = torch.full((num_iter,), float("nan"), dtype=torch.float64, device=p.device)
-    state = {"iterations": 0, "converged": False}
 
-    def em_steps(step0, n):
-        if state["converged"]:
-            return
-        for it in range(step0, step0 + n):
-            _hmm_estep(p, N, F, theta, prior, U, B, out)
-            hmm_mstep(out["rows"], theta, trace, it, U, B)
-        state["iterations"] = step0 + n
-        ll = trace[: step0 + n].cpu()
-        gain = ll[1:] - ll[:-1]
-        state["converged"] = bool((gain <= tol * ll[1:].abs()).any())
+    def step(it):
+        _hmm_estep(p, N, F, theta, prior, U, B, out)
+        hmm_mstep(out["rows"], theta, trace, it, U, B)
 
-    _run_chunks(em_steps, num_iter, chunk, progress_bar)
+    state = _chain_em(step, trace, num_iter, tol, chunk, progress_bar)
     _hmm_estep(p, N, F, theta, prior, U, B, out)
     order = hmm_canonical_order(theta, U, B)
     out = hmm_permute(order, M, theta=theta, **out)
@@ -1014,6 +998,28 @@ def multistart_mstep(rows, thetas, trace, it=0, unbound=1, bound=1, allow=None, 
                                             active=_lib.ptr(active), N=N, it=it, T=trace.shape[1], R=R, U=U, B=B, allow=bits)
     _lib.check(_lib_multistart.lib().tq_multistart_mstep(C.byref(a), _stream(rows.device)), "tq_multistart_mstep")
     return thetas
+
+
+def _chain_em(step, trace, num_iter, tol, chunk, progress_bar=None):
+    """The chunks and the stopping rule of ``smooth_fit``, ``hmm_fit`` and ``timed_fit``.  ``step(it)`` launches iteration
+    ``it`` -- E-step and M-step -- on buffers the caller owns, among them ``trace`` (num_iter,), NaN where nothing is
+    written.  The iterations run in chunks of ``chunk`` with no host synchronisation inside a chunk; after each chunk the
+    trace is read, and the run stops once some iteration has gained at most ``tol * |loglik|`` over the one before.
+    Returns ``{"iterations", "converged"}``: the number run (whole chunks) and whether the rule stopped it."""
+    state = {"iterations": 0, "converged": False}
+
+    def em_steps(step0, n):
+        if state["converged"]:
+            return
+        for it in range(step0, step0 + n):
+            step(it)
+        state["iterations"] = step0 + n
+        ll = trace[: step0 + n].cpu()
+        gain = ll[1:] - ll[:-1]
+        state["converged"] = bool((gain <= tol * ll[1:].abs()).any())
+
+    _run_chunks(em_steps, num_iter, chunk, progress_bar)
+    return state
 
 
 def multistart_em(estep, mstep, trace, active, num_iter, tol, chunk, progress_bar=None):
@@ -1722,16 +1728,7 @@ def timed_mstep(rows, theta, trace, it=0, unbound=1, bound=1, allow=None):
     """One launch of ``tq_timed_mstep``: ``theta`` (M * M + M float64, in place) from the summed ``rows`` of
     ``timed_estep`` -- q_ij = sum E N_ij / sum E T_i, floored at 1e-9 where free and exactly 0 where ``allow`` forbids it,
     rho the mean gamma_0 -- and the total log evidence of those rows into ``trace[it]``.  Returns ``theta``."""
-    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
-        raise HipExtensionError("timed_mstep runs on the HIP device only (no CPU fallback): pass a cuda tensor")
-    U, B, M = _hmm_states("timed_mstep", unbound, bound)
-    cols = _lib_hmm.hmm_cols(M)
-    if rows.ndim != 2 or rows.shape[1] != cols or rows.shape[0] < 1 or rows.dtype != torch.float64 or not rows.is_contiguous():
-        raise ValueError(f"timed_mstep: rows must be contiguous float64 (N, {cols}), N >= 1")
-    for name, x, n in (("theta", theta, M * M + M), ("trace", trace, int(it) + 1)):
-        if (not isinstance(x, torch.Tensor) or x.device != rows.device or x.dtype != torch.float64 or x.ndim != 1
-                or x.numel() < n or not x.is_contiguous() or it < 0):
-            raise ValueError(f"timed_mstep: {name} must be a float64 vector of at least {n} values on the device of rows")
+    U, B, M = _mstep_inputs("timed_mstep", rows, theta, trace, it, (unbound, bound))
     a = _lib_timed.TimedMstepArgs(rows=_lib.ptr(rows), theta=_lib.ptr(theta), trace=_lib.ptr(trace), N=rows.shape[0],
                                   it=int(it), T=trace.numel(), U=U, B=B, allow=_timed_allow("timed_mstep", allow, M))
     _lib.check(_lib_timed.lib().tq_timed_mstep(C.byref(a), _stream(rows.device)), "tq_timed_mstep")
@@ -1801,21 +1798,13 @@ def timed_fit(p, prior, times, unbound=1, bound=1, allow=None, Q0=None, rho0=Non
     out = _hmm_buffers(N, F, M, p.device)
     rows_only = {"filt": out["filt"], "rows": out["rows"]}
     trace = torch.full((num_iter,), float("nan"), dtype=torch.float64, device=p.device)
-    state = {"iterations": 0, "converged": False}
 
-    def em_steps(step0, n):
-        if state["converged"]:
-            return
-        for it in range(step0, step0 + n):
-            _timed_table(theta, d_dev, d_host, D, U, B, bits, P, K)
-            _timed_estep(p, N, F, theta, P, K, cls_dev, cls_host, D, prior, U, B, bits, rows_only)
-            timed_mstep(out["rows"], theta, trace, it, U, B, free)
-        state["iterations"] = step0 + n
-        ll = trace[: step0 + n].cpu()
-        gain = ll[1:] - ll[:-1]
-        state["converged"] = bool((gain <= tol * ll[1:].abs()).any())
+    def step(it):
+        _timed_table(theta, d_dev, d_host, D, U, B, bits, P, K)
+        _timed_estep(p, N, F, theta, P, K, cls_dev, cls_host, D, prior, U, B, bits, rows_only)
+        timed_mstep(out["rows"], theta, trace, it, U, B, free)
 
-    _run_chunks(em_steps, num_iter, chunk, progress_bar)
+    state = _chain_em(step, trace, num_iter, tol, chunk, progress_bar)
     _timed_table(theta, d_dev, d_host, D, U, B, bits, P, K)
     _timed_estep(p, N, F, theta, P, K, cls_dev, cls_host, D, prior, U, B, bits, out)
     order = timed_canonical_order(theta, U, B)

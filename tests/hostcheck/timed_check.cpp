@@ -16,48 +16,17 @@ void table(const double* theta, const double* d, int D, int U, uint32_t allow, d
     for (int ij = 0; ij < M * M; ++ij) tq_timed_table_item<M>(m, d, k, ij, P, K);
 }
 
-// one workgroup of tq_timed_estep_kernel: estep_row of chain_host.h with the bodies of tq_timed.h
-template <int M, bool GAMMA>
-void timed_row(const TqTimedModel<M>& m, const float* pr, const double* P, const double* K, const int32_t* cls, int F,
-               double* filt, double* gam, double* row) {
-  constexpr int COLS = TQ_HMM_COLS(M);
-  const TqTimedEmit<M> em{m, pr};
-  static TqHmmMat<M> pre[64], suf[64], old[64];
-  int lo[64], hi[64];
-  for (int k = 0; k < 64; ++k) {
-    tq_smooth_lane_range(k, F, lo[k], hi[k]);
-    pre[k] = suf[k] = tq_timed_chunk<M>(m, em, P, cls, lo[k], hi[k]);
-  }
-  for (int d = 1; d < 64; d <<= 1) {
-    for (int k = 0; k < 64; ++k) old[k] = pre[k];
-    for (int k = d; k < 64; ++k) pre[k] = tq_hmm_mul(old[k - d], old[k]);
-  }
-  for (int d = 1; d < 64; d <<= 1) {
-    for (int k = 0; k < 64; ++k) old[k] = suf[k];
-    for (int k = 0; k + d < 64; ++k) suf[k] = tq_hmm_mul(old[k], old[k + d]);
-  }
-  static double acc[COLS][64];
-  for (int k = 0; k < 64; ++k) {
-    const TqHmmMat<M> e = k == 0 ? tq_hmm_identity<M>() : pre[k - 1];
-    const TqHmmMat<M> s = k == 63 ? tq_hmm_identity<M>() : suf[k + 1];
-    double v[M], b[M], a[COLS];
-    tq_hmm_prefix_vector(e, v);
-    tq_hmm_suffix_vector(s, b);
-    tq_timed_sweeps<M, GAMMA>(m, em, P, K, cls, lo[k], hi[k], v, b, filt, gam, a);
-    for (int j = 0; j < COLS; ++j) acc[j][k] = a[j];
-  }
-  for (int j = 0; j < COLS; ++j) row[j] = wave_sum(acc[j]);
-}
-
+// tq_timed_estep_kernel: estep_row of chain_host.h given the timed chain, one workgroup per row
 template <int M>
 void estep(const float* p, int N, int F, const double* theta, const double* P, const double* K, const int32_t* cls, int U,
            uint32_t allow, double prior, double* filt, double* gamma, double* rows) {
-  const TqTimedModel<M> m = tq_timed_model<M>(theta, U, prior, allow);
+  const TqTimedChain<M> m = tq_timed_chain<M>(theta, U, prior, allow, P, K, cls);
   for (int64_t n = 0; n < N; ++n) {
+    const TqTimedEmit<M> em{m, p + n * F};
     if (gamma)
-      timed_row<M, true>(m, p + n * F, P, K, cls, F, filt + n * F * M, gamma + n * F * M, rows + n * TQ_HMM_COLS(M));
+      estep_row<M, true>(m, em, F, filt + n * F * M, gamma + n * F * M, rows + n * TQ_HMM_COLS(M));
     else
-      timed_row<M, false>(m, p + n * F, P, K, cls, F, filt + n * F * M, nullptr, rows + n * TQ_HMM_COLS(M));
+      estep_row<M, false>(m, em, F, filt + n * F * M, nullptr, rows + n * TQ_HMM_COLS(M));
   }
 }
 
