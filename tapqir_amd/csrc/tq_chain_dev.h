@@ -1,7 +1,8 @@
 // tq_chain_dev.h -- device-only halves of the hidden-Markov kernels over MxM products, shared by tq_hmm.hip,
-// tq_multistart.hip, tq_joint.hip, tq_refit.hip and tq_timed.hip (bodies in tq_hmm.h): the wave shuffles of a product, the
-// two exclusive scans, the E-step of one row by one wave -- whatever the chain: it reaches the bodies as `m`, with what it
-// overloads of tq_chain_step and tq_chain_pair -- and the M-step's sum of rows.  Only .hip units include it: no header
+// tq_multistart.hip, tq_joint.hip, tq_mixture.hip, tq_refit.hip and tq_timed.hip (bodies in tq_hmm.h): the wave shuffles of
+// a product, the two exclusive scans, the E-step of one row by one wave -- whatever the chain: it reaches the bodies as
+// `m`, with what it overloads of tq_chain_step and tq_chain_pair -- the M-step's sum of rows, and the backward sampler's
+// walk with its staging of thresholds and its interval sink.  Only .hip units include it: no header
 // that the g++ host build reads may, and tests/hostcheck/chain_host.h is its mirror on arrays.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -111,4 +112,66 @@ __device__ __forceinline__ bool tq_chain_reduce_rows(const double* rows, int N, 
 #pragma unroll
   for (int j = 0; j < COLS; ++j) sums[j] = part[j][0];
   return true;
+}
+
+// ---- backward sampler ----------------------------------------------------------------------------
+// The walk of one wave (= one workgroup) over F frames, one lane per sample, in blocks of 64 frames from the highest:
+// stage(f, lane, last) once per frame f = f0 + lane of the block, by the lane of that number (last: f == F - 1), a
+// barrier, visit(f, j) for every frame f = f0 + j of the block, highest first, in the active lanes, and a second barrier
+// before the staging is written again.  Every lane of the workgroup must arrive and reaches every barrier; an inactive lane
+// (a sample beyond S) runs nothing but `stage`, so it may touch no memory but the staging.  Every loop is bounded by F.
+template <class Stage, class Visit>
+__device__ __forceinline__ void tq_chain_sample_row(int F, int lane, bool active, const Stage& stage, const Visit& visit) {
+  for (int f0 = (F - 1) & ~63; f0 >= 0; f0 -= 64) {
+    const int cnt = min(64, F - f0);
+    if (lane < cnt) stage(f0 + lane, lane, f0 + lane == F - 1);
+    __syncthreads();
+    if (active) {
+      for (int j = cnt - 1; j >= 0; --j) visit(f0 + j, j);
+    }
+    __syncthreads();
+  }
+}
+
+// The M (M - 1) thresholds of one frame, from its a_f at `af`, into the LDS row q.  DIRECT writes the quotients to LDS as
+// they come, so that they do not wait in registers; otherwise they go through a local array.  Which is cheaper depends on
+// the kernel around it (section 35 has the register counts), so the kernel says.
+template <int M, bool DIRECT>
+__device__ __forceinline__ void tq_chain_stage_thresholds(const TqHmmModel<M>& m, const double* af, bool last, double* q) {
+  constexpr int T = M * (M - 1);
+  double a[M];
+#pragma unroll
+  for (int i = 0; i < M; ++i) a[i] = af[i];
+  if constexpr (DIRECT) {
+    tq_hmm_thresholds(m, a, last, q);
+  } else {
+    double t[T];
+    tq_hmm_thresholds(m, a, last, t);
+#pragma unroll
+    for (int k = 0; k < T; ++k) q[k] = t[k];
+  }
+}
+
+// Where the runs of row (s, n) go as the walk closes them: one text for every dwell kernel.  The bookkeeping (hb, hu, o,
+// count, closed) stays in the kernel's own locals, set up in the kernel's own text, and the kernel wraps this in a
+// one-line lambda: gathered in a struct, or filled through references by a shared helper, it cost the COUNT kernels a
+// wave per SIMD (section 35).
+// EMIT = false: an interior run adds 1 to bin `length` of the row's bound or unbound histogram (integer atomics:
+// order-free, so deterministic; an interior run is shorter than F), `off` bins further on where a kernel keeps several
+// histograms per sample.  EMIT = true: the k-th run the row closes is written at tq_smooth_emit_slot, with the partner
+// code `pc` beside it where PARTNER.  `closed` counts both.
+template <bool EMIT, bool PARTNER = false>
+__device__ __forceinline__ void tq_chain_sink_put(const TqDwellInterval& v, int& closed, int64_t o, int count, int64_t total,
+                                                  int32_t* intervals, int32_t* hb, int32_t* hu, int s, int n, int off = 0,
+                                                  uint8_t* partner = nullptr, int pc = 0) {
+  if constexpr (EMIT) {
+    const int64_t pos = tq_smooth_emit_slot(o, count, closed, total);
+    if (pos >= 0) {
+      tq_smooth_emit_row(intervals, total, pos, s, n, v);
+      if constexpr (PARTNER) partner[pos] = (uint8_t)pc;
+    }
+  } else {
+    if (v.low_or_high == 0 || v.low_or_high == 1) atomicAdd((v.z ? hb : hu) + off + (v.stop + 1 - v.start), 1);
+  }
+  ++closed;
 }

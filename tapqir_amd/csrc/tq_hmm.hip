@@ -3,7 +3,9 @@
 // hidden states, the backward sampler with its class-level and state-level counts, the same sampler walked into dwell-time
 // intervals and first-binding frames, and the pooled or AOI-resampled estimate of A (DESIGN.md
 // section 22).  The kernels are templates over M; the two-state kernels of tq_smooth.hip stay.  The E-step's body and the
-// M-step's sum of rows are tq_chain_dev.h's, shared with tq_multistart.hip and tq_joint.hip.
+// M-step's sum of rows are tq_chain_dev.h's, shared with tq_multistart.hip and tq_joint.hip, and so
+// are the dwell kernel's walk, its staging of thresholds and its interval sink, shared with tq_mixture.hip and
+// tq_joint.hip (section 35).
 #include <hip/hip_runtime.h>
 
 #include "tq_chain_dev.h"
@@ -89,7 +91,8 @@ extern "C" int tq_hmm_viterbi(const tq_hmm_viterbi_args* a, void* stream) {
 // The geometry of tq_smooth_count_kernel: lane j of the wave stages the M (M - 1) thresholds of frame f0 + j in LDS, then
 // every lane draws its own row through the 64 frames, highest first, and only compares.  The class of a state goes
 // through the row counter of the two-state sampler; the state pairs are counted by M * M compare-and-adds, so that the
-// counters stay in registers.  Inactive lanes reach every barrier and touch no memory but the staging.
+// counters stay in registers.  Inactive lanes reach every barrier and touch no memory but the staging.  The device text
+// is kept as it was: every shared form tried for it cost a wave per SIMD or 5 to 8 % of its time.
 template <int M>
 __global__ __launch_bounds__(64) void tq_hmm_count_kernel(const tq_hmm_count_args a) {
   constexpr int T = M * (M - 1);
@@ -167,31 +170,20 @@ extern "C" int tq_hmm_count(const tq_hmm_count_args* a, void* stream) {
     tq_set_error("tq_hmm_count: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (((uintptr_t)a->counts & 15u) != 0) {
-    tq_set_error("tq_hmm_count: counts must be 16-byte aligned");
+  dim3 grid;
+  if (!tq_chain_counts_aligned("tq_hmm_count", a->counts) || !tq_chain_sampler_ok("tq_hmm_count", a->N, a->F, a->S) ||
+      !tq_chain_states_ok("tq_hmm_count", a->U, a->B) || !tq_chain_sample_grid("tq_hmm_count", a->N, a->S, &grid))
     return TQ_ERR_ARG;
-  }
-  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F) {
-    tq_set_error("tq_hmm_count: N, F and S must be positive and F at most 65536");
-    return TQ_ERR_ARG;
-  }
-  if (!tq_chain_states_ok("tq_hmm_count", a->U, a->B)) return TQ_ERR_ARG;
-  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
-  if (grid.y > 65535u) {
-    tq_set_error("tq_hmm_count: S too large");
-    return TQ_ERR_ARG;
-  }
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_hmm_count_kernel<MM>), grid, dim3(64), 0, (hipStream_t)stream, *a));
   return tq_launch_status("tq_hmm_count_kernel");
 }
 
-// ---- backward sampler walked into intervals: the geometry, the staging and the draws of tq_hmm_count_kernel -------------
-// Row (s, n) is the raster that kernel draws, state for state; here its class z = (state >= U) is walked, as it is drawn,
-// into runs of equal labels (tq_chain_dwell_frame), and neither a raster nor the state pairs are stored.  EMIT = false:
-// per-row interval counts, the interior-run histograms (integer atomics: order-free, so deterministic) and the
-// first-binding frame; EMIT = true: the same draws again, the k-th run a row closes written at tq_smooth_emit_slot, so
-// that the table is the one tq_smooth_dwell writes for that class raster.  Inactive lanes reach every barrier and touch
-// no memory but the staging; every loop is bounded by F.
+// ---- backward sampler walked into intervals -----------------------------------------------------------------------------
+// Row (s, n) is the raster tq_hmm_count_kernel draws, state for state, on the walk of tq_chain_sample_row.  Here its class
+// z = (state >= U) is walked, as it is drawn, into runs of equal labels (tq_chain_dwell_frame), and neither a raster nor
+// the state pairs are stored.  EMIT = false: per-row interval counts, the interior-run histograms and the first-binding
+// frame; EMIT = true: the same draws again, the k-th run a row closes written at tq_smooth_emit_slot, so that the table
+// is the one tq_smooth_dwell writes for that class raster (tq_chain_sink_put).
 template <int M, bool EMIT>
 __global__ __launch_bounds__(64) void tq_chain_dwell_kernel(const tq_chain_dwell_args a) {
   constexpr int T = M * (M - 1);
@@ -211,54 +203,27 @@ __global__ __launch_bounds__(64) void tq_chain_dwell_kernel(const tq_chain_dwell
     o = a.offsets[(int64_t)s * a.N + n];
     count = a.counts[(int64_t)s * a.N + n];
   }
+  int closed = 0;  // runs closed so far
+  auto sink = [&](const TqDwellInterval& v) {
+    tq_chain_sink_put<EMIT>(v, closed, o, count, total, a.intervals, hb, hu, s, n);
+  };
 
   TqHmmDraws draws;
   tq_hmm_draws_begin(draws, a.seed, s, n);
   TqChainDwellRow r;
   tq_chain_dwell_begin(r, F);
   TqDwellInterval iv;
-  int closed = 0;  // runs closed so far
-
-  auto emit = [&](const TqDwellInterval& v) {
-    if (EMIT) {
-      const int64_t pos = tq_smooth_emit_slot(o, count, closed, total);
-      if (pos >= 0) tq_smooth_emit_row(a.intervals, total, pos, s, n, v);
-    } else if (v.low_or_high == 0 || v.low_or_high == 1) {
-      atomicAdd((v.z ? hb : hu) + (v.stop + 1 - v.start), 1);
-    }
-    ++closed;
-  };
-
-  for (int f0 = (F - 1) & ~63; f0 >= 0; f0 -= 64) {
-    const int cnt = min(64, F - f0);
-    if (lane < cnt) {
-      double af[M];
-#pragma unroll
-      for (int i = 0; i < M; ++i) af[i] = fr[(int64_t)(f0 + lane) * M + i];
-      // M = 4 writes its twelve quotients to LDS as they come, so that they do not wait in registers (96 VGPRs in place
-      // of 126); at M = 3 the same costs 30 registers, so the smaller chains go through a local array
-      if constexpr (M == 4) {
-        tq_hmm_thresholds(m, af, f0 + lane == F - 1, qbuf[lane]);
-      } else {
-        double t[T];
-        tq_hmm_thresholds(m, af, f0 + lane == F - 1, t);
-#pragma unroll
-        for (int k = 0; k < T; ++k) qbuf[lane][k] = t[k];
-      }
-    }
-    __syncthreads();
-    if (active) {
-      for (int j = cnt - 1; j >= 0; --j) {
-        const int f = f0 + j;
-        const double u = tq_hmm_draws_next(draws, F - 1 - f);
-        if (tq_chain_dwell_frame<M>(r, u, qbuf[j], f, F, U, iv)) emit(iv);
-      }
-    }
-    __syncthreads();
-  }
+  // M = 4 writes its twelve quotients to LDS as they come (96 VGPRs in place of 126); at M = 3 the same costs 30
+  // registers, so the smaller chains go through a local array
+  tq_chain_sample_row(
+      F, lane, active,
+      [&](int f, int l, bool last) { tq_chain_stage_thresholds<M, M == 4>(m, fr + (int64_t)f * M, last, qbuf[l]); },
+      [&](int f, int j) {
+        if (tq_chain_dwell_frame<M>(r, tq_hmm_draws_next(draws, F - 1 - f), qbuf[j], f, F, U, iv)) sink(iv);
+      });
   if (!active) return;
   tq_chain_dwell_finish(r, iv);
-  emit(iv);
+  sink(iv);
   if (!EMIT) {
     const int64_t row = (int64_t)s * a.N + n;
     a.counts[row] = closed;
@@ -271,22 +236,12 @@ extern "C" int tq_chain_dwell(const tq_chain_dwell_args* a, void* stream) {
     tq_set_error("tq_chain_dwell: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->mode == TQ_DWELL_COUNT ? (!a->hist_bound || !a->hist_unbound)
-                                : (a->mode != TQ_DWELL_EMIT || !a->offsets || (a->total > 0 && !a->intervals))) {
-    tq_set_error(a->mode == TQ_DWELL_COUNT || a->mode == TQ_DWELL_EMIT ? "tq_chain_dwell: NULL required pointer"
-                                                                       : "tq_chain_dwell: unknown mode");
+  dim3 grid;
+  if (!tq_chain_dwell_mode_ok("tq_chain_dwell", a->mode, a->hist_bound && a->hist_unbound,
+                              a->offsets && (a->total <= 0 || a->intervals)) ||
+      !tq_chain_dwell_sampler_ok("tq_chain_dwell", a->N, a->F, a->S, a->total) ||
+      !tq_chain_states_ok("tq_chain_dwell", a->U, a->B) || !tq_chain_sample_grid("tq_chain_dwell", a->N, a->S, &grid))
     return TQ_ERR_ARG;
-  }
-  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F || a->total < 0) {
-    tq_set_error("tq_chain_dwell: N, F and S must be positive, F at most 65536 and total non-negative");
-    return TQ_ERR_ARG;
-  }
-  if (!tq_chain_states_ok("tq_chain_dwell", a->U, a->B)) return TQ_ERR_ARG;
-  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
-  if (grid.y > 65535u) {
-    tq_set_error("tq_chain_dwell: S too large");
-    return TQ_ERR_ARG;
-  }
   if (a->mode == TQ_DWELL_COUNT) {
     TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_chain_dwell_kernel<MM, false>), grid, dim3(64), 0,
                                                     (hipStream_t)stream, *a));

@@ -91,6 +91,29 @@ static inline bool tq_chain_priors_ok(const char* who, double prior_a, double pr
   return tq_chain_require(prior_a > 0.0 && prior_a < 1.0 && prior_b > 0.0 && prior_b < 1.0, who,
                           "prior_a and prior_b must lie in (0, 1)");
 }
+// the backward samplers: a grid of (N, ceil(S / 64)) waves; the dwell launches also take the table's length
+static inline bool tq_chain_sampler_ok(const char* who, int N, int F, int S) {
+  return tq_chain_require(N >= 1 && F >= 1 && S >= 1 && F <= TQ_SMOOTH_MAX_F, who,
+                          "N, F and S must be positive and F at most " TQ_STR(TQ_SMOOTH_MAX_F));
+}
+static inline bool tq_chain_dwell_sampler_ok(const char* who, int N, int F, int S, int64_t total) {
+  return tq_chain_require(N >= 1 && F >= 1 && S >= 1 && F <= TQ_SMOOTH_MAX_F && total >= 0, who,
+                          "N, F and S must be positive, F at most " TQ_STR(TQ_SMOOTH_MAX_F) " and total non-negative");
+}
+static inline bool tq_chain_sample_grid(const char* who, int N, int S, dim3* grid) {
+  *grid = dim3((unsigned)N, (unsigned)((S + 63) / 64));
+  return tq_chain_require(grid->y <= 65535u, who, "S too large");
+}
+// a count kernel stores its four columns as one int4
+static inline bool tq_chain_counts_aligned(const char* who, const void* counts) {
+  return tq_chain_require(((uintptr_t)counts & 15u) == 0, who, "counts must be 16-byte aligned");
+}
+// mode is TQ_DWELL_COUNT or TQ_DWELL_EMIT, and the pointers that mode needs are there
+static inline bool tq_chain_dwell_mode_ok(const char* who, int mode, bool count_ptrs_ok, bool emit_ptrs_ok) {
+  const bool known = mode == TQ_DWELL_COUNT || mode == TQ_DWELL_EMIT;
+  return tq_chain_require(known && (mode == TQ_DWELL_COUNT ? count_ptrs_ok : emit_ptrs_ok), who,
+                          known ? "NULL required pointer" : "unknown mode");
+}
 
 // torch.optim.Adam settings a fit kernel supports (written so that a NaN fails)
 static inline bool tq_adam_settings_ok(double lr, double beta1, double beta2, double eps) {

@@ -102,15 +102,14 @@ extern "C" int tq_joint_viterbi(const tq_joint_viterbi_args* a, void* stream) {
   return tq_launch_status("tq_joint_viterbi_kernel");
 }
 
-// ---- backward sampler walked into one channel's intervals: geometry, staging and draws of tq_chain_dwell_kernel<4, EMIT> --
-// Row (s, n) is the raster tq_hmm_count_kernel<4> draws at (U, B) = (2, 2), state for state: one wave per (row, 64 samples),
-// one lane per sample, the twelve thresholds of 64 frames staged in LDS (6144 B, written as they come), TqHmmDraws against
+// ---- backward sampler walked into one channel's intervals ----------------------------------------------------------------
+// Row (s, n) is the raster tq_hmm_count_kernel<4> draws at (U, B) = (2, 2), state for state: the walk of
+// tq_chain_sample_row, the twelve thresholds of 64 frames staged in LDS (6144 B, written as they come), TqHmmDraws against
 // qbuf[j].  Here the class z = (state >> which) & 1 is walked into runs (tq_pair_dwell_frame) and every run carries the
 // partner's state at its ends; neither a raster nor the state pairs are stored.  EMIT = false: per-row interval counts, the
 // first-binding frame, the partner's first bound frame from there on, and the interior-run histograms by the partner's state
-// at the run's start (integer atomics: order-free, so deterministic); EMIT = true: the same draws again, the k-th run a row
-// closes written at tq_smooth_emit_slot with its partner code beside it.  Inactive lanes reach every barrier and touch no
-// memory but the staging; every loop is bounded by F.
+// at the run's start; EMIT = true: the same draws again, the k-th run a row closes written at tq_smooth_emit_slot with its
+// partner code beside it (tq_chain_sink_put with PARTNER).
 template <bool EMIT>
 __global__ __launch_bounds__(64) void tq_pair_dwell_kernel(const tq_pair_dwell_args a) {
   constexpr int M = TQ_JOINT_M, T = M * (M - 1);
@@ -130,6 +129,10 @@ __global__ __launch_bounds__(64) void tq_pair_dwell_kernel(const tq_pair_dwell_a
     o = a.offsets[(int64_t)s * a.N + n];
     count = a.counts[(int64_t)s * a.N + n];
   }
+  int closed = 0;  // runs closed so far
+  auto sink = [&](const TqDwellInterval& v, int pc) {  // the histograms by the partner's state at the run's start
+    tq_chain_sink_put<EMIT, true>(v, closed, o, count, total, a.intervals, hb, hu, s, n, (pc & 1) * F, a.partner, pc);
+  };
 
   TqHmmDraws draws;
   tq_hmm_draws_begin(draws, a.seed, s, n);
@@ -137,42 +140,15 @@ __global__ __launch_bounds__(64) void tq_pair_dwell_kernel(const tq_pair_dwell_a
   tq_pair_dwell_begin(r, F);
   TqDwellInterval iv;
   int code = 0;
-  int closed = 0;  // runs closed so far
-
-  auto emit = [&](const TqDwellInterval& v, int pc) {
-    if (EMIT) {
-      const int64_t pos = tq_smooth_emit_slot(o, count, closed, total);
-      if (pos >= 0) {
-        tq_smooth_emit_row(a.intervals, total, pos, s, n, v);
-        a.partner[pos] = (uint8_t)pc;
-      }
-    } else if (v.low_or_high == 0 || v.low_or_high == 1) {
-      atomicAdd((v.z ? hb : hu) + (pc & 1) * F + (v.stop + 1 - v.start), 1);  // an interior run is shorter than F
-    }
-    ++closed;
-  };
-
-  for (int f0 = (F - 1) & ~63; f0 >= 0; f0 -= 64) {
-    const int cnt = min(64, F - f0);
-    if (lane < cnt) {
-      double af[M];
-#pragma unroll
-      for (int i = 0; i < M; ++i) af[i] = fr[(int64_t)(f0 + lane) * M + i];
-      tq_hmm_thresholds(m, af, f0 + lane == F - 1, qbuf[lane]);
-    }
-    __syncthreads();
-    if (active) {
-      for (int j = cnt - 1; j >= 0; --j) {
-        const int f = f0 + j;
-        const double u = tq_hmm_draws_next(draws, F - 1 - f);
-        if (tq_pair_dwell_frame(r, u, qbuf[j], f, F, which, iv, code)) emit(iv, code);
-      }
-    }
-    __syncthreads();
-  }
+  tq_chain_sample_row(
+      F, lane, active,
+      [&](int f, int l, bool last) { tq_chain_stage_thresholds<M, true>(m, fr + (int64_t)f * M, last, qbuf[l]); },
+      [&](int f, int j) {
+        if (tq_pair_dwell_frame(r, tq_hmm_draws_next(draws, F - 1 - f), qbuf[j], f, F, which, iv, code)) sink(iv, code);
+      });
   if (!active) return;
   tq_pair_dwell_finish(r, iv, code);
-  emit(iv, code);
+  sink(iv, code);
   if (!EMIT) {
     const int64_t row = (int64_t)s * a.N + n;
     a.counts[row] = closed;
@@ -186,26 +162,16 @@ extern "C" int tq_pair_dwell(const tq_pair_dwell_args* a, void* stream) {
     tq_set_error("tq_pair_dwell: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->mode == TQ_DWELL_COUNT
-          ? (!a->hist_bound || !a->hist_unbound)
-          : (a->mode != TQ_DWELL_EMIT || !a->offsets || (a->total > 0 && (!a->intervals || !a->partner)))) {
-    tq_set_error(a->mode == TQ_DWELL_COUNT || a->mode == TQ_DWELL_EMIT ? "tq_pair_dwell: NULL required pointer"
-                                                                       : "tq_pair_dwell: unknown mode");
+  if (!tq_chain_dwell_mode_ok("tq_pair_dwell", a->mode, a->hist_bound && a->hist_unbound,
+                              a->offsets && (a->total <= 0 || (a->intervals && a->partner))) ||
+      !tq_chain_dwell_sampler_ok("tq_pair_dwell", a->N, a->F, a->S, a->total))
     return TQ_ERR_ARG;
-  }
-  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F || a->total < 0) {
-    tq_set_error("tq_pair_dwell: N, F and S must be positive, F at most 65536 and total non-negative");
-    return TQ_ERR_ARG;
-  }
   if (a->which != 0 && a->which != 1) {
     tq_set_error("tq_pair_dwell: which must be 0 (channel a) or 1 (channel b)");
     return TQ_ERR_ARG;
   }
-  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
-  if (grid.y > 65535u) {
-    tq_set_error("tq_pair_dwell: S too large");
-    return TQ_ERR_ARG;
-  }
+  dim3 grid;
+  if (!tq_chain_sample_grid("tq_pair_dwell", a->N, a->S, &grid)) return TQ_ERR_ARG;
   if (a->mode == TQ_DWELL_COUNT) {
     hipLaunchKernelGGL((tq_pair_dwell_kernel<false>), grid, dim3(64), 0, (hipStream_t)stream, *a);
   } else {

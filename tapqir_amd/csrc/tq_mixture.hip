@@ -2,11 +2,12 @@
 // DESIGN.md section 29; bodies in tq_mixture.h): the M-step that weights every AOI by its responsibility, on a grid of one
 // workgroup per start; the backward sampler that draws a population with every raster; the same sampler walked into
 // dwell-time intervals and first-binding frames (tq_population_dwell, section 30); and the per-population estimate of A.
-// The E-step is tq_multistart_estep with R = P * G.  No atomics but the integer histogram bins of tq_population_dwell, no
-// workgroup waits on another, every loop bounded by N, F, S or G.
+// The E-step is tq_multistart_estep with R = P * G.  tq_population_dwell runs on the walk and the interval sink that
+// tq_chain_dev.h shares with tq_hmm.hip and tq_joint.hip.  No atomics
+// but the integer histogram bins of tq_population_dwell, no workgroup waits on another, every loop bounded by N, F, S or G.
 #include <hip/hip_runtime.h>
 
-#include "tq_dpp.h"
+#include "tq_chain_dev.h"
 #include "tq_host.h"
 #include "tq_mixture.h"
 #include "tq_rates.h"
@@ -108,11 +109,13 @@ extern "C" int tq_mixture_mstep(const tq_mixture_mstep_args* a, void* stream) {
 }
 
 // ---- backward sampler: one wave per (row n, block of 64 samples), one lane per sample ----------------------------------
-// The geometry, the staging and the walk of tq_hmm_count_kernel.  Every lane first draws its population; the lanes of a
-// wave may then hold different ones, so lane j stages the thresholds of frame f0 + j for all G populations and the draw
-// reads qbuf[g][j]: addresses diverge, control flow does not, and every lane reaches every barrier.  qbuf[G][64][M (M - 1)]
-// is the launch's dynamic LDS, so that one population takes the LDS of tq_hmm_count_kernel and four take 24 KB at M = 4.  The
-// G chains as they are read (tq_hmm_model) are set up once, by lanes 0 .. G - 1, in LDS.
+// tq_hmm_count_kernel with a population drawn first.  The lanes of a wave may then hold different ones, so lane j stages
+// the thresholds of frame f0 + j for all G populations and the draw reads qbuf[g][j]: addresses diverge, control flow
+// does not, and every lane reaches every barrier; inactive lanes touch no memory but the staging.
+// qbuf[G][64][M (M - 1)] is the launch's dynamic LDS, so that one population takes the LDS of tq_hmm_count_kernel and four
+// take 24 KB at M = 4.  The G chains as they are read (tq_hmm_model) are set up once, by lanes 0 .. G - 1, in LDS, and a
+// barrier stands between that and the first block.  The device text is kept as it was, as tq_hmm_count_kernel's is
+// (DESIGN.md section 35 says what the shared forms cost it).
 template <int M>
 __global__ __launch_bounds__(64) void tq_mixture_count_kernel(const tq_mixture_count_args a) {
   constexpr int T = M * (M - 1);
@@ -196,34 +199,25 @@ extern "C" int tq_mixture_count(const tq_mixture_count_args* a, void* stream) {
     tq_set_error("tq_mixture_count: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (((uintptr_t)a->counts & 15u) != 0) {
-    tq_set_error("tq_mixture_count: counts must be 16-byte aligned");
+  dim3 grid;
+  if (!tq_chain_counts_aligned("tq_mixture_count", a->counts) || !tq_chain_sampler_ok("tq_mixture_count", a->N, a->F, a->S) ||
+      !tq_chain_states_ok("tq_mixture_count", a->U, a->B) || !tq_mixture_pops_ok("tq_mixture_count", a->G) ||
+      !tq_chain_sample_grid("tq_mixture_count", a->N, a->S, &grid))
     return TQ_ERR_ARG;
-  }
-  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F) {
-    tq_set_error("tq_mixture_count: N, F and S must be positive and F at most 65536");
-    return TQ_ERR_ARG;
-  }
-  if (!tq_chain_states_ok("tq_mixture_count", a->U, a->B) || !tq_mixture_pops_ok("tq_mixture_count", a->G)) return TQ_ERR_ARG;
-  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
-  if (grid.y > 65535u) {
-    tq_set_error("tq_mixture_count: S too large");
-    return TQ_ERR_ARG;
-  }
   TQ_HMM_SWITCH_M(a->U + a->B, hipLaunchKernelGGL((tq_mixture_count_kernel<MM>), grid, dim3(64),
                                                   (size_t)a->G * 64 * MM * (MM - 1) * sizeof(double), (hipStream_t)stream, *a));
   return tq_launch_status("tq_mixture_count_kernel");
 }
 
-// ---- backward sampler walked into intervals: the geometry, the staging and the draws of tq_mixture_count_kernel ---------
-// Row (s, n) is the raster that kernel draws, population for population and state for state (tq_mixture_population, then
-// TqHmmDraws against qbuf[g][j]); here its class z = (state >= U) is walked, as it is drawn, into runs of equal labels as
-// tq_chain_dwell_kernel walks them (tq_chain_dwell_frame), and neither a raster nor the state pairs are kept.  EMIT = false:
-// per-row interval counts, the drawn population, the first-binding frame, and the interior-run histograms of the row's
-// population (integer atomics: order-free, so deterministic); EMIT = true: the same draws again, the k-th run a row closes
-// written at tq_smooth_emit_slot.  Addresses diverge by population, control flow does not; inactive lanes reach every
-// barrier and touch no memory but the staging; every loop is bounded by F or G.  M = 4 writes its quotients to LDS as
-// they come, as tq_chain_dwell_kernel does.
+// ---- backward sampler walked into intervals -----------------------------------------------------------------------------
+// Row (s, n) is the raster tq_mixture_count_kernel draws, population for population and state for state
+// (tq_mixture_population, then TqHmmDraws against qbuf[g][j]), on the walk of tq_chain_sample_row.  Here its class
+// z = (state >= U) is walked, as it is drawn, into runs of equal labels (tq_chain_dwell_frame), and neither a raster nor
+// the state pairs are kept.  EMIT = false: per-row interval counts, the drawn population, the first-binding frame, and
+// the interior-run histograms of the row's population; EMIT = true: the same draws again, the k-th run a row closes
+// written at tq_smooth_emit_slot (tq_chain_sink_put).  Every loop is bounded by F or G.  M = 4 writes its quotients to LDS
+// as they come, as tq_chain_dwell_kernel does, but in its own text: through tq_chain_stage_thresholds the COUNT kernels
+// take 100 and 116 VGPRs at M = 3 and 4 in place of 68 and 76.
 template <int M, bool EMIT>
 __global__ __launch_bounds__(64) void tq_population_dwell_kernel(const tq_population_dwell_args a) {
   constexpr int T = M * (M - 1);
@@ -246,57 +240,42 @@ __global__ __launch_bounds__(64) void tq_population_dwell_kernel(const tq_popula
     o = a.offsets[row];
     count = a.counts[row];
   }
+  int closed = 0;  // runs closed so far
+  auto sink = [&](const TqDwellInterval& v) {
+    tq_chain_sink_put<EMIT>(v, closed, o, count, total, a.intervals, hb, hu, s, n);
+  };
 
   TqHmmDraws draws;
   tq_hmm_draws_begin(draws, a.seed, s, n);
   TqChainDwellRow r;
   tq_chain_dwell_begin(r, F);
   TqDwellInterval iv;
-  int closed = 0;  // runs closed so far
-
-  auto emit = [&](const TqDwellInterval& v) {
-    if (EMIT) {
-      const int64_t pos = tq_smooth_emit_slot(o, count, closed, total);
-      if (pos >= 0) tq_smooth_emit_row(a.intervals, total, pos, s, n, v);
-    } else if (v.low_or_high == 0 || v.low_or_high == 1) {
-      atomicAdd((v.z ? hb : hu) + (v.stop + 1 - v.start), 1);  // an interior run is shorter than F
-    }
-    ++closed;
-  };
   __syncthreads();
-
-  for (int f0 = (F - 1) & ~63; f0 >= 0; f0 -= 64) {
-    const int cnt = min(64, F - f0);
-    if (lane < cnt) {
-      for (int gp = 0; gp < G; ++gp) {
-        const double* fr = a.filt + tq_multistart_filt_at<M>(gp, n, N, F) + (int64_t)(f0 + lane) * M;
-        double* q = qbuf + (gp * 64 + lane) * T;
-        double af[M];
+  tq_chain_sample_row(
+      F, lane, active,
+      [&](int f, int l, bool last) {
+        for (int gp = 0; gp < G; ++gp) {
+          const double* fr = a.filt + tq_multistart_filt_at<M>(gp, n, N, F) + (int64_t)f * M;
+          double* q = qbuf + (gp * 64 + l) * T;
+          double af[M];
 #pragma unroll
-        for (int i = 0; i < M; ++i) af[i] = fr[i];
-        if constexpr (M == 4) {
-          tq_hmm_thresholds(mods[gp], af, f0 + lane == F - 1, q);
-        } else {
-          double t[T];
-          tq_hmm_thresholds(mods[gp], af, f0 + lane == F - 1, t);
+          for (int i = 0; i < M; ++i) af[i] = fr[i];
+          if constexpr (M == 4) {
+            tq_hmm_thresholds(mods[gp], af, last, q);
+          } else {
+            double t[T];
+            tq_hmm_thresholds(mods[gp], af, last, t);
 #pragma unroll
-          for (int k = 0; k < T; ++k) q[k] = t[k];
+            for (int k = 0; k < T; ++k) q[k] = t[k];
+          }
         }
-      }
-    }
-    __syncthreads();
-    if (active) {
-      for (int j = cnt - 1; j >= 0; --j) {
-        const int f = f0 + j;
-        const double u = tq_hmm_draws_next(draws, F - 1 - f);
-        if (tq_chain_dwell_frame<M>(r, u, qbuf + (g * 64 + j) * T, f, F, U, iv)) emit(iv);
-      }
-    }
-    __syncthreads();
-  }
+      },
+      [&](int f, int j) {
+        if (tq_chain_dwell_frame<M>(r, tq_hmm_draws_next(draws, F - 1 - f), qbuf + (g * 64 + j) * T, f, F, U, iv)) sink(iv);
+      });
   if (!active) return;
   tq_chain_dwell_finish(r, iv);
-  emit(iv);
+  sink(iv);
   if (!EMIT) {
     a.counts[row] = closed;
     a.pop[row] = (uint8_t)g;
@@ -309,23 +288,13 @@ extern "C" int tq_population_dwell(const tq_population_dwell_args* a, void* stre
     tq_set_error("tq_population_dwell: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->mode == TQ_DWELL_COUNT ? (!a->pop || !a->hist_bound || !a->hist_unbound)
-                                : (a->mode != TQ_DWELL_EMIT || !a->offsets || (a->total > 0 && !a->intervals))) {
-    tq_set_error(a->mode == TQ_DWELL_COUNT || a->mode == TQ_DWELL_EMIT ? "tq_population_dwell: NULL required pointer"
-                                                                       : "tq_population_dwell: unknown mode");
+  dim3 grid;
+  if (!tq_chain_dwell_mode_ok("tq_population_dwell", a->mode, a->pop && a->hist_bound && a->hist_unbound,
+                              a->offsets && (a->total <= 0 || a->intervals)) ||
+      !tq_chain_dwell_sampler_ok("tq_population_dwell", a->N, a->F, a->S, a->total) ||
+      !tq_chain_states_ok("tq_population_dwell", a->U, a->B) || !tq_mixture_pops_ok("tq_population_dwell", a->G) ||
+      !tq_chain_sample_grid("tq_population_dwell", a->N, a->S, &grid))
     return TQ_ERR_ARG;
-  }
-  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F || a->total < 0) {
-    tq_set_error("tq_population_dwell: N, F and S must be positive, F at most 65536 and total non-negative");
-    return TQ_ERR_ARG;
-  }
-  if (!tq_chain_states_ok("tq_population_dwell", a->U, a->B) || !tq_mixture_pops_ok("tq_population_dwell", a->G))
-    return TQ_ERR_ARG;
-  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
-  if (grid.y > 65535u) {
-    tq_set_error("tq_population_dwell: S too large");
-    return TQ_ERR_ARG;
-  }
   if (a->mode == TQ_DWELL_COUNT) {
     TQ_HMM_SWITCH_M(a->U + a->B,
                     hipLaunchKernelGGL((tq_population_dwell_kernel<MM, false>), grid, dim3(64),

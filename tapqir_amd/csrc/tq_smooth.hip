@@ -187,19 +187,10 @@ extern "C" int tq_smooth_count(const tq_smooth_count_args* a, void* stream) {
     tq_set_error("tq_smooth_count: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (((uintptr_t)a->counts & 15u) != 0) {
-    tq_set_error("tq_smooth_count: counts must be 16-byte aligned");
+  dim3 grid;
+  if (!tq_chain_counts_aligned("tq_smooth_count", a->counts) || !tq_chain_sampler_ok("tq_smooth_count", a->N, a->F, a->S) ||
+      !tq_chain_sample_grid("tq_smooth_count", a->N, a->S, &grid))
     return TQ_ERR_ARG;
-  }
-  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F) {
-    tq_set_error("tq_smooth_count: N, F and S must be positive and F at most 65536");
-    return TQ_ERR_ARG;
-  }
-  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
-  if (grid.y > 65535u) {
-    tq_set_error("tq_smooth_count: S too large");
-    return TQ_ERR_ARG;
-  }
   hipLaunchKernelGGL(tq_smooth_count_kernel, grid, dim3(64), 0, (hipStream_t)stream, *a);
   return tq_launch_status("tq_smooth_count_kernel");
 }
@@ -276,21 +267,12 @@ extern "C" int tq_smooth_dwell(const tq_smooth_dwell_args* a, void* stream) {
     tq_set_error("tq_smooth_dwell: NULL required pointer");
     return TQ_ERR_ARG;
   }
-  if (a->mode == TQ_DWELL_COUNT ? (!a->hist_bound || !a->hist_unbound)
-                                : (a->mode != TQ_DWELL_EMIT || !a->offsets || (a->total > 0 && !a->intervals))) {
-    tq_set_error(a->mode == TQ_DWELL_COUNT || a->mode == TQ_DWELL_EMIT ? "tq_smooth_dwell: NULL required pointer"
-                                                                       : "tq_smooth_dwell: unknown mode");
+  dim3 grid;
+  if (!tq_chain_dwell_mode_ok("tq_smooth_dwell", a->mode, a->hist_bound && a->hist_unbound,
+                              a->offsets && (a->total <= 0 || a->intervals)) ||
+      !tq_chain_dwell_sampler_ok("tq_smooth_dwell", a->N, a->F, a->S, a->total) ||
+      !tq_chain_sample_grid("tq_smooth_dwell", a->N, a->S, &grid))
     return TQ_ERR_ARG;
-  }
-  if (a->N < 1 || a->F < 1 || a->S < 1 || a->F > TQ_SMOOTH_MAX_F || a->total < 0) {
-    tq_set_error("tq_smooth_dwell: N, F and S must be positive, F at most 65536 and total non-negative");
-    return TQ_ERR_ARG;
-  }
-  const dim3 grid((unsigned)a->N, (unsigned)((a->S + 63) / 64));
-  if (grid.y > 65535u) {
-    tq_set_error("tq_smooth_dwell: S too large");
-    return TQ_ERR_ARG;
-  }
   if (a->mode == TQ_DWELL_COUNT) {
     hipLaunchKernelGGL(tq_smooth_dwell_kernel<false>, grid, dim3(64), 0, (hipStream_t)stream, *a);
   } else {
