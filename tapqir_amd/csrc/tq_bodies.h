@@ -496,13 +496,39 @@ TQ_HD void tq_body_probs_globals(const tq_probs_args& a, int s, int particle) {
                          (TqGlobalBase*)a.gbase_p + particle, (TqGlobals*)a.globals_p + particle);
 }
 
+// One coordinate of the read-out's draw of (x_k, y_k): AffineBeta(ax ? ym : xm, size, -H, H) of unit `elem` (its GLOBAL index)
+// and particle p, axis ax = 0: x, 1: y, clamped into the support as the guide's rsample clamps it.
+TQ_HD float tq_probs_draw_coord(uint64_t seed, int p, int k, int ax, uint64_t elem, float xm, float ym, float size, float H,
+                                float eps) {
+  TqPhilox s;
+  tq_philox_init(&s, seed, 0x40000000u + (uint32_t)p, 0x800u + 2 * k + ax, elem);
+  const float mean = ax ? ym : xm;
+  const float c1 = size * (mean + H) / (2.0f * H), c0 = size - c1;
+  const float g1 = tq_sample_std_gamma(&s, c1), g0 = tq_sample_std_gamma(&s, c0);
+  float tt = fminf(fmaxf(g1 / (g1 + g0), 1.17549435e-38f), 1.0f - 5.96046448e-08f);
+  return fminf(fmaxf(-H + 2.0f * H * tt, -H + eps * 2.0f * H), H - eps * 2.0f * H);
+}
+
+// the streams of a unit are keyed by its GLOBAL index, like the step's local draws: a shard draws what the whole set draws
+TQ_HD uint64_t tq_probs_elem(const tq_probs_args& a, int64_t u) {
+  return (uint64_t)u + (uint64_t)a.n_offset * (uint64_t)a.F * (uint64_t)a.C;
+}
+
+// constrained x_mean, y_mean, size of spot k of unit u (K spots per unit)
+TQ_HD void tq_probs_spot_guide(const tq_probs_args& a, int64_t U, int64_t u, int k, int K, float H, float* xm, float* ym,
+                               float* sz) {
+  const float lo = -H + a.eps, hi = H - a.eps;
+  *xm = lo + (hi - lo) * tq_sigmoid(a.params[(int64_t)TQ_ROW(TQ_P_XMEAN, k, K) * U + u]);
+  *ym = lo + (hi - lo) * tq_sigmoid(a.params[(int64_t)TQ_ROW(TQ_P_YMEAN, k, K) * U + u]);
+  *sz = 2.0f + expf(a.params[(int64_t)TQ_ROW(TQ_P_SIZE, k, K) * U + u]);
+}
+
 template <int K>
 TQ_HD void tq_body_probs_unit(const tq_probs_args& a, int64_t u) {
   const int64_t U = (int64_t)a.Nt * a.F * a.C;
   const int c = (int)((uint32_t)u % (uint32_t)a.C);  // U < 2^31 (host-checked)
   const int n = (int)((uint32_t)u / ((uint32_t)a.F * (uint32_t)a.C));
-  // the streams of a unit are keyed by its GLOBAL index, like the step's local draws: a shard draws what the whole set draws
-  const uint64_t elem = (uint64_t)u + (uint64_t)a.n_offset * (uint64_t)a.F * (uint64_t)a.C;
+  const uint64_t elem = tq_probs_elem(a, u);
   float z1 = 0.0f, th[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) th[k] = 0.0f;
@@ -512,10 +538,7 @@ TQ_HD void tq_body_probs_unit(const tq_probs_args& a, int64_t u) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       um[k] = a.params[(int64_t)TQ_ROW(TQ_P_MPROBS, k, K) * U + u];
-      const float lo = -H + a.eps, hi = H - a.eps;
-      xm[k] = lo + (hi - lo) * tq_sigmoid(a.params[(int64_t)TQ_ROW(TQ_P_XMEAN, k, K) * U + u]);
-      ym[k] = lo + (hi - lo) * tq_sigmoid(a.params[(int64_t)TQ_ROW(TQ_P_YMEAN, k, K) * U + u]);
-      sz[k] = 2.0f + expf(a.params[(int64_t)TQ_ROW(TQ_P_SIZE, k, K) * U + u]);
+      tq_probs_spot_guide(a, U, u, k, K, H, &xm[k], &ym[k], &sz[k]);
     }
     for (int p = 0; p < a.particles; ++p) {
       float x[K], y[K];
@@ -524,13 +547,7 @@ TQ_HD void tq_body_probs_unit(const tq_probs_args& a, int64_t u) {
         if (a.draw) {
 #pragma nounroll
           for (int ax = 0; ax < 2; ++ax) {
-            TqPhilox s;
-            tq_philox_init(&s, a.seed, 0x40000000u + (uint32_t)p, 0x800u + 2 * k + ax, elem);
-            const float mean = ax ? ym[k] : xm[k];
-            const float c1 = sz[k] * (mean + H) / (2.0f * H), c0 = sz[k] - c1;
-            const float g1 = tq_sample_std_gamma(&s, c1), g0 = tq_sample_std_gamma(&s, c0);
-            float tt = fminf(fmaxf(g1 / (g1 + g0), 1.17549435e-38f), 1.0f - 5.96046448e-08f);
-            const float v = fminf(fmaxf(-H + 2.0f * H * tt, -H + a.eps * 2.0f * H), H - a.eps * 2.0f * H);
+            const float v = tq_probs_draw_coord(a.seed, p, k, ax, elem, xm[k], ym[k], sz[k], H, a.eps);
             if (ax) y[k] = v; else x[k] = v;
           }
         } else {

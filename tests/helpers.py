@@ -68,6 +68,8 @@ def load_hostcheck():
     lib.hc_ksmogn_rsample.restype = None
     lib.hc_cosmos_probs.argtypes = [C.POINTER(_lib.ProbsArgs)]
     lib.hc_cosmos_probs.restype = None
+    lib.hc_probs_xy_draws.argtypes = [C.POINTER(_lib.ProbsArgs), C.c_void_p]
+    lib.hc_probs_xy_draws.restype = None
     for n in ("hc_cosmos_sample_globals", "hc_cosmos_sample_locals", "hc_cosmos_elbo_grads",
               "hc_cosmos_globals_grad", "hc_cosmos_adam"):
         getattr(lib, n).argtypes = [C.POINTER(_lib.CosmosArgs)]

@@ -441,6 +441,23 @@ extern "C" void hc_cosmos_probs(const tq_probs_args* a) {
   }
 }
 
+// The x / y draws tq_body_probs_unit takes with draw = 1, replayed through the same helpers: xy_out [particles][2K][U] in the
+// layout of xy_given (x rows first).  Off-target AOIs, which the body does not draw for, are drawn here all the same.
+extern "C" void hc_probs_xy_draws(const tq_probs_args* a, float* xy_out) {
+  const int K = a->K;
+  const int64_t U = (int64_t)a->Nt * a->F * a->C;
+  const float H = 0.5f * (a->P + 1);
+  for (int64_t u = 0; u < U; ++u)
+    for (int k = 0; k < K; ++k) {
+      float xm, ym, sz;
+      tq_probs_spot_guide(*a, U, u, k, K, H, &xm, &ym, &sz);
+      for (int p = 0; p < a->particles; ++p)
+        for (int ax = 0; ax < 2; ++ax)
+          xy_out[((int64_t)p * 2 * K + ax * K + k) * U + u] =
+              tq_probs_draw_coord(a->seed, p, k, ax, tq_probs_elem(*a, u), xm, ym, sz, H, a->eps);
+    }
+}
+
 // ---- off-step bodies (tq_aux.h) ------------------------------------------------------------------------------------
 extern "C" void hc_ksmogn_rsample(const tq_rsample_args* a) {
   const int npix = a->P * a->P;
